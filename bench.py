@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scenes/s of the VL-SAT eval forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,12 @@ points, fully-connected edges (E = 1560 per scene), 3 GNN layers, fp32 (exact-fp
 Inputs and weights are resident in HBM before the timed region.  Multi-GPU: scenes are sharded
 (weak scaling, 64 scenes per GPU, no data-path collective); the metrics vector is all-reduced
 once per step over RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps (the roofline object comes from the per-class
+HIP events of those same steps) and prints the line.  --full adds everything else the line can
+carry: the uninstrumented re-run, the evaluation leg, the CPU baseline and the oracle parity of
+every scene, the extra_configs legs (other precisions, the configs[4] scene) and the rocprofv3
+traffic passes.  --dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -276,6 +282,30 @@ def two_in_flight(model, d, n_scenes, steps, warmup, dev):
             "outputs_of_both_handles_bit_identical": bool(same)}
 
 
+OUTPUT_NAMES = ("obj_logits_3d", "obj_logits_2d", "rel_cls_3d", "rel_cls_2d")
+DUMP_CAP_BYTES = 60_000_000
+
+
+def dump_outputs(path, out, metrics, rank, world):
+    """--dump-outputs: what the caller of the timed path received from its last step -- the four outputs (float32) and the
+    all-reduced metrics vector (float64) -- as <path>/<name>.npy (<name>.rank<r>.npy per rank when world > 1).  Above
+    DUMP_CAP_BYTES in all, every output keeps the same fixed, seeded sample of its rows (in row order)."""
+    import numpy as np
+    arrays = {n: t.detach().to(torch.float32).cpu().numpy() for n, t in zip(OUTPUT_NAMES, out)}
+    arrays["metrics"] = metrics.detach().to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        keep = (DUMP_CAP_BYTES - arrays["metrics"].nbytes) / total
+        for n in OUTPUT_NAMES:
+            a = arrays[n]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            arrays[n] = a[rows]
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def eval_leg(model, scenes, d, n_obj, dev):
     """Untimed: the step AFTER the path on this rank's batch with seeded synthetic labels -- forward +
     GPU ranking + the additive counts vector (len(evaluate.fields()) = 361 counts), all-reduced once (evaluate.validation) -- so the line carries real evaluation
@@ -357,14 +387,21 @@ def main():
     ap.add_argument("--heads", type=int, default=8, help="MODEL.NUM_HEADS (4 | 8 | 16; not the headline configuration unless 8)")
     ap.add_argument("--dim-atten", type=int, default=256, help="MODEL.DIM_ATTEN (128 | 256 | 512)")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the uninstrumented re-run, the evaluation leg, the CPU baseline and oracle "
+                         "parity, the extra_configs legs and the rocprofv3 traffic passes (--no-cpu / --no-extra / --no-measure-traffic "
+                         "drop parts of it).  Without it the run only times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32; the metrics vector "
+                         "float64; a fixed seeded sample of rows above 60 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-extra", action="store_true",
-                    help="headline configuration only: skip the extra_configs legs (BASELINE configs[2] modes and configs[4]) "
-                         "and the evaluation leg")
+                    help="with --full: headline configuration only: skip the extra_configs legs (BASELINE configs[2] modes and "
+                         "configs[4]) and the evaluation leg")
     ap.add_argument("--measure-traffic", action="store_true",
                     help="measure roofline.traffic in this run: two extra rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of the same "
-                         "workload on 3 steps (< 1 min).  This is the DEFAULT at --gpus 1 when rocprofv3 is on the box and the run is the "
-                         "full one (no --no-extra); --no-measure-traffic quotes the committed profiles/ summary instead, labelled "
+                         "workload on 3 steps (< 1 min).  This is the DEFAULT at --gpus 1 when rocprofv3 is installed and the run is "
+                         "--full without --no-extra; --no-measure-traffic quotes the committed profiles/ summary instead, labelled "
                          "traffic_measured=false and traffic_stale=<collected on another build>")
     ap.add_argument("--no-measure-traffic", action="store_true", help="never run the counter passes (see --measure-traffic)")
     ap.add_argument("--native-allreduce", action="store_true",
@@ -377,6 +414,9 @@ def main():
                          "(split-bf16 MFMA: <=1e-3; mixed single/split bf16: <=1e-2)")
     ap.add_argument("--lib", default="", help="another build of libvlsat_hip.so to load instead of the in-tree one (same-box A/B of a kernel change)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras_on = args.full and not args.no_extra          # the legs besides the headline steps (see --full)
     if args.lib:
         from vlsat_amd import lib as _L
         _L.LIB_PATH = os.path.abspath(args.lib)
@@ -411,10 +451,12 @@ def main():
 
     run = timed_run(model, d, n_scenes, args.steps, args.warmup, prof, dev)
     dt, out, metrics, classes = run["dt"], run["out"], run["metrics"], run["classes"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, metrics, rank, world)
     rank_ms = vdist.minmax_over_ranks(run["local_ms"], dev)
     default_wl = (args.scenes, args.objects, args.points, args.layers, args.heads, args.dim_atten) == (64, 40, 256, 3, 8, 256)
     evaluation, plain = None, None
-    if not args.no_extra:                                # collectives: every rank takes part
+    if extras_on:                                        # collectives: every rank takes part
         if prof:
             # The same K steps again without the per-class HIP events (both runs execute the 2D twin stages on the library's
             # second stream; the instrumented one, the headline `value`, records an event per kernel-class change on either
@@ -439,7 +481,7 @@ def main():
         dom = max(classes, key=lambda k: classes[k]["ms"])
         traffic, traffic_src, measured, stale = None, None, False, None
         import shutil as _sh
-        want_measure = args.measure_traffic or (not args.no_measure_traffic and not args.no_extra and _sh.which("rocprofv3") is not None)
+        want_measure = args.measure_traffic or (not args.no_measure_traffic and extras_on and _sh.which("rocprofv3") is not None)
         if want_measure and world == 1:
             # the counter passes of this very workload, now (minutes: opt-in; the driver's plain run reads the committed summary)
             wl = ["--scenes", str(args.scenes), "--objects", str(args.objects), "--points", str(args.points), "--layers", str(args.layers),
@@ -451,7 +493,7 @@ def main():
         roofline = roofline_of(classes, args.gemm_precision, args.steps, falg, value, world, traffic, traffic_src, stale, measured)
 
     cpu, err, ref = None, None, None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         cpu, _ = cpu_baseline(cfg, args.objects, args.points)
         ref = oracle_all_scenes(cfg, batch, cpu["cores"])
         err = {k: float((g.cpu() - r).abs().max()) for k, g, r in zip(("obj3d", "obj2d", "rel3d", "rel2d"), out, ref)}
@@ -459,7 +501,7 @@ def main():
 
     # ---- BASELINE configs[2] (bf16 matrix cores, same batch) and configs[4] (200 x 1024 stress scene) in the same line ----
     extra = []
-    if world == 1 and not args.no_extra and default_wl and args.gemm_precision == "fp32":
+    if world == 1 and extras_on and default_wl and args.gemm_precision == "fp32":
         names = ("obj3d", "obj2d", "rel3d", "rel2d")
 
         def dom_traffic(workload, mode, cl):             # committed PMC summary of that configuration (not measured in this run)

@@ -1,8 +1,10 @@
 """Reference checkpoint directory layout (model_base.py:47-129): round trip, DataParallel key
-prefix, best/last selection -- and, in the build container only, files written by the REAL
-reference's BaseModel.save()."""
+prefix, best/last selection -- and the files written by the REAL reference's BaseModel.save(),
+rebuilt from their record under tests/golden/."""
+import hashlib
+import json
 import os
-import sys
+from collections import OrderedDict
 
 import numpy as np
 import pytest
@@ -35,17 +37,37 @@ def test_round_trip_and_selection(tmp_path):
         CK.load_reference_checkpoint(d, VLSATConfig(N_LAYERS=2), best=True)       # layer 1 tensors absent
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference only exists in the build container")
-def test_reads_what_the_real_reference_saves(tmp_path):
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden as G
-    G.install_standins()
+def test_reads_what_the_real_reference_saves(tmp_path, golden_dir):
+    """The directory the real reference's BaseModel.save() wrote for an L=1 model holding the seed-5 formula weights, rebuilt
+    from its record (tests/golden/make_golden_checkpoint.py): the same files, keys, shapes and dtypes, and every tensor the
+    loader reads byte-identical to what the reference saved (SHA-256 of the recorded tensor against synth)."""
     cfg = VLSATConfig(N_LAYERS=1)
-    m = G.build_reference(1)
-    G.load_formula_weights(m, cfg, seed=5)
-    m.eva_res, m.iteration = 12.0, 33
-    m.save()                                         # BaseModel.save -> one .pth per sub-module
-    got, meta = CK.load_reference_checkpoint(m.saving_pth, cfg, best=True)
     want = synth.make_weights(cfg, seed=5)
-    assert meta["iteration"] == 33 and meta["suffix"] == "_best.pth"
-    assert all(np.array_equal(got[k], want[k]) for k in want)
+    rec = json.load(open(os.path.join(golden_dir, "reference_checkpoint_l1.json")))["files"]
+    d = tmp_path / "ckp" / "Mmgnet" / "golden"
+    d.mkdir(parents=True)
+    matched = 0
+    for fname, entry in rec.items():
+        if "value" in entry:
+            obj = dict(entry["value"])
+        elif "model" in entry:
+            mod = fname[:-len("_best.pth")]
+            sd = OrderedDict()
+            for key, shape, dtype, sha in entry["model"]:
+                full = f"{mod}.{key}"
+                if full in want:
+                    t = torch.from_numpy(want[full])
+                    assert list(t.shape) == shape and str(t.dtype) == "torch." + dtype, (full, shape, dtype)
+                    assert hashlib.sha256(t.numpy().tobytes()).hexdigest() == sha, f"{full}: not what the reference saved"
+                    matched += 1
+                else:                                # dead at eval (triplet projectors, logit scale, BN counters): any value
+                    t = torch.zeros(shape, dtype=getattr(torch, dtype))
+                sd[key] = t
+            obj = {"model": sd}
+        else:
+            obj = {k: {} for k in entry["keys"]}     # optimizer / lr_scheduler state: not read by the loader
+        torch.save(obj, d / fname)
+    assert matched == len(want)
+    got, meta = CK.load_reference_checkpoint(str(d), cfg, best=True)
+    assert meta["iteration"] == 33 and meta["eva_res"] == 12.0 and meta["suffix"] == "_best.pth"
+    assert set(got) == set(want) and all(np.array_equal(got[k], want[k]) for k in want)

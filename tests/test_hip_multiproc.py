@@ -20,7 +20,7 @@ def _bench(n_ranks, scenes_per_rank, port, backend="gloo", extra=()):
         env["VLSAT_DIST_BACKEND"] = backend
     else:
         env.pop("VLSAT_DIST_BACKEND", None)
-    tail = ["bench.py", "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--no-cpu", "--scenes", str(scenes_per_rank)] + list(extra)
+    tail = ["bench.py", "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--scenes", str(scenes_per_rank)] + list(extra)
     if n_ranks == 1:
         cmd = [sys.executable] + tail
     else:

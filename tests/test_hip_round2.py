@@ -266,7 +266,7 @@ def test_native_rccl_allreduce_single_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for extra in ([], ["--native-allreduce"]):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scenes", "4", "--steps", "1", "--warmup", "1", "--no-cpu",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scenes", "4", "--steps", "1", "--warmup", "1", "--full", "--no-cpu",
                             "--no-profile", *extra], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))

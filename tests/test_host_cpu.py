@@ -96,6 +96,35 @@ def test_profile_stamps_and_stale_detection(L, tmp_path, monkeypatch):
     assert bench.committed_traffic("cfg2", "fp32", "gemm_f32")[2] is True
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the four outputs of the last timed step (float32) and the metrics vector (float64) as .npy files,
+    whole when they fit the cap, otherwise the same seeded row sample on every run and within the cap."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = (torch.randn(80, 160, generator=g), torch.randn(80, 160, generator=g),
+           torch.randn(3120, 26, generator=g), torch.randn(3120, 26, generator=g))
+    metrics = torch.arange(9, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), out, metrics, 0, 1)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(n + ".npy" for n in bench.OUTPUT_NAMES + ("metrics",))
+    for n, t in zip(bench.OUTPUT_NAMES, out):
+        a = np.load(tmp_path / "a" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
+    m = np.load(tmp_path / "a" / "metrics.npy")
+    assert m.dtype == np.float64 and np.array_equal(m, metrics.numpy())
+    cap = 200_000
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", cap)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, metrics, 0, 1)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= cap + 128 * 5                                    # (.npy headers)
+    for n, t in zip(bench.OUTPUT_NAMES, out):
+        b, c = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert 0 < b.shape[0] < t.shape[0] and b.shape[1:] == tuple(t.shape[1:]) and np.array_equal(b, c)
+        assert all(any(np.array_equal(r, x) for x in t.numpy()) for r in b[:3])   # rows of the output, not something else
+
+
 def test_c_abi_argument_validation_without_gpu(L):
     lib = L.load()
     h = C.c_void_p()

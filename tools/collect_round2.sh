@@ -5,12 +5,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/r02
 mkdir -p "$OUT"
 cd "$ROOT"
-python bench.py > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"
-python bench.py --gemm-precision bf16x3 > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
-python bench.py --gemm-precision bf16_mixed > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
-python bench.py --no-cpu --gemm-precision bf16 > "$OUT/bench_cfg3_bf16.json" 2> "$OUT/bench_cfg3_bf16.err"
+python bench.py --full > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"
+python bench.py --full --gemm-precision bf16x3 > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
+python bench.py --full --gemm-precision bf16_mixed > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
+python bench.py --full --no-cpu --gemm-precision bf16 > "$OUT/bench_cfg3_bf16.json" 2> "$OUT/bench_cfg3_bf16.err"
 for m in fp32 bf16x3; do
-  python bench.py --scenes 1 --objects 200 --points 1024 --steps 10 --warmup 2 --no-cpu --gemm-precision $m > "$OUT/bench_cfg5_$m.json" 2> "$OUT/bench_cfg5_$m.err"
+  python bench.py --full --scenes 1 --objects 200 --points 1024 --steps 10 --warmup 2 --no-cpu --gemm-precision $m > "$OUT/bench_cfg5_$m.json" 2> "$OUT/bench_cfg5_$m.err"
 done
 tools/profile_run.sh r02/prof_fp32 > /dev/null 2>&1
 tools/profile_run.sh r02/prof_cfg3 --gemm-precision bf16x3 > /dev/null 2>&1

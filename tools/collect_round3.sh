@@ -6,9 +6,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/r03
 mkdir -p "$OUT"
 cd "$ROOT"
-python bench.py > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"                       # the driver's command: headline + extra_configs
-python bench.py --gemm-precision bf16x3 --no-extra > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
-python bench.py --gemm-precision bf16_mixed --no-extra > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
+python bench.py --full > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"                # the full line: headline + extra_configs
+python bench.py --full --gemm-precision bf16x3 --no-extra > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
+python bench.py --full --gemm-precision bf16_mixed --no-extra > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
 tools/profile_run.sh r03/prof_fp32 --no-extra > /dev/null 2>&1
 tools/profile_run.sh r03/prof_cfg3 --gemm-precision bf16x3 --no-extra > /dev/null 2>&1
 tools/profile_run.sh r03/prof_cfg3_mixed --gemm-precision bf16_mixed --no-extra > /dev/null 2>&1

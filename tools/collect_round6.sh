@@ -8,9 +8,9 @@ PART=${PART:-abc}
 mkdir -p "$OUT"
 cd "$ROOT"
 if [[ $PART == *a* ]]; then
-python bench.py > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"                       # the driver's command: headline + extra_configs
-python bench.py --gemm-precision bf16x3 --no-extra > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
-python bench.py --gemm-precision bf16_mixed --no-extra > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
+python bench.py --full > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"                # the full line: headline + extra_configs
+python bench.py --full --gemm-precision bf16x3 --no-extra > "$OUT/bench_cfg3_bf16x3.json" 2> "$OUT/bench_cfg3_bf16x3.err"
+python bench.py --full --gemm-precision bf16_mixed --no-extra > "$OUT/bench_cfg3_bf16_mixed.json" 2> "$OUT/bench_cfg3_bf16_mixed.err"
 tools/profile_run.sh r06/prof_fp32 --no-extra > /dev/null 2>&1
 tools/profile_run.sh r06/prof_cfg3 --gemm-precision bf16x3 --no-extra > /dev/null 2>&1
 tools/profile_run.sh r06/prof_cfg3_mixed --gemm-precision bf16_mixed --no-extra > /dev/null 2>&1

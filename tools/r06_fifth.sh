@@ -9,7 +9,7 @@ timeout 2400 python -m pytest tests -q -m gpu -x > "$OUT/tests_gpu.txt" 2>&1; ta
 python tools/val_loop_probe.py > "$OUT/val_loop_fp32.txt" 2>&1; cat "$OUT/val_loop_fp32.txt"
 python tools/val_loop_probe.py --gemm-precision bf16_mixed > "$OUT/val_loop_bf16_mixed.txt" 2>&1; cat "$OUT/val_loop_bf16_mixed.txt"
 python tools/latency_probe.py > "$OUT/latency_fp32.txt" 2>&1; head -12 "$OUT/latency_fp32.txt"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - "$OUT/bench.json" <<'PY'
 import json,sys
 j=[json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]

@@ -8,7 +8,7 @@ cd "$ROOT"
 timeout 900 python -m pytest tests/test_hip_metrics.py tests/test_hip_scan.py tests/test_hip_prep.py tests/test_hip_round5.py -x -q > "$OUT/tests.txt" 2>&1
 tail -15 "$OUT/tests.txt"
 python tools/metrics_bench.py > "$OUT/metrics_bench.txt" 2>&1; cat "$OUT/metrics_bench.txt"
-python bench.py --steps 10 --warmup 3 --no-cpu --no-measure-traffic > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --steps 10 --warmup 3 --full --no-cpu --no-measure-traffic > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - <<'PY' "$OUT/bench.json"
 import json,sys
 j=[json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]
