@@ -296,6 +296,22 @@ int64_t vlsat_eval_ranks_scratch_floats(int32_t n_nodes, int32_t n_obj_class, in
     return (int64_t)n_nodes * eval_ranks_sorted_k(n_obj_class, topk_triplet);
 }
 
+int64_t vlsat_eval_recallk_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes) {
+    if (n_nodes < 0 || n_edges < 0 || n_obj_class < 0 || n_rel_class < 0 || n_scenes < 0) return 0;
+    return (int64_t)eval_recallk_scratch_bytes(n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes);
+}
+
+int vlsat_eval_recallk(const float* obj_probs, const float* rel_probs, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges,
+                       const int64_t* batch_ids, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                       int32_t n_scenes, int32_t variants_mask, void* scratch, int64_t* counts, void* stream) {
+    if (n_scenes > 0 && (!counts || !scratch)) return fail(VLSAT_EINVAL, "eval_recallk: null counts or scratch");
+    if (n_edges > 0 && (!rel_probs || !gt_rel || !edges || ((variants_mask & 12) && (!obj_probs || !gt_class))))
+        return fail(VLSAT_EINVAL, "eval_recallk: null edge argument");
+    if (n_scenes > 1 && !batch_ids) return fail(VLSAT_EINVAL, "eval_recallk: batch_ids is required for more than one scene");
+    return launch_eval_recallk(obj_probs, rel_probs, gt_class, gt_rel, edges, batch_ids, n_nodes, n_edges, n_obj_class, n_rel_class,
+                               n_scenes, variants_mask, scratch, reinterpret_cast<long long*>(counts), static_cast<hipStream_t>(stream));
+}
+
 int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, const int32_t* rel_rank_3d, const int32_t* rel_rank_2d,
                       const int32_t* tri_rank_3d, const int32_t* tri_rank_2d, const int32_t* cnt, const int64_t* gt_class,
                       const int64_t* gt_rel, const int64_t* edges, int32_t n_nodes, int32_t n_edges, int32_t n_rel_class,

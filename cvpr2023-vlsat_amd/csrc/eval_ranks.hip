@@ -410,6 +410,13 @@ int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const
     return 0;
 }
 
+int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s) {
+    if (N <= 0) return 0;
+    hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, probs, N, C, K, sorted);
+    VLSAT_LAUNCH_CHECK("sort_probs");
+    return 0;
+}
+
 int launch_softmax_rows(const float* x, int ld, int rows, int cols, float* out, int log_out, hipStream_t s) {
     if (rows <= 0) return 0;
     if (x == out && ld != cols) return fail(-1, "softmax_rows: in-place needs ld == cols");

@@ -212,6 +212,14 @@ int launch_eval_ranks(const float* obj_logits, const float* obj_probs, const flo
 // columns of the per-node sorted-probability scratch of launch_eval_ranks ([N, K] floats): only the topk largest matter
 inline int eval_ranks_sorted_k(int C, int topk_tri) { return C < topk_tri ? C : topk_tri; }
 
+// sorted[n, 0:K] = the K largest entries of probs[n, :] (C <= 1024), descending
+int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s);
+// Recall@K / mR@K counts per scene (eval_recall.hip): counts [n_scenes][1 + R + 4 (3 + 3 R)] int64, every field written
+size_t eval_recallk_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes);
+int launch_eval_recallk(const float* obj_probs, const float* rel, const int64_t* gt_cls, const int64_t* gt_rel, const int64_t* edges,
+                        const int64_t* batch_ids, int N, int E, int C, int R, int n_scenes, int vmask, void* scratch,
+                        long long* counts, hipStream_t s);
+
 // rank arrays of one batch -> += the additive counts vector of evaluate.validation (uint64 [1 + R + 2 (11 + 6 R)]; layout:
 // evaluate.fields()); integer atomics only, safe from concurrent streams
 int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const int32_t* rel_rank3, const int32_t* rel_rank2,

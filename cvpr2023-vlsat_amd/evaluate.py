@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import dist as vdist
+from .metrics import RECALL_K as _RK_K, RECALL_VARIANTS as _RK_VARIANTS, recallk_offset
 
 N_REL = 26
 # layout of the metrics vector (fp64): see fields()
@@ -106,6 +107,63 @@ def summarize(vec: np.ndarray, n_rel: int = N_REL) -> Dict[str, float]:
     return out
 
 
+# ---- Recall@K / mR@K (validation(recall_k=True)): a second additive vector, concatenated onto fields() for the one all-reduce ----
+def recall_fields(n_rel: int = N_REL):
+    """Layout of the Recall@K vector (fp64, additive over scenes and ranks): rk_scenes (scenes with >= 1 gt edge), rk_gt_edges,
+    rk_gt_cls{c}; then per branch, variant and K: the pooled hit count, the sum over scenes of the per-scene recall
+    (rsum) and of the per-scene mean recall over the scene's predicate classes (mrsum), and the pooled per-class hits."""
+    f = ["rk_scenes", "rk_gt_edges"] + [f"rk_gt_cls{c}" for c in range(n_rel)]
+    for br in ("3d", "2d"):
+        for v in _RK_VARIANTS:
+            for k in _RK_K:
+                f += [f"{v}_hit@{k}_{br}", f"{v}_rsum@{k}_{br}", f"{v}_mrsum@{k}_{br}"]
+                f += [f"{v}_cls{c}_hit@{k}_{br}" for c in range(n_rel)]
+    return f
+
+
+def recall_vector(c3: torch.Tensor, c2: torch.Tensor, n_rel: int = N_REL) -> torch.Tensor:
+    """The recall_fields() vector (fp64, on the counts' device, no synchronisation) of one batch from the per-scene counts
+    ``metrics.recallk_counts`` returned for its 3D (``c3``) and 2D (``c2``) outputs."""
+    r = n_rel
+    gt = c3[:, 0].double()
+    gtc = c3[:, 1:1 + r].double()
+    valid = gt > 0
+    cls_on = gtc > 0
+    n_cls = cls_on.sum(1).clamp(min=1).double()
+    parts = [valid.sum().double().view(1), gt.sum().view(1), gtc.sum(0)]
+    for c in (c3, c2):
+        for v in _RK_VARIANTS:
+            base = recallk_offset(v, r)
+            hits = c[:, base:base + 3].double()                                        # [S, 3]
+            ch = c[:, base + 3:base + 3 + 3 * r].double().view(-1, 3, r)              # [S, 3, R]
+            rsum = (hits / gt.clamp(min=1)[:, None] * valid[:, None]).sum(0)
+            mr = (ch / gtc.clamp(min=1)[:, None, :] * cls_on[:, None, :]).sum(2) / n_cls[:, None]
+            mrsum = (mr * valid[:, None]).sum(0)
+            parts.append(torch.cat([hits.sum(0)[:, None], rsum[:, None], mrsum[:, None], ch.sum(0)], 1).reshape(-1))
+    return torch.cat(parts)
+
+
+def recall_summarize(vec: np.ndarray, n_rel: int = N_REL) -> Dict[str, float]:
+    """Percentages from the (all-reduced) recall_fields() vector.  ``{v}_R@{K}_{br}`` / ``{v}_mR@{K}_{br}``: the per-scene
+    Recall@K / mR@K (what evaluate_triplet_recallk / _mrecallk return for one scene; mR = mean over the scene's predicate
+    classes) averaged over the scenes with at least one gt edge.  ``..._pooled``: hits over gt edges of all scenes, and the
+    mean over predicate classes of the pooled per-class recall.  The reference never aggregates across scenes; both are given."""
+    idx = {k: i for i, k in enumerate(recall_fields(n_rel))}
+    n_sc, n_gt = vec[idx["rk_scenes"]], vec[idx["rk_gt_edges"]]
+    gtc = np.array([vec[idx[f"rk_gt_cls{c}"]] for c in range(n_rel)])
+    out = {}
+    for br in ("3d", "2d"):
+        for v in _RK_VARIANTS:
+            for k in _RK_K:
+                ch = np.array([vec[idx[f"{v}_cls{c}_hit@{k}_{br}"]] for c in range(n_rel)])
+                out[f"{v}_R@{k}_{br}"] = float(vec[idx[f"{v}_rsum@{k}_{br}"]] * 100 / n_sc) if n_sc else float("nan")
+                out[f"{v}_mR@{k}_{br}"] = float(vec[idx[f"{v}_mrsum@{k}_{br}"]] * 100 / n_sc) if n_sc else float("nan")
+                out[f"{v}_R@{k}_{br}_pooled"] = float(vec[idx[f"{v}_hit@{k}_{br}"]] * 100 / n_gt) if n_gt else float("nan")
+                on = gtc > 0
+                out[f"{v}_mR@{k}_{br}_pooled"] = float(np.mean(ch[on] / gtc[on]) * 100) if on.any() else float("nan")
+    return out
+
+
 _warned_sync = False
 
 
@@ -155,7 +213,7 @@ def merge_batches(bs) -> dict:
 
 
 @torch.no_grad()
-def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1) -> np.ndarray:
+def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False):
     """The counts vector of this rank's batches with NO host round trip per batch and ``workers`` batches in flight:
     every worker thread owns a replica of the model (its own library handle: a handle is driven by one host thread and one
     stream at a time) and a stream; forward, ranking and counting of a batch are enqueued back to back
@@ -171,6 +229,7 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     dev = torch.device(device)
     models = [model] + model.replicas(workers - 1)        # (kept by the model: building one uploads and prepares every weight)
     counts = [torch.zeros(len(fields()), dtype=torch.int64, device=dev) for _ in range(workers)]
+    recall = [torch.zeros(len(recall_fields()), dtype=torch.float64, device=dev) if recall_k else None for _ in range(workers)]
     it, lock, errors = iter(batches), threading.Lock(), []
 
     def work(k):
@@ -185,7 +244,8 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
                         break
                     b = merge_batches(group)
                     M.process_val_counts(models[k], counts[k], b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"],
-                                         b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"))
+                                         b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"),
+                                         recall=recall[k])
             stream.synchronize()
         except BaseException as ex:             # (re-raised in the caller's thread)
             errors.append(ex)
@@ -202,11 +262,15 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
             t.join()
     if errors:
         raise errors[0]
-    return torch.stack(counts).sum(0).cpu().numpy().astype(np.float64)
+    vec = torch.stack(counts).sum(0).cpu().numpy().astype(np.float64)
+    if recall_k:
+        return vec, torch.stack(recall).sum(0).cpu().numpy()
+    return vec
 
 
 @torch.no_grad()
-def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1) -> Dict[str, float]:
+def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1,
+               recall_k: bool = False) -> Dict[str, float]:
     """``batches`` yields this rank's dicts with the reference loader's item names
     (obj_points [N,3,P], obj_2d_feats, gt_class, gt_rel_cls, edge_indices [E,2], descriptor, batch_ids; optionally
     ``fc_sizes``: objects per scene when edge_indices is the canonical fully-connected list, which spares the graph plan a
@@ -214,24 +278,46 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
     workers = 0: the reference-compatible path -- ``process_val`` per batch (numpy rank lists on the host, like
     ``Mmgnet.process_val``) and host-side accumulation.  workers >= 1: counts accumulated on the device, no host round trip
     per batch, ``workers`` batches in flight on as many streams and model replicas (for one-scene-per-call loops);
-    ``merge`` = B > 1 additionally collates B consecutive batches into one call (``merge_batches``)."""
+    ``merge`` = B > 1 additionally collates B consecutive batches into one call (``merge_batches``).
+    recall_k = True: the result also holds the scene-graph Recall@K / mR@K of both branches (recall_summarize: PredCls /
+    SGCls, with and without graph constraint, K = 20, 50, 100), from a recall_fields() vector concatenated onto the counts
+    so that the run still does one all-reduce."""
     from . import metrics as M
     if workers > 0:
         if device is None:
             raise ValueError("validation(workers > 0) needs the device")
-        vec = _validation_pipelined(model, batches, device, int(workers), int(merge))
+        vec = _validation_pipelined(model, batches, device, int(workers), int(merge), bool(recall_k))
+        if recall_k:
+            return _summaries(vdist.allreduce_metrics(torch.from_numpy(np.concatenate(vec)).to(device)).cpu().numpy())
         t = vdist.allreduce_metrics(torch.from_numpy(vec).to(device))
         return summarize(t.cpu().numpy())
     vec = np.zeros(len(fields()), dtype=np.float64)
+    rvec = np.zeros(len(recall_fields()), dtype=np.float64) if recall_k else None
     for b in batches:
-        out = M.process_val(model, b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"], b["gt_rel_cls"],
-                            b["edge_indices"], b["batch_ids"], use_triplet=True)
+        # process_val, with the forward's outputs kept for the recall counts
+        outs = M._forward_eval(model, b["obj_points"], b["obj_2d_feats"], b["descriptor"], b["edge_indices"], b["batch_ids"])
+        out = M._process_val_from(model, outs, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], True)
         ranks = dict(top_k_obj=out[0], top_k_obj_2d=out[1], top_k_rel=out[2], top_k_rel_2d=out[3],
                      top_k_triplet=out[4], top_k_triplet_2d=out[5])
         n_scenes = int(b["batch_ids"].max().item()) + 1 if b["batch_ids"].numel() else 0
         accumulate(vec, ranks, out[6], n_scenes)
-    t = torch.from_numpy(vec)
+        if recall_k:
+            multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
+            bid = b["batch_ids"].view(-1)
+            c3, c2 = (M.recallk_counts(o, rl, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], bid, n_scenes, multi)
+                      for o, rl in ((outs[0], outs[2]), (outs[1], outs[3])))
+            rvec += recall_vector(c3, c2, outs[2].shape[1]).cpu().numpy()
+    t = torch.from_numpy(vec if rvec is None else np.concatenate([vec, rvec]))
     if device is not None:
         t = t.to(device)
     t = vdist.allreduce_metrics(t)
+    if recall_k:
+        return _summaries(t.cpu().numpy())
     return summarize(t.cpu().numpy())
+
+
+def _summaries(v: np.ndarray) -> Dict[str, float]:
+    n = len(fields())
+    out = summarize(v[:n])
+    out.update(recall_summarize(v[n:]))
+    return out

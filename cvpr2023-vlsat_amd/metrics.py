@@ -124,14 +124,15 @@ def eval_counts(counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str,
 
 @torch.no_grad()
 def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices,
-                       batch_ids=None, n_scenes: int = 1, fc_sizes=None):
+                       batch_ids=None, n_scenes: int = 1, fc_sizes=None, recall: torch.Tensor | None = None):
     """``process_val`` for an evaluation LOOP: forward + both ranking passes + the counts, all enqueued on the current stream,
     nothing read back (``Mmgnet.process_val`` returns numpy rank lists, i.e. four host round trips per scene, reference
     SGFN_MMG/model.py:463-480; ``validation()`` only ever turns them into the counts accumulated here).
-    ``edge_indices`` is [E,2] as the data loader yields it, on the device."""
+    ``edge_indices`` is [E,2] as the data loader yields it, on the device.  ``recall``: a device fp64 vector of
+    ``evaluate.recall_fields()`` that additionally accumulates the Recall@K / mR@K of both branches (``recallk_counts``)."""
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
     edges = edge_indices.to(torch.int64).contiguous()
-    if multi and hasattr(model, "process_val_counts"):           # one library call: forward + ranking + counts in the plan's scratch
+    if multi and recall is None and hasattr(model, "process_val_counts"):           # one library call: forward + ranking + counts in the plan's scratch
         r = model.config.num_rel_class
         if model.process_val_counts(counts, obj_points, obj_2d_feats, gt_cls.to(torch.int64).contiguous().view(-1), descriptor,
                                     multihot_targets(gt_rel_cls, r).to(torch.int64).contiguous(), edges, batch_ids, n_scenes, fc_sizes):
@@ -143,6 +144,12 @@ def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt
     gt_cls = gt_cls.to(torch.int64).contiguous().view(-1)
     t3 = rank_tables(obj3, rel3, gt_cls, gt_rel, edges, multi)
     t2 = rank_tables(obj2, rel2, gt_cls, gt_rel, edges, multi)
+    if recall is not None:
+        from . import evaluate as EV
+        bid = None if batch_ids is None else batch_ids.view(-1)
+        c3 = recallk_counts(obj3, rel3, gt_cls, gt_rel, edges, bid, n_scenes, multi)
+        c2 = recallk_counts(obj2, rel2, gt_cls, gt_rel, edges, bid, n_scenes, multi)
+        recall += EV.recall_vector(c3, c2, rel3.shape[1])
     return eval_counts(counts, t3, t2, gt_cls, gt_rel, edges, n_scenes)
 
 
@@ -162,14 +169,23 @@ def cls_matrix(gt_class: torch.Tensor, gt_rel: torch.Tensor, edges: torch.Tensor
     return torch.stack([gt_class[a], obj_topk[a].long(), gt_class[b], obj_topk[b].long(), ki - 1], 1)
 
 
+def _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids):
+    ei_t = edge_indices.t().contiguous()
+    return model(obj_points, obj_2d_feats, ei_t, descriptor, batch_ids, istrain=False)
+
+
 @torch.no_grad()
 def process_val(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids=None,
                 use_triplet=True):
     """Same call and 10-tuple as ``Mmgnet.process_val`` (reference SGFN_MMG/model.py:458-480);
     ``edge_indices`` is [E,2] as the data loader yields it.  Rank arrays are numpy int64 like the
     reference's; the score lists come back stacked as tensors."""
-    ei_t = edge_indices.t().contiguous()
-    obj3, obj2, rel3, rel2 = model(obj_points, obj_2d_feats, ei_t, descriptor, batch_ids, istrain=False)
+    outs = _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids)
+    return _process_val_from(model, outs, gt_cls, gt_rel_cls, edge_indices, use_triplet)
+
+
+def _process_val_from(model, outs, gt_cls, gt_rel_cls, edge_indices, use_triplet):
+    obj3, obj2, rel3, rel2 = outs
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))     # self.mconfig.multi_rel_outputs
     gt_rel_cls = multihot_targets(gt_rel_cls, rel3.shape[1])
     r3 = eval_ranks(obj3, rel3, gt_cls, gt_rel_cls, edge_indices, multi_rel_outputs=multi)
@@ -206,3 +222,278 @@ def summarize(top_k_obj, top_k_rel, top_k_triplet, cls_mat=None) -> Dict[str, fl
         if rec[0]:
             out["mean_recall@50"], out["mean_recall@100"] = float(np.mean(rec[0])), float(np.mean(rec[1]))
     return out
+
+
+# ---- Recall@K / mR@K (reference src/utils/eval_utils_recall.py, process_val2 / process_val3 of SGFN_MMG/model_in21k.py) ----
+RECALL_K = (20, 50, 100)
+RECALL_VARIANTS = ("predcls_gc", "predcls_ngc", "sgcls_gc", "sgcls_ngc")     # bits 1, 2, 4, 8 of vlsat_eval_recallk's mask
+_NGC_CAP = 100                                                               # topk_each of the NGC variants
+
+
+def recallk_width(n_rel: int) -> int:
+    """Fields per scene of the counts ``recallk_counts`` returns: gt_edges, gt_per_class[R], then per variant (in
+    RECALL_VARIANTS order) hit@{20,50,100} and class_hit@{20,50,100}[R]."""
+    return 1 + n_rel + len(RECALL_VARIANTS) * (3 + 3 * n_rel)
+
+
+def recallk_offset(variant: str, n_rel: int) -> int:
+    """Index of ``variant``'s hit@20 in a counts row; hit@K, then class_hit@K[R] for K = 20, 50, 100 follow."""
+    return 1 + n_rel + RECALL_VARIANTS.index(variant) * (3 + 3 * n_rel)
+
+
+def _variant_mask(variants) -> int:
+    m = 0
+    for v in variants:
+        if v not in RECALL_VARIANTS:
+            raise ValueError(f"recallk: unknown variant {v!r} (one of {RECALL_VARIANTS})")
+        m |= 1 << RECALL_VARIANTS.index(v)
+    return m
+
+
+def _recallk_inputs(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids, multi_rel_outputs, obj_probs):
+    e, r = rel.shape
+    gt_cls = gt_cls.to(torch.int64).contiguous().view(-1)
+    gt_rel = multihot_targets(gt_rel, r).to(torch.int64).contiguous()
+    edges = edges.to(torch.int64).contiguous().view(-1, 2)
+    if batch_ids is not None:
+        batch_ids = batch_ids.to(torch.int64).contiguous().view(-1)
+    r_probs = (rel if multi_rel_outputs else rel.exp()).float().contiguous()
+    if edges.shape[0] != e or gt_rel.shape != (e, r) or gt_cls.numel() != obj_logits.shape[0]:
+        raise L.VlsatError("recallk: edges must be [E,2], gt_rel [E,R] (or [E]), gt_cls [N]")
+    return gt_cls, gt_rel, edges, batch_ids, r_probs, obj_probs
+
+
+def recallk_counts(obj_logits: torch.Tensor, rel: torch.Tensor, gt_cls: torch.Tensor, gt_rel: torch.Tensor,
+                   edges: torch.Tensor, batch_ids: torch.Tensor | None, n_scenes: int, multi_rel_outputs: bool = True,
+                   variants=RECALL_VARIANTS, obj_probs: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-scene Recall@K counts, int64 [n_scenes, recallk_width(R)] (layout: ``recallk_width``), of the four variants
+    PredCls / SGCls x graph constraint (topk_each = 1) / none (topk_each = 100) at K = 20, 50, 100.
+    ``obj_logits`` [N, C] (the object probabilities are their softmax -- use_clip=True -- unless ``obj_probs`` is given),
+    ``rel`` [E, R] predicate probabilities (log-probabilities when ``multi_rel_outputs`` is False), ``gt_rel`` the
+    multi-hot [E, R] or single-label [E] target, ``edges`` [E, 2] grouped by scene in ascending order, the scene of an edge
+    being ``batch_ids[edges[e, 0]]`` (None: one scene).  Counting rule and tie convention: include/vlsat.h
+    (vlsat_eval_recallk).  Device tensors: the HIP kernels (csrc/eval_recall.hip), asynchronous, no host round trip.
+    CPU tensors: ``recallk_counts_host``.  Variants left out of ``variants`` are zeros."""
+    if not obj_logits.is_cuda:
+        return recallk_counts_host(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids, n_scenes, multi_rel_outputs, variants,
+                                   obj_probs)
+    lib = L.load()
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    n_scenes = int(n_scenes)
+    gt_cls, gt_rel, edges, batch_ids, r_probs, obj_probs = _recallk_inputs(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids,
+                                                                          multi_rel_outputs, obj_probs)
+    mask = _variant_mask(variants)
+    if obj_probs is None:
+        obj_probs = softmax_rows(obj_logits.float())
+    obj_probs = obj_probs.float().contiguous()
+    dev = obj_logits.device
+    out = torch.empty(n_scenes, recallk_width(r), dtype=torch.int64, device=dev)
+    nbytes = int(lib.vlsat_eval_recallk_scratch_bytes(n, e, c, r, n_scenes))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L.check(lib.vlsat_eval_recallk(obj_probs.data_ptr(), r_probs.data_ptr(), gt_cls.data_ptr(), gt_rel.data_ptr(), edges.data_ptr(),
+                                   L.ptr(batch_ids), n, e, c, r, n_scenes, mask, scratch.data_ptr(), out.data_ptr(), L.stream_ptr()))
+    return out
+
+
+def _tri_table(ks: int, r: int, dev) -> torch.Tensor:
+    """Index triples (i, j, k) of sorted positions with (i+1)(j+1)(k+1) <= 100: an entry outside is dominated by at least
+    100 others, so an edge's 100 largest products lie inside (eval_recall.hip)."""
+    t = [(a - 1, b - 1, q - 1) for a in range(1, ks + 1) for b in range(1, min(ks, _NGC_CAP // a) + 1)
+         for q in range(1, min(r, _NGC_CAP // (a * b)) + 1)]
+    return torch.tensor(t, dtype=torch.int64, device=dev).view(-1, 3)
+
+
+@torch.no_grad()
+def recallk_counts_host(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids, n_scenes, multi_rel_outputs=True,
+                        variants=RECALL_VARIANTS, obj_probs=None, chunk: int = 8192) -> torch.Tensor:
+    """The counting definition of ``recallk_counts`` stated directly in PyTorch, on whatever device the inputs are:
+    every correct entry c of an edge is tested for (1) being one of the edge's topk_each candidates and (2) having fewer than K
+    candidates of its scene strictly above it.  The candidates of an SGCls NGC edge (its 100 largest products) are taken
+    from the dominance-pruned index set (``_tri_table``) instead of the 665 600 products.  Exact, slow; for CPU tests and
+    devices without the HIP library."""
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    n_scenes = int(n_scenes)
+    dev = obj_logits.device
+    gt_cls, gt_rel, edges, batch_ids, rp, obj_probs = _recallk_inputs(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids,
+                                                                      multi_rel_outputs, obj_probs)
+    mask = _variant_mask(variants)
+    probs = (torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()).contiguous()
+    out = torch.zeros(n_scenes, recallk_width(r), dtype=torch.int64, device=dev)
+    if e == 0 or n_scenes == 0:
+        return out
+    a, b = edges[:, 0], edges[:, 1]
+    scene = batch_ids[a] if batch_ids is not None else torch.zeros(e, dtype=torch.int64, device=dev)
+    hot = gt_rel == 1
+    has = hot.any(1)
+    out[:, 0] = torch.bincount(scene[has], minlength=n_scenes)[:n_scenes]
+    out[:, 1:1 + r].index_add_(0, scene, hot.long())
+    neg = torch.tensor(-float("inf"), device=dev)
+    for vi, name in enumerate(RECALL_VARIANTS):
+        if not (mask >> vi) & 1:
+            continue
+        sg, gc = name.startswith("sgcls"), name.endswith("_gc")
+        if sg:
+            corr = (probs[a, gt_cls[a]] * probs[b, gt_cls[b]])[:, None] * rp          # fl(fl(s*o)*r), the correct entries
+            n_entries = c * c * r
+        else:
+            corr = rp
+            n_entries = r
+        corr = torch.where(hot, corr, neg)
+        if gc:                                                                       # one candidate: the edge's maximum
+            if sg:
+                smax = probs.max(1).values
+                cand = ((smax[a] * smax[b]) * rp.max(1).values)[:, None]
+            else:
+                cand = rp.max(1, keepdim=True).values
+        elif not sg:
+            cand = rp                                                                 # R < 100: every entry is a candidate
+        else:
+            ks = min(c, _NGC_CAP)
+            ss = probs.topk(ks, 1).values
+            rs = rp.sort(1, descending=True).values
+            tri = _tri_table(ks, r, dev)
+            cand = torch.empty(e, min(_NGC_CAP, n_entries), dtype=torch.float32, device=dev)
+            for e0 in range(0, e, chunk):
+                sl = slice(e0, min(e, e0 + chunk))
+                vals = (ss[a[sl]][:, tri[:, 0]] * ss[b[sl]][:, tri[:, 1]]) * rs[sl][:, tri[:, 2]]
+                cand[sl] = vals.topk(cand.shape[1], 1).values
+        cap = 1 if gc else _NGC_CAP
+        if cap < n_entries:                                                           # (1) #{entries of e > c} < topk_each
+            kth = cand[:, cap - 1:cap]
+            cond1 = corr >= kth
+        else:
+            cond1 = torch.ones_like(hot)
+        base = recallk_offset(name, r)
+        for s in range(n_scenes):
+            sel = scene == s
+            if not bool(sel.any()):
+                continue
+            cs = cand[sel].reshape(-1).sort().values                                  # ascending
+            cc = corr[sel]
+            above = cs.numel() - torch.searchsorted(cs, cc.contiguous(), right=True)  # #{candidates of the scene > c}
+            for q, k in enumerate(RECALL_K):
+                hit = (hot[sel] & cond1[sel] & (above < k)).any(1)                    # (2)
+                out[s, base + q] = hit.sum()
+                out[s, base + 3 + q * r: base + 3 + (q + 1) * r] = (hot[sel] & hit[:, None]).sum(0)
+    return out
+
+
+def _edges_list(edges):
+    return [(int(x[0]), int(x[1])) for x in (edges.tolist() if torch.is_tensor(edges) else np.asarray(edges).tolist())]
+
+
+def _recall_call(objs_pred, rels_pred, gt_rel, edges, multi_rel_outputs, topk, topk_each, use_clip, evaluate):
+    """The counts row of one reference-style call (one scene, get_gt's list of (sub, obj, [predicates]))."""
+    topk_list = list(topk) if isinstance(topk, (list, tuple)) else [topk]
+    if any(k not in RECALL_K for k in topk_list):
+        raise NotImplementedError(f"recallk: K must be among {RECALL_K}")
+    if evaluate not in ("triplet", "rels"):
+        raise NotImplementedError("evaluate type", evaluate)
+    if topk_each == 1:
+        gc = True
+    elif topk_each >= max(topk_list):                                  # the candidate cap never binds
+        gc = False
+    else:
+        raise NotImplementedError("recallk: topk_each must be 1 or at least max(topk)")
+    variant = ("sgcls" if evaluate == "triplet" else "predcls") + ("_gc" if gc else "_ngc")
+    objs_pred = torch.as_tensor(objs_pred)
+    dev = objs_pred.device
+    n, _ = objs_pred.shape
+    if multi_rel_outputs:
+        rel = torch.as_tensor(rels_pred).float()
+    elif dev.type == "cpu":
+        rel = torch.as_tensor(np.exp(np.asarray(rels_pred, dtype=np.float32)))  # the reference's np.exp
+    else:
+        rel = torch.as_tensor(rels_pred).float().exp()
+    e, r = rel.shape
+    el = _edges_list(edges)
+    gt_cls = torch.zeros(n, dtype=torch.int64)
+    hot = torch.zeros(e, r, dtype=torch.int64)
+    for i, (sub, obj, rels) in enumerate(gt_rel):
+        gt_cls[el[i][0]], gt_cls[el[i][1]] = int(sub), int(obj)
+        for k in rels:
+            hot[i, int(k)] = 1
+    probs = torch.softmax(objs_pred.float(), -1) if use_clip else objs_pred.float().exp()
+    ed = torch.tensor(el, dtype=torch.int64).view(-1, 2)
+    row = recallk_counts(objs_pred.float(), rel.to(dev), gt_cls.to(dev), hot.to(dev), ed.to(dev), None, 1, True,
+                         variants=(variant,), obj_probs=probs)[0].cpu().numpy()
+    return row, variant, topk_list, r
+
+
+def _row_recall(row, variant, r, topk_list):
+    base = recallk_offset(variant, r)
+    return [int(row[base + RECALL_K.index(k)]) for k in topk_list], int(row[0])
+
+
+def evaluate_triplet_recallk(objs_pred, rels_pred, gt_rel, edges, multi_rel_outputs, topk, topk_each, use_clip=False,
+                             evaluate='triplet'):
+    """Drop-in for the reference's ``evaluate_triplet_recallk`` (eval_utils_recall.py): same arguments (``gt_rel`` is
+    get_gt's list), same result -- numpy ``hits / #edges with a gt predicate`` per K (NaN when there is none)."""
+    row, variant, topk_list, r = _recall_call(objs_pred, rels_pred, gt_rel, edges, multi_rel_outputs, topk, topk_each, use_clip,
+                                              evaluate)
+    correct_number, all_number = _row_recall(row, variant, r, topk_list)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.array(correct_number) / all_number
+
+
+def evaluate_triplet_mrecallk(objs_pred, rels_pred, gt_rel, edges, multi_rel_outputs, topk, topk_each, use_clip=False,
+                              evaluate='triplet'):
+    """Drop-in for the reference's ``evaluate_triplet_mrecallk``: 26 rows of 3 per-predicate recalls (a hit edge counts for
+    every predicate of its gt set; -1 for a predicate no edge has), the reference's fixed 26 x 3 shape included."""
+    row, variant, topk_list, r = _recall_call(objs_pred, rels_pred, gt_rel, edges, multi_rel_outputs, topk, topk_each, use_clip,
+                                              evaluate)
+    base = recallk_offset(variant, r)
+    correct = np.zeros((26, len(topk_list)), dtype=np.int64)
+    all_pc = [0] * 26
+    for j in range(min(26, r)):
+        all_pc[j] = int(row[1 + j])
+        for i, k in enumerate(topk_list):
+            correct[j][i] = row[base + 3 + RECALL_K.index(k) * r + j]
+    return [[correct[j][i] / all_pc[j] if all_pc[j] != 0 else -1 for i in range(3)] for j in range(26)]
+
+
+def _process_val_recall(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids, use_triplet,
+                        mean: bool):
+    outs = _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids)
+    obj3, _, rel3, _ = outs
+    multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
+    r = rel3.shape[1]
+    gt_hot = multihot_targets(gt_rel_cls, r)
+    rk = eval_ranks(obj3, rel3, gt_cls, gt_hot, edge_indices, multi_rel_outputs=multi)
+    np64 = lambda t: t.cpu().numpy().astype(np.int64)
+    top_k_obj, top_k_rel = np64(rk["top_k_obj"]), np64(rk["top_k_rel"])
+    if not use_triplet:
+        z = np.array([0, 0, 0])
+        return top_k_obj, top_k_obj, top_k_rel, top_k_rel, z, z, z, z
+    # the whole call is ONE scene, as the reference's functions see it
+    row = recallk_counts(obj3, rel3, gt_cls, gt_hot, edge_indices, None, 1, multi, obj_probs=rk["obj_probs"])[0].cpu().numpy()
+    res = []
+    for v in RECALL_VARIANTS:
+        base = recallk_offset(v, r)
+        if mean:
+            res.append([[row[base + 3 + i * r + j] / row[1 + j] if j < r and row[1 + j] != 0 else -1 for i in range(3)]
+                        for j in range(26)])
+        else:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                res.append(np.array([int(row[base + q]) for q in range(3)]) / int(row[0]))
+    return (top_k_obj, top_k_obj, top_k_rel, top_k_rel, *res)
+
+
+@torch.no_grad()
+def process_val2(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids=None, with_log=False,
+                 use_triplet=False):
+    """``Mmgnet.process_val2`` (reference SGFN_MMG/model_in21k.py:439-468): 3D object / predicate ranks (each twice, as the
+    reference returns them) and the Recall@{20,50,100} of predcls_gc, predcls_ngc, sgcls_gc, sgcls_ngc on the 3D branch."""
+    return _process_val_recall(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids,
+                               use_triplet, mean=False)
+
+
+@torch.no_grad()
+def process_val3(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids=None, with_log=False,
+                 use_triplet=False):
+    """``Mmgnet.process_val3`` (model_in21k.py:470-500): as process_val2 with the per-predicate recalls of
+    evaluate_triplet_mrecallk (26 x 3, -1 for absent predicates) in place of the recalls."""
+    return _process_val_recall(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices, batch_ids,
+                               use_triplet, mean=True)

@@ -350,6 +350,35 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
                       const int64_t* gt_rel, const int64_t* edges, int32_t n_nodes, int32_t n_edges, int32_t n_rel_class,
                       int32_t n_scenes, uint64_t* counts, void* stream);
 
+/* Scene-graph Recall@K and mR@K: the counts behind evaluate_triplet_recallk / evaluate_triplet_mrecallk (reference
+ * src/utils/eval_utils_recall.py, called per scene by process_val2 / process_val3, SGFN_MMG/model_in21k.py:439-500) for
+ * the four variants PredCls GC / NGC (evaluate='rels', topk_each = 1 / 100) and SGCls GC / NGC (evaluate='triplet'),
+ * at K = 20, 50, 100, for every scene of a batch in one call (csrc/eval_recall.hip).
+ *   scores   SGCls conf(e,i,j,k) = fl(fl(s_i * o_j) * r_k) (no FMA), s / o = obj_probs[from] / obj_probs[to] (the softmax of
+ *            the logits: use_clip=True); PredCls conf(e,k) = r_k; r = rel_probs[e] -- pass exp(log-probabilities) when the
+ *            model has multi_rel_outputs = false.  gt_rel is the multi-hot [E, R] int64 target (get_gt's predicate set).
+ *   hit      edge e hits at K when some correct entry c (sub class gt_class[from], obj class gt_class[to], predicate in the
+ *            gt set; PredCls: the predicate only) is one of e's min(topk_each, #entries) largest entries and fewer than K
+ *            candidates of its scene are STRICTLY greater than c.  Ties at the K boundary therefore resolve optimistically
+ *            (the reference's order among equal scores is torch.topk's); whenever the boundary values differ the counts
+ *            are the reference's.
+ *   counts   int64 [n_scenes][F], F = 1 + R + 4 (3 + 3 R), every field written (no zeroing needed):
+ *            gt_edges (edges with >= 1 gt predicate), gt_per_class[R], then for predcls_gc, predcls_ngc, sgcls_gc,
+ *            sgcls_ngc in this order: hit@{20,50,100}, class_hit@20[R], class_hit@50[R], class_hit@100[R] (a hit edge adds
+ *            1 to every class of its gt set, as evaluate_triplet_mrecallk does).  Recall@K = hit@K / gt_edges.
+ *            Variants whose bit (1, 2, 4, 8 in that order) is clear in variants_mask are written as zeros and cost nothing.
+ * Preconditions: the scene of edge e is batch_ids[edges[e, 0]] in [0, n_scenes) (batch_ids may be NULL for one scene), and
+ * edges arrive grouped by scene in ascending scene order (collate_fn_mmg, evaluate.merge_batches); node and class indices
+ * are in range; no NaN.  n_obj_class <= 1024, n_rel_class <= 32.  scratch: vlsat_eval_recallk_scratch_bytes(...) bytes of
+ * device memory the call may overwrite (about 4 (N x min(C, 100) + E x (R + 104)) bytes: 50.5 MiB for the 64-scene,
+ * 99 840-edge batch, 19.8 MiB for one 39 800-edge scene).  All device pointers;
+ * asynchronous on `stream`: no host synchronisation, no runtime fill. */
+int vlsat_eval_recallk(const float* obj_probs, const float* rel_probs, const int64_t* gt_class, const int64_t* gt_rel,
+                       const int64_t* edges, const int64_t* batch_ids, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class,
+                       int32_t n_rel_class, int32_t n_scenes, int32_t variants_mask, void* scratch, int64_t* counts, void* stream);
+int64_t vlsat_eval_recallk_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                                         int32_t n_scenes);
+
 /* One scene (or batch) of an evaluation loop in ONE call: vlsat_forward + softmax of the object logits + vlsat_eval_ranks for both
  * branches + vlsat_eval_counts, enqueued back to back on `stream` with every intermediate in the plan's own scratch -- what
  * Mmgnet.process_val (reference src/model/SGFN_MMG/model.py:458-480) computes per scene, reduced to what MMGNet.validation keeps of
