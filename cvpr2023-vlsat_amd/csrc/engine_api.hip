@@ -325,6 +325,16 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
                               static_cast<hipStream_t>(stream));
 }
 
+int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank_2d, const int32_t* cnt, const int64_t* gt_class,
+                             const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int32_t n_edges, int32_t n_obj_class,
+                             int32_t n_rel_class, uint64_t* counts, void* stream) {
+    if (!counts || n_edges < 0) return fail(VLSAT_EINVAL, "eval_triplet_split: bad argument");
+    if (n_edges > 0 && (!tri_rank_3d || !tri_rank_2d || !cnt || !gt_class || !gt_rel || !edges || !table))
+        return fail(VLSAT_EINVAL, "eval_triplet_split: null edge argument");
+    return launch_eval_triplet_split(tri_rank_3d, tri_rank_2d, cnt, gt_class, gt_rel, edges, table, n_edges, n_obj_class, n_rel_class,
+                                     reinterpret_cast<unsigned long long*>(counts), static_cast<hipStream_t>(stream));
+}
+
 // One scene (or batch) of an evaluation loop in ONE call: forward + softmax of the object logits + both ranking passes + the
 // additive counts (vlsat_forward, vlsat_k_softmax_rows, vlsat_eval_ranks x 2, vlsat_eval_counts), all enqueued on `stream`,
 // intermediates in the plan's own scratch -- what Mmgnet.process_val (reference SGFN_MMG/model.py:458-480) computes per scene,
@@ -333,9 +343,10 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
 // the loader yields it, in the plan's edge order; counts: device uint64 [1 + R + 2 (11 + 6 R)], zeroed once by the caller.
 // Top-k bounds and threshold are process_val's constants (topk 11 / 6 / 101, 0.5: reference :463-472).
 // MODEL.multi_rel_outputs only (the single-label variant ranks exp(log-softmax) in a second pass: use the separate entry points).
-int vlsat_process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
-                             const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2, int32_t n_scenes,
-                             uint64_t* counts, void* stream) {
+// split_table / split_counts (vlsat_process_val_counts_split): the zero-shot split of the triplet ranks is counted as well.
+static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                              const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2, int32_t n_scenes,
+                              uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts, void* stream) {
     if (!h || !p || !gt_class || !counts) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: null argument");
     if (p->h != h) return fail(VLSAT_EINVAL, "plan belongs to a different handle");
     if (!h->d.multi_rel_outputs) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: built for MODEL.multi_rel_outputs (use vlsat_forward + vlsat_eval_ranks + vlsat_eval_counts)");
@@ -359,8 +370,28 @@ int vlsat_process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_poin
     }
     RUN(launch_eval_counts(or3, or2, rr3, rr2, tr3, tr2, cn3, gt_class, gt_rel, edges_e2, N, E, R, n_scenes,
                            reinterpret_cast<unsigned long long*>(counts), s));
+    if (split_counts)
+        RUN(launch_eval_triplet_split(tr3, tr2, cn3, gt_class, gt_rel, edges_e2, split_table, E, C, R,
+                                      reinterpret_cast<unsigned long long*>(split_counts), s));
     VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the counting)
     return 0;
+}
+
+int vlsat_process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                             const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2, int32_t n_scenes,
+                             uint64_t* counts, void* stream) {
+    return process_val_counts(h, p, obj_points, obj_2d_feats, descriptor, gt_class, gt_rel, edges_e2, n_scenes, counts, nullptr, nullptr,
+                              stream);
+}
+
+// vlsat_process_val_counts + the zero-shot split of the triplet ranks (vlsat_eval_triplet_split) on the plan-scratch rank tables:
+// a one-scene-per-call loop with the split on stays one library call per scene.  split_table: uint8 [C*C*R] of the model's classes.
+int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                                   const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2, int32_t n_scenes,
+                                   uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts, void* stream) {
+    if (!split_table || !split_counts) return fail(VLSAT_EINVAL, "vlsat_process_val_counts_split: null split table or counts");
+    return process_val_counts(h, p, obj_points, obj_2d_feats, descriptor, gt_class, gt_rel, edges_e2, n_scenes, counts, split_table,
+                              split_counts, stream);
 }
 
 int vlsat_scene_checksums(const float* obj3d, const float* obj2d, int64_t n_nodes, int32_t n_obj_class, const float* rel3d,

@@ -410,6 +410,78 @@ int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const
     return 0;
 }
 
+// ---- zero-shot split of the triplet recall (get_zero_shot_recall, reference eva_utils_acc.py:267-333; model.py:253) ----
+// A cls_matrix row with a predicate (the -1 "no relation" rows are skipped) is zero-shot when its (subject class, object class,
+// predicate) key is set in `table` (uint8 [C*C*R], flat index (s*C + o)*R + p: keys of the validation annotations that never occur
+// in the training annotations, built on the host once per run).  out[12] += per branch (3D, then 2D): all_n, all_hit@{50,100},
+// zs_n, zs_hit@{50,100}; non-zero-shot = all - zs.  Same slot walk as eval_counts_kernel: slot j of edge t is its j-th gt predicate
+// in ascending class order and holds tri_rank[t, j].  A row whose classes fall outside [0, C) is non-zero-shot (the table is not read).
+// One thread per edge.  The gt_rel rows of a block's 256 edges are one contiguous piece: read with coalesced, independent loads into
+// a per-edge predicate bit mask in LDS (a thread walking its own 208-byte row stalls on every load: 21 us per 1 560-edge scene);
+// every later read of a thread (node classes, table bytes, rank slots) then has a known address.  Per-thread counts are packed two
+// to a word (16 bits each: <= 64 lanes x 32 slots), summed across the wave with shuffles, one LDS atomic per counter and wave, one
+// 64-bit global atomic per counter and block: exact and order-independent.
+__global__ __launch_bounds__(256) void eval_triplet_split_kernel(const int32_t* __restrict__ tri_rank3, const int32_t* __restrict__ tri_rank2,
+                                                                 const int32_t* __restrict__ cnt, const int64_t* __restrict__ gt_cls,
+                                                                 const int64_t* __restrict__ gt_rel, const int64_t* __restrict__ edges,
+                                                                 const uint8_t* __restrict__ table, int E, int C, int R,
+                                                                 unsigned long long* __restrict__ out) {
+    __shared__ unsigned s_h[12];
+    __shared__ unsigned s_gt[256];                       // bit q of s_gt[i]: gt_rel[e0 + i, q] == 1
+    const int e0 = blockIdx.x * 256, ne = min(256, E - e0);
+    if (threadIdx.x < 12) s_h[threadIdx.x] = 0;
+    s_gt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t* g = gt_rel + (size_t)e0 * R;
+    const int nel = ne * R;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < nel; i += 256)
+        if (g[i] == 1) atomicOr(s_gt + i / R, 1u << (i % R));
+    __syncthreads();
+    const int t = e0 + threadIdx.x;
+    unsigned p[6] = {0, 0, 0, 0, 0, 0};                  // counter i in bits 16 (i & 1) .. of p[i >> 1]
+    auto add = [&](int i, bool c) { p[i >> 1] += (unsigned)c << (16 * (i & 1)); };
+    if (t < E) {
+        const int a = (int)edges[2 * (size_t)t], b = (int)edges[2 * (size_t)t + 1];
+        const int64_t sc = gt_cls[a], oc = gt_cls[b];
+        const bool in = sc >= 0 && sc < C && oc >= 0 && oc < C;
+        const uint8_t* row = table + (in ? ((size_t)sc * C + (size_t)oc) * R : 0);
+        const int n = cnt[t];
+        unsigned m = s_gt[threadIdx.x];
+        for (int j = 0; m && j < n; ++j, m &= m - 1) {   // slot j: the j-th set column, ascending
+            const int q = __ffs(m) - 1;
+            const bool zs = in && row[q] != 0;
+            const int r3 = tri_rank3[(size_t)t * R + j], r2 = tri_rank2[(size_t)t * R + j];
+            add(0, true); add(1, r3 <= 50); add(2, r3 <= 100); add(3, zs); add(4, zs && r3 <= 50); add(5, zs && r3 <= 100);
+            add(6, true); add(7, r2 <= 50); add(8, r2 <= 100); add(9, zs); add(10, zs && r2 <= 50); add(11, zs && r2 <= 100);
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < 6; ++w)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) p[w] += __shfl_xor(p[w], o);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            const unsigned v = (p[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+            if (v) atomicAdd(s_h + i, v);
+        }
+    __syncthreads();
+    if (threadIdx.x < 12 && s_h[threadIdx.x]) atomicAdd(out + threadIdx.x, (unsigned long long)s_h[threadIdx.x]);
+}
+
+int launch_eval_triplet_split(const int32_t* tri_rank3, const int32_t* tri_rank2, const int32_t* cnt, const int64_t* gt_cls,
+                              const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int E, int C, int R,
+                              unsigned long long* out, hipStream_t s) {
+    if (R <= 0 || R > CNT_MAX_R) return fail(-1, "eval_triplet_split: at most 32 relation classes");
+    if (C <= 0) return fail(-1, "eval_triplet_split: the object class count must be positive");
+    if (E <= 0) return 0;
+    hipLaunchKernelGGL(eval_triplet_split_kernel, dim3((E + 255) / 256), dim3(256), 0, s, tri_rank3, tri_rank2, cnt, gt_cls, gt_rel, edges,
+                       table, E, C, R, out);
+    VLSAT_LAUNCH_CHECK("eval_triplet_split");
+    return 0;
+}
+
 int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s) {
     if (N <= 0) return 0;
     hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, probs, N, C, K, sorted);

@@ -226,6 +226,11 @@ int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const
                        const int32_t* tri_rank3, const int32_t* tri_rank2, const int32_t* cnt, const int64_t* gt_cls,
                        const int64_t* gt_rel, const int64_t* edges, int N, int E, int R, int n_scenes, unsigned long long* out,
                        hipStream_t s);
+// zero-shot split of the triplet recall: out[12] += per branch (3D, 2D) all_n, all_hit@{50,100}, zs_n, zs_hit@{50,100} over the
+// rows with a predicate; table uint8 [C*C*R] (1 = zero-shot key (s*C + o)*R + p); R <= 32; integer atomics only
+int launch_eval_triplet_split(const int32_t* tri_rank3, const int32_t* tri_rank2, const int32_t* cnt, const int64_t* gt_cls,
+                              const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int E, int C, int R,
+                              unsigned long long* out, hipStream_t s);
 
 // the additive metrics vector {scenes, N, E, four fp64 output sums, two top-1 agreement counts}; scratch: 256 * 6 doubles
 int launch_scene_checksums(const float* obj3d, const float* obj2d, long N, int C, const float* rel3d, const float* rel2d, long E, int R,

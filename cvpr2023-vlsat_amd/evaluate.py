@@ -164,6 +164,41 @@ def recall_summarize(vec: np.ndarray, n_rel: int = N_REL) -> Dict[str, float]:
     return out
 
 
+# ---- zero-shot split of the triplet recall (validation(zero_shot=table)): a third additive vector, concatenated like the others ----
+def split_fields():
+    """Layout of the zero-shot split vector (additive over scenes and ranks; vlsat_eval_triplet_split's counts): per branch
+    (3D, 2D) the triplet rows with a predicate (zs_all_n), their hits at 50 / 100, then the same over the zero-shot rows.
+    Non-zero-shot = all - zero-shot."""
+    f = []
+    for br in ("3d", "2d"):
+        f += [f"zs_all_n_{br}", f"zs_all_hit@50_{br}", f"zs_all_hit@100_{br}", f"zs_n_{br}", f"zs_hit@50_{br}", f"zs_hit@100_{br}"]
+    return f
+
+
+def accumulate_split(vec: np.ndarray, top_k_triplet, top_k_triplet_2d, cls_matrix, table, n_rel: int = N_REL):
+    """Add one batch's zero-shot split counts (the split_fields() vector) from process_val's triplet ranks of both branches
+    (``out[4]``, ``out[5]``) and its ``cls_matrix`` (``out[6]``), in place; ``table`` from zeroshot.zero_shot_table."""
+    from .zeroshot import split_counts_host
+    vec[0:6] += split_counts_host(top_k_triplet, cls_matrix, table, n_rel)
+    vec[6:12] += split_counts_host(top_k_triplet_2d, cls_matrix, table, n_rel)
+    return vec
+
+
+def split_summarize(vec: np.ndarray) -> Dict[str, float]:
+    """``zero_shot_recall@K_{br}``, ``non_zero_shot_recall@K_{br}`` and ``all_zero_shot_recall@K_{br}`` (K = 50, 100) from the
+    (all-reduced) split_fields() vector: what get_zero_shot_recall returns (reference eva_utils_acc.py:267-333; NaN for an empty
+    group).  The reference reports the 3D branch; the 2D values, the same definition on the 2D triplet ranks, are an extension."""
+    from .zeroshot import recall_from_counts
+    out = {}
+    for b, br in enumerate(("3d", "2d")):
+        an, a50, a100, zn, z50, z100 = (int(x) for x in vec[6 * b:6 * b + 6])
+        for k, ah, zh in ((50, a50, z50), (100, a100, z100)):
+            out[f"zero_shot_recall@{k}_{br}"] = recall_from_counts(zn, zh)
+            out[f"non_zero_shot_recall@{k}_{br}"] = recall_from_counts(an - zn, ah - zh)
+            out[f"all_zero_shot_recall@{k}_{br}"] = recall_from_counts(an, ah)
+    return out
+
+
 _warned_sync = False
 
 
@@ -213,7 +248,8 @@ def merge_batches(bs) -> dict:
 
 
 @torch.no_grad()
-def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False):
+def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False,
+                          zero_shot=None):
     """The counts vector of this rank's batches with NO host round trip per batch and ``workers`` batches in flight:
     every worker thread owns a replica of the model (its own library handle: a handle is driven by one host thread and one
     stream at a time) and a stream; forward, ranking and counting of a batch are enqueued back to back
@@ -223,13 +259,16 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     them.  The host side scales too: the library call that enqueues a forward releases the GIL (ctypes).
     ``merge`` > 1: every worker takes that many consecutive batches at a time and collates them on the device into one call
     (``merge_batches``): the forward then runs at its batched rate.  Counts are additive, so the summary is the same up to
-    near-ties (a batched forward differs from a one-scene forward in the last bits: a rank may move by one)."""
+    near-ties (a batched forward differs from a one-scene forward in the last bits: a rank may move by one).
+    Returns the counts vector; with ``recall_k`` or ``zero_shot`` (the device uint8 table) the tuple (counts, recall vector or
+    None, split vector or None)."""
     import threading
     from . import metrics as M
     dev = torch.device(device)
     models = [model] + model.replicas(workers - 1)        # (kept by the model: building one uploads and prepares every weight)
     counts = [torch.zeros(len(fields()), dtype=torch.int64, device=dev) for _ in range(workers)]
     recall = [torch.zeros(len(recall_fields()), dtype=torch.float64, device=dev) if recall_k else None for _ in range(workers)]
+    split = [torch.zeros(len(split_fields()), dtype=torch.int64, device=dev) if zero_shot is not None else None for _ in range(workers)]
     it, lock, errors = iter(batches), threading.Lock(), []
 
     def work(k):
@@ -245,7 +284,7 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
                     b = merge_batches(group)
                     M.process_val_counts(models[k], counts[k], b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"],
                                          b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"),
-                                         recall=recall[k])
+                                         recall=recall[k], split_table=zero_shot, split_counts=split[k])
             stream.synchronize()
         except BaseException as ex:             # (re-raised in the caller's thread)
             errors.append(ex)
@@ -263,14 +302,15 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     if errors:
         raise errors[0]
     vec = torch.stack(counts).sum(0).cpu().numpy().astype(np.float64)
-    if recall_k:
-        return vec, torch.stack(recall).sum(0).cpu().numpy()
+    if recall_k or zero_shot is not None:
+        return (vec, torch.stack(recall).sum(0).cpu().numpy() if recall_k else None,
+                torch.stack(split).sum(0).cpu().numpy().astype(np.float64) if zero_shot is not None else None)
     return vec
 
 
 @torch.no_grad()
 def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1,
-               recall_k: bool = False) -> Dict[str, float]:
+               recall_k: bool = False, zero_shot=None) -> Dict[str, float]:
     """``batches`` yields this rank's dicts with the reference loader's item names
     (obj_points [N,3,P], obj_2d_feats, gt_class, gt_rel_cls, edge_indices [E,2], descriptor, batch_ids; optionally
     ``fc_sizes``: objects per scene when edge_indices is the canonical fully-connected list, which spares the graph plan a
@@ -281,18 +321,31 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
     ``merge`` = B > 1 additionally collates B consecutive batches into one call (``merge_batches``).
     recall_k = True: the result also holds the scene-graph Recall@K / mR@K of both branches (recall_summarize: PredCls /
     SGCls, with and without graph constraint, K = 20, 50, 100), from a recall_fields() vector concatenated onto the counts
-    so that the run still does one all-reduce."""
+    so that the run still does one all-reduce.
+    zero_shot = the uint8 [C*C*R] table of zeroshot.zero_shot_table (built once per run from the training and validation
+    annotations): the result also holds the zero-shot split of the triplet recall (split_summarize: zero_shot_recall@K,
+    non_zero_shot_recall@K, all_zero_shot_recall@K, K = 50, 100) of both branches -- get_zero_shot_recall, reference
+    src/model/model.py:253; the reference reports the 3D branch, the ``_2d`` values are an extension -- from a split_fields()
+    vector concatenated onto the others, still one all-reduce.  None: the result and the work are unchanged."""
     from . import metrics as M
+    if zero_shot is not None:
+        if workers > 0:
+            zero_shot = torch.as_tensor(zero_shot, dtype=torch.uint8).to(device).contiguous()
+        else:                                   # (host accumulation: read the table once, not per batch)
+            zero_shot = zero_shot.cpu().numpy() if isinstance(zero_shot, torch.Tensor) else np.asarray(zero_shot)
+        n_rel = int(getattr(getattr(model, "config", None), "num_rel_class", N_REL))
     if workers > 0:
         if device is None:
             raise ValueError("validation(workers > 0) needs the device")
-        vec = _validation_pipelined(model, batches, device, int(workers), int(merge), bool(recall_k))
-        if recall_k:
-            return _summaries(vdist.allreduce_metrics(torch.from_numpy(np.concatenate(vec)).to(device)).cpu().numpy())
+        vec = _validation_pipelined(model, batches, device, int(workers), int(merge), bool(recall_k), zero_shot)
+        if recall_k or zero_shot is not None:
+            vec = np.concatenate([v for v in vec if v is not None])
+            return _summaries(vdist.allreduce_metrics(torch.from_numpy(vec).to(device)).cpu().numpy(), recall_k, zero_shot is not None)
         t = vdist.allreduce_metrics(torch.from_numpy(vec).to(device))
         return summarize(t.cpu().numpy())
     vec = np.zeros(len(fields()), dtype=np.float64)
     rvec = np.zeros(len(recall_fields()), dtype=np.float64) if recall_k else None
+    svec = np.zeros(len(split_fields()), dtype=np.float64) if zero_shot is not None else None
     for b in batches:
         # process_val, with the forward's outputs kept for the recall counts
         outs = M._forward_eval(model, b["obj_points"], b["obj_2d_feats"], b["descriptor"], b["edge_indices"], b["batch_ids"])
@@ -307,17 +360,24 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
             c3, c2 = (M.recallk_counts(o, rl, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], bid, n_scenes, multi)
                       for o, rl in ((outs[0], outs[2]), (outs[1], outs[3])))
             rvec += recall_vector(c3, c2, outs[2].shape[1]).cpu().numpy()
-    t = torch.from_numpy(vec if rvec is None else np.concatenate([vec, rvec]))
+        if svec is not None:
+            accumulate_split(svec, out[4], out[5], out[6], zero_shot, n_rel)
+    t = torch.from_numpy(np.concatenate([v for v in (vec, rvec, svec) if v is not None]))
     if device is not None:
         t = t.to(device)
     t = vdist.allreduce_metrics(t)
-    if recall_k:
-        return _summaries(t.cpu().numpy())
+    if recall_k or svec is not None:
+        return _summaries(t.cpu().numpy(), recall_k, svec is not None)
     return summarize(t.cpu().numpy())
 
 
-def _summaries(v: np.ndarray) -> Dict[str, float]:
+def _summaries(v: np.ndarray, recall_k: bool = True, split: bool = False) -> Dict[str, float]:
     n = len(fields())
     out = summarize(v[:n])
-    out.update(recall_summarize(v[n:]))
+    if recall_k:
+        m = n + len(recall_fields())
+        out.update(recall_summarize(v[n:m]))
+        n = m
+    if split:
+        out.update(split_summarize(v[n:n + len(split_fields())]))
     return out

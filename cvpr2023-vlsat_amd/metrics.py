@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .zeroshot import get_zero_shot_recall, table_shape, zero_shot_table  # noqa: F401  (get_zero_shot_recall: drop-in of eva_utils_acc's)
 
 TOPK_OBJ, TOPK_REL, TOPK_TRIPLET, THRESHOLD = 11, 6, 101, 0.5     # process_val's constants (:463-472)
 
@@ -122,20 +123,46 @@ def eval_counts(counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str,
     return counts
 
 
+def eval_triplet_split(split_counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str, torch.Tensor], gt_class: torch.Tensor,
+                       gt_rel: torch.Tensor, edges: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """split_counts (device int64 [12], zeroed once by the caller) += the zero-shot split of one batch's triplet ranks, from the
+    rank tables of its 3D (``t3``) and 2D (``t2``) outputs (``rank_tables``) and the uint8 [C*C*R] table of
+    ``zeroshot.zero_shot_table``: ``vlsat_eval_triplet_split`` (layout: ``evaluate.split_fields``).  No synchronisation."""
+    lib = L.load()
+    e, r = t3["tri_rank"].shape
+    c = table_shape(table, r)
+    if split_counts.dtype != torch.int64 or split_counts.numel() != 12 or not split_counts.is_contiguous():
+        raise L.VlsatError("eval_triplet_split: split_counts must be a contiguous int64 vector of 12 entries")
+    if (table.dtype != torch.uint8 or not table.is_contiguous() or not split_counts.is_cuda or table.device != split_counts.device
+            or t3["tri_rank"].device != split_counts.device):
+        raise L.VlsatError("eval_triplet_split: the table must be a contiguous uint8 tensor on the device of the counts and ranks")
+    L.check(lib.vlsat_eval_triplet_split(t3["tri_rank"].data_ptr(), t2["tri_rank"].data_ptr(), t3["cnt"].data_ptr(), gt_class.data_ptr(),
+                                         gt_rel.data_ptr(), edges.data_ptr(), table.data_ptr(), e, c, r, split_counts.data_ptr(),
+                                         L.stream_ptr()))
+    return split_counts
+
+
 @torch.no_grad()
 def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls, edge_indices,
-                       batch_ids=None, n_scenes: int = 1, fc_sizes=None, recall: torch.Tensor | None = None):
+                       batch_ids=None, n_scenes: int = 1, fc_sizes=None, recall: torch.Tensor | None = None,
+                       split_table: torch.Tensor | None = None, split_counts: torch.Tensor | None = None):
     """``process_val`` for an evaluation LOOP: forward + both ranking passes + the counts, all enqueued on the current stream,
     nothing read back (``Mmgnet.process_val`` returns numpy rank lists, i.e. four host round trips per scene, reference
     SGFN_MMG/model.py:463-480; ``validation()`` only ever turns them into the counts accumulated here).
     ``edge_indices`` is [E,2] as the data loader yields it, on the device.  ``recall``: a device fp64 vector of
-    ``evaluate.recall_fields()`` that additionally accumulates the Recall@K / mR@K of both branches (``recallk_counts``)."""
+    ``evaluate.recall_fields()`` that additionally accumulates the Recall@K / mR@K of both branches (``recallk_counts``).
+    ``split_table`` / ``split_counts``: the device uint8 zero-shot table (``zeroshot.zero_shot_table``) and the device int64 [12]
+    vector of ``evaluate.split_fields()`` that additionally accumulates the zero-shot split of the triplet ranks."""
+    if (split_table is None) != (split_counts is None):
+        raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
     edges = edge_indices.to(torch.int64).contiguous()
     if multi and recall is None and hasattr(model, "process_val_counts"):           # one library call: forward + ranking + counts in the plan's scratch
         r = model.config.num_rel_class
+        split = {} if split_table is None else {"split_table": split_table, "split_counts": split_counts}
         if model.process_val_counts(counts, obj_points, obj_2d_feats, gt_cls.to(torch.int64).contiguous().view(-1), descriptor,
-                                    multihot_targets(gt_rel_cls, r).to(torch.int64).contiguous(), edges, batch_ids, n_scenes, fc_sizes):
+                                    multihot_targets(gt_rel_cls, r).to(torch.int64).contiguous(), edges, batch_ids, n_scenes, fc_sizes,
+                                    **split):
             return counts
     # with the fully-connected hint the plan never reads the edge list: the [2,E] view is enough (no transpose kernel)
     ei_t = edges.t() if fc_sizes is not None else edges.t().contiguous()
@@ -150,6 +177,8 @@ def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt
         c3 = recallk_counts(obj3, rel3, gt_cls, gt_rel, edges, bid, n_scenes, multi)
         c2 = recallk_counts(obj2, rel2, gt_cls, gt_rel, edges, bid, n_scenes, multi)
         recall += EV.recall_vector(c3, c2, rel3.shape[1])
+    if split_table is not None:
+        eval_triplet_split(split_counts, t3, t2, gt_cls, gt_rel, edges, split_table)
     return eval_counts(counts, t3, t2, gt_cls, gt_rel, edges, n_scenes)
 
 

@@ -483,20 +483,37 @@ class VLSATModel:
 
     @torch.no_grad()
     def process_val_counts(self, counts, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_multihot, edges_e2, batch_ids=None,
-                           n_scenes: int = 1, fc_sizes: Optional[Sequence[int]] = None) -> bool:
+                           n_scenes: int = 1, fc_sizes: Optional[Sequence[int]] = None, split_table=None, split_counts=None) -> bool:
         """``vlsat_process_val_counts``: forward + ranking of both branches + the additive counts of ``evaluate.fields()`` for one
         batch in ONE library call, intermediates in the plan's scratch (nothing allocated, nothing read back).  ``edges_e2`` is the
         loader's int64 [E,2] list, ``gt_rel_multihot`` int64 [E,R], ``gt_cls`` int64 [N], ``counts`` the device int64 vector.
+        ``split_table`` (device uint8 [C*C*R], zeroshot.zero_shot_table) with ``split_counts`` (device int64 [12]): the same call
+        also counts the zero-shot split of the triplet ranks (``vlsat_process_val_counts_split``; layout: evaluate.split_fields).
         Returns False (nothing enqueued) when the plan had to permute the edges -- the caller then takes the separate calls."""
+        if (split_table is None) != (split_counts is None):
+            raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
+        if split_table is not None:
+            c, r = self.config.num_obj_class, self.config.num_rel_class
+            if (split_table.dtype != torch.uint8 or split_table.numel() != c * c * r or not split_table.is_contiguous()
+                    or split_counts.dtype != torch.int64 or split_counts.numel() != 12 or not split_counts.is_contiguous()
+                    or split_table.device != counts.device or split_counts.device != counts.device):
+                raise L.VlsatError(f"process_val_counts: split_table must be contiguous uint8 [{c}*{c}*{r}], split_counts int64 [12], "
+                                   "both on the counts' device")
         ei = edges_e2.t() if fc_sizes is not None else edges_e2.t().contiguous()
         pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, ei, descriptor)
         with torch.cuda.device(self.device):
             plan = self._plan(ei, batch_ids, n, p, fc_sizes)
             if plan.perm is not None:
                 return False
-            L.check(self._lib.vlsat_process_val_counts(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
-                                                       gt_cls.data_ptr(), gt_rel_multihot.data_ptr(), edges_e2.data_ptr(), int(n_scenes),
-                                                       counts.data_ptr(), L.stream_ptr()))
+            if split_table is None:
+                L.check(self._lib.vlsat_process_val_counts(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+                                                           gt_cls.data_ptr(), gt_rel_multihot.data_ptr(), edges_e2.data_ptr(),
+                                                           int(n_scenes), counts.data_ptr(), L.stream_ptr()))
+            else:
+                L.check(self._lib.vlsat_process_val_counts_split(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+                                                                 gt_cls.data_ptr(), gt_rel_multihot.data_ptr(), edges_e2.data_ptr(),
+                                                                 int(n_scenes), counts.data_ptr(), split_table.data_ptr(),
+                                                                 split_counts.data_ptr(), L.stream_ptr()))
         return True
 
     @torch.no_grad()

@@ -350,6 +350,24 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
                       const int64_t* gt_rel, const int64_t* edges, int32_t n_nodes, int32_t n_edges, int32_t n_rel_class,
                       int32_t n_scenes, uint64_t* counts, void* stream);
 
+/* Zero-shot split of the triplet recall: the counts behind get_zero_shot_recall (reference src/utils/eva_utils_acc.py:267-333,
+ * called by MMGNet.validation at src/model/model.py:253), for both branches.
+ *   rows     the cls_matrix rows that carry a predicate (the -1 "no relation" rows are not counted, unlike vlsat_eval_counts'
+ *            tri_n): slot j of edge e is its j-th gt predicate in ascending class order (gt_rel[e, p] == 1), with key
+ *            (gt_class[edges[e, 0]], gt_class[edges[e, 1]], p) and ranks tri_rank_{3d,2d}[e * n_rel_class + j] -- the layout
+ *            vlsat_eval_ranks writes (cnt as it writes it).
+ *   table    uint8 [n_obj_class * n_obj_class * n_rel_class]; table[(s * n_obj_class + o) * n_rel_class + p] = 1 marks a
+ *            zero-shot key: one that occurs in the validation annotations and never in the training annotations
+ *            (cvpr2023-vlsat_amd/zeroshot.py zero_shot_table; 665 600 bytes for 160 x 160 x 26).  A row whose subject or
+ *            object class lies outside [0, n_obj_class) is non-zero-shot; the table is then not read.
+ *   counts   uint64 [12], counts[i] += ...: for the 3D and then the 2D ranks, all_n, all_hit@50, all_hit@100, zs_n, zs_hit@50,
+ *            zs_hit@100 (hit@K: rank <= K).  Non-zero-shot = all - zs.  Recall = hit / n * 100; an empty group is NaN.
+ * n_rel_class <= 32 (as vlsat_eval_counts).  Zeroed by the caller before the first scene; integer atomics only, so scenes may be
+ * accumulated from several streams.  All device pointers; asynchronous: no host synchronisation, no runtime fill. */
+int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank_2d, const int32_t* cnt, const int64_t* gt_class,
+                             const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int32_t n_edges, int32_t n_obj_class,
+                             int32_t n_rel_class, uint64_t* counts, void* stream);
+
 /* Scene-graph Recall@K and mR@K: the counts behind evaluate_triplet_recallk / evaluate_triplet_mrecallk (reference
  * src/utils/eval_utils_recall.py, called per scene by process_val2 / process_val3, SGFN_MMG/model_in21k.py:439-500) for
  * the four variants PredCls GC / NGC (evaluate='rels', topk_each = 1 / 100) and SGCls GC / NGC (evaluate='triplet'),
@@ -388,6 +406,15 @@ int64_t vlsat_eval_recallk_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32
 int vlsat_process_val_counts(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                              const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
                              int32_t n_scenes, uint64_t* counts, void* stream);
+
+/* vlsat_process_val_counts, then vlsat_eval_triplet_split on the triplet ranks it left in the plan's scratch: split_table is the
+ * uint8 [C * C * R] zero-shot table of the model's n_obj_class C and n_rel_class R (layout: vlsat_eval_triplet_split),
+ * split_counts the device uint64 [12] it accumulates into.  A one-scene-per-call loop with the zero-shot split on stays one
+ * library call per scene.  counts and every other argument as for vlsat_process_val_counts. */
+int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
+                                   const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
+                                   int32_t n_scenes, uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts,
+                                   void* stream);
 
 /* The additive fp64 metrics vector of one rank's batch -- what the path's one all-reduce carries when no labels are at hand
  * (bench.py; the label-based counts of validation(), reference src/model/model.py:214-242, come from vlsat_eval_ranks):
