@@ -562,8 +562,8 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmArgs p, int n_tiles
 }  // namespace
 
 // full rounds of a large-M launch on 256 x 256 tiles: half-row bf16 operands (prec 1), exact fp32 (prec 0) or split-bf16
-// on split-pair operands (prec 3); 1 = operand combination not built (the caller falls back to the older kernels)
-int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
+// on split-pair operands (prec 3); 1 = operand combination not built (the caller falls back to the older kernels); dry: decide only
+int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s, bool dry) {
     const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
     const bool f32 = a.prec == 0, x3 = a.prec == 3;
     if (a.rowscale || a.act == ACT_SIGMOID || (add != 0 && add != 1 && add != 6)) return 1;
@@ -582,8 +582,9 @@ int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
     if (a.N % P8_BN || a.K % (2 * kt) || a.K < 4 * kt || n_tiles > (long)((a.M + P8_BM - 1) / P8_BM) * (a.N / P8_BN)) return 1;
     const int nbn = a.N / P8_BN;
     if (grid % 8 || (grid / 8) % nbn) return 1;      // the kernel keeps one column tile per block (bias registers)
-#define VLSAT_P8(MODE, ADD, RELU, CF) hipLaunchKernelGGL((gemm_p8_kernel<MODE, ADD, RELU, CF>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn)
-#define VLSAT_P8_ABL(X) hipLaunchKernelGGL((gemm_p8_kernel<0, 0, false, 2, X>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn)
+#define VLSAT_P8_K(...) do { if (!dry) hipLaunchKernelGGL((gemm_p8_kernel<__VA_ARGS__>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn); } while (0)
+#define VLSAT_P8(MODE, ADD, RELU, CF) VLSAT_P8_K(MODE, ADD, RELU, CF)
+#define VLSAT_P8_ABL(X) VLSAT_P8_K(0, 0, false, 2, X)
     const bool c16 = a.c_f16_cols > 0;            // (the whole output as fp16 half rows: half-row launches only)
     if (c16 && (a.c_f16_cols != a.N || f32 || x3 || a.c_split)) return 1;
     if (a.half_f16 && (f32 || x3 || a.c_split)) return 1;         // (fp16 operands: half-row launches; their half-row outputs come as c_f16_cols == N)
@@ -611,8 +612,8 @@ int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
 #ifdef VLSAT_EXPERIMENTS
     } else if (a.ablate && key == 27) {               // timing experiments on the gathered-row launch
         switch (a.ablate) {
-            case 1: hipLaunchKernelGGL((gemm_p8_kernel<0, 6, true, 2, 256>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn); break;
-            default: hipLaunchKernelGGL((gemm_p8_kernel<0, 6, true, 2, 512>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn); break;
+            case 1: VLSAT_P8_K(0, 6, true, 2, 256); break;
+            default: VLSAT_P8_K(0, 6, true, 2, 512); break;
         }
     } else if (a.ablate && key == 1) {                // timing experiments (tools/p8_check.py --ablate)
         switch (a.ablate) {
@@ -655,6 +656,8 @@ int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
     }
 #undef VLSAT_P8_ABL
 #undef VLSAT_P8
+#undef VLSAT_P8_K
+    if (dry) return 0;
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_p8");
     return 0;

@@ -320,13 +320,13 @@ static void ring_launch(bool wide, const GemmArgs& a, int n_tiles, int nbn, int 
 }
 
 // full rounds of a large-M bf16 launch; returns 1 if this operand combination is not built (the caller then uses the
-// 128 x 128 kernel for everything)
-int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s) {
+// 128 x 128 kernel for everything); dry: decide only
+int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s, bool dry) {
     const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
     if (a.rowscale || (add != 0 && add != 1 && add != 6)) return 1;
     const bool wide = rbn == 256;
     const int nbn = (a.N + rbn - 1) / rbn;
-#define VLSAT_RING(T, S, ADD) ring_launch<T, S, ADD>(wide, a, n_tiles, nbn, grid, s)
+#define VLSAT_RING(T, S, ADD) do { if (!dry) ring_launch<T, S, ADD>(wide, a, n_tiles, nbn, grid, s); } while (0)
 #define VLSAT_RING_ADD(T, S)                      \
     switch (add) {                                \
         case 0: VLSAT_RING(T, S, 0); break;       \
@@ -341,6 +341,7 @@ int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStrea
     }
 #undef VLSAT_RING_ADD
 #undef VLSAT_RING
+    if (dry) return 0;
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_bf16_ring");
     return 0;

@@ -176,23 +176,22 @@ static int slots() {
     return cache[dev];
 }
 
-template <int BM, int BN, int KSL = 1>
-static int launch_t(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
+// persistent kernel on BM x BN tiles; TWIN: problems a and b in one launch (grid.y = 2; launch_gemm_pair) -- 1 = not pairable,
+// for everything a single launch would refuse and for the combinations that have no TWIN variant
+template <int BM, int BN, int KSL = 1, bool TWIN = false>
+static int launch_t(const GemmArgs& a, const GemmArgs& b, int n_tiles, int grid, hipStream_t s) {
     const int nbn = (a.N + BN - 1) / BN;
     const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
+    auto refuse = [](const char* why) { return TWIN ? 1 : fail(-1, why); };
+    if (a.prec == 0 && (a.a_split || a.r_split || a.c_split || a.c_scale != 1.f))
+        return refuse("gemm: operand formats and c_scale exist in the bf16 modes only");      // (the fp32 kernels fold them away)
+    const char* why = nullptr;
+    const int prec = gemm_pipe_prec(a, a.relu_a || b.relu_a, true, &why);
+    if (prec < 0) return refuse(why);
 #define VLSAT_GEMM_CASE(ADD, PREC) \
-    case (PREC) * 8 + (ADD): hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, ADD, PREC, KSL>), dim3(grid), dim3(256), 0, s, a, a, n_tiles, nbn); break;
-    // exact fp32 launches without ReLU-on-A take the LDS-direct staging pipe (internal precision code 4) when
-    // the operands are addressable with 32-bit byte offsets and the additive mode is one the forward uses
-    int prec = a.prec;
-    const bool dma_ok = !a.no_dma && (add == 0 || add == 1 || add == 6) &&
-                        ((size_t)a.M + 256) * a.lda * 4 < (1ull << 32) && ((size_t)a.N + 256) * a.ldw * 4 < (1ull << 32);
-    if (prec == 0 && (a.a_split || a.r_split || a.c_split || a.c_scale != 1.f))
-        return fail(-1, "gemm: operand formats and c_scale exist in the bf16 modes only");      // (the fp32 kernels fold them away)
-    if (prec == 0 && dma_ok && !a.relu_a) prec = 4;
-    if (a.a_split == 2 && !(prec == 1 && dma_ok)) return fail(-1, "gemm: half-row A needs the single-rounding bf16 precision and the LDS-direct pipe");
-    if ((prec == 1 || prec == 3) && dma_ok) prec += a.a_split == 2 ? (a.half_f16 ? 14 : 12) : a.a_split ? 8 : 4;   // bf16 modes: A split on the fragment-read side, so ReLU-on-A is fine
-    else if (a.a_split) return fail(-1, "gemm: split-pair A needs a bf16 precision and the LDS-direct pipe");
+    case (PREC) * 8 + (ADD): hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, ADD, PREC, KSL, TWIN>), dim3(grid, TWIN ? 2 : 1), dim3(256), 0, s, a, b, n_tiles, nbn); break;
+#define VLSAT_GEMM_SINGLE(ADD, PREC) \
+    case (PREC) * 8 + (ADD): if constexpr (TWIN) return 1; else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, ADD, PREC, KSL>), dim3(grid), dim3(256), 0, s, a, b, n_tiles, nbn); break;
     switch (prec * 8 + add) {
         VLSAT_GEMM_CASE(0, 13) VLSAT_GEMM_CASE(1, 13) VLSAT_GEMM_CASE(6, 13)
         VLSAT_GEMM_CASE(0, 15) VLSAT_GEMM_CASE(6, 15)
@@ -201,15 +200,16 @@ static int launch_t(const GemmArgs& a, int n_tiles, int grid, hipStream_t s) {
         VLSAT_GEMM_CASE(0, 4) VLSAT_GEMM_CASE(1, 4) VLSAT_GEMM_CASE(6, 4)
         VLSAT_GEMM_CASE(0, 5) VLSAT_GEMM_CASE(1, 5) VLSAT_GEMM_CASE(6, 5)
         VLSAT_GEMM_CASE(0, 7) VLSAT_GEMM_CASE(1, 7) VLSAT_GEMM_CASE(6, 7)
-        VLSAT_GEMM_CASE(0, 0) VLSAT_GEMM_CASE(1, 0) VLSAT_GEMM_CASE(2, 0) VLSAT_GEMM_CASE(3, 0)
-        VLSAT_GEMM_CASE(4, 0) VLSAT_GEMM_CASE(5, 0) VLSAT_GEMM_CASE(6, 0) VLSAT_GEMM_CASE(7, 0)
-        VLSAT_GEMM_CASE(0, 1) VLSAT_GEMM_CASE(1, 1) VLSAT_GEMM_CASE(6, 1)
-        VLSAT_GEMM_CASE(0, 3) VLSAT_GEMM_CASE(1, 3) VLSAT_GEMM_CASE(6, 3)
-        default: return fail(-1, "gemm: this precision / additive-operand combination is not built");
+        VLSAT_GEMM_CASE(0, 0) VLSAT_GEMM_CASE(1, 0) VLSAT_GEMM_SINGLE(2, 0) VLSAT_GEMM_SINGLE(3, 0)
+        VLSAT_GEMM_SINGLE(4, 0) VLSAT_GEMM_SINGLE(5, 0) VLSAT_GEMM_CASE(6, 0) VLSAT_GEMM_SINGLE(7, 0)
+        VLSAT_GEMM_SINGLE(0, 1) VLSAT_GEMM_SINGLE(1, 1) VLSAT_GEMM_SINGLE(6, 1)
+        VLSAT_GEMM_SINGLE(0, 3) VLSAT_GEMM_SINGLE(1, 3) VLSAT_GEMM_SINGLE(6, 3)
+        default: return refuse("gemm: this precision / additive-operand combination is not built");
     }
+#undef VLSAT_GEMM_SINGLE
 #undef VLSAT_GEMM_CASE
     if (a.launches) ++*a.launches;         // a logical GEMM is a main launch plus (usually) a small-tile tail launch
-    VLSAT_LAUNCH_CHECK("gemm_f32");
+    VLSAT_LAUNCH_CHECK((TWIN ? "gemm_f32 (pair)" : "gemm_f32"));
     return 0;
 }
 
@@ -226,133 +226,57 @@ static GemmArgs tail_of(const GemmArgs& a, int row0) {
     return t;
 }
 
-template <int BM, int BN>
-static int run_tiled(const GemmArgs& a, hipStream_t s, int slot_mult2 = 2) {
-    const int G = slots() / 2 * slot_mult2;            // resident block slots the grid may use (default: two per CU)
-    const int nbm = (a.M + BM - 1) / BM, nbn = (a.N + BN - 1) / BN;
+// the persistent kernel on BM x BN tiles, a grid of slot_mult blocks per CU (G: resident slots at two per CU)
+static GemmPlan plan_tiled(const GemmArgs& a, int G, int bm, int bn, int slot_mult = 2) {
+    GemmPlan p;
+    p.bm = bm;
+    p.bn = bn;
+    p.slot_mult = slot_mult;
+    p.rows = a.M;
+    const int Gs = G / 2 * slot_mult;
+    const int nbm = (a.M + bm - 1) / bm, nbn = (a.N + bn - 1) / bn;
     const long T = (long)nbm * nbn;
-    if (T <= G) {                                   // one round: grid = tiles (rounded up to 8)
-        const int grid = (int)((T + 7) / 8) * 8;
+    p.n_tiles = (int)T;
+    if (T <= Gs) {                                  // one round: grid = tiles (rounded up to 8)
+        p.grid = (int)((T + 7) / 8) * 8;
         // latency-bound: two k-slices per pipeline step (four per step measured no faster: tools/latency_probe.py, round 2)
-        if (BM == 64 && BN == 64 && a.K % (2 * BK) == 0) return launch_t<64, 64, 2>(a, (int)T, grid, s);
-        return launch_t<BM, BN>(a, (int)T, grid, s);
+        if (bm == 64 && bn == 64 && a.K % (2 * BK) == 0) p.ksl = 2;
+        return p;
     }
     // full rounds with this tile; the remaining M-panels go to a smaller tile (see header)
-    const long rounds = T / G;
-    long main_panels = (rounds * G) / nbn;
-    if (main_panels <= 0 || main_panels >= nbm || (BM == 64 && BN == 64)) return launch_t<BM, BN>(a, (int)T, G, s);
-    GemmArgs m = a;
-    m.M = (int)(main_panels * BM);
-    int r = launch_t<BM, BN>(m, (int)(main_panels * nbn), G, s);
-    if (r) return r;
-    return launch_gemm(tail_of(a, (int)(main_panels * BM)), s);   // strictly fewer rows: terminates
+    p.grid = Gs;
+    const long main_panels = (T / Gs * Gs) / nbn;
+    if (main_panels > 0 && main_panels < nbm && !(bm == 64 && bn == 64)) {
+        p.rows = (int)(main_panels * bm);
+        p.n_tiles = (int)(main_panels * nbn);
+    }
+    return p;
 }
 
-static bool g_clock_probe_on();
-// ---- two problems, one launch (one-scene plans, round 6) ----
-static bool twin_shapes(const GemmArgs& a, const GemmArgs& b) {
-    return a.M == b.M && a.N == b.N && a.K == b.K && a.lda == b.lda && a.ldw == b.ldw && a.ldc == b.ldc && a.ldr == b.ldr &&
-           a.ldg0 == b.ldg0 && a.ldg1 == b.ldg1 && a.act == b.act && a.prec == b.prec && a.a_split == b.a_split && a.r_split == b.r_split &&
-           a.c_split == b.c_split && a.c_scale == b.c_scale && a.resid_scale == b.resid_scale && !a.bias == !b.bias && !a.resid == !b.resid &&
-           !a.g0 == !b.g0 && !a.g1 == !b.g1 && !a.rowscale == !b.rowscale && a.no_dma == b.no_dma && a.no_ring == b.no_ring &&
-           a.no_p8 == b.no_p8 && a.k_rot == b.k_rot && a.c_f16_cols == b.c_f16_cols && a.g_f16 == b.g_f16 && a.half_f16 == b.half_f16 && !a.force_tile && !b.force_tile && !a.ablate && !b.ablate && a.prefetch == b.prefetch;
-}
-// single round of 64 x 64 tiles, two k-slices per step (what run_tiled<64, 64> launches for T <= G), grid.y = 2
-static int launch_t_twin(const GemmArgs& a, const GemmArgs& b, int n_tiles, int grid, hipStream_t s) {
-    const int nbn = (a.N + 63) / 64;
-    const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
-#define VLSAT_GEMM_CASE(ADD, PREC) \
-    case (PREC) * 8 + (ADD): hipLaunchKernelGGL((gemm_f32_kernel<64, 64, ADD, PREC, 2, true>), dim3(grid, 2), dim3(256), 0, s, a, b, n_tiles, nbn); break;
-    int prec = a.prec;
-    const bool dma_ok = !a.no_dma && (add == 0 || add == 1 || add == 6) &&
-                        ((size_t)a.M + 256) * a.lda * 4 < (1ull << 32) && ((size_t)a.N + 256) * a.ldw * 4 < (1ull << 32);
-    if (prec == 0 && (a.a_split || a.r_split || a.c_split || a.c_scale != 1.f)) return 1;
-    if (prec == 0 && dma_ok && !(a.relu_a || b.relu_a)) prec = 4;     // (ReLU-on-A of either problem: the VGPR-staged pipe for both -- same products)
-    if (a.a_split == 2 && !(prec == 1 && dma_ok)) return 1;
-    if ((prec == 1 || prec == 3) && dma_ok) prec += a.a_split == 2 ? (a.half_f16 ? 14 : 12) : a.a_split ? 8 : 4;
-    else if (a.a_split) return 1;
-    switch (prec * 8 + add) {
-        VLSAT_GEMM_CASE(0, 13) VLSAT_GEMM_CASE(1, 13) VLSAT_GEMM_CASE(6, 13)
-        VLSAT_GEMM_CASE(0, 15) VLSAT_GEMM_CASE(6, 15)
-        VLSAT_GEMM_CASE(0, 9) VLSAT_GEMM_CASE(1, 9) VLSAT_GEMM_CASE(6, 9)
-        VLSAT_GEMM_CASE(0, 11) VLSAT_GEMM_CASE(1, 11) VLSAT_GEMM_CASE(6, 11)
-        VLSAT_GEMM_CASE(0, 4) VLSAT_GEMM_CASE(1, 4) VLSAT_GEMM_CASE(6, 4)
-        VLSAT_GEMM_CASE(0, 5) VLSAT_GEMM_CASE(1, 5) VLSAT_GEMM_CASE(6, 5)
-        VLSAT_GEMM_CASE(0, 7) VLSAT_GEMM_CASE(1, 7) VLSAT_GEMM_CASE(6, 7)
-        VLSAT_GEMM_CASE(0, 0) VLSAT_GEMM_CASE(1, 0) VLSAT_GEMM_CASE(6, 0)
-        default: return 1;
-    }
-#undef VLSAT_GEMM_CASE
-    if (a.launches) ++*a.launches;
-    VLSAT_LAUNCH_CHECK("gemm_f32 (pair)");
-    return 0;
+// the 8-phase / ring kernel on rows [0, rows)
+static GemmPlan big_plan(int family, int rows, int bm, int bn, long n_tiles, long grid) {
+    GemmPlan p;
+    p.family = family;
+    p.rows = rows;
+    p.bm = bm;
+    p.bn = bn;
+    p.n_tiles = (int)n_tiles;
+    p.grid = (int)grid;
+    return p;
 }
 
-int launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
-    // anything launch_gemm would refuse or treat specially stays with launch_gemm (the caller falls back to two launches)
-    if (!a.A || !a.W || !a.C || !b.A || !b.W || !b.C || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % BK || !twin_shapes(a, b)) return 1;
-    if ((a.lda & 3) || (a.ldw & 3) || (a.prec != 0 && a.prec != 1 && a.prec != 3)) return 1;
-    if (a.prec && (!a.Whi || !b.Whi || (a.prec == 3 && (!a.Wlo || !b.Wlo)) || (a.ldw & 7))) return 1;
-    if (a.rowscale && (a.resid || a.g0 || a.g1)) return 1;
-    for (const GemmArgs* q : {&a, &b})
-        if ((reinterpret_cast<uintptr_t>(q->A) & 15) || (reinterpret_cast<uintptr_t>(q->W) & 15)) return 1;
-    if (g_clock_probe_on()) return 1;
-    const int G = slots();
-    if (a.sk_ws && b.sk_ws) {
-        const int r = launch_gemm_splitk(a, G, s, &b);
-        if (r <= 0) return r;
-    }
-    // Mirror of launch_gemm's cascade for a problem this small: only the case that ends in ONE round of 64 x 64 tiles with two
-    // k-slices per step is paired; everything else (8-phase partial rounds, ring kernel, wider tiles, several rounds) is not.
-    const long T = (long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    if (T > G || a.K % (2 * BK)) return 1;
-    if (a.N % 256 == 0 && a.K % 128 == 0 && !a.no_dma && !a.no_ring && !a.no_p8 && !a.rowscale && (!a.c_f16_cols || a.c_f16_cols == a.N)) {           // 8-phase partial round?
-        const bool p8_fmt = (a.prec == 1 && a.a_split == 2) || (a.prec == 3 && a.a_split == 1) || (a.prec == 0 && !a.a_split && !a.c_split && !a.r_split);
-        const long panels = (a.M + 255) / 256, nbn = a.N / 256, part_min = a.p8_part_min > 0 ? a.p8_part_min : a.prec == 1 ? 32 : (G / 2 * 5) / 8;
-        if (p8_fmt && panels * nbn >= part_min) return 1;
-    }
-    if ((a.prec == 1 || a.prec == 3) && !a.no_dma && !a.no_ring && a.N > 64 && !a.rowscale && (long)((a.M + 255) / 256) * ((a.N + 127) / 128) >= G / 2) return 1;   // ring kernel
-    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    if (a.prec == 3 && !a.a_split && a.N >= 1024 && a.N <= 2048 && blocks(64, 128) <= G && blocks(64, 128) >= G / 2) return 1;
-    if ((a.N > 64 && blocks(128, 128) >= G) || (a.N <= 64 && blocks(128, 64) >= G) || (a.N > 64 && blocks(64, 128) >= G)) return 1;
-    return launch_t_twin(a, b, (int)T, (int)((T + 7) / 8) * 8, s);
-}
-
-static long long* g_clock_probe = nullptr;       // debug only (vlsat_debug_gemm_clock_probe): process-wide on purpose
-void gemm_set_clock_probe(long long* buf) { g_clock_probe = buf; }
-static bool g_clock_probe_on() { return g_clock_probe != nullptr; }
-
-int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
-    GemmArgs a = a_in;
-    a.clock_probe = g_clock_probe;
-    if (!a.A || !a.W || !a.C) return fail(-1, "gemm: null A/W/C");
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.K <= 0 || a.K % BK) return fail(-1, "gemm: K must be a positive multiple of 32");
-    if ((a.lda & 3) || (a.ldw & 3)) return fail(-1, "gemm: lda/ldw must be multiples of 4 floats");
-    if (a.prec != 0 && a.prec != 1 && a.prec != 3) return fail(-1, "gemm: prec must be 0 (fp32), 1 (bf16) or 3 (bf16x3)");
-    if (a.prec && (!a.Whi || (a.prec == 3 && !a.Wlo) || (a.ldw & 7))) return fail(-1, "gemm: bf16 path needs pre-split weights and ldw % 8 == 0");
-    if (a.rowscale && (a.resid || a.g0 || a.g1))
-        return fail(-1, "gemm: rowscale cannot be combined with resid/g0/g1 (additive operands are accumulator inits)");
-    if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.W) & 15))
-        return fail(-1, "gemm: A/W must be 16-byte aligned");
-    if (a.half_f16 && (a.prec != 1 || a.a_split != 2 || a.c_split || a.r_split)) return fail(-1, "gemm: fp16 operands are half-row A launches of the single-rounding precision; their half-row output is c_f16_cols == N");
-    if ((a.c_f16_cols || a.g_f16) && a.prec == 0) return fail(-1, "gemm: fp16 half-row columns / tables belong to the bf16 modes (the exact-fp32 kernels read and write fp32)");
-    if (a.c_f16_cols && ((a.c_f16_cols != a.N && a.c_f16_cols % 256) || a.c_f16_cols > a.N || a.c_split)) return fail(-1, "gemm: c_f16_cols must be N or a multiple of 256 within N, of an fp32 output");
-    if (a.g_f16 && (a.resid || !(a.g0 || a.g1) || a.N % 256 || ((a.ldg0 | a.ldg1) & 1) || ((reinterpret_cast<uintptr_t>(a.g0) | reinterpret_cast<uintptr_t>(a.g1)) & 7)))
-        return fail(-1, "gemm: g_f16 needs gathered rows, no residual, N % 256 == 0 and 8-byte aligned tables");
-    const int G = slots();
-    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    if (a.sk_ws && !a.clock_probe) {                  // small launch: k range spread over otherwise idle CUs
-        const int r = launch_gemm_splitk(a, G, s);
-        if (r <= 0) return r;
-    }
+// The first launch of a GEMM (launch_gemm plans the rows it leaves as a problem of their own).  Pure: no HIP call, no state; the
+// kernels with operand combinations they do not build (split-K, 8-phase, ring) decide for themselves whether they take a launch.
+// G: resident 256-thread blocks at two per CU (slots()).
+static GemmPlan plan_gemm(const GemmArgs& a, int G) {
+    GemmPlan p;
+    if (a.sk_ws && !a.clock_probe && plan_gemm_splitk(a, G, p) == 0) return p;     // small launch: k range spread over otherwise idle CUs
+    const int G1 = G / 2;
     // Large M; exact fp32, single-rounding bf16 with half-row operands or split-bf16 with split-pair operands: the full rounds of 256 x 256 tiles go to the 8-phase
     // kernel (gemm_bf16_p8.hip: one 8-wave block per CU), the remaining row panels to the kernels below
     if (((a.prec == 1 && a.a_split == 2) || (a.prec == 3 && a.a_split == 1) || (a.prec == 0 && !a.a_split && !a.c_split && !a.r_split)) && !a.no_dma && !a.no_ring &&
         !a.no_p8 && !a.rowscale && !a.clock_probe && (!a.c_f16_cols || (a.c_f16_cols == a.N && a.prec == 1 && !a.resid && (a.half_f16 || (!a.g0 && !a.g1 && !a.relu_a)))) && a.N % 256 == 0 && a.K % 128 == 0 &&
-        ((size_t)a.M + 256) * a.lda * 4 < (1ull << 32) && ((size_t)a.M + 256) * a.ldc * 4 < (1ull << 32) &&
-        ((size_t)a.N + 256) * a.ldw * 4 < (1ull << 32)) {
-        const int G1 = G / 2;
+        offsets32(a.M, a.lda) && offsets32(a.M, a.ldc) && offsets32(a.N, a.ldw)) {
         // (a last, partly filled panel rides along with a partial round: rows past M read as zeros through the buffer descriptors,
         //  their stores are dropped by them, additive operands clamp the row -- round 5: the 120-row remainder of the cfg 5 scene
         //  no longer is a launch of its own)
@@ -379,70 +303,130 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
         // lanes' kernels (round 5: kproj 41.7 -> 30.1 us, nn_edge.2 64.7 -> 48.6 at E = 39 800; cfg 5 step +3 %)
         if (rounds >= 1 && main_panels > 0 && main_panels < panels && (panels - main_panels) * nbn >= rem_min) {
             const long step = 8 * nbn, g2 = ((panels * nbn + rounds) / (rounds + 1) + step - 1) / step * step;
-            if (g2 <= G1) {
-                const int r = launch_gemm_p8(a, (int)(panels * nbn), (int)g2, s);
-                if (r <= 0) return r;
-            }
+            if (g2 <= G1 && launch_gemm_p8(a, (int)(panels * nbn), (int)g2, nullptr, true) == 0) return big_plan(GemmPlan::P8, a.M, 256, 256, panels * nbn, g2);
         }
         if (main_panels > 0) {
             GemmArgs m = a;
             m.M = (int)std::min<long>(main_panels * 256, a.M);
-            const int r = launch_gemm_p8(m, (int)(main_panels * nbn), G1, s);
-            if (r < 0) return r;
-            if (r == 0) {
-                if (m.M == a.M) return 0;
-                return launch_gemm(tail_of(a, m.M), s);
-            }
+            if (launch_gemm_p8(m, (int)(main_panels * nbn), G1, nullptr, true) == 0) return big_plan(GemmPlan::P8, m.M, 256, 256, main_panels * nbn, G1);
         }
     }
     // bf16 modes, large M: the full rounds go to the 3-stage ring kernel (gemm_bf16_ring.hip: one 8-wave block per CU,
     // 256 x 128 tiles, two slices in flight), the remaining row panels to the kernels below
-    if ((a.prec == 1 || a.prec == 3) && !a.no_dma && !a.no_ring && a.N > 64 && !a.rowscale &&
-        ((size_t)a.M + 256) * a.lda * 4 < (1ull << 32) && ((size_t)a.N + 256) * a.ldw * 4 < (1ull << 32)) {
-        const int G1 = G / 2;
+    if ((a.prec == 1 || a.prec == 3) && !a.no_dma && !a.no_ring && a.N > 64 && !a.rowscale && offsets32(a.M, a.lda) && offsets32(a.N, a.ldw)) {
         // 128 x 256 tiles when N is a multiple of 256 and they still make full rounds (half the A bytes per flop), else 256 x 128
         for (int rbn = (a.ring_wide && a.N % 256 == 0) ? 256 : 128; rbn >= 128; rbn -= 128) {
             const int rbm = 32768 / rbn;
             const long nbm = (a.M + rbm - 1) / rbm, nbn = (a.N + rbn - 1) / rbn;
-            const long rounds = nbm * nbn / G1;
-            const long main_panels = rounds * G1 / nbn;
+            const long main_panels = nbm * nbn / G1 * G1 / nbn;
             if (main_panels <= 0) continue;
             GemmArgs m = a;
             m.M = (int)std::min<long>(main_panels * rbm, a.M);
-            const int r = launch_gemm_ring(m, rbn, (int)(main_panels * nbn), G1, s);
-            if (r < 0) return r;
-            if (r == 0) {
-                if (m.M == a.M) return 0;
-                return launch_gemm(tail_of(a, m.M), s);
-            }
+            if (launch_gemm_ring(m, rbn, (int)(main_panels * nbn), G1, nullptr, true) == 0) return big_plan(GemmPlan::RING, m.M, rbm, rbn, main_panels * nbn, G1);
             break;
         }
     }
     switch (a.force_tile) {                       // (experiment switch: the tile the sweep asks for)
-        case 1: return run_tiled<128, 128>(a, s);
-        case 2: return run_tiled<128, 64>(a, s);
-        case 3: return run_tiled<64, 128>(a, s);
-        case 4: return run_tiled<64, 64>(a, s);
-        case 5: return run_tiled<64, 64>(a, s, 4);        // (experiment: four 64 x 64 blocks per CU)
-        case 6: return run_tiled<64, 128>(a, s, 3);       // (experiment: three 64 x 128 blocks per CU)
-        case 7: return run_tiled<64, 64>(a, s, 3);
+        case 1: return plan_tiled(a, G, 128, 128);
+        case 2: return plan_tiled(a, G, 128, 64);
+        case 3: return plan_tiled(a, G, 64, 128);
+        case 4: return plan_tiled(a, G, 64, 64);
+        case 5: return plan_tiled(a, G, 64, 64, 4);        // (experiment: four 64 x 64 blocks per CU)
+        case 6: return plan_tiled(a, G, 64, 128, 3);       // (experiment: three 64 x 128 blocks per CU)
+        case 7: return plan_tiled(a, G, 64, 64, 3);
         default: break;
     }
+    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
     // split-bf16 node-row launches with 1024..2048 output columns (self-attention QKV, cross-attention KV at the bench batch):
     // one round of 64 x 128 tiles beats two rounds of 64 x 64 by 6-8 us per launch (tools/gemm_tile_sweep.py, round 4:
     // 30.1 -> 24.2 us and 29.4 -> 22.0 us; every other node-row shape is best on what the rule below picks, fp32 within 2-4 us)
     if (a.prec == 3 && !a.a_split && a.N >= 1024 && a.N <= 2048 && blocks(64, 128) <= G && blocks(64, 128) >= G / 2)
-        return run_tiled<64, 128>(a, s);
+        return plan_tiled(a, G, 64, 128);
     // Largest tile that still gives every resident slot a tile; small problems (and the tails
     // of big ones) take smaller tiles so the launch covers as many CUs as the problem allows.
-    if (a.N > 64 && blocks(128, 128) >= G) return run_tiled<128, 128>(a, s);
-    if (a.N <= 64 && blocks(128, 64) >= G) return run_tiled<128, 64>(a, s);
-    if (a.N > 64 && blocks(64, 128) >= G) return run_tiled<64, 128>(a, s);
+    if (a.N > 64 && blocks(128, 128) >= G) return plan_tiled(a, G, 128, 128);
+    if (a.N <= 64 && blocks(128, 64) >= G) return plan_tiled(a, G, 128, 64);
+    if (a.N > 64 && blocks(64, 128) >= G) return plan_tiled(a, G, 64, 128);
     // exact fp32 on 64 x 64 tiles over more than one round of two blocks per CU (node rows of a batch: QKV 960 tiles, KV 640,
     // the node-side projection 2080): the kernel holds 80 VGPRs and 32 KB of LDS, so four blocks fit a CU and these latency-bound
     // launches take the wider grid -- KV 42.6 -> 31.0 us, QKV 46.5 -> 39.9, wnode 90.3 -> 78.9 (tools/gemm_tile_sweep.py, round 4)
-    if (a.prec == 0 && blocks(64, 64) > G) return run_tiled<64, 64>(a, s, 4);
-    return run_tiled<64, 64>(a, s);
+    if (a.prec == 0 && blocks(64, 64) > G) return plan_tiled(a, G, 64, 64, 4);
+    return plan_tiled(a, G, 64, 64);
+}
+
+// the launch of a plan on rows [0, m.M) (m.M == p.rows)
+static int launch_plan(const GemmArgs& m, const GemmPlan& p, hipStream_t s) {
+    switch (p.family) {
+        case GemmPlan::SPLITK: return launch_gemm_splitk(m, p, s);
+        case GemmPlan::P8: return launch_gemm_p8(m, p.n_tiles, p.grid, s);
+        case GemmPlan::RING: return launch_gemm_ring(m, p.bn, p.n_tiles, p.grid, s);
+    }
+    if (p.bm == 128) return p.bn == 128 ? launch_t<128, 128>(m, m, p.n_tiles, p.grid, s) : launch_t<128, 64>(m, m, p.n_tiles, p.grid, s);
+    if (p.bn == 128) return launch_t<64, 128>(m, m, p.n_tiles, p.grid, s);
+    return p.ksl == 2 ? launch_t<64, 64, 2>(m, m, p.n_tiles, p.grid, s) : launch_t<64, 64>(m, m, p.n_tiles, p.grid, s);
+}
+
+static long long* g_clock_probe = nullptr;       // debug only (vlsat_debug_gemm_clock_probe): process-wide on purpose
+void gemm_set_clock_probe(long long* buf) { g_clock_probe = buf; }
+
+// nullptr when launch_gemm takes the problem (an empty one included), else what it reports
+static const char* gemm_invalid(const GemmArgs& a) {
+    if (!a.A || !a.W || !a.C) return "gemm: null A/W/C";
+    if (a.M <= 0 || a.N <= 0) return nullptr;
+    if (a.K <= 0 || a.K % BK) return "gemm: K must be a positive multiple of 32";
+    if ((a.lda & 3) || (a.ldw & 3)) return "gemm: lda/ldw must be multiples of 4 floats";
+    if (a.prec != 0 && a.prec != 1 && a.prec != 3) return "gemm: prec must be 0 (fp32), 1 (bf16) or 3 (bf16x3)";
+    if (a.prec && (!a.Whi || (a.prec == 3 && !a.Wlo) || (a.ldw & 7))) return "gemm: bf16 path needs pre-split weights and ldw % 8 == 0";
+    if (a.rowscale && (a.resid || a.g0 || a.g1)) return "gemm: rowscale cannot be combined with resid/g0/g1 (additive operands are accumulator inits)";
+    if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.W) & 15)) return "gemm: A/W must be 16-byte aligned";
+    if (a.half_f16 && (a.prec != 1 || a.a_split != 2 || a.c_split || a.r_split)) return "gemm: fp16 operands are half-row A launches of the single-rounding precision; their half-row output is c_f16_cols == N";
+    if ((a.c_f16_cols || a.g_f16) && a.prec == 0) return "gemm: fp16 half-row columns / tables belong to the bf16 modes (the exact-fp32 kernels read and write fp32)";
+    if (a.c_f16_cols && ((a.c_f16_cols != a.N && a.c_f16_cols % 256) || a.c_f16_cols > a.N || a.c_split)) return "gemm: c_f16_cols must be N or a multiple of 256 within N, of an fp32 output";
+    if (a.g_f16 && (a.resid || !(a.g0 || a.g1) || a.N % 256 || ((a.ldg0 | a.ldg1) & 1) || ((reinterpret_cast<uintptr_t>(a.g0) | reinterpret_cast<uintptr_t>(a.g1)) & 7)))
+        return "gemm: g_f16 needs gathered rows, no residual, N % 256 == 0 and 8-byte aligned tables";
+    return nullptr;
+}
+
+int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
+    GemmArgs a = a_in;
+    a.clock_probe = g_clock_probe;
+    if (const char* why = gemm_invalid(a)) return fail(-1, why);
+    if (a.M <= 0 || a.N <= 0) return 0;
+    const int G = slots();
+    while (true) {
+        const GemmPlan p = plan_gemm(a, G);
+        if (p.rows == a.M) return launch_plan(a, p, s);
+        GemmArgs m = a;
+        m.M = p.rows;
+        if (const int r = launch_plan(m, p, s)) return r;
+        a = tail_of(a, p.rows);                 // strictly fewer rows: terminates
+    }
+}
+
+// ---- two problems, one launch (one-scene plans, round 6) ----
+static bool twin_shapes(const GemmArgs& a, const GemmArgs& b) {
+    return a.M == b.M && a.N == b.N && a.K == b.K && a.lda == b.lda && a.ldw == b.ldw && a.ldc == b.ldc && a.ldr == b.ldr &&
+           a.ldg0 == b.ldg0 && a.ldg1 == b.ldg1 && a.act == b.act && a.prec == b.prec && a.a_split == b.a_split && a.r_split == b.r_split &&
+           a.c_split == b.c_split && a.c_scale == b.c_scale && a.resid_scale == b.resid_scale && !a.bias == !b.bias && !a.resid == !b.resid &&
+           !a.g0 == !b.g0 && !a.g1 == !b.g1 && !a.rowscale == !b.rowscale && a.no_dma == b.no_dma && a.no_ring == b.no_ring &&
+           a.no_p8 == b.no_p8 && a.k_rot == b.k_rot && a.c_f16_cols == b.c_f16_cols && a.g_f16 == b.g_f16 && a.half_f16 == b.half_f16 && !a.force_tile && !b.force_tile && !a.ablate && !b.ablate && a.prefetch == b.prefetch;
+}
+static bool same_plan(const GemmPlan& p, const GemmPlan& q) {
+    return p.family == q.family && p.rows == q.rows && p.bm == q.bm && p.bn == q.bn && p.ksl == q.ksl && p.slot_mult == q.slot_mult &&
+           p.ks == q.ks && p.slices == q.slices && p.n_tiles == q.n_tiles && p.grid == q.grid;
+}
+
+int launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
+    // (no pair under the clock probe: the blocks of both problems would write the same probe rows)
+    if (gemm_invalid(a) || gemm_invalid(b) || a.M <= 0 || a.N <= 0 || !twin_shapes(a, b) || g_clock_probe) return 1;
+    // the launches with a twin form: split-K, and one round of 64 x 64 tiles at two blocks per CU with two k-slices per step
+    const int G = slots();
+    const GemmPlan p = plan_gemm(a, G);
+    const bool splitk = p.family == GemmPlan::SPLITK;
+    if (p.rows != a.M || !(splitk || (p.family == GemmPlan::TILED && p.bm == 64 && p.bn == 64 && p.ksl == 2 && p.slot_mult == 2))) return 1;
+    // b's own plan too: twin_shapes leaves out what may differ between the twins (ReLU-on-A), and each problem must run what it would alone
+    if (!same_plan(p, plan_gemm(b, G))) return 1;
+    return splitk ? launch_gemm_splitk(a, p, s, &b) : launch_t<64, 64, 2, true>(a, b, p.n_tiles, p.grid, s);
 }
 
 }  // namespace vlsat

@@ -108,13 +108,10 @@ __global__ __launch_bounds__(256, 2) void gemm_splitk_kernel(GemmArgs pa, GemmAr
 
 }  // namespace
 
-// Decides whether the launch is one of the small ones this kernel is for and, if so, runs it.  Returns 0 = launched,
-// 1 = not applicable (the caller falls through to the persistent kernel), < 0 = error.
-// twin: a second problem of the same shape and flags (gemm_f32.hip launch_gemm_pair has checked that) for the same launch; every
-// decision below is taken from `a` exactly as for a single launch, so each problem is computed as it would be alone.
-int launch_gemm_splitk(const GemmArgs& a, int slots, hipStream_t s, const GemmArgs* twin) {
+// Decides whether the launch is one of the small ones this kernel is for: 0 = yes (p: its geometry), 1 = not applicable (the caller
+// falls through to the persistent kernel).
+int plan_gemm_splitk(const GemmArgs& a, int slots, GemmPlan& p) {
     if (!a.sk_ws || !a.sk_counters) return 1;
-    if (twin && (!twin->sk_ws || !twin->sk_counters || twin->sk_ws == a.sk_ws || twin->sk_counters == a.sk_counters)) return 1;
     const long nbm = (a.M + 63) / 64, nbn = (a.N + 63) / 64, T = nbm * nbn;
     const int total = a.K / BK;                                      // k-slices
     if (total < 4 || T > slots / 2 || (a.sk_max_tiles > 0 && T > a.sk_max_tiles)) return 1;      // at least two parts of >= 2 slices, and room for them
@@ -125,22 +122,30 @@ int launch_gemm_splitk(const GemmArgs& a, int slots, hipStream_t s, const GemmAr
     const int slices = (total + ks - 1) / ks;
     ks = (total + slices - 1) / slices;                              // no empty parts
     if ((size_t)T * ks * 4096 > a.sk_ws_floats || (size_t)T > a.sk_n_counters) return 1;
-    if (twin && ((size_t)T * ks * 4096 > twin->sk_ws_floats || (size_t)T > twin->sk_n_counters)) return 1;
-    int prec = a.prec;
-    const bool relu_a = a.relu_a || (twin && twin->relu_a);          // (a pair takes the staging pipe that can apply ReLU to A if either needs it: same products)
-    const bool dma_ok = !a.no_dma && ((size_t)a.M + 256) * a.lda * 4 < (1ull << 32) && ((size_t)a.N + 256) * a.ldw * 4 < (1ull << 32);
-    if (prec == 0 && dma_ok && !relu_a) prec = 4;
-    if (a.a_split == 2 && !(prec == 1 && dma_ok)) return 1;
-    if ((prec == 1 || prec == 3) && dma_ok) prec += a.a_split == 2 ? (a.half_f16 ? 14 : 12) : a.a_split ? 8 : 4;
-    else if (a.a_split) return 1;
-    const int grid = (int)((T + 7) / 8) * 8 * ks;
+    if (gemm_pipe_prec(a, a.relu_a, false) < 0) return 1;
+    p.family = GemmPlan::SPLITK;
+    p.rows = a.M;
+    p.bm = p.bn = 64;
+    p.ks = ks;
+    p.slices = slices;
+    p.n_tiles = (int)T;
+    p.grid = (int)((T + 7) / 8) * 8 * ks;
+    return 0;
+}
+
+// twin: a second problem of the same shape and flags whose own plan is p (launch_gemm_pair has checked both), in the same launch:
+// each problem is computed as it would be alone.
+int launch_gemm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s, const GemmArgs* twin) {
+    if (twin && (twin->sk_ws == a.sk_ws || twin->sk_counters == a.sk_counters)) return 1;
     const GemmArgs& b = twin ? *twin : a;
+    const int nbn = (a.N + 63) / 64;
+    // (a pair takes the staging pipe that can apply ReLU to A if either needs it: same products)
 #define VLSAT_SK_CASE(PREC) \
     case PREC: \
-        if (twin) hipLaunchKernelGGL((gemm_splitk_kernel<PREC, true>), dim3(grid, 2), dim3(256), 0, s, a, b, (int)T, (int)nbn, ks, slices, a.sk_ws, a.sk_counters, b.sk_ws, b.sk_counters); \
-        else hipLaunchKernelGGL((gemm_splitk_kernel<PREC, false>), dim3(grid), dim3(256), 0, s, a, a, (int)T, (int)nbn, ks, slices, a.sk_ws, a.sk_counters, a.sk_ws, a.sk_counters); \
+        if (twin) hipLaunchKernelGGL((gemm_splitk_kernel<PREC, true>), dim3(p.grid, 2), dim3(256), 0, s, a, b, p.n_tiles, nbn, p.ks, p.slices, a.sk_ws, a.sk_counters, b.sk_ws, b.sk_counters); \
+        else hipLaunchKernelGGL((gemm_splitk_kernel<PREC, false>), dim3(p.grid), dim3(256), 0, s, a, a, p.n_tiles, nbn, p.ks, p.slices, a.sk_ws, a.sk_counters, a.sk_ws, a.sk_counters); \
         break;
-    switch (prec) {
+    switch (gemm_pipe_prec(a, a.relu_a || b.relu_a, false)) {
         VLSAT_SK_CASE(0) VLSAT_SK_CASE(1) VLSAT_SK_CASE(3) VLSAT_SK_CASE(4) VLSAT_SK_CASE(5) VLSAT_SK_CASE(7)
         VLSAT_SK_CASE(9) VLSAT_SK_CASE(11) VLSAT_SK_CASE(13) VLSAT_SK_CASE(15)
         default: return 1;

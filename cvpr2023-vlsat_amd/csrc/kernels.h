@@ -56,20 +56,35 @@ struct GemmArgs {
     unsigned* sk_counters = nullptr; size_t sk_n_counters = 0;
 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
-// small launches: k range cut over several CUs, deterministic in-kernel reduction; 1 = not applicable, 0 = launched
-int launch_gemm_splitk(const GemmArgs& a, int slots, hipStream_t s, const GemmArgs* twin = nullptr);
+// The first launch of a GEMM as the planner of launch_gemm (gemm_f32.hip plan_gemm) chooses it: kernel family, geometry, and the
+// rows [0, rows) it covers -- the rows after them are planned again as a problem of their own (the tail).
+struct GemmPlan {
+    enum Family { SPLITK, P8, RING, TILED };
+    int family = TILED;
+    int rows = 0;
+    int bm = 64, bn = 64;           // output tile (8-phase: 256 x 256; ring: 32768 / bn x bn)
+    int ksl = 1, slot_mult = 2;     // persistent kernel: k-slices per pipeline step, resident blocks per CU its grid is sized for
+    int ks = 0, slices = 0;         // split-K: parts of the k range, k-slices per part
+    int n_tiles = 0, grid = 0;
+};
+// small launches: k range cut over several CUs, deterministic in-kernel reduction.  plan: 0 = this kernel takes the launch (p),
+// 1 = not applicable; launch: runs the plan, twin = a second problem whose own plan is p in the same launch (1 = not pairable)
+int plan_gemm_splitk(const GemmArgs& a, int slots, GemmPlan& p);
+int launch_gemm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s, const GemmArgs* twin = nullptr);
 // two problems of the same shape and flags in ONE launch (round 6: the 3D / 2D twins of a one-scene forward): 0 = launched,
-// 1 = not pairable (different shapes / flags, or a launch the single-round small-tile kernels would not take): the caller
-// launches them one after the other; results are bit-identical either way
+// 1 = not pairable: invalid or different problems, or plans of launch_gemm that are not the same single launch of a kernel with a
+// twin form (split-K, one round of 64 x 64 tiles at two k-slices per step).  The caller then launches them one after the other;
+// results are bit-identical either way
 int launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s);
 constexpr size_t SPLITK_WS_FLOATS = (size_t)768 * 4096;    // room for 768 partial 64 x 64 tiles (12 MB)
 constexpr size_t SPLITK_COUNTERS = 512;
 // bf16 modes, full rounds of large-M launches: 3-stage LDS ring, 256 x 128 tiles, one 8-wave block per CU
-// (gemm_bf16_ring.hip); returns 1 if the operand combination is not built
-int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s);   // rbn: tile width 128 | 256
+// (gemm_bf16_ring.hip); returns 1 if the operand combination is not built.  dry: decide only (the planner), launch nothing
+int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s, bool dry = false);   // rbn: tile width 128 | 256
 // full rounds of large-M launches, exact fp32 or single-rounding bf16 with half-row A: 256 x 256 tiles, 8-phase pipeline,
-// one 8-wave block per CU (gemm_bf16_p8.hip); needs M % 256 == 0, N % 256 == 0, K % 128 == 0; returns 1 if the combination is not built
-int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s);
+// one 8-wave block per CU (gemm_bf16_p8.hip); needs N % 256 == 0, K % 128 == 0; returns 1 if the combination is not built.
+// dry: decide only (the planner), launch nothing
+int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s, bool dry = false);
 double gemm_flops(const GemmArgs& a);
 void gemm_set_clock_probe(long long* buf);
 
