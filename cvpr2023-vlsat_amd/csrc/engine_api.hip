@@ -394,6 +394,76 @@ int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan p, const float* ob
                               split_counts, stream);
 }
 
+// out = exp(x), n floats (out may be x): the predicate probabilities of a single-label model, by the kernel vlsat_forward_scene_graph uses
+int vlsat_k_exp(const float* x, int64_t n, float* out, void* stream) {
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(VLSAT_EINVAL, "k_exp: bad argument");
+    return launch_exp(x, out, (size_t)n, static_cast<hipStream_t>(stream));
+}
+
+// The predicted scene graph of every scene of a batch (scene_graph.hip; contract and tie rule: include/vlsat.h)
+int64_t vlsat_scene_graph_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes,
+                                        int32_t top_k, int32_t topk_each) {
+    if (n_nodes < 0 || n_edges < 0 || n_scenes < 0 || scene_graph_check_args(n_obj_class, n_rel_class, 0, top_k, topk_each)) return 0;
+    return (int64_t)scene_graph_scratch_bytes(n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes, topk_each);
+}
+
+int vlsat_scene_graph_topk(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids,
+                           int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes, int32_t mode,
+                           int32_t top_k, int32_t topk_each, void* scratch, int32_t* triplets, float* scores, int32_t* n_valid,
+                           void* stream) {
+    RUN(scene_graph_check_args(n_obj_class, n_rel_class, mode, top_k, topk_each));
+    if (n_scenes > 0 && (!triplets || !scores || !n_valid || !scratch)) return fail(VLSAT_EINVAL, "scene_graph_topk: null output or scratch");
+    if (n_edges > 0 && (!rel_probs || !edges || (mode == 0 && !obj_probs))) return fail(VLSAT_EINVAL, "scene_graph_topk: null edge argument");
+    if (n_scenes > 1 && !batch_ids) return fail(VLSAT_EINVAL, "scene_graph_topk: batch_ids is required for more than one scene");
+    if (n_scenes < 0 || n_nodes < 0 || n_edges < 0) return fail(VLSAT_EINVAL, "scene_graph_topk: bad sizes");
+    const SceneGraphWs ws = scene_graph_carve(scratch, n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes, topk_each);
+    return launch_scene_graph_topk(obj_probs, rel_probs, edges, batch_ids, nullptr, n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes,
+                                   mode, top_k, topk_each, ws, triplets, scores, n_valid, static_cast<hipStream_t>(stream));
+}
+
+// The label-free sibling of vlsat_process_val_counts: forward + softmax of both object heads + the selection for both branches,
+// enqueued back to back on `stream`, one library call per scene.  Every intermediate lives in the plan's memory: logits,
+// probabilities and predicate scores in the evaluation scratch (the class indices of the node argsort take the place of a branch's
+// logits once its softmax has run, the sorted values the ranking's sorted-probability table), the scene offsets in the rank
+// scratch, and the candidate slots (8 bytes x topk_each per edge) in Hbig, the 4 KB-per-edge hidden buffer that is dead once the
+// forward has finished -- the arena does not grow.  With MODEL.multi_rel_outputs = false the log-probabilities are exponentiated
+// in place first.
+int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                              const int64_t* edges_e2, int32_t n_scenes, int32_t mode, int32_t top_k, int32_t topk_each,
+                              int32_t* triplets_3d, float* scores_3d, int32_t* n_valid_3d, int32_t* triplets_2d, float* scores_2d,
+                              int32_t* n_valid_2d, void* stream) {
+    if (!h || !p) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null argument");
+    if (p->h != h) return fail(VLSAT_EINVAL, "plan belongs to a different handle");
+    const int N = (int)p->N, E = (int)p->E, C = h->d.n_obj_class, R = h->d.n_rel_class;
+    RUN(scene_graph_check_args(C, R, mode, top_k, topk_each));
+    if (n_scenes != p->S) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: n_scenes is not the plan's scene count");
+    if (!triplets_3d || !scores_3d || !n_valid_3d || !triplets_2d || !scores_2d || !n_valid_2d)
+        return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null output");
+    if (E > 0 && !edges_e2) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null edge argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* f = p->ev_f;
+    float *obj3 = f, *obj2 = f + (size_t)N * C, *prob3 = f + (size_t)2 * N * C, *prob2 = f + (size_t)3 * N * C;
+    float *rel3 = f + (size_t)4 * N * C, *rel2 = rel3 + (size_t)std::max(E, 1) * R;
+    float* sorted = rel2 + (size_t)std::max(E, 1) * R;          // [N, min(C, 100)] of the [N, C] the plan holds
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, obj3, obj2, rel3, rel2, stream));
+    for (int br = 0; br < 2; ++br) {
+        float* lg = br ? obj2 : obj3;
+        float* rl = br ? rel2 : rel3;
+        RUN(launch_softmax_rows(lg, C, N, C, br ? prob2 : prob3, 0, s));
+        if (!h->d.multi_rel_outputs) RUN(launch_exp(rl, rl, (size_t)E * R, s));
+        SceneGraphWs ws;
+        ws.sv = sorted;
+        ws.si = reinterpret_cast<int32_t*>(lg);                 // (the logits are dead behind the softmax)
+        ws.ptr = p->ev_i;                                       // (S + 1 <= 2 max(N, 1) entries)
+        ws.keys = reinterpret_cast<uint32_t*>(p->Hbig);         // (2 x E x <= 100 of the E x 1024 words)
+        ws.packs = ws.keys + (size_t)std::max(E, 1) * 100;
+        RUN(launch_scene_graph_topk(br ? prob2 : prob3, rl, edges_e2, nullptr, p->d_scene_ptr, N, E, C, R, n_scenes, mode, top_k, topk_each,
+                                    ws, br ? triplets_2d : triplets_3d, br ? scores_2d : scores_3d, br ? n_valid_2d : n_valid_3d, s));
+    }
+    VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the selection)
+    return 0;
+}
+
 int vlsat_scene_checksums(const float* obj3d, const float* obj2d, int64_t n_nodes, int32_t n_obj_class, const float* rel3d,
                           const float* rel2d, int64_t n_edges, int32_t n_rel_class, int32_t n_scenes, double* out9, double* scratch,
                           void* stream) {

@@ -235,6 +235,18 @@ int launch_eval_recallk(const float* obj_probs, const float* rel, const int64_t*
                         const int64_t* batch_ids, int N, int E, int C, int R, int n_scenes, int vmask, void* scratch,
                         long long* counts, hipStream_t s);
 
+// the predicted scene graph (scene_graph.hip): per scene the top_k candidates with their indices -- triplets [n_scenes][top_k][4]
+// (edge, subject class, object class, predicate), scores [n_scenes][top_k], n_valid [n_scenes]; mode 0 triplet | 1 rels.
+// The scene of an edge comes from batch_ids, else from node_ptr ([n_scenes + 1] node offsets), else there is one scene.
+struct SceneGraphWs { float* sv; int32_t* si; int32_t* ptr; uint32_t* keys; uint32_t* packs; };   // [N, min(C,100)] x 2, [S + 1], [E, L] x 2
+size_t scene_graph_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes, int each);
+SceneGraphWs scene_graph_carve(void* scratch, int64_t N, int64_t E, int C, int R, int n_scenes, int each);
+int scene_graph_check_args(int C, int R, int mode, int top_k, int each);
+int launch_scene_graph_topk(const float* obj_probs, const float* rel, const int64_t* edges, const int64_t* batch_ids,
+                            const int32_t* node_ptr, int N, int E, int C, int R, int n_scenes, int mode, int top_k, int each,
+                            const SceneGraphWs& ws, int32_t* trip, float* score, int32_t* nvalid, hipStream_t s);
+int launch_exp(const float* x, float* out, size_t n, hipStream_t s);      // out = exp(x) (out may be x): log-probabilities of a single-label model
+
 // rank arrays of one batch -> += the additive counts vector of evaluate.validation (uint64 [1 + R + 2 (11 + 6 R)]; layout:
 // evaluate.fields()); integer atomics only, safe from concurrent streams
 int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const int32_t* rel_rank3, const int32_t* rel_rank2,

@@ -309,6 +309,72 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
 
 
 @torch.no_grad()
+def predict(model, batches: Iterable[dict], device=None, workers: int = 0, **graph_args):
+    """The predicted scene graph of every scene of ``batches`` (the loader's dicts; no labels are read), in input order: yields
+    one ``(graph_3d, graph_2d)`` pair of one-scene ``metrics.SceneGraph`` per scene, edge rows counted within the scene's own
+    edge list.  ``graph_args``: ``top_k``, ``topk_each``, ``evaluate`` of ``VLSATModel.predict_graph``.  workers = 0: one batch
+    after the other on the current stream.  workers >= 1: as the pipelined validation loop -- every worker thread owns a replica
+    of the model and a stream and takes the next batch; nothing is read back per batch."""
+    import threading
+    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
+    workers = int(workers)
+    if workers > 0 and device is None:
+        raise ValueError("predict(workers > 0) needs the device")
+
+    def one(m, b):
+        ids = b.get("batch_ids")
+        return m.predict_graph(b["obj_points"], b["obj_2d_feats"], b["edge_indices"].t(), b["descriptor"], ids,
+                               fc_sizes=b.get("fc_sizes"), **graph_args), b
+
+    def scenes(pair, b):
+        g3, g2 = pair
+        n_sc = g3.n_valid.numel()
+        if n_sc == 1:
+            yield g3, g2
+            return
+        first = b["batch_ids"].view(-1)[b["edge_indices"][:, 0]]                       # scene of every edge
+        start = torch.searchsorted(first.contiguous(), torch.arange(n_sc, device=first.device)).tolist()
+        for s in range(n_sc):
+            yield g3.scene(s, start[s]), g2.scene(s, start[s])
+
+    if workers <= 0:
+        for _, b in it:
+            yield from scenes(*one(model, b))
+        return
+    dev = torch.device(device)
+    models = [model] + model.replicas(workers - 1)
+
+    def work(k):
+        try:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(stream):
+                while not errors:
+                    with lock:
+                        i, b = next(it, (None, None))
+                    if b is None:
+                        break
+                    results[i] = one(models[k], b)
+            stream.synchronize()
+        except BaseException as ex:             # (re-raised in the caller's thread)
+            errors.append(ex)
+
+    if workers == 1:
+        work(0)
+    else:
+        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
+        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise errors[0]
+    for i in sorted(results):
+        yield from scenes(*results[i])
+
+
+@torch.no_grad()
 def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1,
                recall_k: bool = False, zero_shot=None) -> Dict[str, float]:
     """``batches`` yields this rank's dicts with the reference loader's item names

@@ -409,6 +409,163 @@ def recallk_counts_host(obj_logits, rel, gt_cls, gt_rel, edges, batch_ids, n_sce
     return out
 
 
+# ---- the predicted scene graph: per-scene top-K triplets with their indices (csrc/scene_graph.hip) ----
+SG_MAX_TOP_K, SG_MAX_EACH = 1024, 100
+_SG_MODES = {"triplet": 0, "rels": 1}
+
+
+class SceneGraph:
+    """Top-K triplets of every scene of a batch: ``edge`` (row of the batch's edge list), ``sub_cls``, ``obj_cls``, ``pred``
+    int32 [S, K], ``score`` float32 [S, K], ``n_valid`` int32 [S]; rows past ``n_valid[s]`` hold -1 / 0.  Rows are ordered by
+    score descending, then edge, subject class, object class, predicate ascending (include/vlsat.h, vlsat_scene_graph_topk)."""
+    __slots__ = ("edge", "sub_cls", "obj_cls", "pred", "score", "n_valid")
+
+    def __init__(self, triplets: torch.Tensor, score: torch.Tensor, n_valid: torch.Tensor):
+        self.edge, self.sub_cls, self.obj_cls, self.pred = (triplets[..., i] for i in range(4))
+        self.score, self.n_valid = score, n_valid
+
+    def scene(self, s: int, edge_offset: int = 0) -> "SceneGraph":
+        """Scene ``s`` as a one-scene graph; ``edge_offset`` is subtracted from its edge rows (the scene's first row in the batch)."""
+        g = SceneGraph.__new__(SceneGraph)
+        for k in ("sub_cls", "obj_cls", "pred", "score"):
+            setattr(g, k, getattr(self, k)[s:s + 1])
+        e = self.edge[s:s + 1]
+        g.edge = torch.where(e >= 0, e - edge_offset, e) if edge_offset else e
+        g.n_valid = self.n_valid[s:s + 1]
+        return g
+
+    def cpu(self) -> "SceneGraph":
+        g = SceneGraph.__new__(SceneGraph)
+        for k in self.__slots__:
+            setattr(g, k, getattr(self, k).cpu())
+        return g
+
+
+def exp_probs(log_probs: torch.Tensor) -> torch.Tensor:
+    """exp of a single-label model's log-probabilities by the library's kernel (``vlsat_k_exp``), the one ``predict_graph`` uses."""
+    x = log_probs.float().contiguous()
+    out = torch.empty_like(x)
+    L.check(L.load().vlsat_k_exp(x.data_ptr(), x.numel(), out.data_ptr(), L.stream_ptr()))
+    return out
+
+
+def _sg_args(rel, edges, batch_ids, n_scenes, top_k, topk_each, evaluate):
+    if evaluate not in _SG_MODES:
+        raise NotImplementedError("evaluate type", evaluate)
+    top_k, topk_each, n_scenes = int(top_k), int(topk_each), int(n_scenes)
+    if not 1 <= top_k <= SG_MAX_TOP_K:
+        raise L.VlsatError(f"scene_graph_topk: top_k must be in 1..{SG_MAX_TOP_K}")
+    if not 1 <= topk_each <= SG_MAX_EACH:
+        raise L.VlsatError(f"scene_graph_topk: topk_each must be in 1..{SG_MAX_EACH}")
+    if n_scenes < 0 or (n_scenes > 1 and batch_ids is None):
+        raise L.VlsatError("scene_graph_topk: batch_ids is required for more than one scene")
+    edges = edges.to(torch.int64).contiguous().view(-1, 2)
+    if rel.dim() != 2 or edges.shape[0] != rel.shape[0]:
+        raise L.VlsatError("scene_graph_topk: rel must be [E,R] and edges [E,2]")
+    if batch_ids is not None:
+        batch_ids = batch_ids.to(torch.int64).contiguous().view(-1)
+    return edges, batch_ids, n_scenes, top_k, topk_each, _SG_MODES[evaluate]
+
+
+def scene_graph_topk(obj_logits: torch.Tensor, rel: torch.Tensor, edges: torch.Tensor, batch_ids: torch.Tensor | None,
+                     n_scenes: int, multi_rel_outputs: bool = True, top_k: int = 100, topk_each: int = 100,
+                     evaluate: str = "triplet", obj_probs: torch.Tensor | None = None) -> SceneGraph:
+    """The predicted graph of every scene: its ``top_k`` (subject, predicate, object) triplets out of each edge's ``topk_each``
+    best -- the reference's ``pred_triplets`` (evaluate_triplet_recallk, eval_utils_recall.py:24-96), without labels.
+    ``obj_logits`` [N, C] (the object probabilities are their softmax unless ``obj_probs`` is given), ``rel`` [E, R] predicate
+    probabilities (log-probabilities when ``multi_rel_outputs`` is False), ``edges`` [E, 2] grouped by scene in ascending order,
+    the scene of an edge being ``batch_ids[edges[e, 0]]`` (None: one scene).  ``evaluate`` = "triplet" scores
+    fl(fl(s_i * o_j) * r_k); "rels" scores r_k and reports subject / object class as -1.  Output contract and tie rule:
+    include/vlsat.h (vlsat_scene_graph_topk).  Device tensors: the HIP kernels, asynchronous, no host round trip.  CPU tensors:
+    ``scene_graph_topk_host``."""
+    if not obj_logits.is_cuda:
+        return scene_graph_topk_host(obj_logits, rel, edges, batch_ids, n_scenes, multi_rel_outputs, top_k, topk_each, evaluate,
+                                     obj_probs)
+    lib = L.load()
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    edges, batch_ids, n_scenes, top_k, topk_each, mode = _sg_args(rel, edges, batch_ids, n_scenes, top_k, topk_each, evaluate)
+    r_probs = rel.float().contiguous() if multi_rel_outputs else exp_probs(rel)
+    if obj_probs is None and mode == 0:
+        obj_probs = softmax_rows(obj_logits.float())
+    if obj_probs is not None:
+        obj_probs = obj_probs.float().contiguous()
+    dev = obj_logits.device
+    trip = torch.empty(n_scenes, top_k, 4, dtype=torch.int32, device=dev)
+    score = torch.empty(n_scenes, top_k, dtype=torch.float32, device=dev)
+    n_valid = torch.empty(n_scenes, dtype=torch.int32, device=dev)
+    if c > 1024 or r > 32 or c < 1 or r < 1:
+        raise L.VlsatError("scene_graph_topk: 1..1024 object and 1..32 relation classes")
+    nbytes = int(lib.vlsat_scene_graph_scratch_bytes(n, e, c, r, n_scenes, top_k, topk_each))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L.check(lib.vlsat_scene_graph_topk(L.ptr(obj_probs), r_probs.data_ptr(), edges.data_ptr(), L.ptr(batch_ids), n, e, c, r, n_scenes,
+                                       mode, top_k, topk_each, scratch.data_ptr(), trip.data_ptr(), score.data_ptr(),
+                                       n_valid.data_ptr(), L.stream_ptr()))
+    return SceneGraph(trip, score, n_valid)
+
+
+@torch.no_grad()
+def scene_graph_topk_host(obj_logits, rel, edges, batch_ids, n_scenes, multi_rel_outputs=True, top_k=100, topk_each=100,
+                          evaluate="triplet", obj_probs=None, chunk: int = 8192) -> SceneGraph:
+    """``scene_graph_topk`` stated in PyTorch on whatever device the inputs are: per edge its min(topk_each, #entries) largest
+    entries with their classes (triplet mode: out of the dominance-pruned positions of ``_tri_table``, never the C x C x R
+    products), per scene the top_k of them in the contract's order.  Among candidates equal to a boundary value it keeps the
+    smallest (edge, subject class, object class, predicate).  Exact, slow; for CPU tests and devices without the HIP library."""
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    dev = obj_logits.device
+    edges, batch_ids, n_scenes, top_k, topk_each, mode = _sg_args(rel, edges, batch_ids, n_scenes, top_k, topk_each, evaluate)
+    rp = (rel if multi_rel_outputs else rel.exp()).float().contiguous()
+    trip = torch.full((n_scenes, top_k, 4), -1, dtype=torch.int32, device=dev)
+    score = torch.zeros(n_scenes, top_k, dtype=torch.float32, device=dev)
+    n_valid = torch.zeros(n_scenes, dtype=torch.int32, device=dev)
+    if e == 0 or n_scenes == 0:
+        return SceneGraph(trip, score, n_valid)
+    a, b = edges[:, 0], edges[:, 1]
+    scene = batch_ids[a] if batch_ids is not None else torch.zeros(e, dtype=torch.int64, device=dev)
+    rs, ri = rp.sort(dim=1, descending=True, stable=True)
+    if mode == 1:
+        lim = min(topk_each, r)
+        cand, pack = rs[:, :lim], ri[:, :lim]                                         # pack: the predicate
+    else:
+        probs = (torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()).contiguous()
+        ks = min(c, _NGC_CAP)
+        ss, si = probs.sort(dim=1, descending=True, stable=True)
+        ss, si = ss[:, :ks], si[:, :ks]
+        lim = min(topk_each, c * c * r)
+        tri = _tri_table(ks, r, dev)
+        tri = tri[(tri[:, 0] + 1) * (tri[:, 1] + 1) * (tri[:, 2] + 1) <= lim]
+        cand = torch.empty(e, lim, dtype=torch.float32, device=dev)
+        pack = torch.empty(e, lim, dtype=torch.int64, device=dev)
+        for e0 in range(0, e, chunk):
+            sl = slice(e0, min(e, e0 + chunk))
+            vals = (ss[a[sl]][:, tri[:, 0]] * ss[b[sl]][:, tri[:, 1]]) * rs[sl][:, tri[:, 2]]     # fl(fl(s*o)*r)
+            pk = (si[a[sl]][:, tri[:, 0]] * c + si[b[sl]][:, tri[:, 1]]) * r + ri[sl][:, tri[:, 2]]
+            o1 = pk.argsort(dim=1, stable=True)                                           # (value descending, classes ascending)
+            o2 = vals.gather(1, o1).argsort(dim=1, descending=True, stable=True)
+            order = o1.gather(1, o2)[:, :lim]
+            cand[sl], pack[sl] = vals.gather(1, order), pk.gather(1, order)
+    eid = torch.arange(e, device=dev)[:, None].expand(-1, lim)
+    for s in range(n_scenes):
+        sel = scene == s
+        if not bool(sel.any()):
+            continue
+        v, ed, pk = cand[sel].reshape(-1), eid[sel].reshape(-1), pack[sel].reshape(-1)
+        o1 = (ed * (c * c * r if mode == 0 else r) + pk).argsort(stable=True)
+        o2 = v[o1].argsort(descending=True, stable=True)
+        order = o1[o2][:top_k]
+        k = order.numel()
+        n_valid[s] = k
+        score[s, :k] = v[order]
+        trip[s, :k, 0] = ed[order].int()
+        p = pk[order]
+        if mode == 0:
+            trip[s, :k, 1], trip[s, :k, 2], trip[s, :k, 3] = (p // (c * r)).int(), ((p // r) % c).int(), (p % r).int()
+        else:
+            trip[s, :k, 3] = p.int()
+    return SceneGraph(trip, score, n_valid)
+
+
 def _edges_list(edges):
     return [(int(x[0]), int(x[1])) for x in (edges.tolist() if torch.is_tensor(edges) else np.asarray(edges).tolist())]
 

@@ -517,6 +517,38 @@ class VLSATModel:
         return True
 
     @torch.no_grad()
+    def predict_graph(self, obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids=None, top_k: int = 100, topk_each: int = 100,
+                      evaluate: str = "triplet", fc_sizes: Optional[Sequence[int]] = None):
+        """The predicted scene graph of every scene, for both branches: ``(graph_3d, graph_2d)``, two ``metrics.SceneGraph`` with
+        the ``top_k`` triplets per scene out of each edge's ``topk_each`` best (``metrics.scene_graph_topk``).  No labels.
+        ``vlsat_forward_scene_graph``: forward + softmax of both object heads + the selection of both branches in ONE library
+        call, intermediates in the plan's memory.  Inputs as for ``forward`` (``edge_indices`` int64 [2,E]); the edges must be
+        grouped by scene in ascending order, as the loader and ``scan.prepare_scan`` yield them."""
+        from . import metrics as M
+        if evaluate not in M._SG_MODES:
+            raise NotImplementedError("evaluate type", evaluate)
+        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, edge_indices, descriptor)
+        with torch.cuda.device(self.device):
+            plan = self._plan(edge_indices, batch_ids, n, p, fc_sizes)
+            if plan.perm is not None:
+                raise L.VlsatError("predict_graph: edge_indices must be grouped by scene in ascending scene order")
+            s = C.c_int32()
+            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
+            n_scenes, top_k, topk_each = s.value, int(top_k), int(topk_each)
+            if not 1 <= top_k <= M.SG_MAX_TOP_K or not 1 <= topk_each <= M.SG_MAX_EACH:
+                raise L.VlsatError(f"predict_graph: top_k must be in 1..{M.SG_MAX_TOP_K} and topk_each in 1..{M.SG_MAX_EACH}")
+            edges_e2 = edge_indices.to(self.device).t().contiguous()
+            trip = torch.empty(2, n_scenes, top_k, 4, dtype=torch.int32, device=self.device)
+            score = torch.empty(2, n_scenes, top_k, dtype=torch.float32, device=self.device)
+            n_valid = torch.empty(2, n_scenes, dtype=torch.int32, device=self.device)
+            L.check(self._lib.vlsat_forward_scene_graph(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+                                                        edges_e2.data_ptr(), n_scenes, M._SG_MODES[evaluate], top_k, topk_each,
+                                                        trip[0].data_ptr(), score[0].data_ptr(), n_valid[0].data_ptr(),
+                                                        trip[1].data_ptr(), score[1].data_ptr(), n_valid[1].data_ptr(),
+                                                        L.stream_ptr()))
+        return M.SceneGraph(trip[0], score[0], n_valid[0]), M.SceneGraph(trip[1], score[1], n_valid[1])
+
+    @torch.no_grad()
     def forward_3d(self, obj_points, edge_indices, descriptor, batch_ids=None, fc_sizes: Optional[Sequence[int]] = None):
         """3D-only deployment (no image features): returns (obj_logits_3d, rel_cls_3d), bit-identical to
         the first and third outputs of ``forward`` -- the 3D branch never reads the 2D branch

@@ -416,6 +416,56 @@ int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan plan, const float*
                                    int32_t n_scenes, uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts,
                                    void* stream);
 
+/* The predicted scene graph: for every scene of a batch its top_k (subject, predicate, object) triplets WITH their indices -- the
+ * list pred_triplets = ((from, to), (sub cls, obj cls, rel), conf) the reference builds inside evaluate_triplet_recallk
+ * (src/utils/eval_utils_recall.py:24-60, 75-96) from its running global top-K and never returns.  No labels are read
+ * (csrc/scene_graph.hip).
+ *   scores      mode 0 (evaluate='triplet'): conf(e; i, j, k) = fl(fl(s_i * o_j) * r_k) (no FMA), s / o = obj_probs[from] /
+ *               obj_probs[to], r = rel_probs[e] -- pass exp(log-probabilities) when the model has multi_rel_outputs = false.
+ *               mode 1 (evaluate='rels'): conf(e; k) = r_k; subject and object class are reported as -1; obj_probs is not read.
+ *   candidates  per edge its min(topk_each, #entries) largest entries.
+ *   output      triplets int32 [n_scenes][top_k][4] = (edge, subject class, object class, predicate), edge being the row of
+ *               `edges` (batch-wide: edges[edge] gives the two nodes); scores float [n_scenes][top_k]; n_valid int32 [n_scenes]
+ *               = min(top_k, candidates of the scene); rows past n_valid hold -1 / 0.0f.  Every field is written.
+ *               1. scores[s, 0:n_valid] is the descending list of the n_valid largest candidate values, bit for bit.
+ *               2. a row's score is the product at its (edge, sub, obj, pred); the rows of a scene are pairwise distinct; an
+ *                  edge contributes at most topk_each rows.
+ *               3. every candidate strictly greater than the last kept score is present.  Which of several candidates EQUAL to
+ *                  the last kept score (or to an edge's topk_each-th value) are kept is unspecified (the reference leaves it to
+ *                  torch.topk) but a pure function of the scene's own inputs: a batch equals its scenes called one at a time.
+ *               4. rows are ordered by score descending, then edge, subject class, object class, predicate ascending.
+ *               When the kept values and the first one left out are pairwise different this is the reference's pred_triplets.
+ * Limits: top_k 1..1024, topk_each 1..100, n_obj_class <= 1024, n_rel_class <= 32; anything else is an error, never a clamp.
+ * Preconditions (as for vlsat_eval_recallk): the scene of edge e is batch_ids[edges[e, 0]] in [0, n_scenes) (batch_ids may be
+ * NULL for one scene), edges arrive grouped by scene in ascending scene order, node indices are in range, no NaN, probabilities
+ * are non-negative.  scratch: vlsat_scene_graph_scratch_bytes(...) bytes of device memory the call may overwrite
+ * (8 (N x min(C, 100) + E x min(topk_each, C C R)) bytes plus the scene offsets; 0 = arguments out of range).  All device
+ * pointers; asynchronous on `stream`: no host synchronisation, no runtime fill, no allocation, no global atomics. */
+int vlsat_scene_graph_topk(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids,
+                           int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes,
+                           int32_t mode /* 0 triplet, 1 rels */, int32_t top_k, int32_t topk_each, void* scratch,
+                           int32_t* triplets /* [n_scenes][top_k][4]: edge, sub class, obj class, predicate */,
+                           float* scores /* [n_scenes][top_k] */, int32_t* n_valid /* [n_scenes] */, void* stream);
+int64_t vlsat_scene_graph_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                                        int32_t n_scenes, int32_t top_k, int32_t topk_each);
+
+/* out[i] = expf(x[i]) for n floats (out may be x): turns the log-probabilities of a MODEL.multi_rel_outputs = false model into
+ * the rel_probs of vlsat_scene_graph_topk with the kernel vlsat_forward_scene_graph uses (so the separate calls equal the one
+ * call bit for bit).  Device pointers; asynchronous. */
+int vlsat_k_exp(const float* x, int64_t n, float* out, void* stream);
+
+/* The label-free sibling of vlsat_process_val_counts: vlsat_forward + softmax of both object heads + vlsat_scene_graph_topk for
+ * both branches, enqueued back to back on `stream` with every intermediate in the plan's own memory (the selection's candidate
+ * slots re-use an edge tensor that is dead once the forward has finished: the plan's arena does not grow) -- one library call
+ * per scene from an unlabelled scan to its predicted graph.  edges_e2 is the [E, 2] int64 (from, to) list in the plan's edge
+ * order; n_scenes must be the plan's scene count (the scenes are the plan's).  With MODEL.multi_rel_outputs = false the
+ * log-probabilities are exponentiated on the device.  Outputs per branch as for vlsat_scene_graph_topk.  All device pointers;
+ * asynchronous. */
+int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
+                              const float* descriptor, const int64_t* edges_e2, int32_t n_scenes, int32_t mode,
+                              int32_t top_k, int32_t topk_each, int32_t* triplets_3d, float* scores_3d, int32_t* n_valid_3d,
+                              int32_t* triplets_2d, float* scores_2d, int32_t* n_valid_2d, void* stream);
+
 /* The additive fp64 metrics vector of one rank's batch -- what the path's one all-reduce carries when no labels are at hand
  * (bench.py; the label-based counts of validation(), reference src/model/model.py:214-242, come from vlsat_eval_ranks):
  * out9 = {n_scenes, n_nodes, n_edges, sum obj3d, sum obj2d, sum rel3d, sum rel2d, #nodes whose 3D and 2D top-1 class agree,
