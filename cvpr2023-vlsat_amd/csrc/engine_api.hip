@@ -473,6 +473,88 @@ int vlsat_scene_checksums(const float* obj3d, const float* obj2d, int64_t n_node
                                   scratch, static_cast<hipStream_t>(stream));
 }
 
+// The decoded scene graph of every scene of a batch (graph_decode.hip; contract: include/vlsat.h)
+int64_t vlsat_graph_decode_scratch_bytes(int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes, int32_t n_labels,
+                                         int32_t max_rel) {
+    if (n_edges < 0 || n_scenes < 0 || graph_decode_check_args(n_obj_class, n_rel_class, 1, 0, n_labels, max_rel)) return 0;
+    return (int64_t)graph_decode_scratch_bytes(n_edges, n_rel_class, n_scenes);
+}
+
+int vlsat_graph_decode(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids,
+                       const float* thresholds, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                       int32_t n_scenes, int32_t multi_label, int32_t score_mode, int32_t n_labels, int32_t max_rel, void* scratch,
+                       int32_t* labels, float* label_probs, int32_t* rels, float* scores, int32_t* n_valid, int32_t* n_total,
+                       void* stream) {
+    RUN(graph_decode_check_args(n_obj_class, n_rel_class, multi_label, score_mode, n_labels, max_rel));
+    if (n_scenes < 0 || n_nodes < 0 || n_edges < 0) return fail(VLSAT_EINVAL, "graph_decode: bad sizes");
+    if (n_nodes > 0 && (!obj_probs || !labels || !label_probs)) return fail(VLSAT_EINVAL, "graph_decode: null node argument");
+    if (n_scenes > 0 && (!rels || !scores || !n_valid || !n_total || !scratch)) return fail(VLSAT_EINVAL, "graph_decode: null output or scratch");
+    if (n_edges > 0 && (!rel_probs || !edges || !thresholds)) return fail(VLSAT_EINVAL, "graph_decode: null edge argument");
+    if (n_scenes > 1 && !batch_ids) return fail(VLSAT_EINVAL, "graph_decode: batch_ids is required for more than one scene");
+    const GraphDecodeWs ws = graph_decode_carve(scratch, n_edges, n_rel_class, n_scenes);
+    return launch_graph_decode(obj_probs, rel_probs, edges, batch_ids, nullptr, thresholds, n_nodes, n_edges, n_obj_class, n_rel_class,
+                               n_scenes, multi_label, score_mode, n_labels, max_rel, ws, labels, label_probs, rels, scores, n_valid,
+                               n_total, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_graph_decode_counts(const float* obj_probs, const float* rel_probs, const int64_t* gt_class, const int64_t* gt_rel,
+                              const float* thresholds, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                              int32_t multi_label, uint64_t* counts, void* stream) {
+    if (!counts || n_nodes < 0 || n_edges < 0) return fail(VLSAT_EINVAL, "graph_decode_counts: bad argument");
+    if (n_nodes > 0 && (!obj_probs || !gt_class)) return fail(VLSAT_EINVAL, "graph_decode_counts: null node argument");
+    if (n_edges > 0 && (!rel_probs || !gt_rel || !thresholds)) return fail(VLSAT_EINVAL, "graph_decode_counts: null edge argument");
+    return launch_graph_decode_counts(obj_probs, rel_probs, gt_class, gt_rel, thresholds, n_nodes, n_edges, n_obj_class, n_rel_class,
+                                      multi_label, reinterpret_cast<unsigned long long*>(counts), static_cast<hipStream_t>(stream));
+}
+
+// From points to the decoded graph in one call: forward (3D-only when obj_2d_feats is NULL) + softmax of the object heads + the
+// decode per branch, enqueued back to back on `stream`.  Every intermediate lives in the plan's memory: logits, probabilities and
+// predicate scores in the float half of the evaluation scratch, the decode's workspace -- scene offsets, per-edge counts, keys and
+// predicates: 2 N + E (1 + R + R / 4) words -- in its integer half (2 N + E (4 R + 2) words): the arena does not grow.  With
+// MODEL.multi_rel_outputs = false the log-probabilities are exponentiated in place first.
+int vlsat_forward_graph(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                        const int64_t* edges_e2, int32_t n_scenes, int32_t multi_label, int32_t score_mode, int32_t n_labels,
+                        int32_t max_rel, const float* thresholds, int32_t* labels_3d, float* label_probs_3d, int32_t* rels_3d,
+                        float* scores_3d, int32_t* n_valid_3d, int32_t* n_total_3d, int32_t* labels_2d, float* label_probs_2d,
+                        int32_t* rels_2d, float* scores_2d, int32_t* n_valid_2d, int32_t* n_total_2d, void* stream) {
+    if (!h || !p) return fail(VLSAT_EINVAL, "vlsat_forward_graph: null argument");
+    if (p->h != h) return fail(VLSAT_EINVAL, "plan belongs to a different handle");
+    const int N = (int)p->N, E = (int)p->E, C = h->d.n_obj_class, R = h->d.n_rel_class;
+    RUN(graph_decode_check_args(C, R, multi_label, score_mode, n_labels, max_rel));
+    if (n_scenes != p->S) return fail(VLSAT_EINVAL, "vlsat_forward_graph: n_scenes is not the plan's scene count");
+    if (!labels_3d || !label_probs_3d || !rels_3d || !scores_3d || !n_valid_3d || !n_total_3d)
+        return fail(VLSAT_EINVAL, "vlsat_forward_graph: null 3D output");
+    const bool any2 = labels_2d || label_probs_2d || rels_2d || scores_2d || n_valid_2d || n_total_2d;
+    const bool all2 = labels_2d && label_probs_2d && rels_2d && scores_2d && n_valid_2d && n_total_2d;
+    const bool do2d = obj_2d_feats != nullptr;
+    if (do2d ? !all2 : any2)
+        return fail(VLSAT_EINVAL, "vlsat_forward_graph: obj_2d_feats and the six 2D outputs go together (all, or none for 3D-only)");
+    if (!thresholds || (E > 0 && !edges_e2)) return fail(VLSAT_EINVAL, "vlsat_forward_graph: null thresholds or edge argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t Es = (size_t)std::max(E, 1);
+    float* f = p->ev_f;
+    float *obj3 = f, *obj2 = f + (size_t)N * C, *prob3 = f + (size_t)2 * N * C, *prob2 = f + (size_t)3 * N * C;
+    float *rel3 = f + (size_t)4 * N * C, *rel2 = rel3 + Es * R;
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, obj3, do2d ? obj2 : nullptr, rel3, do2d ? rel2 : nullptr, stream));
+    GraphDecodeWs ws;
+    ws.ptr = p->ev_i;                                           // (S + 1 <= 2 max(N, 1) entries)
+    ws.cnt = p->ev_i + 2 * (size_t)N;
+    ws.keys = reinterpret_cast<uint32_t*>(ws.cnt + Es);
+    ws.preds = reinterpret_cast<uint8_t*>(ws.keys + Es * R);
+    for (int br = 0; br < (do2d ? 2 : 1); ++br) {
+        float* pr = br ? prob2 : prob3;
+        float* rl = br ? rel2 : rel3;
+        RUN(launch_softmax_rows(br ? obj2 : obj3, C, N, C, pr, 0, s));
+        if (!h->d.multi_rel_outputs) RUN(launch_exp(rl, rl, (size_t)E * R, s));
+        RUN(launch_graph_decode(pr, rl, edges_e2, nullptr, p->d_scene_ptr, thresholds, N, E, C, R, n_scenes, multi_label, score_mode,
+                                n_labels, max_rel, ws, br ? labels_2d : labels_3d, br ? label_probs_2d : label_probs_3d,
+                                br ? rels_2d : rels_3d, br ? scores_2d : scores_3d, br ? n_valid_2d : n_valid_3d,
+                                br ? n_total_2d : n_total_3d, s));
+    }
+    VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the decode)
+    return 0;
+}
+
 // -------------------------------------------------------------------------------------------
 // Kernel-level entry points of the non-GEMM kernels of the GCN block and the node attention (SURVEY 8b's per-kernel list):
 // test entry points like vlsat_k_flash_attn -- small index tables are built on the host, uploaded, and the call

@@ -245,7 +245,27 @@ int scene_graph_check_args(int C, int R, int mode, int top_k, int each);
 int launch_scene_graph_topk(const float* obj_probs, const float* rel, const int64_t* edges, const int64_t* batch_ids,
                             const int32_t* node_ptr, int N, int E, int C, int R, int n_scenes, int mode, int top_k, int each,
                             const SceneGraphWs& ws, int32_t* trip, float* score, int32_t* nvalid, hipStream_t s);
+// ptr[q] = first edge of scene q, ptr[n_scenes] = E, for edges grouped by scene in ascending order (scene of an edge: see above)
+int launch_scene_edge_ptr(const int64_t* edges, const int64_t* batch_ids, const int32_t* node_ptr, int N, int E, int n_scenes, int32_t* ptr,
+                          hipStream_t s);
 int launch_exp(const float* x, float* out, size_t n, hipStream_t s);      // out = exp(x) (out may be x): log-probabilities of a single-label model
+
+// the decoded scene graph (graph_decode.hip): per node its n_labels best classes (labels / label_probs [N][n_labels]), per scene the
+// asserted (edge, predicate) pairs by (score descending, edge, predicate ascending), capped at max_rel: rels [n_scenes][max_rel][2],
+// score [n_scenes][max_rel], n_valid / n_total [n_scenes].  multi: threshold every predicate | arg-max (0 = none) then threshold;
+// score_mode 0 rel | 1 fl(fl(s * o) * rel) with the nodes' top-1 probabilities.  Scene of an edge: as launch_scene_graph_topk.
+struct GraphDecodeWs { int32_t* ptr; int32_t* cnt; uint32_t* keys; uint8_t* preds; };             // [S + 1], [E], [E, R], [E, R]
+size_t graph_decode_scratch_bytes(int64_t E, int R, int n_scenes);
+GraphDecodeWs graph_decode_carve(void* scratch, int64_t E, int R, int n_scenes);
+int graph_decode_check_args(int C, int R, int multi, int score_mode, int n_labels, int max_rel);
+int launch_graph_decode(const float* obj_probs, const float* rel, const int64_t* edges, const int64_t* batch_ids, const int32_t* node_ptr,
+                        const float* thr, int N, int E, int C, int R, int n_scenes, int multi, int score_mode, int n_labels, int max_rel,
+                        const GraphDecodeWs& ws, int32_t* labels, float* label_probs, int32_t* rels, float* score, int32_t* nvalid,
+                        int32_t* ntotal, hipStream_t s);
+// out[3 R + 2] += per predicate tp, fp, fn of the same decisions (before the cap) against gt, then nodes, nodes with top-1 == gt;
+// gt_rel int64 multi-hot [E, R] (multi) | int64 [E], 0 = none; integer atomics only, safe from concurrent streams
+int launch_graph_decode_counts(const float* obj_probs, const float* rel, const int64_t* gt_cls, const int64_t* gt_rel, const float* thr,
+                               int N, int E, int C, int R, int multi, unsigned long long* out, hipStream_t s);
 
 // rank arrays of one batch -> += the additive counts vector of evaluate.validation (uint64 [1 + R + 2 (11 + 6 R)]; layout:
 // evaluate.fields()); integer atomics only, safe from concurrent streams

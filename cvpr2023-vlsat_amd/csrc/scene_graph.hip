@@ -397,6 +397,13 @@ int launch_exp(const float* x, float* out, size_t n, hipStream_t s) {
     return 0;
 }
 
+int launch_scene_edge_ptr(const int64_t* edges, const int64_t* batch_ids, const int32_t* node_ptr, int N, int E, int n_scenes, int32_t* ptr,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(sg_scene_ptr_kernel, dim3(E / 256 + 1), dim3(256), 0, s, edges, batch_ids, node_ptr, N, E, n_scenes, ptr);
+    VLSAT_LAUNCH_CHECK("scene_graph scene_ptr");
+    return 0;
+}
+
 int launch_scene_graph_topk(const float* obj_probs, const float* rel, const int64_t* edges, const int64_t* batch_ids,
                             const int32_t* node_ptr, int N, int E, int C, int R, int n_scenes, int mode, int top_k, int each,
                             const SceneGraphWs& ws, int32_t* trip, float* score, int32_t* nvalid, hipStream_t s) {
@@ -406,8 +413,8 @@ int launch_scene_graph_topk(const float* obj_probs, const float* rel, const int6
     if (n_scenes == 0) return 0;
     const int Ks = C < SG_EACH ? C : SG_EACH;
     const int L = sg_slots(C, R, mode, each);
-    hipLaunchKernelGGL(sg_scene_ptr_kernel, dim3(E / 256 + 1), dim3(256), 0, s, edges, batch_ids, node_ptr, N, E, n_scenes, ws.ptr);
-    VLSAT_LAUNCH_CHECK("scene_graph scene_ptr");
+    const int rp = launch_scene_edge_ptr(edges, batch_ids, node_ptr, N, E, n_scenes, ws.ptr, s);
+    if (rp) return rp;
     if (E > 0) {
         if (mode == 0) {
             hipLaunchKernelGGL(sg_node_argsort_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, obj_probs, N, C, Ks,

@@ -375,6 +375,108 @@ def predict(model, batches: Iterable[dict], device=None, workers: int = 0, **gra
 
 
 @torch.no_grad()
+def decode(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d: bool = True, **decode_args):
+    """The decoded scene graph of every scene of ``batches`` (the loader's dicts; no labels are read), in input order: yields one
+    ``(graph_3d, graph_2d)`` pair of one-scene ``metrics.DecodedGraph`` per scene -- its own node rows, edge rows counted within
+    the scene's own edge list.  ``use_2d=False`` takes the 3D-only forward (``obj_2d_feats`` is not read; ``graph_2d`` is None):
+    the route of unlabelled scans.  ``decode_args``: ``threshold``, ``score``, ``n_labels``, ``max_rel``, ``multi_rel_outputs`` of
+    ``VLSATModel.decode_graph``.  workers = 0: one batch after the other on the current stream.  workers >= 1: as ``predict`` --
+    every worker thread owns a replica of the model and a stream and takes the next batch; nothing is read back per batch."""
+    import threading
+    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
+    workers = int(workers)
+    if workers > 0 and device is None:
+        raise ValueError("decode(workers > 0) needs the device")
+
+    def one(m, b):
+        return m.decode_graph(b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["edge_indices"].t(), b["descriptor"],
+                              b.get("batch_ids"), fc_sizes=b.get("fc_sizes"), **decode_args), b
+
+    def scenes(pair, b):
+        g3, g2 = pair
+        n_sc = g3.n_valid.numel()
+        if n_sc == 1:
+            yield g3, g2
+            return
+        ids = b["batch_ids"].view(-1).contiguous()
+        arange = torch.arange(n_sc + 1, device=ids.device)
+        node = torch.searchsorted(ids, arange).tolist()                               # first node row of every scene
+        start = torch.searchsorted(ids[b["edge_indices"][:, 0]].contiguous(), arange).tolist()      # ... and first edge row
+        for s in range(n_sc):
+            nodes = (node[s], node[s + 1])
+            yield g3.scene(s, start[s], nodes), (None if g2 is None else g2.scene(s, start[s], nodes))
+
+    if workers <= 0:
+        for _, b in it:
+            yield from scenes(*one(model, b))
+        return
+    dev = torch.device(device)
+    models = [model] + model.replicas(workers - 1)
+
+    def work(k):
+        try:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(stream):
+                while not errors:
+                    with lock:
+                        i, b = next(it, (None, None))
+                    if b is None:
+                        break
+                    results[i] = one(models[k], b)
+            stream.synchronize()
+        except BaseException as ex:             # (re-raised in the caller's thread)
+            errors.append(ex)
+
+    if workers == 1:
+        work(0)
+    else:
+        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
+        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise errors[0]
+    for i in sorted(results):
+        yield from scenes(*results[i])
+
+
+def graph_quality(counts, n_rel: int = N_REL) -> Dict[str, float]:
+    """Precision, recall and F1 of the decoded relations and the accuracy of the decoded labels, from the (all-reduced) counts of
+    ``metrics.decode_counts``: one vector [3 R + 2], or the vectors of several branches stacked ([B, 3 R + 2] -> keys suffixed
+    ``_0``, ``_1``, ...; a dict maps branch names to vectors).  micro: over the summed tp / fp / fn.  macro: the mean over the
+    predicates that occur (tp + fp + fn > 0) of the per-predicate value, a value whose denominator is 0 counting as 0.  An empty
+    group is NaN.  ``per_class_{precision,recall,f1}`` hold the per-predicate values (NaN where the denominator is 0)."""
+    if isinstance(counts, dict):
+        out = {}
+        for name, v in counts.items():
+            out.update({f"{k}_{name}": x for k, x in graph_quality(v, n_rel).items()})
+        return out
+    v = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts, dtype=np.float64)
+    if v.ndim == 2:
+        return graph_quality({str(i): row for i, row in enumerate(v)}, n_rel)
+    if v.shape != (3 * n_rel + 2,):
+        raise ValueError(f"graph_quality: expected {3 * n_rel + 2} counts")
+    tp, fp, fn = v[0:3 * n_rel:3], v[1:3 * n_rel:3], v[2:3 * n_rel:3]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        def prf(t, p, n):
+            pr, rc, f1 = t / (t + p), t / (t + n), 2 * t / (2 * t + p + n)
+            return pr, rc, f1
+        micro = prf(tp.sum(), fp.sum(), fn.sum())
+        per = prf(tp, fp, fn)
+        seen = (tp + fp + fn) > 0
+        macro = [float(np.nan_to_num(x[seen]).mean()) if seen.any() else float("nan") for x in per]
+        acc = v[3 * n_rel + 1] / v[3 * n_rel]
+    out = {"rel_asserted": float(tp.sum() + fp.sum()), "rel_gt": float(tp.sum() + fn.sum()), "nodes": float(v[3 * n_rel]),
+           "node_acc": float(acc)}
+    for name, m, M_, p in zip(("precision", "recall", "f1"), micro, macro, per):
+        out[f"micro_{name}"], out[f"macro_{name}"], out[f"per_class_{name}"] = float(m), M_, p
+    return out
+
+
+@torch.no_grad()
 def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1,
                recall_k: bool = False, zero_shot=None) -> Dict[str, float]:
     """``batches`` yields this rank's dicts with the reference loader's item names

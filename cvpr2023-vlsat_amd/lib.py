@@ -84,6 +84,10 @@ _SIGNATURES = {
     "vlsat_scene_graph_scratch_bytes": (C.c_int64, [_i64, _i64, _i32, _i32, _i32, _i32, _i32]),
     "vlsat_k_exp": (C.c_int, [_vp, _i64, _vp, _vp]),
     "vlsat_forward_scene_graph": (C.c_int, [_vp] * 6 + [_i32] * 4 + [_vp] * 6 + [_vp]),
+    "vlsat_graph_decode": (C.c_int, [_vp] * 5 + [_i32] * 9 + [_vp] * 7 + [_vp]),
+    "vlsat_graph_decode_scratch_bytes": (C.c_int64, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "vlsat_graph_decode_counts": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_vp, _vp]),
+    "vlsat_forward_graph": (C.c_int, [_vp] * 6 + [_i32] * 5 + [_vp] * 13 + [_vp]),
     "vlsat_scene_checksums": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "vlsat_comm_unique_id": (C.c_int, [_vp]),
     "vlsat_comm_init": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),

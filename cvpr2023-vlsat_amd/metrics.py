@@ -566,6 +566,241 @@ def scene_graph_topk_host(obj_logits, rel, edges, batch_ids, n_scenes, multi_rel
     return SceneGraph(trip, score, n_valid)
 
 
+# ---- the decoded scene graph: labels per object, asserted predicates per pair (csrc/graph_decode.hip) ----
+GD_MAX_LABELS, GD_MAX_REL = 8, 4096
+_GD_SCORES = {"rel": 0, "triplet": 1}
+
+
+class DecodedGraph:
+    """The graph a model asserts for every scene of a batch.  Nodes: ``labels`` int32 / ``label_probs`` float32 [N, n_labels], the
+    most probable classes of every object, descending.  Relations: ``edge`` (row of the batch's edge list) and ``pred`` int32
+    [S, max_rel], ``score`` float32 [S, max_rel], ordered by score descending, then edge, predicate ascending; ``n_total`` int32
+    [S] asserted (edge, predicate) pairs, ``n_valid`` = min(n_total, max_rel) rows kept; rows past ``n_valid[s]`` hold -1 / 0
+    (include/vlsat.h, vlsat_graph_decode)."""
+    __slots__ = ("labels", "label_probs", "edge", "pred", "score", "n_valid", "n_total")
+
+    def __init__(self, labels, label_probs, rels, score, n_valid, n_total):
+        self.labels, self.label_probs = labels, label_probs
+        self.edge, self.pred = rels[..., 0], rels[..., 1]
+        self.score, self.n_valid, self.n_total = score, n_valid, n_total
+
+    def scene(self, s: int, edge_offset: int = 0, nodes=None) -> "DecodedGraph":
+        """Scene ``s`` as a one-scene graph; ``edge_offset`` is subtracted from its edge rows (the scene's first row in the batch);
+        ``nodes`` = (first, end) node rows of the scene (None: the node tables stay the batch's)."""
+        g = DecodedGraph.__new__(DecodedGraph)
+        for k in ("pred", "score", "n_valid", "n_total"):
+            setattr(g, k, getattr(self, k)[s:s + 1])
+        e = self.edge[s:s + 1]
+        g.edge = torch.where(e >= 0, e - edge_offset, e) if edge_offset else e
+        sl = slice(None) if nodes is None else slice(int(nodes[0]), int(nodes[1]))
+        g.labels, g.label_probs = self.labels[sl], self.label_probs[sl]
+        return g
+
+    def cpu(self) -> "DecodedGraph":
+        g = DecodedGraph.__new__(DecodedGraph)
+        for k in self.__slots__:
+            setattr(g, k, getattr(self, k).cpu())
+        return g
+
+
+def decode_thresholds(threshold, n_rel: int, device) -> torch.Tensor:
+    """``threshold`` (a float, or a length-R sequence / tensor) as the float32 [R] device vector the kernels compare with."""
+    if torch.is_tensor(threshold):
+        t = threshold.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    elif isinstance(threshold, (int, float)):
+        t = torch.full((n_rel,), float(threshold), dtype=torch.float32, device=device)
+    else:
+        t = torch.tensor([float(x) for x in threshold], dtype=torch.float32, device=device)
+    if t.numel() == 1 and n_rel != 1:
+        t = t.expand(n_rel)
+    if t.numel() != n_rel:
+        raise L.VlsatError(f"decode_graph: threshold must be a number or hold one value per predicate ({n_rel})")
+    return t.contiguous()
+
+
+def _gd_args(obj_logits, rel, edges, batch_ids, n_scenes, score, n_labels, max_rel):
+    if score not in _GD_SCORES:
+        raise NotImplementedError("score type", score)
+    n_labels, max_rel, n_scenes = int(n_labels), int(max_rel), int(n_scenes)
+    if obj_logits.dim() != 2 or rel.dim() != 2:
+        raise L.VlsatError("decode_graph: obj_logits must be [N,C] and rel [E,R]")
+    c, r = obj_logits.shape[1], rel.shape[1]
+    if not 1 <= c <= 1024 or not 1 <= r <= 32:
+        raise L.VlsatError("decode_graph: 1..1024 object and 1..32 relation classes")
+    if not 1 <= n_labels <= GD_MAX_LABELS or n_labels > c:
+        raise L.VlsatError(f"decode_graph: n_labels must be in 1..{GD_MAX_LABELS} (and at most the object class count)")
+    if not 1 <= max_rel <= GD_MAX_REL:
+        raise L.VlsatError(f"decode_graph: max_rel must be in 1..{GD_MAX_REL}")
+    if n_scenes < 0 or (n_scenes > 1 and batch_ids is None):
+        raise L.VlsatError("decode_graph: batch_ids is required for more than one scene")
+    edges = edges.to(torch.int64).contiguous().view(-1, 2)
+    if edges.shape[0] != rel.shape[0]:
+        raise L.VlsatError("decode_graph: rel must be [E,R] and edges [E,2]")
+    if batch_ids is not None:
+        batch_ids = batch_ids.to(torch.int64).contiguous().view(-1)
+    return edges, batch_ids, n_scenes, _GD_SCORES[score], n_labels, max_rel
+
+
+def decode_graph(obj_logits: torch.Tensor, rel: torch.Tensor, edges: torch.Tensor, batch_ids: torch.Tensor | None, n_scenes: int,
+                 multi_rel_outputs: bool = True, threshold=0.5, score: str = "rel", n_labels: int = 3, max_rel: int = 1024,
+                 obj_probs: torch.Tensor | None = None, rel_probs: torch.Tensor | None = None) -> DecodedGraph:
+    """The graph the outputs assert, per scene: for every object its ``n_labels`` most probable classes, and the (edge,
+    predicate) pairs that pass the reference's decision rule (eva_utils_acc.py:42-63, 176-181; get_gt :19-22) -- multi-label:
+    every predicate with probability >= its threshold; single label (``rel`` holds log-probabilities): the arg-max predicate
+    unless it is class 0 = none or below its threshold.  ``score`` = "rel" ranks by the predicate probability, "triplet" by
+    fl(fl(s * o) * r) with the two nodes' top-1 probabilities; at most ``max_rel`` pairs per scene are kept, in (score
+    descending, edge, predicate ascending) order.  ``threshold``: a float or one value per predicate.  Inputs as for
+    ``scene_graph_topk``; ``rel_probs`` [E, R], when given, are the predicate probabilities themselves (``rel`` is then not read).  Device tensors: the HIP kernels, asynchronous, no host round trip.  CPU tensors: ``decode_graph_host``."""
+    if not obj_logits.is_cuda:
+        return decode_graph_host(obj_logits, rel, edges, batch_ids, n_scenes, multi_rel_outputs, threshold, score, n_labels, max_rel,
+                                 obj_probs, rel_probs)
+    lib = L.load()
+    n, c = obj_logits.shape
+    edges, batch_ids, n_scenes, mode, n_labels, max_rel = _gd_args(obj_logits, rel, edges, batch_ids, n_scenes, score, n_labels, max_rel)
+    e, r = rel.shape
+    dev = obj_logits.device
+    thr = decode_thresholds(threshold, r, dev)
+    r_probs = _rel_probs(rel, rel_probs, multi_rel_outputs, exp_probs)
+    obj_probs = softmax_rows(obj_logits.float()) if obj_probs is None else obj_probs.float().contiguous()
+    labels = torch.empty(n, n_labels, dtype=torch.int32, device=dev)
+    label_probs = torch.empty(n, n_labels, dtype=torch.float32, device=dev)
+    rels = torch.empty(n_scenes, max_rel, 2, dtype=torch.int32, device=dev)
+    sc = torch.empty(n_scenes, max_rel, dtype=torch.float32, device=dev)
+    n_valid = torch.empty(n_scenes, dtype=torch.int32, device=dev)
+    n_total = torch.empty(n_scenes, dtype=torch.int32, device=dev)
+    nbytes = int(lib.vlsat_graph_decode_scratch_bytes(e, c, r, n_scenes, n_labels, max_rel))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L.check(lib.vlsat_graph_decode(obj_probs.data_ptr(), r_probs.data_ptr(), edges.data_ptr(), L.ptr(batch_ids), thr.data_ptr(), n, e, c,
+                                   r, n_scenes, int(bool(multi_rel_outputs)), mode, n_labels, max_rel, scratch.data_ptr(),
+                                   labels.data_ptr(), label_probs.data_ptr(), rels.data_ptr(), sc.data_ptr(), n_valid.data_ptr(),
+                                   n_total.data_ptr(), L.stream_ptr()))
+    return DecodedGraph(labels, label_probs, rels, sc, n_valid, n_total)
+
+
+def _rel_probs(rel, rel_probs, multi_rel_outputs, exp):
+    if rel_probs is not None:
+        if rel_probs.shape != rel.shape:
+            raise L.VlsatError("decode_graph: rel_probs must have the shape of rel")
+        return rel_probs.float().contiguous()
+    return rel.float().contiguous() if multi_rel_outputs else exp(rel)
+
+
+def _asserted(rp: torch.Tensor, thr: torch.Tensor, multi_rel_outputs: bool) -> torch.Tensor:
+    """bool [E, R]: the decisions of the decode on predicate probabilities ``rp``."""
+    on = rp >= thr[None, :]
+    if not multi_rel_outputs and rp.shape[0]:
+        best = rp.sort(dim=1, descending=True, stable=True).indices[:, 0]                # lowest index of the row maximum
+        pick = torch.zeros_like(on)
+        pick[torch.arange(rp.shape[0], device=rp.device), best] = True
+        pick[:, 0] = False                                                            # class 0 = none
+        on = on & pick
+    return on
+
+
+@torch.no_grad()
+def decode_graph_host(obj_logits, rel, edges, batch_ids, n_scenes, multi_rel_outputs=True, threshold=0.5, score="rel", n_labels=3,
+                      max_rel=1024, obj_probs=None, rel_probs=None) -> DecodedGraph:
+    """``decode_graph`` stated in PyTorch on whatever device the inputs are (the role ``scene_graph_topk_host`` plays for the
+    top-K list).  Exact; for CPU tests and devices without the HIP library."""
+    n, c = obj_logits.shape
+    edges, batch_ids, n_scenes, mode, n_labels, max_rel = _gd_args(obj_logits, rel, edges, batch_ids, n_scenes, score, n_labels, max_rel)
+    e, r = rel.shape
+    dev = obj_logits.device
+    thr = decode_thresholds(threshold, r, dev)
+    rp = _rel_probs(rel, rel_probs, multi_rel_outputs, lambda x: x.float().exp().contiguous())
+    probs = (torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()).contiguous()
+    sv, si = probs.sort(dim=1, descending=True, stable=True)                             # equal values: ascending class
+    labels, label_probs = si[:, :n_labels].to(torch.int32).contiguous(), sv[:, :n_labels].contiguous()
+    rels = torch.full((n_scenes, max_rel, 2), -1, dtype=torch.int32, device=dev)
+    sc = torch.zeros(n_scenes, max_rel, dtype=torch.float32, device=dev)
+    n_valid = torch.zeros(n_scenes, dtype=torch.int32, device=dev)
+    n_total = torch.zeros(n_scenes, dtype=torch.int32, device=dev)
+    if e == 0 or n_scenes == 0:
+        return DecodedGraph(labels, label_probs, rels, sc, n_valid, n_total)
+    a, b = edges[:, 0], edges[:, 1]
+    scene = batch_ids[a] if batch_ids is not None else torch.zeros(e, dtype=torch.int64, device=dev)
+    val = rp if mode == 0 else (label_probs[a, 0] * label_probs[b, 0])[:, None] * rp      # fl(fl(s * o) * r)
+    on = _asserted(rp, thr, multi_rel_outputs)
+    ed, pr = on.nonzero(as_tuple=True)                                                # (edge, predicate) ascending
+    v = val[ed, pr]
+    for s in range(n_scenes):
+        sel = scene[ed] == s
+        es, ps, vs = ed[sel], pr[sel], v[sel]
+        order = vs.argsort(descending=True, stable=True)[:max_rel]
+        k = order.numel()
+        n_total[s], n_valid[s] = es.numel(), k
+        rels[s, :k, 0], rels[s, :k, 1], sc[s, :k] = es[order].int(), ps[order].int(), vs[order]
+    return DecodedGraph(labels, label_probs, rels, sc, n_valid, n_total)
+
+
+def decode_counts_width(n_rel: int) -> int:
+    """Fields of the decode counts: per predicate tp, fp, fn, then nodes, nodes whose top-1 label is right."""
+    return 3 * n_rel + 2
+
+
+def _gt_hot(gt_rel: torch.Tensor, e: int, r: int, multi_rel_outputs: bool) -> torch.Tensor:
+    """bool [E, R] ground truth of the counts: the multi-hot target (== 1), or a single label's one-hot with 0 = none."""
+    if multi_rel_outputs:
+        if gt_rel.shape != (e, r):
+            raise L.VlsatError("decode_counts: gt_rel must be the multi-hot [E,R] target")
+        return gt_rel == 1
+    if gt_rel.shape != (e,):
+        raise L.VlsatError("decode_counts: gt_rel must be the [E] label vector of a single-label model")
+    k = torch.arange(r, device=gt_rel.device)[None, :]
+    return (gt_rel[:, None] == k) & (k != 0)
+
+
+def decode_counts(obj_logits: torch.Tensor, rel: torch.Tensor, gt_cls: torch.Tensor, gt_rel: torch.Tensor,
+                  multi_rel_outputs: bool = True, threshold=0.5, obj_probs: torch.Tensor | None = None,
+                  counts: torch.Tensor | None = None, rel_probs: torch.Tensor | None = None) -> torch.Tensor:
+    """The decisions of ``decode_graph`` before its cap, counted against ground truth: int64 [3 R + 2] -- per predicate tp, fp, fn
+    at 3 k + {0, 1, 2}, then nodes and nodes whose top-1 label is ``gt_cls``.  ``gt_rel``: the int64 multi-hot [E, R] target, or
+    int64 [E] (0 = none) for a single-label model.  Additive: pass ``counts`` (device int64, zeroed once) to accumulate over
+    batches, from several streams if need be.  ``evaluate.graph_quality`` turns the sums into precision / recall / F1."""
+    if not obj_logits.is_cuda:
+        out = decode_counts_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs, threshold, obj_probs, rel_probs)
+        return out if counts is None else counts.add_(out)
+    lib = L.load()
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    dev = obj_logits.device
+    thr = decode_thresholds(threshold, r, dev)
+    gt_rel = gt_rel.to(torch.int64).contiguous()
+    if gt_rel.shape != ((e, r) if multi_rel_outputs else (e,)):
+        raise L.VlsatError("decode_counts: gt_rel must be multi-hot [E,R] (multi-label) or [E] (single label)")
+    gt_cls = gt_cls.to(torch.int64).contiguous().view(-1)
+    if gt_cls.numel() != n:
+        raise L.VlsatError("decode_counts: gt_cls must hold one class per node")
+    r_probs = _rel_probs(rel, rel_probs, multi_rel_outputs, exp_probs)
+    obj_probs = softmax_rows(obj_logits.float()) if obj_probs is None else obj_probs.float().contiguous()
+    if counts is None:
+        counts = torch.zeros(decode_counts_width(r), dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or counts.numel() != decode_counts_width(r) or not counts.is_contiguous() or counts.device != dev:
+        raise L.VlsatError(f"decode_counts: counts must be a contiguous int64 [{decode_counts_width(r)}] tensor on the inputs' device")
+    L.check(lib.vlsat_graph_decode_counts(obj_probs.data_ptr(), r_probs.data_ptr(), gt_cls.data_ptr(), gt_rel.data_ptr(), thr.data_ptr(),
+                                          n, e, c, r, int(bool(multi_rel_outputs)), counts.data_ptr(), L.stream_ptr()))
+    return counts
+
+
+@torch.no_grad()
+def decode_counts_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs=True, threshold=0.5, obj_probs=None,
+                       rel_probs=None) -> torch.Tensor:
+    """``decode_counts`` stated in PyTorch."""
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    dev = obj_logits.device
+    thr = decode_thresholds(threshold, r, dev)
+    rp = _rel_probs(rel, rel_probs, multi_rel_outputs, lambda x: x.float().exp())
+    probs = torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()
+    on = _asserted(rp, thr, multi_rel_outputs)
+    hot = _gt_hot(gt_rel.to(torch.int64), e, r, multi_rel_outputs)
+    out = torch.zeros(decode_counts_width(r), dtype=torch.int64, device=dev)
+    out[0:3 * r:3], out[1:3 * r:3], out[2:3 * r:3] = (on & hot).sum(0), (on & ~hot).sum(0), (hot & ~on).sum(0)
+    top1 = probs.sort(dim=1, descending=True, stable=True).indices[:, 0] if n else torch.zeros(0, dtype=torch.int64, device=dev)
+    out[3 * r], out[3 * r + 1] = n, (top1 == gt_cls.to(torch.int64).view(-1)).sum()
+    return out
+
+
 def _edges_list(edges):
     return [(int(x[0]), int(x[1])) for x in (edges.tolist() if torch.is_tensor(edges) else np.asarray(edges).tolist())]
 

@@ -549,7 +549,52 @@ class VLSATModel:
         return M.SceneGraph(trip[0], score[0], n_valid[0]), M.SceneGraph(trip[1], score[1], n_valid[1])
 
     @torch.no_grad()
-    def forward_3d(self, obj_points, edge_indices, descriptor, batch_ids=None, fc_sizes: Optional[Sequence[int]] = None):
+    def decode_graph(self, obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids=None, threshold=0.5, score: str = "rel",
+                     n_labels: int = 3, max_rel: int = 1024, multi_rel_outputs: Optional[bool] = None,
+                     fc_sizes: Optional[Sequence[int]] = None):
+        """The decoded scene graph of every scene: ``(graph_3d, graph_2d)``, two ``metrics.DecodedGraph`` -- per object its
+        ``n_labels`` most probable classes, per scene the (edge, predicate) pairs the model asserts (``metrics.decode_graph``:
+        the reference's decision rule, ``threshold`` a float or one value per predicate), at most ``max_rel`` per scene.  No labels.
+        ``vlsat_forward_graph``: forward + softmax of the object heads + the decode in ONE library call, intermediates in the
+        plan's memory.  ``obj_2d_feats=None`` takes the 3D-only forward and returns ``(graph_3d, None)``: the route of an
+        unlabelled scan, whose 2D features cannot exist (the reference's feature files are named after the ground-truth class).
+        ``multi_rel_outputs`` (default: the model's) selects the decision rule.  Inputs as for ``forward`` (``edge_indices`` int64
+        [2,E]); the edges must be grouped by scene in ascending order, as the loader and ``scan.prepare_scan`` yield them."""
+        from . import metrics as M
+        if score not in M._GD_SCORES:
+            raise NotImplementedError("score type", score)
+        use_2d = obj_2d_feats is not None
+        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, edge_indices, descriptor, need_2d=use_2d)
+        c = self.config
+        n_labels, max_rel = int(n_labels), int(max_rel)
+        if not 1 <= n_labels <= min(M.GD_MAX_LABELS, c.num_obj_class) or not 1 <= max_rel <= M.GD_MAX_REL:
+            raise L.VlsatError(f"decode_graph: n_labels must be in 1..{M.GD_MAX_LABELS} and max_rel in 1..{M.GD_MAX_REL}")
+        multi = bool(c.multi_rel_outputs if multi_rel_outputs is None else multi_rel_outputs)
+        with torch.cuda.device(self.device):
+            plan = self._plan(edge_indices, batch_ids, n, p, fc_sizes)
+            if plan.perm is not None:
+                raise L.VlsatError("decode_graph: edge_indices must be grouped by scene in ascending scene order")
+            s = C.c_int32()
+            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
+            n_scenes, nb = s.value, 2 if use_2d else 1
+            thr = M.decode_thresholds(threshold, c.num_rel_class, self.device)
+            edges_e2 = edge_indices.to(self.device).t().contiguous()
+            labels = torch.empty(nb, n, n_labels, dtype=torch.int32, device=self.device)
+            label_probs = torch.empty(nb, n, n_labels, dtype=torch.float32, device=self.device)
+            rels = torch.empty(nb, n_scenes, max_rel, 2, dtype=torch.int32, device=self.device)
+            sc = torch.empty(nb, n_scenes, max_rel, dtype=torch.float32, device=self.device)
+            n_valid = torch.empty(nb, n_scenes, dtype=torch.int32, device=self.device)
+            n_total = torch.empty(nb, n_scenes, dtype=torch.int32, device=self.device)
+            outs = [[t[b].data_ptr() for t in (labels, label_probs, rels, sc, n_valid, n_total)] if b < nb else [None] * 6
+                    for b in range(2)]
+            L.check(self._lib.vlsat_forward_graph(self._h, plan.handle, pts.data_ptr(), L.ptr(f2d), desc.data_ptr(), edges_e2.data_ptr(),
+                                                  n_scenes, int(multi), M._GD_SCORES[score], n_labels, max_rel, thr.data_ptr(),
+                                                  *outs[0], *outs[1], L.stream_ptr()))
+        graphs = [M.DecodedGraph(labels[b], label_probs[b], rels[b], sc[b], n_valid[b], n_total[b]) for b in range(nb)]
+        return graphs[0], (graphs[1] if use_2d else None)
+
+    @torch.no_grad()
+    def forward_3d(self,obj_points, edge_indices, descriptor, batch_ids=None, fc_sizes: Optional[Sequence[int]] = None):
         """3D-only deployment (no image features): returns (obj_logits_3d, rel_cls_3d), bit-identical to
         the first and third outputs of ``forward`` -- the 3D branch never reads the 2D branch
         (cf. reference src/model/SGFN_MMG/model_single.py:247-281) -- at about half the work."""

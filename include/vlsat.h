@@ -466,6 +466,65 @@ int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan plan, const float* obj_
                               int32_t top_k, int32_t topk_each, int32_t* triplets_3d, float* scores_3d, int32_t* n_valid_3d,
                               int32_t* triplets_2d, float* scores_2d, int32_t* n_valid_2d, void* stream);
 
+/* The decoded scene graph: one label per object with a few alternatives, and per ordered pair the predicates the model ASSERTS --
+ * the decision rule the reference's evaluation states (src/utils/eva_utils_acc.py:42-63, 176-181: a multi-label edge predicts "none"
+ * exactly when no predicate reaches confidence_threshold = 0.5; get_gt :19-22: class 0 of a single-label edge is "none") applied
+ * to the outputs of every scene of a batch (csrc/graph_decode.hip).  No labels are read.
+ *   nodes       labels int32 / label_probs float [n_nodes][n_labels]: the n_labels largest entries of obj_probs[n, :], descending,
+ *               equal values in ascending class order.
+ *   decisions   multi_label = 1: predicate k of edge e is asserted iff rel_probs[e, k] >= thresholds[k] (fp32 compare; equality
+ *               passes).  multi_label = 0: k* = the lowest index of the row maximum; the edge asserts k* iff k* != 0 and
+ *               rel_probs[e, k*] >= thresholds[k*] -- pass exp(log-probabilities) of a MODEL.multi_rel_outputs = false model.
+ *               thresholds: float [n_rel_class] in DEVICE memory.
+ *   score       score_mode 0: rel_probs[e, k].  score_mode 1: fl(fl(s * o) * rel_probs[e, k]) (two roundings, no FMA), s / o the
+ *               top-1 probabilities of the edge's two nodes.
+ *   output      n_total int32 [n_scenes] = asserted (e, k) pairs of the scene; n_valid = min(n_total, max_rel); rels int32
+ *               [n_scenes][max_rel][2] = (edge, predicate), edge being the row of `edges` (batch-wide); scores float
+ *               [n_scenes][max_rel]; the rows of a scene are the first n_valid of its asserted pairs under the total order (score
+ *               descending, edge ascending, predicate ascending); rows past n_valid hold -1 / 0.0f.  Every field is written, and
+ *               the output is fully determined by the inputs: there is no unspecified tie rule.
+ * Limits: n_labels 1..8 (and <= n_obj_class), max_rel 1..4096, n_obj_class <= 1024, n_rel_class <= 32, n_edges <= 2^26 and
+ * n_edges * n_rel_class < 2^31; anything else is an error, never a clamp.  Preconditions (as for vlsat_scene_graph_topk): the
+ * scene of edge e is batch_ids[edges[e, 0]] in [0, n_scenes) (batch_ids may be NULL for one scene), edges arrive grouped by scene
+ * in ascending scene order, node indices are in range, no NaN, probabilities are non-negative.  scratch:
+ * vlsat_graph_decode_scratch_bytes(...) bytes of device memory the call may overwrite (n_edges x (5 n_rel_class + 4) bytes -- per
+ * edge its asserted predicates as sorted 4-byte keys with a 1-byte predicate each, and their number -- plus the scene offsets;
+ * 0 = arguments out of range).  All device pointers; asynchronous on `stream`: no host synchronisation, no runtime fill, no
+ * allocation, no global atomics. */
+int vlsat_graph_decode(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids,
+                       const float* thresholds, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                       int32_t n_scenes, int32_t multi_label, int32_t score_mode /* 0 rel, 1 triplet */, int32_t n_labels,
+                       int32_t max_rel, void* scratch, int32_t* labels /* [n_nodes][n_labels] */,
+                       float* label_probs /* [n_nodes][n_labels] */, int32_t* rels /* [n_scenes][max_rel][2]: edge, predicate */,
+                       float* scores /* [n_scenes][max_rel] */, int32_t* n_valid /* [n_scenes] */, int32_t* n_total /* [n_scenes] */,
+                       void* stream);
+int64_t vlsat_graph_decode_scratch_bytes(int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes,
+                                         int32_t n_labels, int32_t max_rel);
+
+/* The decisions of vlsat_graph_decode BEFORE the cap, counted against ground truth: what a user chooses thresholds by.
+ * counts uint64 [3 * n_rel_class + 2], counts[i] += ...: per predicate k tp, fp, fn at 3 k + {0, 1, 2} (asserted and in gt,
+ * asserted and not in gt, in gt and not asserted), then nodes, then nodes whose top-1 class (lowest index of the row maximum) is
+ * gt_class.  gt_rel: multi_label = 1 the int64 multi-hot [n_edges][n_rel_class] vlsat_process_val_counts takes; multi_label = 0
+ * int64 [n_edges] with 0 = none (the counts of predicate 0 stay zero).  Zeroed by the caller before the first batch; integer
+ * atomics only, so batches may be accumulated from several streams and the sums are exact.  All device pointers; asynchronous. */
+int vlsat_graph_decode_counts(const float* obj_probs, const float* rel_probs, const int64_t* gt_class, const int64_t* gt_rel,
+                              const float* thresholds, int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
+                              int32_t multi_label, uint64_t* counts, void* stream);
+
+/* From points to the decoded graph in ONE call: vlsat_forward + softmax of the object heads (+ exp of the log-probabilities when
+ * MODEL.multi_rel_outputs = false) + vlsat_graph_decode per branch, enqueued back to back on `stream` with every intermediate in
+ * the plan's own memory (the compaction slots live in the evaluation scratch the plan already owns: the arena does not grow).
+ * obj_2d_feats == NULL selects the 3D-only forward (vlsat_forward with NULL 2D arguments): an unlabelled scan has no 2D features,
+ * because the reference's feature files are named after the ground-truth class.  Every 2D output pointer must then be NULL too;
+ * with obj_2d_feats every output is required; any other mix is VLSAT_EINVAL.  edges_e2 is the [E, 2] int64 (from, to) list in the
+ * plan's edge order; n_scenes must be the plan's scene count.  thresholds: device float [n_rel_class].  Outputs per branch as for
+ * vlsat_graph_decode.  All device pointers; asynchronous. */
+int vlsat_forward_graph(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
+                        const int64_t* edges_e2, int32_t n_scenes, int32_t multi_label, int32_t score_mode, int32_t n_labels,
+                        int32_t max_rel, const float* thresholds, int32_t* labels_3d, float* label_probs_3d, int32_t* rels_3d,
+                        float* scores_3d, int32_t* n_valid_3d, int32_t* n_total_3d, int32_t* labels_2d, float* label_probs_2d,
+                        int32_t* rels_2d, float* scores_2d, int32_t* n_valid_2d, int32_t* n_total_2d, void* stream);
+
 /* The additive fp64 metrics vector of one rank's batch -- what the path's one all-reduce carries when no labels are at hand
  * (bench.py; the label-based counts of validation(), reference src/model/model.py:214-242, come from vlsat_eval_ranks):
  * out9 = {n_scenes, n_nodes, n_edges, sum obj3d, sum obj2d, sum rel3d, sum rel2d, #nodes whose 3D and 2D top-1 class agree,
