@@ -274,6 +274,28 @@ int vlsat_fc_edges(const int32_t* node_ptr, const int64_t* edge_ptr, int32_t n_s
     return launch_fc_edges(node_ptr, edge_ptr, n_scenes, n_nodes, n_edges, edges, batch_ids, static_cast<hipStream_t>(stream));
 }
 
+// Proximity-pruned edge lists (csrc/proximity.hip; the rule is stated in include/vlsat.h)
+int vlsat_instance_boxes(const int32_t* instances, const float* scene_points, int64_t n_points, const int32_t* instance_ids, int32_t n_obj,
+                         int32_t* id_map, int32_t map_size, float* boxes, void* stream) {
+    if (!instance_ids || !id_map || !boxes || (n_points > 0 && (!instances || !scene_points)))
+        return fail(VLSAT_EINVAL, "instance_boxes: null argument");
+    return launch_instance_boxes(instances, scene_points, n_points, instance_ids, n_obj, id_map, map_size, boxes, static_cast<hipStream_t>(stream));
+}
+int32_t vlsat_proximity_lds_boxes(void) { return proximity_lds_boxes(); }
+size_t vlsat_proximity_scratch_bytes(int64_t n_nodes) { return proximity_scratch_bytes(n_nodes); }
+int vlsat_proximity_count(const float* boxes, const int32_t* node_ptr, int32_t n_scenes, int64_t n_nodes, float padding, int32_t max_neighbors,
+                          void* scratch, int64_t* edge_ptr, int64_t* batch_ids, void* stream) {
+    if (!node_ptr || !edge_ptr || (n_nodes > 0 && (!boxes || !scratch || !batch_ids))) return fail(VLSAT_EINVAL, "proximity_count: null argument");
+    return launch_proximity_count(boxes, node_ptr, n_scenes, n_nodes, padding, max_neighbors, scratch, edge_ptr, batch_ids,
+                                  static_cast<hipStream_t>(stream));
+}
+int vlsat_proximity_fill(const float* boxes, const int32_t* node_ptr, int32_t n_scenes, int64_t n_nodes, float padding, int32_t max_neighbors,
+                         const void* scratch, int64_t n_edges, int64_t capacity, int64_t* edges, void* stream) {
+    if (!node_ptr || (n_nodes > 0 && (!boxes || !scratch)) || (n_edges > 0 && !edges)) return fail(VLSAT_EINVAL, "proximity_fill: null argument");
+    return launch_proximity_fill(boxes, node_ptr, n_scenes, n_nodes, padding, max_neighbors, scratch, n_edges, capacity, edges,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int vlsat_k_softmax_rows(const float* x, int32_t ld, int32_t rows, int32_t cols, float* out, void* stream) {
     if (!x || !out) return fail(VLSAT_EINVAL, "softmax_rows: null argument");
     return launch_softmax_rows(x, ld, rows, cols, out, 0, static_cast<hipStream_t>(stream));

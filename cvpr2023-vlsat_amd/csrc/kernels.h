@@ -298,4 +298,15 @@ int launch_sample_objects(const int32_t* instances, int64_t n_points, const int3
 int launch_fc_edges(const int32_t* node_ptr, const int64_t* edge_ptr, int n_scenes, int64_t n_nodes, int64_t n_edges,
                     int64_t* edges, int64_t* batch_ids, hipStream_t s);
 
+// ---- proximity-pruned edge lists (proximity.hip; the rule is stated in include/vlsat.h) ----
+int proximity_lds_boxes();
+int launch_instance_boxes(const int32_t* instances, const float* scene_points, int64_t n_points, const int32_t* ids, int n_obj,
+                          int32_t* id_map, int map_size, float* boxes, hipStream_t s);
+// scratch: thr u64 [N] | row_off i64 [N+1] | row_count i32 [N]; count fills it, fill reads it
+size_t proximity_scratch_bytes(int64_t n_nodes);
+int launch_proximity_count(const float* boxes, const int32_t* node_ptr, int n_scenes, int64_t n_nodes, float padding, int max_neighbors,
+                           void* scratch, int64_t* edge_ptr, int64_t* batch_ids, hipStream_t s);
+int launch_proximity_fill(const float* boxes, const int32_t* node_ptr, int n_scenes, int64_t n_nodes, float padding, int max_neighbors,
+                          const void* scratch, int64_t n_edges, int64_t capacity, int64_t* edges, hipStream_t s);
+
 }  // namespace vlsat

@@ -71,6 +71,11 @@ _SIGNATURES = {
     "vlsat_fc_edges": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
     "vlsat_sample_objects_scratch": (_sz, [_i64, _i32]),
     "vlsat_sample_objects": (C.c_int, [_vp, _i64, _vp, _i32, _i32, C.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_instance_boxes": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "vlsat_proximity_lds_boxes": (_i32, []),
+    "vlsat_proximity_scratch_bytes": (_sz, [_i64]),
+    "vlsat_proximity_count": (C.c_int, [_vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_proximity_fill": (C.c_int, [_vp, _vp, _i32, _i64, _f32, _i32, _vp, _i64, _i64, _vp, _vp]),
     "vlsat_k_softmax_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "vlsat_eval_ranks": (C.c_int, [_vp] * 6 + [_i32] * 7 + [_f32] + [_vp] * 5 + [_vp]),
     "vlsat_eval_ranks_scratch_floats": (C.c_int64, [_i32] * 3),

@@ -221,7 +221,8 @@ def multi_view_feature_path(root: str, scene_id: str, instance_id: int, label: s
 def prepare_scan(mesh_or_path, instance2label: Dict[int, str], class_names: Sequence[str], rel_json: Sequence[Sequence],
                  relation_names: Sequence[str], num_points: int, seed: int, device="cuda:0", multi_rel_outputs: bool = True,
                  all_edge: bool = True, use_rgb: bool = False, use_normal: bool = False, multi_view_root: Optional[str] = None,
-                 scene_id: str = "", feature_loader: Optional[Callable[[int, str], np.ndarray]] = None) -> dict:
+                 scene_id: str = "", feature_loader: Optional[Callable[[int, str], np.ndarray]] = None,
+                 edge_mode: Optional[str] = None, padding: float = 0.2, max_neighbors: int = 0) -> dict:
     """One scene, from the label mesh to the batch dict of ``evaluate.validation`` / ``VLSATModel.forward``: obj_points [N,C,P],
     obj_2d_feats [N,512], descriptor [N,11], edge_indices [E,2] (the loader's layout: ``forward`` takes its transpose, like the
     reference's ``process_val``), batch_ids [N,1], gt_class [N], gt_rel_cls [E,R] | [E], plus
@@ -229,7 +230,14 @@ def prepare_scan(mesh_or_path, instance2label: Dict[int, str], class_names: Sequ
     = the selected vertex indices [N,P]).  Points are selected, centred and described on the device
     (``prep.sample_objects`` / ``prep.prepare_objects``); extra channels (rgb, normals) are gathered with the same selection and are
     not centred (dataset_3dssg.py:291-293 centres xyz only).  ``feature_loader(instance id, label) -> f32[512]`` overrides the
-    reference's file layout; without it and without ``multi_view_root`` the 2D features are zeros (as in the reference)."""
+    reference's file layout; without it and without ``multi_view_root`` the 2D features are zeros (as in the reference).
+
+    ``edge_mode=None`` leaves the edge list to ``all_edge``.  ``edge_mode="proximity"`` builds a sparse list on the device instead
+    (``prep.instance_boxes`` + ``prep.proximity_edges``: pairs whose boxes, padded by ``padding``, intersect; with ``max_neighbors > 0``
+    only pairs in which one node is among the other's ``max_neighbors`` nearest -- the list is symmetric, so an out-degree can exceed
+    the cap), computes the labels on that list, returns the unpadded ``boxes`` [N,6] too and omits ``fc_sizes``.  A pruned graph
+    changes the model's outputs (edge attention and aggregation see fewer edges); ``annotation_coverage`` tells how many annotated
+    pairs a setting keeps."""
     import torch
 
     from . import prep
@@ -238,16 +246,26 @@ def prepare_scan(mesh_or_path, instance2label: Dict[int, str], class_names: Sequ
     nodes = scene_nodes(mesh["instances"], instance2label)
     if not nodes:
         raise ScanError("no annotated instance owns a point of this mesh")
-    edges = edge_list(nodes, rel_json, all_edge)
-    gt_class, gt_rel = ground_truth(nodes, edges, instance2label, class_names, rel_json, relation_names, multi_rel_outputs)
+    if edge_mode not in (None, "proximity"):
+        raise ScanError(f"edge_mode {edge_mode!r}: None (all_edge decides) or 'proximity'")
+    proximity = edge_mode == "proximity"
     pts = scene_points(mesh, use_rgb, use_normal)
     dev = torch.device(device)
     d_inst = torch.from_numpy(mesh["instances"].astype(np.int32)).to(dev)
     d_ids = torch.tensor(nodes, dtype=torch.int32, device=dev)
     if len(set(nodes)) != len(nodes) or min(nodes) < 0 or max(nodes) >= (1 << 24):
         raise ScanError("instance ids of the scene's nodes must be distinct integers in [0, 2^24)")
-    choice, counts = prep.sample_objects(d_inst, d_ids, num_points, seed, map_size=max(65536, max(nodes) + 1))
+    map_size = max(65536, max(nodes) + 1)
     d_xyz = torch.from_numpy(np.ascontiguousarray(pts[:, :3], dtype=np.float32)).to(dev)
+    if proximity:
+        boxes = prep.instance_boxes(d_xyz, d_inst, d_ids, map_size)
+        d_edges = prep.proximity_edges(boxes, [len(nodes)], padding, max_neighbors)[0].t().contiguous()      # the loader's [E,2]
+        edges = d_edges.cpu().numpy()
+    else:
+        edges = edge_list(nodes, rel_json, all_edge)
+        d_edges = torch.from_numpy(edges).to(dev)
+    gt_class, gt_rel = ground_truth(nodes, edges, instance2label, class_names, rel_json, relation_names, multi_rel_outputs)
+    choice, counts = prep.sample_objects(d_inst, d_ids, num_points, seed, map_size=map_size)
     obj_points, descriptor = prep.prepare_objects(d_xyz, choice)
     if pts.shape[1] > 3:                 # colour / normal channels ride along with the same selection
         extra = torch.from_numpy(np.ascontiguousarray(pts[:, 3:], dtype=np.float32)).to(dev)
@@ -260,10 +278,22 @@ def prepare_scan(mesh_or_path, instance2label: Dict[int, str], class_names: Sequ
                         else np.load(multi_view_feature_path(multi_view_root, scene_id, i, name)))
     n = len(nodes)
     batch = {"obj_points": obj_points, "obj_2d_feats": torch.from_numpy(feats).to(dev), "descriptor": descriptor,
-             "edge_indices": torch.from_numpy(edges).to(dev),
+             "edge_indices": d_edges,
              "batch_ids": torch.zeros(n, 1, dtype=torch.int64, device=dev),
              "gt_class": torch.from_numpy(gt_class).to(dev), "gt_rel_cls": torch.from_numpy(gt_rel).to(dev),
              "n_scenes": 1, "instance_ids": nodes, "points_per_instance": counts, "choice": choice}
-    if all_edge:
+    if proximity:
+        batch["boxes"] = boxes
+    elif all_edge:
         batch["fc_sizes"] = [n]
     return batch
+
+
+def annotation_coverage(nodes: Sequence[int], edges: np.ndarray, rel_json: Sequence[Sequence]) -> Tuple[int, int]:
+    """(kept, total): the annotated ordered pairs between the scene's ``nodes`` (instance ids, node order; distinct pairs, whatever
+    number of relations a pair carries) that are present in ``edges`` (i64[E,2] node-index pairs), against all of them -- what a
+    pruned edge list can still be right about; the number to tune ``padding`` and ``max_neighbors`` with."""
+    pos = {n: k for k, n in enumerate(nodes)}
+    annotated = {(pos[r[0]], pos[r[1]]) for r in rel_json if r[0] in pos and r[1] in pos}
+    present = {(int(a), int(b)) for a, b in np.asarray(edges, dtype=np.int64).reshape(-1, 2)}
+    return len(annotated & present), len(annotated)

@@ -156,3 +156,16 @@ def switch_scenes(cfg: VLSATConfig) -> list:
             sc["obj_points"] = np.concatenate([sc["obj_points"], extra], 1)
         out.append(sc)
     return out
+
+
+def make_room(n_obj: int, pts_per_obj: int, seed: int, extent=(10.0, 10.0, 3.0)):
+    """A room with spatial structure (``make_scene`` has none: its objects all overlap): ``n_obj`` small boxes scattered over
+    ``extent`` metres, ``pts_per_obj`` points each -> (scene_points f32[n_obj * pts_per_obj, 3], instances i32[...] with ids
+    1..n_obj, object-major).  Objects are 0.2-1.2 m wide and up to 1 m tall, centres uniform in the room (the lower half in z)."""
+    g = np.random.default_rng([int(seed) & 0x7FFFFFFF, 0x200F])
+    ext = np.asarray(extent, dtype=np.float64)
+    centre = g.uniform(0.0, 1.0, (n_obj, 1, 3)) * ext * np.array([1.0, 1.0, 0.5])
+    size = g.uniform(0.2, 1.2, (n_obj, 1, 3)) * np.array([1.0, 1.0, 1.0 / 1.2])
+    pts = (centre + g.uniform(-0.5, 0.5, (n_obj, pts_per_obj, 3)) * size).astype(np.float32)
+    inst = np.repeat(np.arange(1, n_obj + 1, dtype=np.int32), pts_per_obj)
+    return np.ascontiguousarray(pts.reshape(-1, 3)), inst

@@ -314,6 +314,43 @@ int vlsat_sample_objects(const int32_t* instances, int64_t n_points, const int32
 int vlsat_fc_edges(const int32_t* node_ptr, const int64_t* edge_ptr, int32_t n_scenes, int64_t n_nodes, int64_t n_edges,
                    int64_t* edges, int64_t* batch_ids, void* stream);
 
+/* -------- proximity-pruned edge lists: the sparse alternative to vlsat_fc_edges for large scenes (csrc/proximity.hip) --------
+ *
+ * The rule (exact; prep.proximity_edges_host restates it in numpy, bit for bit):
+ *   boxes f32 [N,6] = lo.xyz, hi.xyz: the unpadded axis-aligned box of ALL points of an instance (the reference pads the same box by
+ *     0.2 per side, src/dataset/dataset_3dssg.py:286-288).  An instance without points has lo = +inf, hi = -inf.
+ *   cand(i,j):  i != j, same scene, and on each of the three axes  lo_i[a] - padding < hi_j[a] + padding  and
+ *     lo_j[a] - padding < hi_i[a] + padding  (strict; each side one fp32 operation).  An empty box is never a candidate.
+ *   d(i,j):  g_a = max(0, max(lo_i[a] - hi_j[a], lo_j[a] - hi_i[a]));  d = (g_x*g_x + g_y*g_y) + g_z*g_z in fp32, every operation
+ *     rounded to nearest on its own (no fused multiply-add), so d(i,j) and d(j,i) are the same bits.
+ *   key_i(j) = (bits(d) << 32) | local index of j in its scene  (d >= 0, so the bit order is the value order; ties go to the lower index).
+ *   keep_i(j):  key_i(j) is among the max_neighbors smallest keys over i's candidates.
+ *   edge (i,j) is emitted iff cand(i,j) and (max_neighbors <= 0  or  keep_i(j)  or  keep_j(i)).
+ * The list is symmetric ((i,j) present iff (j,i) is); a node's out-degree can EXCEED max_neighbors (it is kept by every node that
+ * ranks it among its own nearest), and per scene E <= min(n(n-1), 2 n max_neighbors).  Order: scenes in node order, source-major,
+ * targets ascending, node offsets applied -- the order of vlsat_fc_edges with the dropped pairs removed (a padding larger than the
+ * scene and no cap give vlsat_fc_edges' output element for element).
+ *
+ * vlsat_instance_boxes: instances int32 [Npts], scene_points f32 [Npts,3], instance_ids int32 [N] (distinct, each < map_size; id_map is
+ *   an int32 [map_size] scratch as in vlsat_sample_objects) -> boxes.  Points of other ids (background included) are ignored.  Exact:
+ *   min / max by integer atomics on an order-preserving code of the float.
+ * vlsat_proximity_count: node_ptr int32 [S+1] (device) -> edge_ptr int64 [S+1] and batch_ids int64 [N] in device memory, and the
+ *   scratch (vlsat_proximity_scratch_bytes(N) bytes) that vlsat_proximity_fill reads.  The caller reads edge_ptr[S] (the one host
+ *   wait), allocates edges int64 [2, capacity] and passes the count back as n_edges.
+ * vlsat_proximity_fill: same boxes / node_ptr / padding / max_neighbors / scratch -> edges (row 0 = from, row 1 = to, row stride =
+ *   capacity).  n_edges > capacity is VLSAT_EINVAL and nothing is written; no element at or beyond capacity of either row is written
+ *   whatever n_edges says.  No global atomics; memory O(N + E), work O(sum n_s^2).
+ * vlsat_proximity_lds_boxes: a block keeps the boxes of its rows' scenes in LDS up to this many, and reads global memory above it
+ *   (same result).  All pointers are device pointers; the calls are asynchronous. */
+int vlsat_instance_boxes(const int32_t* instances, const float* scene_points, int64_t n_points, const int32_t* instance_ids, int32_t n_obj,
+                         int32_t* id_map, int32_t map_size, float* boxes, void* stream);
+int32_t vlsat_proximity_lds_boxes(void);
+size_t vlsat_proximity_scratch_bytes(int64_t n_nodes);
+int vlsat_proximity_count(const float* boxes, const int32_t* node_ptr, int32_t n_scenes, int64_t n_nodes, float padding, int32_t max_neighbors,
+                          void* scratch, int64_t* edge_ptr, int64_t* batch_ids, void* stream);
+int vlsat_proximity_fill(const float* boxes, const int32_t* node_ptr, int32_t n_scenes, int64_t n_nodes, float padding, int32_t max_neighbors,
+                         const void* scratch, int64_t n_edges, int64_t capacity, int64_t* edges, void* stream);
+
 /* -------- eval ranking step (the caller of the path: process_val, reference SGFN_MMG/model.py:463-472) --- */
 
 /* out[r, :] = softmax(x[r, 0:cols]) -- F.softmax(objs_pred) of evaluate_triplet_topk
