@@ -296,6 +296,30 @@ int vlsat_proximity_fill(const float* boxes, const int32_t* node_ptr, int32_t n_
                                  static_cast<hipStream_t>(stream));
 }
 
+// Annotation transfer onto a predicted segmentation (csrc/label_transfer.hip; the rule is stated in include/vlsat.h)
+size_t vlsat_nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref) { return nearest_points_scratch_bytes(n_query, n_ref); }
+int vlsat_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
+                         int32_t* nn_index, float* nn_sqdist, void* stream) {
+    if (n_query > 0 && (!query || !nn_index || !nn_sqdist || (n_ref > 0 && (!ref || !scratch))))
+        return fail(VLSAT_EINVAL, "nearest_points: null argument");
+    return launch_nearest_points(query, n_query, ref, n_ref, max_sq_dist, scratch, nn_index, nn_sqdist, static_cast<hipStream_t>(stream));
+}
+size_t vlsat_segment_overlap_scratch_bytes(int32_t seg_map_size, int32_t gt_map_size) {
+    return segment_overlap_scratch_bytes(seg_map_size, gt_map_size);
+}
+int vlsat_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, int64_t n_query, const int32_t* gt_instances, int64_t n_ref,
+                          const int32_t* segment_ids, int32_t n_seg, const int32_t* gt_ids, int32_t n_gt, int32_t* id_maps,
+                          int32_t seg_map_size, int32_t gt_map_size, int32_t min_seg_size, double corr_thres, double occ_thres,
+                          int32_t occ_min_candidates, int32_t* size, int32_t* counts, int32_t* match, int32_t* best, int32_t* second,
+                          int32_t* n_candidates, void* stream) {
+    if (n_seg > 0 && (!segment_ids || !id_maps || !size || !match || !best || !second || !n_candidates || (n_gt > 0 && (!gt_ids || !counts)) ||
+                      (n_query > 0 && (!pd_segments || !nn_index)) || (n_ref > 0 && !gt_instances)))
+        return fail(VLSAT_EINVAL, "segment_overlap: null argument");
+    return launch_segment_overlap(pd_segments, nn_index, n_query, gt_instances, n_ref, segment_ids, n_seg, gt_ids, n_gt, id_maps, seg_map_size,
+                                  gt_map_size, min_seg_size, corr_thres, occ_thres, occ_min_candidates, size, counts, match, best, second,
+                                  n_candidates, static_cast<hipStream_t>(stream));
+}
+
 int vlsat_k_softmax_rows(const float* x, int32_t ld, int32_t rows, int32_t cols, float* out, void* stream) {
     if (!x || !out) return fail(VLSAT_EINVAL, "softmax_rows: null argument");
     return launch_softmax_rows(x, ld, rows, cols, out, 0, static_cast<hipStream_t>(stream));

@@ -309,4 +309,15 @@ int launch_proximity_count(const float* boxes, const int32_t* node_ptr, int n_sc
 int launch_proximity_fill(const float* boxes, const int32_t* node_ptr, int n_scenes, int64_t n_nodes, float padding, int max_neighbors,
                           const void* scratch, int64_t n_edges, int64_t capacity, int64_t* edges, hipStream_t s);
 
+// ---- annotation transfer onto a predicted segmentation (label_transfer.hip; the rule is stated in include/vlsat.h) ----
+size_t nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref);
+int launch_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
+                          int32_t* nn_index, float* nn_sqdist, hipStream_t s);
+// id_maps: int32 [seg_map_size + gt_map_size] scratch (segment id -> slot, then instance id -> slot)
+size_t segment_overlap_scratch_bytes(int32_t seg_map_size, int32_t gt_map_size);
+int launch_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, int64_t n_query, const int32_t* gt_instances, int64_t n_ref,
+                           const int32_t* segment_ids, int n_seg, const int32_t* gt_ids, int n_gt, int32_t* id_maps, int seg_map_size,
+                           int gt_map_size, int min_seg_size, double corr_thres, double occ_thres, int occ_min_candidates, int32_t* size,
+                           int32_t* counts, int32_t* match, int32_t* best, int32_t* second, int32_t* n_candidates, hipStream_t s);
+
 }  // namespace vlsat

@@ -76,6 +76,11 @@ _SIGNATURES = {
     "vlsat_proximity_scratch_bytes": (_sz, [_i64]),
     "vlsat_proximity_count": (C.c_int, [_vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),
     "vlsat_proximity_fill": (C.c_int, [_vp, _vp, _i32, _i64, _f32, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "vlsat_nearest_points_scratch_bytes": (_sz, [_i64, _i64]),
+    "vlsat_nearest_points": (C.c_int, [_vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "vlsat_segment_overlap_scratch_bytes": (_sz, [_i32, _i32]),
+    "vlsat_segment_overlap": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32]
+                              + [_vp] * 6 + [_vp]),
     "vlsat_k_softmax_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "vlsat_eval_ranks": (C.c_int, [_vp] * 6 + [_i32] * 7 + [_f32] + [_vp] * 5 + [_vp]),
     "vlsat_eval_ranks_scratch_floats": (C.c_int64, [_i32] * 3),

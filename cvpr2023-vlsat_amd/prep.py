@@ -169,3 +169,180 @@ def proximity_edges(boxes, n_per_scene: Sequence[int], padding: float = 0.2, max
     L.check(lib.vlsat_proximity_fill(boxes.data_ptr(), d_node.data_ptr(), S, N, float(padding), int(max_neighbors), scratch.data_ptr(),
                                      E, E, edges.data_ptr(), L.stream_ptr()))
     return edges, bids, edge_ptr
+
+
+# ---- annotation transfer onto a predicted segmentation (csrc/label_transfer.hip; the rule is stated in include/vlsat.h) ----------------
+def nearest_points_host(query, ref, max_sq_dist: float, chunk: int = 256):
+    """The rule of ``nearest_points`` in numpy, in the same fp32 operations (so every index and distance bit is the device's) ->
+    (nn_index i32[Q], nn_sqdist f32[Q]).  A sweep along x instead of the device's grid: the queries go in x order, a chunk at a time,
+    against the annotated points whose x lies within sqrt(max_sq_dist) of the chunk's (only those can have d2 <= max_sq_dist); the
+    answer is the minimum of the key (bits(d2) << 32) | index, which does not depend on how the candidates were found."""
+    import numpy as np
+
+    q = np.ascontiguousarray(np.asarray(query, dtype=np.float32)).reshape(-1, 3)
+    r = np.ascontiguousarray(np.asarray(ref, dtype=np.float32)).reshape(-1, 3)
+    m = np.float32(max_sq_dist)
+    if not m >= 0:
+        raise L.VlsatError("nearest_points: max_sq_dist must be >= 0 (it is a squared distance)")
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    best = np.full(len(q), none, dtype=np.uint64)
+    r_idx = np.nonzero(np.isfinite(r).all(1))[0]
+    q_idx = np.nonzero(np.isfinite(q).all(1))[0]
+    if len(r_idx) and len(q_idx):
+        r_idx = r_idx[np.argsort(r[r_idx, 0], kind="stable")]
+        rs, rx = r[r_idx], r[r_idx, 0].astype(np.float64)
+        q_idx = q_idx[np.argsort(q[q_idx, 0], kind="stable")]
+        # |q.x - r.x| of a pair with d2 <= m: the rounded dx dx is at most d2, the difference and the product are off by 2^-24 each,
+        # and a product that underflows to zero belongs to a |dx| below 2^-74
+        w = float(np.sqrt(np.float64(m))) * (1.0 + 2.0 ** -20) + 1e-20 if np.isfinite(m) else np.inf
+        with np.errstate(over="ignore", invalid="ignore"):
+            for c0 in range(0, len(q_idx), chunk):
+                qi = q_idx[c0:c0 + chunk]
+                qc = q[qi]
+                a = np.searchsorted(rx, float(qc[0, 0]) - w, "left")
+                b = np.searchsorted(rx, float(qc[-1, 0]) + w, "right")
+                acc = np.full(len(qi), none, dtype=np.uint64)
+                for p0 in range(a, b, 16384):
+                    rp, ri = rs[p0:min(p0 + 16384, b)], r_idx[p0:min(p0 + 16384, b)]
+                    dx, dy, dz = (qc[:, None, k] - rp[None, :, k] for k in range(3))
+                    d2 = (dx * dx + dy * dy) + dz * dz
+                    key = (np.ascontiguousarray(d2).view(np.uint32).astype(np.uint64) << np.uint64(32)) | ri.astype(np.uint64)[None, :]
+                    acc = np.minimum(acc, np.where(d2 <= m, key, none).min(1))
+                best[qi] = acc
+    found = best != none
+    nn_index = np.where(found, best & np.uint64(0xFFFFFFFF), 0).astype(np.int64).astype(np.int32)
+    nn_index[~found] = -1
+    nn_sqdist = np.where(found, (best >> np.uint64(32)).astype(np.uint32).view(np.float32), np.float32(np.inf)).astype(np.float32)
+    return nn_index, nn_sqdist
+
+
+def nearest_points(query, ref, max_sq_dist: float):
+    """query f32[Q,3] (the predicted cloud), ref f32[G,3] (the annotated cloud) -> (nn_index i32[Q], nn_sqdist f32[Q]): per query the
+    annotated point with the smallest ``d2 = (dx*dx + dy*dy) + dz*dz`` (fp32, every operation rounded on its own; ties to the lower
+    index) among those with ``d2 <= max_sq_dist``, else -1 and +inf.
+
+    ``max_sq_dist`` is a SQUARED distance: the reference compares Open3D's squared distance with its ``--max_dist`` (default 0.1;
+    data_processing/gen_data.py:268-269), so 0.1 means 0.316 in the units of the cloud.  Non-finite queries have no correspondence and
+    non-finite annotated points are never returned.  Exact and deterministic.  Device tensors run the HIP kernels (nothing is read
+    back); CPU tensors or arrays run ``nearest_points_host``."""
+    if not (isinstance(query, torch.Tensor) and query.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x   # noqa: E731
+        i, d = nearest_points_host(as_np(query), as_np(ref), max_sq_dist)
+        return torch.from_numpy(i), torch.from_numpy(d)
+    lib = L.load()
+    dev = query.device
+    query = query.contiguous()
+    ref = ref.to(dev).contiguous()
+    for name, t in (("query", query), ("ref", ref)):
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise L.VlsatError(f"nearest_points: {name} must be float32 [n,3]")
+    if not float(max_sq_dist) >= 0:
+        raise L.VlsatError("nearest_points: max_sq_dist must be >= 0 (it is a squared distance)")
+    Q, G = query.shape[0], ref.shape[0]
+    scratch = torch.empty(int(lib.vlsat_nearest_points_scratch_bytes(Q, G)), dtype=torch.uint8, device=dev)
+    nn_index = torch.empty(Q, dtype=torch.int32, device=dev)
+    nn_sqdist = torch.empty(Q, dtype=torch.float32, device=dev)
+    L.check(lib.vlsat_nearest_points(query.data_ptr(), Q, ref.data_ptr(), G, float(max_sq_dist), scratch.data_ptr(), nn_index.data_ptr(),
+                                     nn_sqdist.data_ptr(), L.stream_ptr()))
+    return nn_index, nn_sqdist
+
+
+def _overlap_ids(segment_ids, gt_ids):
+    import numpy as np
+
+    seg_ids = np.asarray(segment_ids, dtype=np.int64).reshape(-1)
+    g_ids = np.asarray(gt_ids, dtype=np.int64).reshape(-1)
+    for name, ids in (("segment_ids", seg_ids), ("gt_ids", g_ids)):
+        if len(ids) and (len(np.unique(ids)) != len(ids) or ids.min() < 0 or ids.max() >= (1 << 24)):
+            raise L.VlsatError(f"segment_overlap: {name} must be distinct integers in [0, 2^24)")
+    return seg_ids, g_ids
+
+
+def segment_overlap_host(pd_segments, nn_index, gt_instances, segment_ids, gt_ids, min_seg_size: int = 512, corr_thres: float = 0.5,
+                         occ_thres: float = 0.75, occ_min_candidates: int = 3) -> dict:
+    """The rule of ``segment_overlap`` in numpy and Python floats (fp64, the reference's own divisions) -> the same dict of numpy
+    arrays."""
+    import numpy as np
+
+    seg_ids, g_ids = _overlap_ids(segment_ids, gt_ids)
+    seg = np.asarray(pd_segments, dtype=np.int64).reshape(-1)
+    nn = np.asarray(nn_index, dtype=np.int64).reshape(-1)
+    inst = np.asarray(gt_instances, dtype=np.int64).reshape(-1)
+    if len(seg) != len(nn):
+        raise L.VlsatError("segment_overlap: one nearest index per predicted point")
+    if corr_thres != corr_thres or occ_thres != occ_thres:
+        raise L.VlsatError("segment_overlap: a threshold is NaN")
+    S, n_gt = len(seg_ids), len(g_ids)
+
+    def slots(values, ids):                          # slot of every value in ids, -1 when absent
+        if not len(ids):
+            return np.full(len(values), -1, dtype=np.int64)
+        order = np.argsort(ids)
+        pos = np.minimum(np.searchsorted(ids[order], values), len(ids) - 1)
+        return np.where(ids[order][pos] == values, order[pos], -1)
+
+    s_slot = slots(seg, seg_ids)
+    size = np.bincount(s_slot[s_slot >= 0], minlength=S).astype(np.int32)
+    has = (s_slot >= 0) & (nn >= 0) & (nn < len(inst))
+    g_slot = slots(inst[nn[has]], g_ids)
+    flat = s_slot[has][g_slot >= 0] * n_gt + g_slot[g_slot >= 0]
+    counts = np.bincount(flat, minlength=S * n_gt).astype(np.int32).reshape(S, n_gt)
+    match, best, second, n_cand = (np.full(S, v, dtype=np.int32) for v in (-1, 0, 0, 0))
+    for s in range(S):
+        c = counts[s]
+        n_cand[s] = int((c > 0).sum())
+        if not n_cand[s]:
+            continue
+        j = int(np.lexsort((g_ids, -c.astype(np.int64)))[0])       # the largest count, ties to the lower instance id
+        best[s], second[s] = c[j], np.delete(c, j).max(initial=0)
+        if size[s] > min_seg_size:
+            r1, r2 = float(best[s]) / float(size[s]), float(second[s]) / float(size[s])
+            occ = r2 / r1 if n_cand[s] >= occ_min_candidates else 0.0
+            if r1 > corr_thres and occ < occ_thres:
+                match[s] = j
+    return {"size": size, "counts": counts, "match": match, "best": best, "second": second, "n_candidates": n_cand}
+
+
+def segment_overlap(pd_segments, nn_index, gt_instances, segment_ids, gt_ids, min_seg_size: int = 512, corr_thres: float = 0.5,
+                    occ_thres: float = 0.75, occ_min_candidates: int = 3) -> dict:
+    """pd_segments i32[Q] (segment id per predicted point), nn_index i32[Q] (``nearest_points``), gt_instances i32[G] (instance id per
+    annotated point), segment_ids (the segments to consider: host sequence, distinct) and gt_ids (the label-eligible instances: those
+    with a label other than 'none'; host sequence, distinct) -> dict of ``size`` i32[S] (ALL points of a segment), ``counts``
+    i32[S, n_gt] (its points whose nearest annotated point belongs to the instance), ``match`` i32[S] (slot in ``gt_ids`` of the
+    accepted instance, or -1), ``best`` / ``second`` i32[S] (the largest count and the largest among the other instances) and
+    ``n_candidates`` i32[S] (instances with a non-zero count).
+
+    Accepted iff ``size > min_seg_size`` and ``best / size > corr_thres`` and ``occ < occ_thres``, all strict and in fp64, where
+    ``occ = second / best`` (as the ratio of the two ratios) when at least ``occ_min_candidates`` instances have a non-zero count and 0
+    otherwise.  The default 3 reproduces the reference's ``len(list) > 2`` (gen_data.py:331), under which a segment shared 51 : 49 by
+    exactly two instances is accepted; 2 is probably what was meant.  Device tensors run the HIP kernels (nothing is read back); CPU
+    tensors or arrays run ``segment_overlap_host``."""
+    if not (isinstance(pd_segments, torch.Tensor) and pd_segments.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x   # noqa: E731
+        out = segment_overlap_host(as_np(pd_segments), as_np(nn_index), as_np(gt_instances), segment_ids, gt_ids, min_seg_size, corr_thres,
+                                   occ_thres, occ_min_candidates)
+        return {k: torch.from_numpy(v) for k, v in out.items()}
+    lib = L.load()
+    dev = pd_segments.device
+    seg_ids, g_ids = _overlap_ids(segment_ids, gt_ids)
+    seg = pd_segments.to(torch.int32).contiguous().view(-1)
+    nn = nn_index.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    inst = gt_instances.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    if seg.numel() != nn.numel():
+        raise L.VlsatError("segment_overlap: one nearest index per predicted point")
+    S, n_gt = len(seg_ids), len(g_ids)
+    if S * n_gt >= 1 << 31:
+        raise L.VlsatError("segment_overlap: the table of counts has more than 2^31 - 1 entries")
+    seg_map_size = max(65536, int(seg_ids.max(initial=0)) + 1)
+    gt_map_size = max(65536, int(g_ids.max(initial=0)) + 1)
+    d_seg_ids = torch.from_numpy(seg_ids.astype("int32")).to(dev)
+    d_gt_ids = torch.from_numpy(g_ids.astype("int32")).to(dev)
+    id_maps = torch.empty(int(lib.vlsat_segment_overlap_scratch_bytes(seg_map_size, gt_map_size)), dtype=torch.uint8, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)   # noqa: E731
+    out = {"size": i32(S), "counts": i32(S, n_gt), "match": i32(S), "best": i32(S), "second": i32(S), "n_candidates": i32(S)}
+    L.check(lib.vlsat_segment_overlap(seg.data_ptr(), nn.data_ptr(), seg.numel(), inst.data_ptr(), inst.numel(), d_seg_ids.data_ptr(), S,
+                                      d_gt_ids.data_ptr(), n_gt, id_maps.data_ptr(), seg_map_size, gt_map_size, int(min_seg_size),
+                                      float(corr_thres), float(occ_thres), int(occ_min_candidates), out["size"].data_ptr(),
+                                      out["counts"].data_ptr(), out["match"].data_ptr(), out["best"].data_ptr(), out["second"].data_ptr(),
+                                      out["n_candidates"].data_ptr(), L.stream_ptr()))
+    return out

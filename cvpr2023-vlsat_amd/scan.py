@@ -297,3 +297,103 @@ def annotation_coverage(nodes: Sequence[int], edges: np.ndarray, rel_json: Seque
     annotated = {(pos[r[0]], pos[r[1]]) for r in rel_json if r[0] in pos and r[1] in pos}
     present = {(int(a), int(b)) for a, b in np.asarray(edges, dtype=np.int64).reshape(-1, 2)}
     return len(annotated & present), len(annotated)
+
+
+# ---- scoring a segmentation of one's own: which predicted segment is which annotated object --------------------------------------------
+def read_semseg(path_or_data) -> Dict[int, str]:
+    """3RScan ``semseg.v2.json`` -> {objectId: label} from ``segGroups`` in the file's order, unmapped (the reference's ``load_semseg``
+    without a label mapping, utils/util.py:44-61).  Mapping the names onto a class list is the caller's."""
+    data = path_or_data
+    if isinstance(path_or_data, (str, os.PathLike)):
+        with open(path_or_data) as f:
+            data = json.load(f)
+    if "segGroups" not in data:
+        raise ScanError("semseg: no segGroups")
+    return {int(g["objectId"]): g["label"] for g in data["segGroups"]}
+
+
+class LabelTransfer:
+    """What ``transfer_labels`` found.  ``instance2label`` {segment id: label} (ascending segment id; what ``prepare_scan`` takes for the
+    predicted mesh), ``segment_to_gt`` {segment id: annotated instance id}, ``gt_to_segments`` {instance id: [segment ids]} (instances
+    in the order of their first segment), and per considered-or-not segment of ``segment_ids`` (ascending, 0 excluded) the arrays
+    ``size``, ``best``, ``second``, ``n_candidates`` and ``matched_gt`` (instance id or -1); ``counts`` [S, len(gt_ids)] is the table
+    they come from, ``n_without_correspondence`` the number of predicted points with no annotated point within the distance."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return (f"LabelTransfer({len(self.segment_to_gt)} of {len(self.segment_ids)} segments matched to {len(self.gt_to_segments)} instances, "
+                f"{self.n_without_correspondence} points without a correspondence)")
+
+
+def transfer_labels(pd_mesh, gt_mesh, gt_instance2label: Dict[int, str], max_sq_dist: float = 0.1, min_seg_size: int = 512,
+                    corr_thres: float = 0.5, occ_thres: float = 0.75, occ_min_candidates: int = 3, device="cuda:0") -> LabelTransfer:
+    """Which annotated object is each segment of a predicted segmentation?  ``pd_mesh`` / ``gt_mesh``: a path or the dict of
+    ``read_ply`` (``instances`` = the segment id per vertex of the predicted cloud, the annotators' instance id per vertex of the label
+    mesh); ``gt_instance2label`` {instance id: label}, already mapped to the class list (``read_semseg`` gives the raw names); an
+    instance that is absent or labelled ``'none'`` takes no part.
+
+    The rule of the reference's data_processing/gen_data.py:196-349, stated in include/vlsat.h: every predicted point looks up its
+    nearest annotated point (``prep.nearest_points``; ``max_sq_dist`` is a SQUARED distance, as the reference's ``--max_dist`` is
+    compared with a squared distance), a segment with more than ``min_seg_size`` points takes the instance most of its points land on
+    when that share is above ``corr_thres`` and the runner-up is below ``occ_thres`` of it (``prep.segment_overlap``, where
+    ``occ_min_candidates`` is explained).  Segment 0 is background.  ``device=None`` (or "cpu") runs the numpy restatement, which gives
+    the same result.  The reference program cannot be run here, so agreement with it is by reading."""
+    import torch
+
+    from . import prep
+
+    pd = read_ply(pd_mesh) if isinstance(pd_mesh, (str, os.PathLike)) else pd_mesh
+    gt = read_ply(gt_mesh) if isinstance(gt_mesh, (str, os.PathLike)) else gt_mesh
+    pd_seg = np.asarray(pd["instances"]).astype(np.int64).reshape(-1)
+    gt_inst = np.asarray(gt["instances"]).astype(np.int64).reshape(-1)
+    segment_ids = np.unique(pd_seg)
+    segment_ids = segment_ids[segment_ids != 0]
+    gt_ids = np.asarray(sorted(int(i) for i, name in gt_instance2label.items() if name != "none"), dtype=np.int64)
+    for ids in (segment_ids, gt_ids):
+        if len(ids) and (ids.min() < 0 or ids.max() >= (1 << 24)):
+            raise ScanError("segment and instance ids must be integers in [0, 2^24)")
+    arrays = [np.ascontiguousarray(pd["points"][:, :3], dtype=np.float32), np.ascontiguousarray(gt["points"][:, :3], dtype=np.float32),
+              np.clip(pd_seg, -1, 1 << 24).astype(np.int32), np.clip(gt_inst, -1, 1 << 24).astype(np.int32)]
+    on_host = device is None or torch.device(device).type == "cpu"
+    d_pd, d_gt, d_seg, d_inst = (torch.from_numpy(a) if on_host else torch.from_numpy(a).to(device) for a in arrays)
+    nn_index, _ = prep.nearest_points(d_pd, d_gt, max_sq_dist)
+    ov = prep.segment_overlap(d_seg, nn_index, d_inst, segment_ids, gt_ids, min_seg_size, corr_thres, occ_thres, occ_min_candidates)
+    n_without = int((nn_index < 0).sum())
+    ov = {k: v.cpu().numpy() for k, v in ov.items()}
+    segment_to_gt, gt_to_segments, instance2label = {}, {}, {}
+    for s, slot in zip(segment_ids, ov["match"]):
+        if slot >= 0:
+            g = int(gt_ids[slot])
+            segment_to_gt[int(s)] = g
+            gt_to_segments.setdefault(g, []).append(int(s))
+            instance2label[int(s)] = gt_instance2label[g]
+    matched = np.where(ov["match"] >= 0, gt_ids[np.maximum(ov["match"], 0)] if len(gt_ids) else -1, -1).astype(np.int64)
+    return LabelTransfer(instance2label=instance2label, segment_to_gt=segment_to_gt, gt_to_segments=gt_to_segments,
+                         segment_ids=segment_ids, gt_ids=gt_ids, size=ov["size"], best=ov["best"], second=ov["second"],
+                         n_candidates=ov["n_candidates"], counts=ov["counts"], matched_gt=matched, n_without_correspondence=n_without)
+
+
+def inherit_relationships(match, rel_json: Sequence[Sequence], relation_names: Sequence[str], same_part: str = "same part") -> List[list]:
+    """The annotated relationships, carried over to the segments (gen_data.py:426-481) -> a ``rel_json`` for the predicted mesh.
+    ``match``: a ``LabelTransfer`` (or its ``gt_to_segments``).  Every annotated ``[src, tgt, k, name]`` whose two instances both have
+    accepted segments becomes one entry per (segment of src x segment of tgt), in the annotation's order; ``k`` is the name's index in
+    ``relation_names`` and a name outside the list is dropped.  When ``same_part`` is in ``relation_names`` every ordered pair of
+    distinct segments of one instance gets that relation; when it is not (the 26-name list), none is added -- the reference would
+    raise there."""
+    gt_to_segments = match if isinstance(match, dict) else match.gt_to_segments
+    pos = {n: k for k, n in enumerate(relation_names)}
+    out = []
+    for r in rel_json:
+        src, tgt, name = int(r[0]), int(r[1]), r[3]
+        if name not in pos or src not in gt_to_segments or tgt not in gt_to_segments:
+            continue
+        out.extend([int(a), int(b), pos[name], name] for a in gt_to_segments[src] for b in gt_to_segments[tgt])
+    if same_part in pos:
+        for group in gt_to_segments.values():
+            for i in range(len(group)):
+                for j in range(i + 1, len(group)):
+                    out.append([int(group[i]), int(group[j]), pos[same_part], same_part])
+                    out.append([int(group[j]), int(group[i]), pos[same_part], same_part])
+    return out

@@ -351,6 +351,52 @@ int vlsat_proximity_count(const float* boxes, const int32_t* node_ptr, int32_t n
 int vlsat_proximity_fill(const float* boxes, const int32_t* node_ptr, int32_t n_scenes, int64_t n_nodes, float padding, int32_t max_neighbors,
                          const void* scratch, int64_t n_edges, int64_t capacity, int64_t* edges, void* stream);
 
+/* -------- annotation transfer onto a predicted segmentation (csrc/label_transfer.hip) --------
+ *
+ * Which annotated instance is a segment of the user's own segmentation?  The rule of the reference's data_processing/gen_data.py
+ * (:196-216, :242-283 correspondence and counts, :312-349 decision), restated; prep.nearest_points_host / segment_overlap_host restate
+ * it in numpy with the same operations, so every index, distance bit and count is equal.  The reference program itself cannot be run
+ * (it needs open3d, trimesh and two modules that are not in its tree), so agreement with it is by reading, not by a recorded output.
+ *
+ * Nearest point (:249, :265-271).  For a predicted point q and an annotated point r:  d2 = (dx*dx + dy*dy) + dz*dz,  dx = q.x - r.x ...,
+ *   in fp32, every operation rounded to nearest on its own (no fused multiply-add).  key(r) = (bits(d2) << 32) | index of r (d2 >= 0:
+ *   the bit order is the value order; ties go to the lower index).  nn_index[q] = the index of the smallest key among the r with
+ *   d2 <= max_sq_dist, nn_sqdist[q] = its d2; without one, nn_index = -1 and nn_sqdist = +inf.  max_sq_dist is a SQUARED distance: the
+ *   reference compares Open3D's squared distance with its --max_dist (default 0.1).  A query with a non-finite coordinate has no
+ *   correspondence; an annotated point with one is never returned.
+ * Counts (:254-281).  size[s] = the number of ALL points of predicted segment s, with or without a correspondence.  count[s,g] = the
+ *   number of its points whose nearest annotated point belongs to instance g, for the instances the caller lists in gt_ids: those that
+ *   have a label other than 'none'.  Points that land on other instances count in size only.
+ * Decision (:215, :315-346), in fp64 with the reference's operations.  A segment is considered iff size[s] > min_seg_size (strict;
+ *   default 512).  ratio = count / size.  best = the instance with the largest count, ties to the lower instance id (a tie is never
+ *   accepted: acceptance needs ratio > 0.5).  occ = ratio_second / ratio_best when at least occ_min_candidates instances have a
+ *   non-zero count, else 0.  The default occ_min_candidates = 3 reproduces the reference's `len(list) > 2`, which lets a segment shared
+ *   51 : 49 between exactly two instances pass; 2 is probably what was meant.  Accept iff ratio_best > corr_thres and occ < occ_thres
+ *   (defaults 0.5 and 0.75, both strict).
+ *
+ * vlsat_nearest_points: query f32 [Q,3], ref f32 [G,3] -> nn_index int32 [Q], nn_sqdist f32 [Q].  Exact and deterministic: a uniform
+ *   grid over the finite annotated points, built as a counting sort (bounding box by integer atomics on an order-preserving code of
+ *   the float, per-cell histogram by int32 atomics, exclusive scan, fill), cell edge >= sqrt(max_sq_dist), at most 1024 cells per axis
+ *   and 2^21 in all (the edge grows until the extent fits, which keeps the search of the 27 cells around a query exact).  The order of
+ *   the points inside a cell varies from run to run, the result does not: every query takes the minimum of the 64-bit key.  Q = 0,
+ *   G = 0 and max_sq_dist = 0 (exact coincidence only) are valid; a negative or NaN max_sq_dist is VLSAT_EINVAL.  scratch:
+ *   vlsat_nearest_points_scratch_bytes(Q, G) bytes, 16-byte aligned.
+ * vlsat_segment_overlap: pd_segments int32 [Q], nn_index int32 [Q], gt_instances int32 [G], segment_ids int32 [S] (distinct, each in
+ *   [0, seg_map_size)), gt_ids int32 [n_gt] (distinct, each in [0, gt_map_size)); id_maps is an int32 [seg_map_size + gt_map_size]
+ *   scratch (vlsat_segment_overlap_scratch_bytes; id -> slot tables as in vlsat_sample_objects) -> size [S], counts [S, n_gt],
+ *   match [S] (the slot in gt_ids of the accepted instance, or -1), best / second [S] (the largest count and the largest among the
+ *   other instances), n_candidates [S] (instances with a non-zero count).  Integer atomics only; the library reads nothing back.
+ * All pointers are device pointers; the calls are asynchronous. */
+size_t vlsat_nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref);
+int vlsat_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
+                         int32_t* nn_index, float* nn_sqdist, void* stream);
+size_t vlsat_segment_overlap_scratch_bytes(int32_t seg_map_size, int32_t gt_map_size);
+int vlsat_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, int64_t n_query, const int32_t* gt_instances, int64_t n_ref,
+                          const int32_t* segment_ids, int32_t n_seg, const int32_t* gt_ids, int32_t n_gt, int32_t* id_maps,
+                          int32_t seg_map_size, int32_t gt_map_size, int32_t min_seg_size, double corr_thres, double occ_thres,
+                          int32_t occ_min_candidates, int32_t* size, int32_t* counts, int32_t* match, int32_t* best, int32_t* second,
+                          int32_t* n_candidates, void* stream);
+
 /* -------- eval ranking step (the caller of the path: process_val, reference SGFN_MMG/model.py:463-472) --- */
 
 /* out[r, :] = softmax(x[r, 0:cols]) -- F.softmax(objs_pred) of evaluate_triplet_topk
