@@ -320,6 +320,33 @@ int vlsat_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, i
                                   n_candidates, static_cast<hipStream_t>(stream));
 }
 
+// Segments merged into objects along "same part" edges (csrc/segment_merge.hip; the rule is stated in include/vlsat.h)
+size_t vlsat_merge_segments_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes) {
+    if (merge_segments_check_args(n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes)) return 0;
+    return merge_segments_scratch_bytes(n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes);
+}
+int vlsat_merge_segments(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids, const float* weights,
+                         int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes, int32_t same_part,
+                         float threshold, int32_t mutual, void* scratch, int32_t* root, int32_t* object, int32_t* n_objects, int32_t* totals,
+                         int32_t* member_ptr, int32_t* members, float* merged_probs, float* obj_weight, int64_t* obj_batch_ids,
+                         int32_t* edge_to_pair, int64_t* pair_edges, int32_t* pair_count, float* pair_probs, void* stream) {
+    RUN(merge_segments_check_args(n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes));
+    if (same_part < 0 || same_part >= n_rel_class) return fail(VLSAT_EINVAL, "merge_segments: same_part is not a predicate class");
+    if (threshold != threshold) return fail(VLSAT_EINVAL, "merge_segments: threshold is NaN");
+    if (mutual != 0 && mutual != 1) return fail(VLSAT_EINVAL, "merge_segments: mutual must be 0 or 1");
+    if (n_scenes > 1 && !batch_ids) return fail(VLSAT_EINVAL, "merge_segments: batch_ids is required for more than one scene");
+    if (n_nodes > 0 && n_scenes < 1) return fail(VLSAT_EINVAL, "merge_segments: nodes without a scene");
+    if (!scratch || !totals || !member_ptr || (n_scenes > 0 && !n_objects))
+        return fail(VLSAT_EINVAL, "merge_segments: null output or scratch");
+    if (n_nodes > 0 && (!obj_probs || !root || !object || !members || !merged_probs || !obj_weight || !obj_batch_ids))
+        return fail(VLSAT_EINVAL, "merge_segments: null node argument");
+    if (n_edges > 0 && (!rel_probs || !edges || !edge_to_pair || !pair_edges || !pair_count || !pair_probs))
+        return fail(VLSAT_EINVAL, "merge_segments: null edge argument");
+    return launch_merge_segments(obj_probs, rel_probs, edges, batch_ids, weights, n_nodes, n_edges, n_obj_class, n_rel_class, n_scenes, same_part,
+                                 threshold, mutual, scratch, root, object, n_objects, totals, member_ptr, members, merged_probs, obj_weight,
+                                 obj_batch_ids, edge_to_pair, pair_edges, pair_count, pair_probs, static_cast<hipStream_t>(stream));
+}
+
 int vlsat_k_softmax_rows(const float* x, int32_t ld, int32_t rows, int32_t cols, float* out, void* stream) {
     if (!x || !out) return fail(VLSAT_EINVAL, "softmax_rows: null argument");
     return launch_softmax_rows(x, ld, rows, cols, out, 0, static_cast<hipStream_t>(stream));

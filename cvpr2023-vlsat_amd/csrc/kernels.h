@@ -320,4 +320,13 @@ int launch_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, 
                            int gt_map_size, int min_seg_size, double corr_thres, double occ_thres, int occ_min_candidates, int32_t* size,
                            int32_t* counts, int32_t* match, int32_t* best, int32_t* second, int32_t* n_candidates, hipStream_t s);
 
+// ---- segments merged into objects along "same part" edges (segment_merge.hip; the rule is stated in include/vlsat.h) ----
+int merge_segments_check_args(int64_t N, int64_t E, int C, int R, int n_scenes);
+size_t merge_segments_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes);
+int launch_merge_segments(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids, const float* weights,
+                          int n_nodes, int n_edges, int C, int R, int n_scenes, int same_part, float threshold, int mutual, void* scratch,
+                          int32_t* root, int32_t* object, int32_t* n_objects, int32_t* totals, int32_t* member_ptr, int32_t* members,
+                          float* out_probs, float* out_weight, int64_t* obj_batch_ids, int32_t* edge_to_pair, int64_t* pair_edges,
+                          int32_t* pair_count, float* pair_probs, hipStream_t s);
+
 }  // namespace vlsat

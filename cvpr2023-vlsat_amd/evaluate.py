@@ -443,6 +443,122 @@ def decode(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d
         yield from scenes(*results[i])
 
 
+@torch.no_grad()
+def merged(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d: bool = True, same_part: Optional[int] = None,
+           threshold: float = 0.5, mutual: bool = False, **decode_args):
+    """Over-segmented scans as graphs of objects, in input order: yields per scene ``((merged_3d, decoded_3d), (merged_2d,
+    decoded_2d))`` -- one-scene ``metrics.MergedGraph`` / ``metrics.DecodedGraph``, rows counted within the scene (segments,
+    objects, merged edges) -- from ``VLSATModel.merge_graph``; the second pair is None with ``use_2d=False``.  ``same_part``: the
+    index of the "same part" predicate among the model's classes.  The weights of the pooled class probabilities are the batch's
+    ``weights`` or, without, its ``points_per_instance`` (None: all 1).  workers as for ``decode``; the merge reads two totals back
+    per batch and branch."""
+    import threading
+    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
+    workers = int(workers)
+    if workers > 0 and device is None:
+        raise ValueError("merged(workers > 0) needs the device")
+
+    def one(m, b):
+        w = b.get("weights", b.get("points_per_instance"))
+        return m.merge_graph(b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["edge_indices"].t(), b["descriptor"],
+                             b.get("batch_ids"), same_part=same_part, weights=w, threshold=threshold, mutual=mutual,
+                             fc_sizes=b.get("fc_sizes"), **decode_args), b
+
+    def scenes(pairs, b):
+        n_sc = pairs[0][0].n_objects.numel()
+        if n_sc == 1:
+            yield pairs
+            return
+        ids = b["batch_ids"].view(-1).contiguous()
+        arange = torch.arange(n_sc + 1, device=ids.device)
+        start = torch.searchsorted(ids[b["edge_indices"][:, 0]].contiguous(), arange).tolist()      # first edge row of every scene
+        for s in range(n_sc):
+            out = []
+            for pair in pairs:
+                if pair is None:
+                    out.append(None)
+                    continue
+                g, d = pair
+                gs = g.scene(s, (start[s], start[s + 1]))
+                n_obj = g.n_objects.tolist()
+                o0 = sum(n_obj[:s])
+                src = g.pair_edges[:, 0]
+                rows = ((src >= o0) & (src < o0 + n_obj[s])).nonzero().view(-1)
+                out.append((gs, d.scene(s, int(rows[0]) if rows.numel() else 0, (o0, o0 + n_obj[s]))))
+            yield tuple(out)
+
+    if workers <= 0:
+        for _, b in it:
+            yield from scenes(*one(model, b))
+        return
+    dev = torch.device(device)
+    models = [model] + model.replicas(workers - 1)
+
+    def work(k):
+        try:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(stream):
+                while not errors:
+                    with lock:
+                        i, b = next(it, (None, None))
+                    if b is None:
+                        break
+                    results[i] = one(models[k], b)
+            stream.synchronize()
+        except BaseException as ex:             # (re-raised in the caller's thread)
+            errors.append(ex)
+
+    if workers == 1:
+        work(0)
+    else:
+        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
+        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise errors[0]
+    for i in sorted(results):
+        yield from scenes(*results[i])
+
+
+def merge_quality(root, gt_of_segment) -> Dict[str, float]:
+    """How well merged objects agree with the annotation, on the host.  ``root[i]``: any id of the merged object of segment i
+    (``MergedGraph.root`` or ``.object``); ``gt_of_segment[i]``: the annotated instance of segment i, negative or None for a
+    segment without one (from ``LabelTransfer.segment_to_gt``).  Over the pairs of matched segments: ``pairs_same_pred`` /
+    ``pairs_same_gt`` / ``pairs_both`` and the pairwise ``precision`` = both / pred, ``recall`` = both / gt and ``f1`` of "same
+    object" (NaN where the denominator is 0; all 1 when neither side joins any pair).  ``over_merged`` = merged objects whose
+    matched segments belong to more than one instance; ``split`` = instances whose segments ended in more than one object."""
+    root = np.asarray(root.cpu() if torch.is_tensor(root) else root).astype(np.int64).reshape(-1)
+    gt = np.asarray([-1 if g is None else int(g) for g in (gt_of_segment.tolist() if hasattr(gt_of_segment, "tolist") else gt_of_segment)],
+                    dtype=np.int64)
+    if root.shape != gt.shape:
+        raise ValueError("merge_quality: one object and one instance per segment")
+    keep = gt >= 0
+    r, g = root[keep], gt[keep]
+
+    def pairs(*keys):
+        if not r.size:
+            return 0
+        _, cnt = np.unique(np.stack(keys, 1), axis=0, return_counts=True)
+        return int((cnt * (cnt - 1) // 2).sum())
+
+    pred, true, both = pairs(r), pairs(g), pairs(r, g)
+    nan = float("nan")
+    if pred == 0 and true == 0:
+        prec = rec = f1 = 1.0
+    else:
+        prec, rec = (both / pred if pred else nan), (both / true if true else nan)
+        f1 = 2 * both / (pred + true)
+    cells = np.unique(np.stack([r, g], 1), axis=0) if r.size else np.zeros((0, 2), np.int64)
+    over = int((np.unique(cells[:, 0], return_counts=True)[1] > 1).sum()) if cells.size else 0
+    split = int((np.unique(cells[:, 1], return_counts=True)[1] > 1).sum()) if cells.size else 0
+    return {"segments": int(keep.sum()), "pairs_same_pred": pred, "pairs_same_gt": true, "pairs_both": both, "precision": prec,
+            "recall": rec, "f1": f1, "over_merged": over, "split": split}
+
+
 def graph_quality(counts, n_rel: int = N_REL) -> Dict[str, float]:
     """Precision, recall and F1 of the decoded relations and the accuracy of the decoded labels, from the (all-reduced) counts of
     ``metrics.decode_counts``: one vector [3 R + 2], or the vectors of several branches stacked ([B, 3 R + 2] -> keys suffixed

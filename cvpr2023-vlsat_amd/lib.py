@@ -81,6 +81,8 @@ _SIGNATURES = {
     "vlsat_segment_overlap_scratch_bytes": (_sz, [_i32, _i32]),
     "vlsat_segment_overlap": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, C.c_double, C.c_double, _i32]
                               + [_vp] * 6 + [_vp]),
+    "vlsat_merge_segments_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "vlsat_merge_segments": (C.c_int, [_vp] * 5 + [_i32] * 6 + [_f32, _i32] + [_vp] * 14 + [_vp]),
     "vlsat_k_softmax_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "vlsat_eval_ranks": (C.c_int, [_vp] * 6 + [_i32] * 7 + [_f32] + [_vp] * 5 + [_vp]),
     "vlsat_eval_ranks_scratch_floats": (C.c_int64, [_i32] * 3),

@@ -801,6 +801,222 @@ def decode_counts_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs=True, 
     return out
 
 
+# ---- segments of an over-segmentation merged into objects along "same part" edges ------------------------------------------------------
+_MG_FIELDS = ("root", "object", "n_objects", "totals", "member_ptr", "members", "obj_probs", "obj_weight", "obj_batch_ids",
+              "edge_to_pair", "pair_edges", "pair_count", "pair_probs")
+
+
+class MergedGraph:
+    """The objects an over-segmentation's "same part" links assert, and the batch's graph folded onto them (include/vlsat.h,
+    vlsat_merge_segments).  Per segment (node row): ``root`` int32 [N] the lowest row of its component, ``object`` int32 [N] its
+    object.  Per scene ``n_objects`` int32 [S]; ``totals`` int32 [2] = (M, E').  ``member_ptr`` int32 / ``members`` int32 [N]: CSR
+    of the segments of every object in ascending row.  Per object ``obj_probs`` float32 [M, C] (weighted mean of the members'
+    class probabilities), ``obj_weight`` float32 [M], ``obj_batch_ids`` int64 [M].  Per input edge ``edge_to_pair`` int32 [E] (-1:
+    inside one object, or dropped).  Per merged edge ``pair_edges`` int64 [E', 2] (object rows), ``pair_count`` int32 [E'],
+    ``pair_probs`` float32 [E', R] (maximum over the folded edges).  ``trimmed``: the per-object / per-pair tables are cut to
+    M / E' rows (``member_ptr`` to M + 1); otherwise they are full size ([N] / [E] rows; rows past the end hold 0 / -1,
+    ``member_ptr`` N) and nothing was read back."""
+    __slots__ = _MG_FIELDS + ("trimmed",)
+
+    def __init__(self, trimmed=False, **tables):
+        for k in _MG_FIELDS:
+            setattr(self, k, tables[k])
+        self.trimmed = bool(trimmed)
+
+    def trim(self) -> "MergedGraph":
+        """The tables cut to M objects and E' merged edges.  Reads ``totals`` back: ONE host synchronisation."""
+        if self.trimmed:
+            return self
+        m, e = (int(x) for x in self.totals.tolist())
+        t = {k: getattr(self, k) for k in _MG_FIELDS}
+        for k in ("obj_probs", "obj_weight", "obj_batch_ids"):
+            t[k] = t[k][:m]
+        t["member_ptr"] = t["member_ptr"][:m + 1]
+        for k in ("pair_edges", "pair_count", "pair_probs"):
+            t[k] = t[k][:e]
+        return MergedGraph(True, **t)
+
+    def cpu(self) -> "MergedGraph":
+        return MergedGraph(self.trimmed, **{k: getattr(self, k).cpu() for k in _MG_FIELDS})
+
+    def scene(self, s: int, edges=None) -> "MergedGraph":
+        """Scene ``s`` as a one-scene graph with its own segment, object and pair rows counted from 0.  ``edges`` = (first, end)
+        rows of the scene in the batch's edge list (None: ``edge_to_pair`` is left empty).  Reads the counts back."""
+        g = self.trim()
+        n_obj = g.n_objects.tolist()
+        o0 = sum(n_obj[:s])
+        o1 = o0 + n_obj[s]
+        ptr = g.member_ptr.tolist()
+        n0, n1 = (ptr[o0], ptr[o1]) if len(ptr) > 1 else (0, 0)
+        src = g.pair_edges[:, 0] if g.pair_edges.numel() else g.pair_edges.new_zeros(0)
+        rows = ((src >= o0) & (src < o1)).nonzero().view(-1)
+        p0 = int(rows[0]) if rows.numel() else 0
+        e2p = g.edge_to_pair[0:0] if edges is None else g.edge_to_pair[int(edges[0]):int(edges[1])]
+        dev = g.totals.device
+        return MergedGraph(True, root=g.root[n0:n1] - n0, object=g.object[n0:n1] - o0, n_objects=g.n_objects[s:s + 1],
+                           totals=torch.tensor([o1 - o0, rows.numel()], dtype=torch.int32, device=dev),
+                           member_ptr=g.member_ptr[o0:o1 + 1] - n0, members=g.members[n0:n1] - n0, obj_probs=g.obj_probs[o0:o1],
+                           obj_weight=g.obj_weight[o0:o1], obj_batch_ids=torch.zeros_like(g.obj_batch_ids[o0:o1]),
+                           edge_to_pair=torch.where(e2p >= 0, e2p - p0, e2p), pair_edges=g.pair_edges[rows] - o0,
+                           pair_count=g.pair_count[rows], pair_probs=g.pair_probs[rows])
+
+    def decode(self, multi_rel_outputs: bool = True, **decode_args) -> "DecodedGraph":
+        """``decode_graph`` on the merged tables (``obj_probs=`` / ``rel_probs=``): one label per object, the asserted predicates per
+        merged edge; ``threshold``, ``score``, ``n_labels``, ``max_rel`` as there.  The graph's ``edge`` rows index ``pair_edges``.
+        Merged edges keep the input's scene order, so an edge list grouped by scene gives pairs grouped by scene."""
+        g = self.trim()
+        fn = decode_graph if g.obj_probs.is_cuda else decode_graph_host
+        return fn(g.obj_probs, g.pair_probs, g.pair_edges, g.obj_batch_ids, int(g.n_objects.numel()), multi_rel_outputs,
+                  obj_probs=g.obj_probs, rel_probs=g.pair_probs, **decode_args)
+
+
+def _mg_args(obj_logits, rel, edges, batch_ids, n_scenes, same_part, threshold, weights):
+    if obj_logits.dim() != 2 or rel.dim() != 2:
+        raise L.VlsatError("merge_segments: obj_logits must be [N,C] and rel [E,R]")
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    n_scenes, same_part, threshold = int(n_scenes), int(same_part), float(threshold)
+    if not 1 <= c <= 1024 or not 1 <= r <= 32:
+        raise L.VlsatError("merge_segments: 1..1024 object and 1..32 relation classes")
+    if not 0 <= same_part < r:
+        raise L.VlsatError(f"merge_segments: same_part must be a predicate class in [0, {r})")
+    if threshold != threshold:
+        raise L.VlsatError("merge_segments: threshold is NaN")
+    if n_scenes < 0 or (n_scenes > 1 and batch_ids is None) or (n > 0 and n_scenes < 1):
+        raise L.VlsatError("merge_segments: batch_ids is required for more than one scene (and nodes need a scene)")
+    edges = edges.to(torch.int64).contiguous().view(-1, 2)
+    if edges.shape[0] != e:
+        raise L.VlsatError("merge_segments: rel must be [E,R] and edges [E,2]")
+    if batch_ids is not None:
+        batch_ids = batch_ids.to(torch.int64).contiguous().view(-1)
+        if batch_ids.numel() != n:
+            raise L.VlsatError("merge_segments: batch_ids must hold one scene per node")
+    if weights is not None:
+        weights = weights.to(device=obj_logits.device, dtype=torch.float32).contiguous().view(-1)
+        if weights.numel() != n:
+            raise L.VlsatError("merge_segments: weights must hold one value per node")
+    return edges, batch_ids, n_scenes, same_part, threshold, weights
+
+
+def merge_segments(obj_logits: torch.Tensor, rel: torch.Tensor, edges: torch.Tensor, batch_ids: torch.Tensor | None, n_scenes: int,
+                   same_part: int, threshold: float = 0.5, mutual: bool = False, weights: torch.Tensor | None = None,
+                   multi_rel_outputs: bool = True, obj_probs: torch.Tensor | None = None, rel_probs: torch.Tensor | None = None,
+                   trim: bool = True) -> MergedGraph:
+    """The segments of an over-segmentation merged into objects: segments joined by an edge whose predicate ``same_part`` has
+    probability >= ``threshold`` (``mutual``: in both directions) form one object -- connected components, the lowest row as root
+    -- the members' class probabilities are pooled as a mean weighted by ``weights`` (``points_per_instance``; None: all 1), and
+    every edge between two objects folds onto the ordered pair of objects with the maximum of the predicate probabilities
+    (include/vlsat.h, vlsat_merge_segments, states the rule and its orders).  Probabilities are derived as ``decode_graph``
+    derives them.  Device tensors: the HIP kernels, asynchronous; ``trim=True`` then reads the two totals back -- the ONE host
+    synchronisation -- and cuts the tables to M objects / E' merged edges, ``trim=False`` leaves them full size and reads nothing.
+    CPU tensors: ``merge_segments_host``."""
+    if not obj_logits.is_cuda:
+        return merge_segments_host(obj_logits, rel, edges, batch_ids, n_scenes, same_part, threshold, mutual, weights, multi_rel_outputs,
+                                   obj_probs, rel_probs, trim)
+    lib = L.load()
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    edges, batch_ids, n_scenes, same_part, threshold, weights = _mg_args(obj_logits, rel, edges, batch_ids, n_scenes, same_part, threshold,
+                                                                         weights)
+    dev = obj_logits.device
+    r_probs = _rel_probs(rel, rel_probs, multi_rel_outputs, exp_probs)
+    probs = softmax_rows(obj_logits.float()) if obj_probs is None else obj_probs.float().contiguous()
+    i32 = dict(dtype=torch.int32, device=dev)
+    t = {"root": torch.empty(n, **i32), "object": torch.empty(n, **i32), "n_objects": torch.empty(n_scenes, **i32),
+         "totals": torch.empty(2, **i32), "member_ptr": torch.empty(n + 1, **i32), "members": torch.empty(n, **i32),
+         "obj_probs": torch.empty(n, c, dtype=torch.float32, device=dev), "obj_weight": torch.empty(n, dtype=torch.float32, device=dev),
+         "obj_batch_ids": torch.empty(n, dtype=torch.int64, device=dev), "edge_to_pair": torch.empty(e, **i32),
+         "pair_edges": torch.empty(e, 2, dtype=torch.int64, device=dev), "pair_count": torch.empty(e, **i32),
+         "pair_probs": torch.empty(e, r, dtype=torch.float32, device=dev)}
+    nbytes = int(lib.vlsat_merge_segments_scratch_bytes(n, e, c, r, n_scenes))
+    if nbytes == 0:
+        raise L.VlsatError("merge_segments: sizes out of range (E <= 2^26, E * R and N * C below 2^31)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.vlsat_merge_segments(probs.data_ptr(), r_probs.data_ptr(), edges.data_ptr(), L.ptr(batch_ids), L.ptr(weights), n, e, c, r,
+                                     n_scenes, same_part, threshold, int(bool(mutual)), scratch.data_ptr(),
+                                     *(t[k].data_ptr() for k in _MG_FIELDS), L.stream_ptr()))
+    g = MergedGraph(False, **t)
+    return g.trim() if trim else g
+
+
+@torch.no_grad()
+def merge_segments_host(obj_logits, rel, edges, batch_ids, n_scenes, same_part, threshold=0.5, mutual=False, weights=None,
+                        multi_rel_outputs=True, obj_probs=None, rel_probs=None, trim=True) -> MergedGraph:
+    """``merge_segments`` stated in numpy float32 with the kernel's operations and orders: every table equal, the pooled
+    probabilities bit for bit (the role ``decode_graph_host`` plays for ``decode_graph``).  Returns CPU tensors."""
+    edges, batch_ids, n_scenes, same_part, threshold, weights = _mg_args(obj_logits, rel, edges, batch_ids, n_scenes, same_part, threshold,
+                                                                         weights)
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    rp = _rel_probs(rel, rel_probs, multi_rel_outputs, lambda x: x.float().exp().contiguous()).cpu().numpy()
+    probs = (torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()).contiguous().cpu().numpy()
+    ed = edges.cpu().numpy()
+    bid = np.zeros(n, dtype=np.int64) if batch_ids is None else batch_ids.cpu().numpy()
+    w = np.ones(n, dtype=np.float32) if weights is None else weights.cpu().numpy().astype(np.float32)
+    a, b = (ed[:, 0], ed[:, 1]) if e else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    ok = (a >= 0) & (b >= 0) & (a < n) & (b < n) & (a != b)
+    ok[ok] &= bid[a[ok]] == bid[b[ok]]                                          # an edge across scenes never links and is dropped
+    link = ok & (rp[:, same_part] >= np.float32(threshold)) if e else ok
+    if mutual and e:
+        passed = set(zip(a[link].tolist(), b[link].tolist()))
+        link = link & np.fromiter(((y, x) in passed for x, y in zip(a.tolist(), b.tolist())), dtype=bool, count=e)
+    root = np.arange(n, dtype=np.int64)
+    la, lb = a[link], b[link]
+    while True:                                                                 # minimum label over links, to the fixed point
+        new = root.copy()
+        np.minimum.at(new, la, root[lb])
+        np.minimum.at(new, lb, root[la])
+        new = new[new]
+        if (new == root).all():
+            break
+        root = new
+    is_root = root == np.arange(n)
+    number = np.cumsum(is_root) - 1
+    obj = number[root] if n else np.zeros(0, np.int64)
+    m = int(is_root.sum())
+    order = np.argsort(obj, kind="stable")                                      # members: by object, ascending row inside
+    count = np.bincount(obj, minlength=n) if n else np.zeros(0, np.int64)
+    member_ptr = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    out_probs = np.zeros((n, c), dtype=np.float32)
+    out_w = np.zeros(n, dtype=np.float32)
+    for k in range(int(count.max()) if n else 0):                               # the k-th member of every object that has one
+        objs = np.nonzero(count > k)[0]
+        i = order[member_ptr[objs] + k]
+        out_probs[objs] = out_probs[objs] + w[i][:, None] * probs[i]            # fl(s + fl(w p))
+        out_w[objs] = out_w[objs] + w[i]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out_probs[:m] = out_probs[:m] / out_w[:m, None]
+    obj_bid = np.full(n, -1, dtype=np.int64)
+    obj_bid[:m] = bid[np.nonzero(is_root)[0]]
+    n_objects = np.bincount(obj_bid[:m], minlength=n_scenes)[:n_scenes].astype(np.int32) if n_scenes else np.zeros(0, np.int32)
+    edge_to_pair = np.full(e, -1, dtype=np.int32)
+    pair_edges = np.full((e, 2), -1, dtype=np.int64)
+    pair_count = np.zeros(e, dtype=np.int32)
+    pair_probs = np.zeros((e, r), dtype=np.float32)
+    n_pairs = 0
+    if e:
+        oa, ob = obj[np.where(ok, a, 0)], obj[np.where(ok, b, 0)]
+        rows = np.nonzero(ok & (oa != ob))[0]
+        if rows.size:
+            key = oa[rows] * np.int64(n) + ob[rows]
+            _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+            rank = np.empty(first.size, dtype=np.int64)
+            rank[np.argsort(first, kind="stable")] = np.arange(first.size)     # pairs in the order of their lowest edge row
+            pair = rank[inv.reshape(-1)]
+            n_pairs = first.size
+            edge_to_pair[rows] = pair
+            reps = rows[first]
+            pair_edges[rank, 0], pair_edges[rank, 1] = oa[reps], ob[reps]
+            np.add.at(pair_count, pair, 1)
+            np.maximum.at(pair_probs, pair, rp[rows])
+    t = {"root": root.astype(np.int32), "object": obj.astype(np.int32), "n_objects": n_objects,
+         "totals": np.asarray([m, n_pairs], dtype=np.int32), "member_ptr": member_ptr, "members": order.astype(np.int32),
+         "obj_probs": out_probs, "obj_weight": out_w, "obj_batch_ids": obj_bid, "edge_to_pair": edge_to_pair, "pair_edges": pair_edges,
+         "pair_count": pair_count, "pair_probs": pair_probs}
+    g = MergedGraph(False, **{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in t.items()})
+    return g.trim() if trim else g
+
+
 def _edges_list(edges):
     return [(int(x[0]), int(x[1])) for x in (edges.tolist() if torch.is_tensor(edges) else np.asarray(edges).tolist())]
 

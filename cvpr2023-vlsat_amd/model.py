@@ -612,6 +612,41 @@ class VLSATModel:
                 rel3 = r3
         return obj3, rel3
 
+    @torch.no_grad()
+    def merge_graph(self, obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids=None, same_part: Optional[int] = None, weights=None,
+                    threshold: float = 0.5, mutual: bool = False, multi_rel_outputs: Optional[bool] = None,
+                    fc_sizes: Optional[Sequence[int]] = None, **decode_args):
+        """One node per object for an over-segmented scan: the forward, then per branch ``metrics.merge_segments`` along the edges
+        whose predicate ``same_part`` (its index among the model's predicate classes; required) reaches ``threshold``, then
+        ``MergedGraph.decode(**decode_args)`` on the merged tables.  Returns ``((merged_3d, decoded_3d), (merged_2d, decoded_2d))``;
+        ``obj_2d_feats=None`` runs the 3D-only forward and the second pair is None.  ``weights``: per segment, normally the batch's
+        ``points_per_instance``.  Every step is enqueued on the current stream; the merge reads its two totals back once per branch
+        (the decode needs the merged sizes).  ``edge_indices`` int64 [2,E] in any order (a list grouped by scene gives merged edges
+        grouped by scene, which the decode requires for more than one scene)."""
+        from . import metrics as M
+        if same_part is None:
+            raise L.VlsatError("merge_graph: same_part (the index of the 'same part' predicate among the model's classes) is required")
+        c = self.config
+        multi = bool(c.multi_rel_outputs if multi_rel_outputs is None else multi_rel_outputs)
+        if obj_2d_feats is None:
+            obj3, rel3 = self.forward_3d(obj_points, edge_indices, descriptor, batch_ids, fc_sizes)
+            branches = [(obj3, rel3)]
+        else:
+            obj3, obj2, rel3, rel2 = self.forward(obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids, fc_sizes=fc_sizes)
+            branches = [(obj3, rel3), (obj2, rel2)]
+        with torch.cuda.device(self.device):
+            plan = self._plan(edge_indices, batch_ids, obj3.shape[0], obj_points.shape[2], fc_sizes)
+            s = C.c_int32()
+            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
+            edges_e2 = edge_indices.to(self.device).t().contiguous()
+            ids = None if batch_ids is None else batch_ids.to(self.device).view(-1)
+            w = None if weights is None else torch.as_tensor(weights).to(self.device)
+            out = []
+            for obj, rel in branches:
+                g = M.merge_segments(obj, rel, edges_e2, ids, s.value, same_part, threshold, mutual, w, multi)
+                out.append((g, g.decode(multi, **decode_args)))
+        return out[0], (out[1] if len(out) > 1 else None)
+
     # ---- profiling / debug hooks -----------------------------------------------------------------
     def profile_enable(self, on: bool):
         L.check(self._lib.vlsat_profile_enable(self._h, int(on)))

@@ -397,3 +397,23 @@ def inherit_relationships(match, rel_json: Sequence[Sequence], relation_names: S
                     out.append([int(group[i]), int(group[j]), pos[same_part], same_part])
                     out.append([int(group[j]), int(group[i]), pos[same_part], same_part])
     return out
+
+
+
+def merge_instances(instances: np.ndarray, instance_ids: Sequence[int], merged) -> np.ndarray:
+    """The per-vertex object id of a merged label mesh: every vertex whose segment id is ``instance_ids[n]`` takes the id of the
+    object segment n was merged into -- the instance id of that object's root segment (``scene_graph.merged_node_ids``); a vertex of
+    any other segment (background, segments that are no node) keeps 0.  ``merged``: a one-scene ``metrics.MergedGraph``."""
+    instances = np.asarray(instances).astype(np.int64).reshape(-1)
+    ids = np.asarray(list(instance_ids), dtype=np.int64)
+    root = np.asarray(merged.root.cpu() if hasattr(merged.root, "cpu") else merged.root).astype(np.int64).reshape(-1)
+    if root.shape != ids.shape:
+        raise ScanError("merge_instances: the graph's segments and instance_ids differ in length")
+    out = np.zeros_like(instances)
+    if not ids.size:
+        return out
+    order = np.argsort(ids, kind="stable")
+    pos = np.clip(np.searchsorted(ids[order], instances), 0, ids.size - 1)
+    hit = ids[order][pos] == instances
+    out[hit] = ids[root[order[pos[hit]]]]
+    return out

@@ -59,6 +59,25 @@ def to_annotation(graph, scene: int, edges, node_ids: Sequence[int], class_names
             "relationships": rels}
 
 
+def merged_node_ids(merged, instance_ids: Sequence[int]) -> List[int]:
+    """The ids of the objects of a one-scene ``metrics.MergedGraph``: an object is named by the instance id of its root segment
+    (``instance_ids[n]`` = the id of segment row n, ``scan.prepare_scan``'s ``instance_ids``).  What ``to_annotation`` takes as
+    ``node_ids`` with ``merged.decode()`` and ``merged.pair_edges``."""
+    ptr, members = merged.member_ptr.tolist(), merged.members.tolist()
+    if len(members) != len(instance_ids):
+        raise ValueError("merged_node_ids: the graph's segments and instance_ids differ in length")
+    return [int(instance_ids[members[ptr[o]]]) for o in range(int(merged.totals[0]))]
+
+
+def add_segments(entry: dict, merged, instance_ids: Sequence[int]) -> dict:
+    """Writes ``"segments": {object id: [segment ids]}`` (members in ascending row) into an annotation entry of a one-scene
+    ``metrics.MergedGraph`` and returns the entry."""
+    ptr, members = merged.member_ptr.tolist(), merged.members.tolist()
+    ids = merged_node_ids(merged, instance_ids)
+    entry["segments"] = {str(ids[o]): [int(instance_ids[n]) for n in members[ptr[o]:ptr[o + 1]]] for o in range(len(ids))}
+    return entry
+
+
 def write_annotations(path, entries) -> None:
     """``{"scans": [entries]}``: the layout of ``relationships_{train,validation}.json``."""
     with open(path, "w") as f:

@@ -397,6 +397,52 @@ int vlsat_segment_overlap(const int32_t* pd_segments, const int32_t* nn_index, i
                           int32_t occ_min_candidates, int32_t* size, int32_t* counts, int32_t* match, int32_t* best, int32_t* second,
                           int32_t* n_candidates, void* stream);
 
+/* -------- segments of an over-segmentation merged into objects along "same part" edges (csrc/segment_merge.hip) --------
+ *
+ * An over-segmentation splits every object into several segments; the data the reference generates for that setting joins the segments
+ * of one object by the relation "same part" (NAME_SAME_PART, utils/define.py:26; built at data_processing/gen_data.py:467-481;
+ * scan.inherit_relationships(..., same_part=...) emits it in both directions).  A model trained on such data predicts those edges; this
+ * call consumes them: one node per object.  metrics.merge_segments_host restates the rule in numpy with the same operations, so every
+ * table and every bit of the pooled probabilities is equal.
+ *
+ * Inputs (per batch, as for vlsat_graph_decode): obj_probs f32 [N,C]; rel_probs f32 [E,R], finite and non-negative (no -0); edges int64
+ *   [E,2] node rows in ANY order, duplicates and self loops allowed; batch_ids int64 [N] or NULL (one scene), the nodes of a scene
+ *   contiguous and scenes ascending; same_part in [0,R); threshold f32; mutual 0/1; weights f32 [N], positive, or NULL (all 1) -- the
+ *   caller passes the points per segment.
+ * Link.  Edge e = (a,b) is a link iff a != b, batch_ids[a] == batch_ids[b] and rel_probs[e,same_part] >= threshold (fp32 compare;
+ *   equality passes).  With mutual = 1 some edge (b,a) must pass the threshold as well (of duplicates any one suffices).  An edge whose
+ *   endpoints lie in different scenes (or out of range) never links and is dropped from the output.
+ * Objects = the connected components of the undirected link graph.  root[n] = the lowest node row of n's component; object[n] = the
+ *   dense index of that root among all roots in ascending order, so the objects of a scene are contiguous and in scene order.
+ *   n_objects[s] = objects of scene s; totals = {M, E'} = objects and merged edges of the batch.
+ * Members.  member_ptr int32 [N+1], members int32 [N]: CSR; the members of object o are members[member_ptr[o] .. member_ptr[o+1]) in
+ *   ascending node row (the first one is its root).  member_ptr[o] = N for o > M.
+ * Pooled node probabilities.  For object o and class c, over the members i in ascending row, starting from 0:
+ *   s = fl(s + fl(w_i * p_ic)),  W = fl(W + w_i),  merged_probs[o,c] = fl(s / W) -- fp32, every operation rounded on its own (no fused
+ *   multiply-add).  obj_weight[o] = W;  obj_batch_ids[o] = the scene of the object.
+ * Merged edges.  An input edge with object[a] != object[b] maps to the ordered pair (object[a], object[b]); an edge inside one object,
+ *   a self loop and a dropped edge map to -1.  Unique pairs are numbered in the order of their lowest contributing input edge row (no
+ *   global sort; a source-major list stays source-major, a list grouped by scene stays grouped).  edge_to_pair int32 [E]; pair_edges
+ *   int64 [E,2]; pair_count int32 [E] = input edges folded into the pair; pair_probs f32 [E,R] = the maximum over the contributing
+ *   edges, column same_part included (a maximum does not depend on order: exact).
+ * Rows past M / E' hold zero; index tables (root is full; members is full; obj_batch_ids, pair_edges, edge_to_pair) hold -1.  Every
+ *   field of every output is written by the call.
+ * Determinism: the result does not depend on scheduling -- the minimum row defines roots and pair order, the maximum the pair
+ *   probabilities, the member order the sums.
+ * Limits: n_obj_class 1..1024, n_rel_class 1..32, n_edges <= 2^26, n_edges * n_rel_class < 2^31, n_nodes * n_obj_class < 2^31;
+ *   n_scenes > 1 needs batch_ids; anything else is VLSAT_EINVAL, never a clamp.  scratch: vlsat_merge_segments_scratch_bytes(...) bytes,
+ *   16-byte aligned (0 = arguments out of range): an open-addressing table of 64-bit keys with the power of two >= 2 n_edges slots
+ *   (12 bytes per slot) and 12 bytes per node + 4 per edge + 8 per max(node, edge).  All device pointers; asynchronous on `stream`: no
+ *   host synchronisation, no allocation, no runtime fill; integer vector atomics and plain stores only. */
+size_t vlsat_merge_segments_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes);
+int vlsat_merge_segments(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids, const float* weights,
+                         int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class, int32_t n_scenes, int32_t same_part,
+                         float threshold, int32_t mutual, void* scratch, int32_t* root /* [N] */, int32_t* object /* [N] */,
+                         int32_t* n_objects /* [n_scenes] */, int32_t* totals /* [2] */, int32_t* member_ptr /* [N+1] */,
+                         int32_t* members /* [N] */, float* merged_probs /* [N,C] */, float* obj_weight /* [N] */,
+                         int64_t* obj_batch_ids /* [N] */, int32_t* edge_to_pair /* [E] */, int64_t* pair_edges /* [E,2] */,
+                         int32_t* pair_count /* [E] */, float* pair_probs /* [E,R] */, void* stream);
+
 /* -------- eval ranking step (the caller of the path: process_val, reference SGFN_MMG/model.py:463-472) --- */
 
 /* out[r, :] = softmax(x[r, 0:cols]) -- F.softmax(objs_pred) of evaluate_triplet_topk
