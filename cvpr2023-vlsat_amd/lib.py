@@ -16,6 +16,7 @@ import torch  # noqa: F401  (maps libamdhip64 before our library is loaded)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlsat_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
+SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
 
 
 class VlsatDims(C.Structure):
@@ -113,6 +114,15 @@ _SIGNATURES = {
                                      C.POINTER(_i32)]),
 }
 
+# include/vlsat_split.h: splitting a scan into sub-scenes and fusing the per-split graphs (csrc/scene_split.hip)
+_SIGNATURES_SPLIT = {
+    "vlsat_split_seeds_scratch_bytes": (_sz, [_i64]),
+    "vlsat_split_seeds": (C.c_int, [_vp, _i64, C.c_double, C.c_uint64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_split_groups": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_fuse_splits_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "vlsat_fuse_splits": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_vp] * 15 + [_vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -126,7 +136,7 @@ def identity(lib_path: str = "") -> dict:
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, os.path.join(_HERE, "build.py")]:
+    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -134,11 +144,20 @@ def identity(lib_path: str = "") -> dict:
     return out
 
 
-def declared_symbols() -> list:
-    """Every function include/vlsat.h declares (parsed from the header text)."""
-    txt = open(HEADER_PATH).read()
+def _declared(path: str) -> list:
+    txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(vlsat_[a-z0-9_]+)\s*\(", txt)))
+
+
+def declared_symbols() -> list:
+    """Every function include/vlsat.h declares (parsed from the header text)."""
+    return _declared(HEADER_PATH)
+
+
+def declared_split_symbols() -> list:
+    """Every function include/vlsat_split.h declares."""
+    return _declared(SPLIT_HEADER_PATH)
 
 
 def load():
@@ -150,7 +169,7 @@ def load():
         raise VlsatError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -817,9 +817,11 @@ class MergedGraph:
     M / E' rows (``member_ptr`` to M + 1); otherwise they are full size ([N] / [E] rows; rows past the end hold 0 / -1,
     ``member_ptr`` N) and nothing was read back."""
     __slots__ = _MG_FIELDS + ("trimmed",)
+    _FIELDS = _MG_FIELDS
+    _OBJECT_TABLES = ("obj_probs", "obj_weight", "obj_batch_ids")
 
     def __init__(self, trimmed=False, **tables):
-        for k in _MG_FIELDS:
+        for k in self._FIELDS:
             setattr(self, k, tables[k])
         self.trimmed = bool(trimmed)
 
@@ -828,16 +830,16 @@ class MergedGraph:
         if self.trimmed:
             return self
         m, e = (int(x) for x in self.totals.tolist())
-        t = {k: getattr(self, k) for k in _MG_FIELDS}
-        for k in ("obj_probs", "obj_weight", "obj_batch_ids"):
+        t = {k: getattr(self, k) for k in self._FIELDS}
+        for k in self._OBJECT_TABLES:
             t[k] = t[k][:m]
         t["member_ptr"] = t["member_ptr"][:m + 1]
         for k in ("pair_edges", "pair_count", "pair_probs"):
             t[k] = t[k][:e]
-        return MergedGraph(True, **t)
+        return type(self)(True, **t)
 
     def cpu(self) -> "MergedGraph":
-        return MergedGraph(self.trimmed, **{k: getattr(self, k).cpu() for k in _MG_FIELDS})
+        return type(self)(self.trimmed, **{k: getattr(self, k).cpu() for k in self._FIELDS})
 
     def scene(self, s: int, edges=None) -> "MergedGraph":
         """Scene ``s`` as a one-scene graph with its own segment, object and pair rows counted from 0.  ``edges`` = (first, end)
@@ -1014,6 +1016,168 @@ def merge_segments_host(obj_logits, rel, edges, batch_ids, n_scenes, same_part, 
          "obj_probs": out_probs, "obj_weight": out_w, "obj_batch_ids": obj_bid, "edge_to_pair": edge_to_pair, "pair_edges": pair_edges,
          "pair_count": pair_count, "pair_probs": pair_probs}
     g = MergedGraph(False, **{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in t.items()})
+    return g.trim() if trim else g
+
+
+# ---- the rows of a batch of splits fused into one graph per scan (csrc/scene_split.hip; the rule is stated in include/vlsat_split.h) ----
+class FusedGraph(MergedGraph):
+    """One graph per scan from the predictions of its splits (``fuse_splits``): the fields of ``MergedGraph`` with the same ``trim``
+    semantics -- an "object" is a scan-level instance, its members the rows (of any split) that carry its id, ``root`` the lowest such
+    row, objects in ascending id, ``pair_edges`` sorted by (source, target) -- plus ``obj_ids`` int32 [M], the instance id of every
+    object (what ``scene_graph.to_annotation`` takes as ``node_ids``; ``scene_graph.merged_node_ids(g, row_instance)`` gives the same
+    list).  ``n_objects`` int32 [1]; ``obj_batch_ids`` zeros.  A row whose id is outside the id table has ``root = object = -1``."""
+    __slots__ = ("obj_ids",)
+    _FIELDS = _MG_FIELDS + ("obj_ids",)
+    _OBJECT_TABLES = MergedGraph._OBJECT_TABLES + ("obj_ids",)
+
+    def scene(self, s: int = 0, edges=None) -> "FusedGraph":
+        if int(s) != 0:
+            raise L.VlsatError("FusedGraph: one scan per graph")
+        return self.trim()
+
+    def node_ids(self) -> list:
+        return [int(i) for i in self.trim().obj_ids.tolist()]
+
+
+def _fs_args(obj_logits, rel, edges, row_instance, weights, map_size):
+    if obj_logits.dim() != 2 or rel.dim() != 2:
+        raise L.VlsatError("fuse_splits: obj_logits must be [N,C] and rel [E,R]")
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    if not 1 <= c <= 1024 or not 1 <= r <= 32:
+        raise L.VlsatError("fuse_splits: 1..1024 object and 1..32 relation classes")
+    if n > 16384:
+        raise L.VlsatError("fuse_splits: at most 16384 rows per call")
+    edges = edges.to(torch.int64).contiguous().view(-1, 2)
+    if edges.shape[0] != e:
+        raise L.VlsatError("fuse_splits: rel must be [E,R] and edges [E,2]")
+    if torch.is_tensor(row_instance) and row_instance.is_cuda:                    # device ids: never read back; the table bounds them
+        ids = row_instance.to(torch.int32).contiguous().view(-1)
+        map_size = 65536 if map_size is None else map_size
+    else:
+        host = np.asarray(row_instance.cpu() if torch.is_tensor(row_instance) else list(row_instance), dtype=np.int64).reshape(-1)
+        if map_size is None:                                                      # host ids: checked, and the table sized from them
+            if host.size and (host.min() < 0 or host.max() >= (1 << 24)):
+                raise L.VlsatError("fuse_splits: instance ids must be integers in [0, 2^24)")
+            map_size = max(65536, int(host.max()) + 1 if host.size else 1)
+        ids = torch.from_numpy(np.clip(host, -1, 1 << 24).astype(np.int32))       # (an explicit map_size is taken as given)
+    if ids.numel() != n:
+        raise L.VlsatError("fuse_splits: row_instance must hold one id per row")
+    if not 1 <= int(map_size) <= (1 << 24):
+        raise L.VlsatError("fuse_splits: map_size must be in 1..2^24")
+    if weights is not None:
+        weights = weights.to(device=obj_logits.device, dtype=torch.float32).contiguous().view(-1)
+        if weights.numel() != n:
+            raise L.VlsatError("fuse_splits: weights must hold one value per row")
+    return edges, ids, weights, int(map_size)
+
+
+_FG_FIELDS = FusedGraph._FIELDS
+
+
+def fuse_splits(obj_logits: torch.Tensor, rel: torch.Tensor, edges: torch.Tensor, row_instance, weights: torch.Tensor | None = None,
+                multi_rel_outputs: bool = True, obj_probs: torch.Tensor | None = None, rel_probs: torch.Tensor | None = None,
+                trim: bool = True, map_size: int | None = None) -> FusedGraph:
+    """The predictions of a scan's splits (``scan.split_scan`` -> ``prepare_scan`` per group -> one batched forward) fused into one
+    graph: the rows that carry the same scan-level instance id (``row_instance`` [N]: the batches' ``instance_ids`` concatenated) are
+    one object, objects in ascending id; the rows' class probabilities are pooled as a mean weighted by ``weights``
+    (``points_per_instance``; None: all 1) in ascending row order; every edge folds onto the ordered pair of objects with the maximum
+    of the predicate probabilities over all occurrences, whatever split they come from; pairs are listed by (source, target)
+    ascending, each with its number of occurrences (include/vlsat_split.h, vlsat_fuse_splits).  Probabilities are derived as
+    ``merge_segments`` derives them.  Device tensors: the HIP kernels, asynchronous; ``trim=True`` then reads the two totals back --
+    the ONE host synchronisation -- ``trim=False`` leaves the tables full size and reads nothing.  ``map_size=None``:
+    ``row_instance`` on the host is range-checked and sizes the id table, on the device the table has 65536 entries; an explicit
+    ``map_size`` is taken as given, and an id outside [0, ``map_size``) belongs to no object, wherever the ids live.  CPU tensors:
+    ``fuse_splits_host``."""
+    if not obj_logits.is_cuda:
+        return fuse_splits_host(obj_logits, rel, edges, row_instance, weights, multi_rel_outputs, obj_probs, rel_probs, trim, map_size)
+    lib = L.load()
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    edges, ids, weights, map_size = _fs_args(obj_logits, rel, edges, row_instance, weights, map_size)
+    dev = obj_logits.device
+    ids = ids.to(dev)
+    r_probs = _rel_probs(rel, rel_probs, multi_rel_outputs, exp_probs)
+    probs = softmax_rows(obj_logits.float()) if obj_probs is None else obj_probs.float().contiguous()
+    i32 = dict(dtype=torch.int32, device=dev)
+    t = {"root": torch.empty(n, **i32), "object": torch.empty(n, **i32), "n_objects": torch.empty(1, **i32),
+         "totals": torch.empty(2, **i32), "member_ptr": torch.empty(n + 1, **i32), "members": torch.empty(n, **i32),
+         "obj_probs": torch.empty(n, c, dtype=torch.float32, device=dev), "obj_weight": torch.empty(n, dtype=torch.float32, device=dev),
+         "obj_batch_ids": torch.empty(n, dtype=torch.int64, device=dev), "edge_to_pair": torch.empty(e, **i32),
+         "pair_edges": torch.empty(e, 2, dtype=torch.int64, device=dev), "pair_count": torch.empty(e, **i32),
+         "pair_probs": torch.empty(e, r, dtype=torch.float32, device=dev), "obj_ids": torch.empty(n, **i32)}
+    nbytes = int(lib.vlsat_fuse_splits_scratch_bytes(n, e, c, r, map_size))
+    if nbytes == 0:
+        raise L.VlsatError("fuse_splits: sizes out of range (N <= 16384, E <= 2^26, E * R and N * C below 2^31)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    L.check(lib.vlsat_fuse_splits(probs.data_ptr(), r_probs.data_ptr(), edges.data_ptr(), ids.data_ptr(), L.ptr(weights), n, e, c, r, map_size,
+                                  scratch.data_ptr(), *(t[k].data_ptr() for k in _FG_FIELDS), L.stream_ptr()))
+    g = FusedGraph(False, **t)
+    return g.trim() if trim else g
+
+
+@torch.no_grad()
+def fuse_splits_host(obj_logits, rel, edges, row_instance, weights=None, multi_rel_outputs=True, obj_probs=None, rel_probs=None, trim=True,
+                     map_size=None) -> FusedGraph:
+    """``fuse_splits`` stated in numpy float32 with the kernel's operations and orders: every table equal, the pooled probabilities
+    bit for bit.  Returns CPU tensors."""
+    edges, ids, weights, map_size = _fs_args(obj_logits, rel, edges, row_instance, weights, map_size)
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    rp = _rel_probs(rel, rel_probs, multi_rel_outputs, lambda x: x.float().exp().contiguous()).cpu().numpy()
+    probs = (torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()).contiguous().cpu().numpy()
+    ed = edges.cpu().numpy()
+    inst = ids.cpu().numpy().astype(np.int64)
+    w = np.ones(n, dtype=np.float32) if weights is None else weights.cpu().numpy().astype(np.float32)
+    valid = (inst >= 0) & (inst < map_size)
+    uniq, first, inv = np.unique(inst[valid], return_index=True, return_inverse=True)     # ascending ids; first = lowest row of each
+    rows = np.nonzero(valid)[0]
+    m = len(uniq)
+    obj = np.full(n, -1, dtype=np.int64)
+    obj[rows] = inv.reshape(-1)
+    root = np.full(n, -1, dtype=np.int64)
+    root[rows] = rows[first][inv.reshape(-1)]
+    order = rows[np.argsort(obj[rows], kind="stable")]                                    # members: by object, ascending row inside
+    count = np.bincount(obj[rows], minlength=n) if n else np.zeros(0, np.int64)
+    member_ptr = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    members = np.full(n, -1, dtype=np.int32)
+    members[:len(order)] = order
+    out_probs = np.zeros((n, c), dtype=np.float32)
+    out_w = np.zeros(n, dtype=np.float32)
+    for k in range(int(count.max()) if n else 0):                                         # the k-th member of every object that has one
+        objs = np.nonzero(count > k)[0]
+        i = order[member_ptr[objs] + k]
+        out_probs[objs] = out_probs[objs] + w[i][:, None] * probs[i]                      # fl(s + fl(w p))
+        out_w[objs] = out_w[objs] + w[i]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out_probs[:m] = out_probs[:m] / out_w[:m, None]
+    obj_bid = np.full(n, -1, dtype=np.int64)
+    obj_bid[:m] = 0
+    obj_ids = np.full(n, -1, dtype=np.int32)
+    obj_ids[:m] = uniq
+    edge_to_pair = np.full(e, -1, dtype=np.int32)
+    pair_edges = np.full((e, 2), -1, dtype=np.int64)
+    pair_count = np.zeros(e, dtype=np.int32)
+    pair_probs = np.zeros((e, r), dtype=np.float32)
+    n_pairs = 0
+    if e and n:
+        a, b = ed[:, 0], ed[:, 1]
+        ok = (a >= 0) & (b >= 0) & (a < n) & (b < n)
+        oa, ob = obj[np.where(ok, a, 0)], obj[np.where(ok, b, 0)]
+        hit = np.nonzero(ok & (oa >= 0) & (ob >= 0) & (oa != ob))[0]
+        if hit.size:
+            key, pair = np.unique(oa[hit] * np.int64(n) + ob[hit], return_inverse=True)   # sorted keys: (a, b) ascending
+            pair = pair.reshape(-1)
+            n_pairs = key.size
+            edge_to_pair[hit] = pair
+            pair_edges[:n_pairs, 0], pair_edges[:n_pairs, 1] = key // n, key % n
+            np.add.at(pair_count, pair, 1)
+            np.maximum.at(pair_probs, pair, rp[hit])
+    t = {"root": root.astype(np.int32), "object": obj.astype(np.int32), "n_objects": np.asarray([m], dtype=np.int32),
+         "totals": np.asarray([m, n_pairs], dtype=np.int32), "member_ptr": member_ptr, "members": members,
+         "obj_probs": out_probs, "obj_weight": out_w, "obj_batch_ids": obj_bid, "edge_to_pair": edge_to_pair, "pair_edges": pair_edges,
+         "pair_count": pair_count, "pair_probs": pair_probs, "obj_ids": obj_ids}
+    g = FusedGraph(False, **{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in t.items()})
     return g.trim() if trim else g
 
 

@@ -346,3 +346,199 @@ def segment_overlap(pd_segments, nn_index, gt_instances, segment_ids, gt_ids, mi
                                       out["counts"].data_ptr(), out["match"].data_ptr(), out["best"].data_ptr(), out["second"].data_ptr(),
                                       out["n_candidates"].data_ptr(), L.stream_ptr()))
     return out
+
+
+# ---- a scan split into sub-scenes (csrc/scene_split.hip; the rules are stated in include/vlsat_split.h) --------------------------------
+_M64 = (1 << 64) - 1
+
+
+def split_draw(seed: int, k: int, n: int) -> int:
+    """draw(k, n) of the split seeds: ``sample_objects``' counter-based generator -- splitmix64 of (seed, k), the top 32 bits scaled to n."""
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(k) + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z ^= z >> 31
+    return ((z >> 32) * int(n)) >> 32
+
+
+def split_seed_cap(points, distance: float) -> int:
+    """A bound on the number of seeds, from the xy bounding box of the finite vertices: two seeds are more than ``distance`` apart, so a
+    cell of side distance / sqrt(2) holds at most one (one row and column of cells to spare for the rounding of the division).  ``points``:
+    a host array [V,3]."""
+    import math
+
+    import numpy as np
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    xy = pts[np.isfinite(pts).all(1)][:, :2]
+    if not distance > 0:
+        raise L.VlsatError("split_seeds: distance must be positive")
+    if not len(xy):
+        return 1
+    side = float(distance) / math.sqrt(2.0)
+    ext = xy.max(0) - xy.min(0)
+    cells = (int(ext[0] / side) + 2) * (int(ext[1] / side) + 2)
+    return int(max(1, min(cells, len(pts))))
+
+
+_SEED_ERRORS = {1: "split_seeds: a rank is negative or not below the number of selectable vertices",
+                2: "split_seeds: the ranks ran out while vertices were still selectable",
+                3: "split_seeds: max_seeds reached while vertices were still selectable"}
+
+
+def _seed_args(points, distance, ranks):
+    import numpy as np
+    if tuple(points.shape[1:]) != (3,) or len(points.shape) != 2 or points.shape[0] < 1:
+        raise L.VlsatError("split_seeds: points must be float32 [V,3] with V >= 1")
+    distance = float(distance)
+    if not 0.0 < distance < 1e150:
+        raise L.VlsatError("split_seeds: distance must be positive and finite")
+    if ranks is not None:
+        ranks = np.asarray(ranks.cpu() if torch.is_tensor(ranks) else ranks, dtype=np.int64).reshape(-1)
+    return distance, ranks
+
+
+def split_seeds_host(points, distance: float = 1.0, seed: int = 0, ranks=None):
+    """The seed rule of include/vlsat_split.h (vlsat_split_seeds; reference gen_data.py:69-85) in numpy, in the device's fp64 operations
+    -> seed indices int32 [K] in creation order (numpy).  ``ranks``: the draws of a recorded run (rank of each seed among the
+    selectable vertices); a rank out of range, or ranks running out early, raises."""
+    import numpy as np
+    pts = np.ascontiguousarray(points.cpu().numpy() if torch.is_tensor(points) else points, dtype=np.float32)
+    distance, ranks = _seed_args(pts, distance, ranks)
+    v = pts.shape[0]
+    d2_max = distance * distance
+
+    def draw(k, n):
+        if ranks is None:
+            return split_draw(seed, k, n)
+        if k >= len(ranks):
+            raise L.VlsatError(_SEED_ERRORS[2])
+        if not 0 <= int(ranks[k]) < n:
+            raise L.VlsatError(_SEED_ERRORS[1])
+        return int(ranks[k])
+
+    xy = pts[:, :2].astype(np.float64)
+    finite = np.isfinite(pts).all(1)
+    seeds = [draw(0, v)]
+    dmin2 = None
+    with np.errstate(invalid="ignore", over="ignore"):
+        while True:
+            dx, dy = xy[:, 0] - xy[seeds[-1], 0], xy[:, 1] - xy[seeds[-1], 1]
+            d = dx * dx + dy * dy                                                  # (numpy rounds the products and the sum on their own)
+            dmin2 = np.where(finite, d, np.nan) if dmin2 is None else np.where(d < dmin2, d, dmin2)
+            selectable = np.nonzero(dmin2 > d2_max)[0]
+            if not len(selectable):
+                break
+            seeds.append(int(selectable[draw(len(seeds), len(selectable))]))
+    return np.asarray(seeds, dtype=np.int32)
+
+
+def split_seeds(points: torch.Tensor, distance: float = 1.0, seed: int = 0, ranks=None, max_seeds: int | None = None) -> torch.Tensor:
+    """points f32 [V,3] (device) -> the seed vertices of the scan's sub-scenes, int32 [K] in creation order (include/vlsat_split.h,
+    vlsat_split_seeds): seed 0 is drawn among all vertices, every later one among the vertices more than ``distance`` away (in xy)
+    from all seeds so far, until none is left.  The draws come from ``sample_objects``' counter-based generator (``split_draw``), or
+    from ``ranks``.  ``max_seeds`` bounds K (``split_seed_cap`` of the host copy of the points; None: computed here, which reads the
+    points back).  One short launch chain per seed is enqueued up to that bound and the chain ends itself on the device; the ONE
+    host wait is reading K back.  CPU tensors: ``split_seeds_host``."""
+    if not points.is_cuda:
+        return torch.from_numpy(split_seeds_host(points, distance, seed, ranks))
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("split_seeds: points must be float32 [V,3]")
+    points = points.contiguous()
+    distance, ranks = _seed_args(points, distance, ranks)
+    dev = points.device
+    v = points.shape[0]
+    cap = split_seed_cap(points.cpu().numpy(), distance) if max_seeds is None else int(max_seeds)
+    if not 1 <= cap <= 65536:
+        raise L.VlsatError("split_seeds: more than 65536 possible seeds: distance is too small for this extent")
+    d_ranks = None if ranks is None else torch.from_numpy(ranks).to(dev)
+    scratch = torch.empty(int(lib.vlsat_split_seeds_scratch_bytes(v)), dtype=torch.uint8, device=dev)
+    seeds = torch.empty(cap, dtype=torch.int32, device=dev)
+    state = torch.empty(4, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_split_seeds(points.data_ptr(), v, distance, int(seed) & _M64, L.ptr(d_ranks), 0 if ranks is None else len(ranks), cap,
+                                  scratch.data_ptr(), seeds.data_ptr(), state.data_ptr(), L.stream_ptr()))
+    k, status, done, _ = state.tolist()                                            # the one host wait
+    if status or not done:
+        raise L.VlsatError(_SEED_ERRORS[status or 3])
+    return seeds[:k]
+
+
+def _group_args(points, segments, segment_ids, seeds):
+    import numpy as np
+    ids = np.asarray(segment_ids.cpu() if torch.is_tensor(segment_ids) else segment_ids, dtype=np.int64).reshape(-1)
+    if len(ids) and (ids.min() < 0 or ids.max() >= (1 << 24) or len(np.unique(ids)) != len(ids)):
+        raise L.VlsatError("split_groups: segment_ids must be distinct integers in [0, 2^24)")
+    if len(points.shape) != 2 or points.shape[1] != 3 or segments.shape[0] != points.shape[0]:
+        raise L.VlsatError("split_groups: points must be float32 [V,3] with one segment id per vertex")
+    return ids
+
+
+def _unpack_groups(ids, mask, counts, keep):
+    import numpy as np
+    s = len(ids)
+    if not s:
+        return [[] for _ in range(len(mask))], np.asarray(counts, dtype=np.int32), np.asarray(keep, dtype=bool)
+    bits = np.unpackbits(np.ascontiguousarray(mask).view(np.uint8).reshape(len(mask), -1), axis=1, bitorder="little")[:, :s].astype(bool)
+    order = np.argsort(ids, kind="stable")
+    groups = [[int(i) for i in ids[order][bits[k][order]]] for k in range(len(mask))]
+    return groups, np.asarray(counts, dtype=np.int32), np.asarray(keep, dtype=bool)
+
+
+def split_groups_host(points, segments, segment_ids, seeds, bbox_distance: float = 0.75, min_seg_per_group: int = 5):
+    """The group rule of include/vlsat_split.h (vlsat_split_groups; reference gen_data.py:109-122) in numpy fp64 -> (groups, counts,
+    keep, mask): per seed the ascending ids of the segments with a vertex strictly inside the seed's box, their number,
+    ``counts >= min_seg_per_group``, and the bit table uint32 [K, ceil(S/32)] over the slots of ``segment_ids``."""
+    import numpy as np
+    pts = np.ascontiguousarray(points.cpu().numpy() if torch.is_tensor(points) else points, dtype=np.float32)
+    seg = np.asarray(segments.cpu() if torch.is_tensor(segments) else segments).astype(np.int64).reshape(-1)
+    seeds = np.asarray(seeds.cpu() if torch.is_tensor(seeds) else seeds, dtype=np.int64).reshape(-1)
+    ids = _group_args(pts, seg, segment_ids, seeds)
+    if len(seeds) and (seeds.min() < 0 or seeds.max() >= len(pts)):
+        raise L.VlsatError("split_groups: a seed is not a vertex index")
+    s, k = len(ids), len(seeds)
+    words = (s + 31) // 32
+    slot_of = {int(i): n for n, i in enumerate(ids)}
+    slot = np.asarray([slot_of.get(int(i), -1) for i in seg], dtype=np.int64)
+    p64 = pts.astype(np.float64)
+    hit = np.zeros((k, words * 32), dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for n, sv in enumerate(seeds):
+            lo, hi = p64[sv] - float(bbox_distance), p64[sv] + float(bbox_distance)
+            inside = ((p64 > lo) & (p64 < hi)).all(1) & (slot >= 0)
+            hit[n, slot[inside]] = True
+    mask = np.packbits(hit, axis=1, bitorder="little").view(np.uint32).reshape(k, words) if words else np.zeros((k, 0), np.uint32)
+    counts = hit.sum(1).astype(np.int32)
+    return (*_unpack_groups(ids, mask, counts, counts >= int(min_seg_per_group)), mask)
+
+
+def split_groups(points: torch.Tensor, segments: torch.Tensor, segment_ids, seeds: torch.Tensor, bbox_distance: float = 0.75,
+                 min_seg_per_group: int = 5, map_size: int = 65536):
+    """points f32 [V,3], segments int32 [V] (device), ``segment_ids`` (distinct, on the host or the device), seeds int32 [K] -> (groups,
+    counts, keep, mask) as ``split_groups_host``: group k = the ascending ids of the segments with a vertex strictly inside the box
+    ``seed point -/+ bbox_distance`` (include/vlsat_split.h, vlsat_split_groups); ``keep`` marks the groups the reference keeps.  Id 0
+    counts when it is listed, as the reference's np.unique counts it.  The bit table is read back ONCE.  CPU tensors: the host rule."""
+    import numpy as np
+    if not points.is_cuda:
+        return split_groups_host(points, segments, segment_ids, seeds, bbox_distance, min_seg_per_group)
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("split_groups: points must be float32 [V,3]")
+    points = points.contiguous()
+    dev = points.device
+    segments = segments.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    ids = _group_args(points, segments, segment_ids, seeds)
+    seeds = seeds.to(device=dev, dtype=torch.int32).contiguous().view(-1) if torch.is_tensor(seeds) else torch.tensor(
+        np.asarray(seeds, dtype=np.int32).reshape(-1), dtype=torch.int32, device=dev)
+    s, k = len(ids), seeds.numel()
+    words = (s + 31) // 32
+    map_size = max(int(map_size), int(ids.max()) + 1 if s else 1)
+    d_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
+    id_map = torch.empty(map_size, dtype=torch.int32, device=dev)
+    out = torch.empty(k * words + 2 * k, dtype=torch.int32, device=dev)           # mask | counts | keep: one read-back
+    mask, counts, keep = out[:k * words], out[k * words:k * words + k], out[k * words + k:]
+    L.check(lib.vlsat_split_groups(points.data_ptr(), segments.data_ptr(), points.shape[0], d_ids.data_ptr(), s, id_map.data_ptr(), map_size,
+                                   seeds.data_ptr(), k, float(bbox_distance), int(min_seg_per_group), mask.data_ptr(), counts.data_ptr(),
+                                   keep.data_ptr(), L.stream_ptr()))
+    host = out.cpu().numpy()                                                      # the one host wait
+    mask = host[:k * words].view(np.uint32).reshape(k, words)
+    return (*_unpack_groups(ids, mask, host[k * words:k * words + k], host[k * words + k:]), mask)

@@ -417,3 +417,53 @@ def merge_instances(instances: np.ndarray, instance_ids: Sequence[int], merged) 
     hit = ids[order][pos] == instances
     out[hit] = ids[root[order[pos[hit]]]]
     return out
+
+
+# ---- a scan split into the sub-scenes the models were trained on ---------------------------------------------------------------------
+class ScanSplits:
+    """What ``split_scan`` found.  ``groups``: the kept sub-scenes as lists of ascending instance ids; ``kept``: the seed number of each
+    kept group; ``seeds`` int32 [K] / ``seed_points`` float32 [K,3]: the vertex index and position of EVERY seed, in creation order;
+    ``counts`` int32 [K]: segments per seed's box (a group below ``min_seg_per_group`` is dropped, as the reference drops it)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __iter__(self):                      # groups, seeds, seed_points = split_scan(...)
+        return iter((self.groups, self.seeds, self.seed_points))
+
+    def __repr__(self):
+        return f"ScanSplits({len(self.groups)} groups kept of {len(self.seeds)} seeds, sizes {[len(g) for g in self.groups]})"
+
+
+def split_scan(mesh_or_path, distance: float = 1.0, bbox_distance: float = 0.75, min_seg_per_group: int = 5, seed: int = 0,
+               device="cuda:0", ranks=None) -> ScanSplits:
+    """A scan split into sub-scenes as the reference's ``generate_groups`` splits it (data_processing/gen_data.py:56-183, BBOX method;
+    every entry of its relationships_*.json is one such split): seed vertices more than ``distance`` apart in xy, drawn until no vertex
+    is further than that from all of them, and per seed the segments with a vertex strictly inside the box ``seed -/+ bbox_distance``;
+    a group of fewer than ``min_seg_per_group`` segments is dropped.  The rules are stated in include/vlsat_split.h; both steps run on
+    the device (``prep.split_seeds`` / ``prep.split_groups``; ``device=None`` or "cpu": their numpy restatements, same result).  The
+    draws come from the counter-based generator of ``prep.sample_objects`` under ``seed`` -- not numpy's stream -- or from ``ranks``
+    (a recorded run: the rank of every seed among the selectable vertices).
+
+    Like the reference's np.unique, a group lists id 0 (unlabelled vertices) when the box holds such a vertex.  Feed a group to
+    ``prepare_scan`` as ``{i: instance2label[i] for i in group if i in instance2label}``: ids without a label are ignored there."""
+    import torch
+
+    from . import prep
+
+    mesh = read_ply(mesh_or_path) if isinstance(mesh_or_path, (str, os.PathLike)) else mesh_or_path
+    pts = np.ascontiguousarray(np.asarray(mesh["points"])[:, :3], dtype=np.float32)
+    seg = np.asarray(mesh["instances"]).astype(np.int64).reshape(-1)
+    if len(pts) < 1 or len(seg) != len(pts):
+        raise ScanError("split_scan: the mesh needs at least one vertex and one segment id per vertex")
+    segment_ids = np.unique(seg)
+    if segment_ids.min() < 0 or segment_ids.max() >= (1 << 24):
+        raise ScanError("segment ids must be integers in [0, 2^24)")
+    on_host = device is None or torch.device(device).type == "cpu"
+    d_pts = torch.from_numpy(pts) if on_host else torch.from_numpy(pts).to(device)
+    d_seg = torch.from_numpy(seg.astype(np.int32)) if on_host else torch.from_numpy(seg.astype(np.int32)).to(device)
+    seeds = prep.split_seeds(d_pts, distance, seed, ranks, max_seeds=None if on_host else prep.split_seed_cap(pts, distance))
+    groups, counts, keep, _ = prep.split_groups(d_pts, d_seg, segment_ids, seeds, bbox_distance, min_seg_per_group)
+    seeds = seeds.cpu().numpy().astype(np.int32)
+    kept = [k for k in range(len(seeds)) if keep[k]]
+    return ScanSplits(groups=[groups[k] for k in kept], kept=kept, seeds=seeds, seed_points=pts[seeds], counts=counts)
