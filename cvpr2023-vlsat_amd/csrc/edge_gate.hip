@@ -1,27 +1,12 @@
-// 'fat' edge gate of MultiHeadedEdgeAttention.forward (reference network_MMG.py:96-104):
-//   q = proj_query(x_i).view(E,64,8); k = proj_edge(e).view(E,64,8)          (head = FAST axis)
-//   prob = softmax_dim1( Conv1d(128->32)( ReLU( Conv1d(128->128)( cat[q,k] ) ) ) )   [E,32,8]
-//   gated = prob.reshape(E,256) * proj_value(x_j)
-//
-// Algebra used here (weights prepared once in vlsat_finalize_weights):
-//   * the q half of layer 1 only depends on the SOURCE node -> Gq[n, h*128+o] (bias included)
-//     is computed per node by the node-side GEMM and gathered here;
-//   * proj_edge rows are permuted so k arrives head-major: kproj[e, h*64 + c] == k[e, c, h];
-//     the [E,512] matrix is then a contiguous [8E, 64] matrix of (edge, head) rows.
-// Per (edge, head) row:  hidden = relu(Gq + W0k . kproj_row);  logits = W3 . hidden + b3;
-// prob = softmax(logits);  gated[e, h*32+m] = prob[m] * value[dst[e], h*32+m]   (value and gated are kept
-// HEAD-MAJOR -- the engine permutes proj_value's rows and prop.0's columns once -- so the four consecutive
-// channels m a lane owns per MFMA row group are one float4 load and one float4 store).
-//
-// fp32 MFMA, transposed products so that a lane owns ONE (edge, head) row:
-//   hidden^T[o][row] : A = W0k (LDS), B = kproj rows straight from HBM (float4 per lane)
-//   logits^T[m][row] : A = W3 (LDS), B = hidden^T registers of layer 1 (no LDS round trip)
-// so the softmax over the 32 channels is 15 in-lane ops + one lane^32 exchange.
-// One wave = 32 rows = 4 edges per step (192 MFMAs); a block of 4 waves walks 16-edge groups.
+// Edge gate of MultiHeadedEdgeAttention.forward (algebra, layouts and lane model: gate_core.h), in this file:
+//   * the fp32 MFMA kernel of the shipped 8 x (64, 64, 32) geometry: A = W0k / W3 fp32 rows from LDS, B = kproj rows straight from
+//     HBM (float4 per lane) / the hidden registers, v_mfma_f32_32x32x2_f32.  One wave = 32 rows per step (192 MFMAs); a block of
+//     4 waves;
+//   * the VALU kernel for any head geometry;
+//   * launch_gate: the argument checks and the dispatch to the five kernels' launchers.
 #include <cstdlib>
-#include "gemm_core.h"
+#include "gate_core.h"
 #include "gate_agg.h"
-#include "kernels.h"
 
 namespace vlsat {
 
@@ -41,14 +26,8 @@ __global__ __launch_bounds__(256, 2) void edge_gate_kernel(GateArgs pa, GateArgs
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, hi = lane >> 5;
 
-    for (int i = tid; i < 128 * 16; i += 256) {
-        const int r = i >> 4, c4 = (i & 15) * 4;
-        *reinterpret_cast<f32x4*>(sW0 + r * GT_PITCH + c4) = *reinterpret_cast<const f32x4*>(p.w0k + r * 64 + c4);
-    }
-    for (int i = tid; i < 32 * 32; i += 256) {
-        const int r = i >> 5, c4 = (i & 31) * 4;
-        *reinterpret_cast<f32x4*>(sW3 + r * GT_PITCH3 + c4) = *reinterpret_cast<const f32x4*>(p.w3 + r * 128 + c4);
-    }
+    gate_stage_f32_rows<128, 128, 64, GT_PITCH, 256>(sW0, p.w0k, tid);
+    gate_stage_f32_rows<32, 32, 128, GT_PITCH3, 256>(sW3, p.w3, tid);
     float b3f[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) b3f[r] = p.b3[crow32(r, hi)];
@@ -80,9 +59,9 @@ __global__ __launch_bounds__(256, 2) void edge_gate_kernel(GateArgs pa, GateArgs
         // Per 32-wide slice `to` of the hidden layer: layer 1 (32 MFMAs) then immediately its
         // contribution to layer 2 (16 MFMAs), so only one 32x32 accumulator is live at a time.
         const float* gq = p.node + (size_t)sn * p.ld_node + p.gq_off + h * 128 + 4 * hi;
-        f32x16 lg;
+        f32x16 lg[1];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) lg[r] = b3f[r];
+        for (int r = 0; r < 16; ++r) lg[0][r] = b3f[r];
 #pragma unroll
         for (int to = 0; to < 4; ++to) {
             f32x16 acc;
@@ -104,51 +83,25 @@ __global__ __launch_bounds__(256, 2) void edge_gate_kernel(GateArgs pa, GateArgs
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float hid = fmaxf(acc[r4 * 4 + c] + gqv[c], 0.f);
-                    lg = __builtin_amdgcn_mfma_f32_32x32x2f32(w3v[c], hid, lg, 0, 0, 0);
+                    lg[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w3v[c], hid, lg[0], 0, 0, 0);
                 }
             }
         }
-        // softmax over the 32 channels m = crow32(r, hi) (+ the other 16 in lane^32)
-        float mx = lg[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, lg[r]);
-        mx = half_max(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            lg[r] = __expf(lg[r] - mx);
-            sum += lg[r];
-        }
-        sum = half_sum(sum);
-        const float inv = 1.f / sum;
+        const float inv = gate_softmax<1, 32>(lg);
         if (FUSED && p.agg) {                  // fused max aggregation: the gated rows are never stored (gate_agg.h)
-            gate_aggregate_max(sAgg + wave * AG_WAVE_BYTES, lg, inv, p.node + (size_t)dn * p.ld_node + p.v_off + h * 32 + 4 * hi, valid ? sn : -1,
+            gate_aggregate_max(sAgg + wave * AG_WAVE_BYTES, lg[0], inv, p.node + (size_t)dn * p.ld_node + p.v_off + h * 32 + 4 * hi, valid ? sn : -1,
                                li, hi, lane, h, p.agg, p.ld_agg);
         } else if (valid) {
-            // lane's channels: m = 8*r4 + 4*hi + c  (crow32), c = 0..3 -> one float4 per r4
-            const float* vrow = p.node + (size_t)dn * p.ld_node + p.v_off + h * 32 + 4 * hi;
-            float* grow = p.gated + (size_t)e * 256 + h * 32 + 4 * hi;
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(vrow + 8 * r4);
-                f32x4 o;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = lg[r4 * 4 + c] * inv * v[c];
-                *reinterpret_cast<f32x4*>(grow + 8 * r4) = o;
-            }
-            if (p.prob) {                      // test tap in the reference's [E, 32, 8] order
-#pragma unroll
-                for (int r = 0; r < 16; ++r) p.prob[(size_t)e * 256 + crow32(r, hi) * 8 + h] = lg[r] * inv;
-            }
+            gate_store<1, 32>(lg, inv, p.node + (size_t)dn * p.ld_node + p.v_off + h * 32 + 4 * hi, p.gated + (size_t)e * 256 + h * 32 + 4 * hi,
+                              p.prob, (size_t)e * 256, 8, h, hi);
         }
     }
 }
 
 // Generic head geometry (MODEL.NUM_HEADS / DIM_ATTEN other than 8 / 256; reference network_MMG.py:48-50): d_k = 512 / H
 // query / edge channels per head, hidden width 2 d_k, d_o = DIM_ATTEN / H output channels.  Same algebra and layouts as
-// above (Gq per node, head-major kproj / value / gated), plain VALU: one thread per (edge, head), the hidden vector in
-// LDS (transposed, so a warp's accesses are conflict-free), weights read with wave-uniform (scalar) loads.  The MFMA
-// kernels above are built for the shipped 8 x (64, 64, 32) only.
+// gate_core.h (Gq per node, head-major kproj / value / gated), plain VALU: one thread per (edge, head), the hidden vector in
+// LDS (transposed, so a warp's accesses are conflict-free), weights read with wave-uniform (scalar) loads.
 __global__ __launch_bounds__(64) void edge_gate_generic_kernel(GateArgs p, int n_heads, int dk, int dox) {
     extern __shared__ float hid[];                      // [2 dk][64]
     const int lane = threadIdx.x;
@@ -191,8 +144,7 @@ __global__ __launch_bounds__(64) void edge_gate_generic_kernel(GateArgs p, int n
     }
 }
 
-int launch_edge_gate_generic(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s) {
-    if (a.n_edges <= 0) return 0;
+int launch_gate_valu(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s) {
     if (dk < 1 || dk > 128 || dox < 1) return fail(-1, "edge_gate: unsupported head geometry");
     const long rows = (long)a.n_edges * n_heads;
     hipLaunchKernelGGL(edge_gate_generic_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 2 * dk * 64 * sizeof(float), s, a,
@@ -201,13 +153,7 @@ int launch_edge_gate_generic(const GateArgs& a, int n_heads, int dk, int dox, hi
     return 0;
 }
 
-int launch_edge_gate(const GateArgs& a, hipStream_t s, const GateArgs* twin) {
-    if (a.n_edges <= 0) return 0;
-    if (twin && (twin->n_edges != a.n_edges || !twin->agg != !a.agg || twin->row_map != a.row_map || twin->use_edge != a.use_edge ||
-                 !twin->prob != !a.prob || twin->grid_cap != a.grid_cap || twin->src != a.src || twin->dst != a.dst))
-        return fail(-1, "edge_gate: a twin launch needs two problems on the same edge list with the same options");
-    if (a.agg && (!a.row_map || a.prob || (a.ld_agg & 3))) return fail(-1, "edge_gate: the fused aggregation needs the 32-edges-per-wave row map and no prob tap");
-    if ((a.ld_node & 3) || (a.gq_off & 3) || (a.v_off & 3)) return fail(-1, "edge_gate: ld_node/gq_off/v_off must be multiples of 4");
+int launch_gate_f32(const GateArgs& a, hipStream_t s, const GateArgs* twin) {
     const int n_groups = a.row_map ? 2 * ((a.n_edges + 31) / 32) : (a.n_edges + 15) / 16;
     // persistent: every block stages the weights once and walks ~n_groups / grid groups; the grid is what is resident at once -- 3
     // blocks per CU (51.7 KB of LDS each), 2 with the aggregation's wave buffers (63 KB) -- so there is no partial last wave of blocks
@@ -220,6 +166,38 @@ int launch_edge_gate(const GateArgs& a, hipStream_t s, const GateArgs* twin) {
     else hipLaunchKernelGGL((edge_gate_kernel<false, false>), dim3(grid), dim3(256), 0, s, a, a);
     VLSAT_LAUNCH_CHECK("edge_gate");
     return 0;
+}
+
+// Every check on a gate launch is here, once; the kernels' launchers above and in the other files only size the grid and launch.
+int launch_gate(GateKernel kernel, const GateArgs& a, int n_heads, int dk, int dox, int terms, int kproj_split, hipStream_t s,
+                const GateArgs* twin) {
+    if (a.n_edges <= 0) return 0;
+    const GateChoice can = gate_choice(kernel);
+    if (a.agg && !can.fuse_agg) return fail(-1, "edge_gate: this kernel does not implement the fused aggregation");
+    if (twin && !can.twin) return fail(-1, "edge_gate: this kernel does not implement a twin launch");
+    if (!a.row_map && !can.row_map0) return fail(-1, "edge_gate: this kernel has the 32-edges-per-wave row map only");
+    if (twin && (twin->n_edges != a.n_edges || !twin->agg != !a.agg || twin->row_map != a.row_map || twin->use_edge != a.use_edge ||
+                 !twin->prob != !a.prob || twin->grid_cap != a.grid_cap || twin->src != a.src || twin->dst != a.dst))
+        return fail(-1, "edge_gate: a twin launch needs two problems on the same edge list with the same options");
+    if (a.agg && (!a.row_map || a.prob || (a.ld_agg & 3))) return fail(-1, "edge_gate: the fused aggregation needs the 32-edges-per-wave row map and no prob tap");
+    if (kernel != GATE_VALU && ((a.ld_node & 3) || (a.gq_off & 3) || (a.v_off & 3)))       // (float4 accesses; the VALU kernel reads scalars)
+        return fail(-1, "edge_gate: ld_node/gq_off/v_off must be multiples of 4");
+    if (can.bits16()) {
+        if (terms != 1 && terms != 3) return fail(-1, "edge_gate_bf16: terms must be 1 or 3");
+        if (kproj_split >= 2 && terms != 1) return fail(-1, "edge_gate_bf16: half-row kproj needs terms = 1");
+    }
+    const bool shipped = n_heads == 8 && dk == 64 && dox == 32;
+    switch (kernel) {
+        case GATE_VALU: return launch_gate_valu(a, n_heads, dk, dox, s);
+        case GATE_F32: case GATE_16:
+            if (!shipped) return fail(-1, "edge_gate: the shipped kernels are built for 8 heads x (64, 32) only");
+            return kernel == GATE_F32 ? launch_gate_f32(a, s, twin) : launch_gate_16(a, terms, kproj_split, s, twin);
+        case GATE_F32_HEADS: case GATE_16_HEADS:
+            if (!gate_heads_built(n_heads, dk, dox) || (kernel == GATE_16_HEADS && terms == 3 && dk == 128))
+                return fail(-1, "edge_gate: head geometry / terms not built on the MFMA template");
+            return kernel == GATE_F32_HEADS ? launch_gate_f32_heads(a, n_heads, dk, dox, s) : launch_gate_16_heads(a, n_heads, dk, dox, terms, kproj_split, s);
+    }
+    return fail(-1, "edge_gate: unknown kernel");
 }
 
 }  // namespace vlsat

@@ -1,20 +1,13 @@
-// 'fat' edge gate on the fp32 matrix cores for the head geometries other than the shipped 8 x (64, 64, 32):
-// MODEL.NUM_HEADS in {4, 8, 16} and DIM_ATTEN in {128, 256, 512} (reference network_MMG.py:48-50,69-79,96-104) give
-// d_k = 512 / H query / edge channels per head in {128, 64, 32}, a hidden layer of 2 d_k and d_o = DIM_ATTEN / H output
-// channels in {8 .. 128}.  Same algebra, data flow and lane model as edge_gate.hip:
-//   per (edge, head) row:  hidden = relu(Gq[src] + W0k . kproj_row),  logits = W3 . hidden + b3,
-//                          prob = softmax over the d_o channels,  gated = prob * value[dst]   (head-major)
-//   a wave owns 32 consecutive EDGES of one head (source-major edge lists: its Gq loads name one or two node rows);
-//   both layers as transposed v_mfma_f32_32x32x2_f32 products so that a lane owns one row and the softmax stays in-lane;
-//   the hidden layer goes 32 outputs at a time from the layer-1 accumulator straight into the layer-2 product.
-// What the template adds: TO = 2 d_k / 32 hidden slices, d_k / 2 MFMAs per slice, MO = ceil(d_o / 32) logit blocks (rows of
-// W3 past d_o are zero, their channels masked out of the softmax).  Weights: W0k [2 d_k][d_k] and W3 [d_o][2 d_k] in LDS; at
-// d_k = 128 W0k alone is 135 KB, so there the block is 8 waves (one block per CU) and W3's fragments come from global
-// memory (64 .. 128 KB, L2-resident; 25 GB/s per CU against the 49 000 MFMA cycles of a wave step).
-// Before this kernel these geometries ran on the VALU kernel of edge_gate.hip (kept for anything else): 266 ms per bench
-// step at 4 heads, 77 ms at 16, against 1.1 ms at 8.
-#include "gemm_core.h"
-#include "kernels.h"
+// Edge gate on the fp32 matrix cores for the head geometries other than the shipped 8 x (64, 64, 32): MODEL.NUM_HEADS in {4, 8, 16}
+// and DIM_ATTEN in {128, 256, 512} (reference network_MMG.py:48-50,69-79,96-104) give d_k = 512 / H in {128, 64, 32}, a hidden layer
+// of 2 d_k and d_o = DIM_ATTEN / H in {8 .. 128}.  Algebra and lane model: gate_core.h; a wave owns 32 consecutive EDGES of one head
+// (source-major edge lists: its Gq loads name one or two node rows), v_mfma_f32_32x32x2_f32 as in edge_gate.hip.
+// What the template adds: TO = 2 d_k / 32 hidden slices, d_k / 2 MFMAs per slice, MO = ceil(d_o / 32) logit blocks.  Weights:
+// W0k [2 d_k][d_k] and W3 [d_o][2 d_k] in LDS; at d_k = 128 W0k alone is 135 KB, so there the block is 8 waves (one block per CU)
+// and W3's fragments come from global memory (64 .. 128 KB, L2-resident; 25 GB/s per CU against the 49 000 MFMA cycles of a wave
+// step).  On the VALU kernel of edge_gate.hip (kept for anything else) these geometries took 266 ms per bench step at 4 heads,
+// 77 ms at 16, against 1.1 ms at 8.
+#include "gate_core.h"
 
 namespace vlsat {
 
@@ -35,18 +28,8 @@ __global__ __launch_bounds__(DK == 128 ? 512 : 256, DK == 128 ? 1 : 2) void edge
     const int li = lane & 31, hi = lane >> 5;
     const int A = n_heads * DOX;                              // row width of gated / prob / the value columns
 
-    for (int i = tid; i < HID * (DK / 4); i += NT) {
-        const int r = i / (DK / 4), c4 = (i % (DK / 4)) * 4;
-        *reinterpret_cast<f32x4*>(sW0 + r * P0 + c4) = *reinterpret_cast<const f32x4*>(p.w0k + r * DK + c4);
-    }
-    if (W3_LDS) {
-        for (int i = tid; i < MO * 32 * (HID / 4); i += NT) {
-            const int r = i / (HID / 4), c4 = (i % (HID / 4)) * 4;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (r < DOX) v = *reinterpret_cast<const f32x4*>(p.w3 + r * HID + c4);
-            *reinterpret_cast<f32x4*>(sW3 + r * P3 + c4) = v;
-        }
-    }
+    gate_stage_f32_rows<HID, HID, DK, P0, NT>(sW0, p.w0k, tid);
+    if (W3_LDS) gate_stage_f32_rows<MO * 32, DOX, HID, P3, NT>(sW3, p.w3, tid);
     __syncthreads();
 
     const long n_wu = (long)((p.n_edges + 31) / 32) * n_heads;          // wave units: (block of 32 edges, head)
@@ -67,15 +50,7 @@ __global__ __launch_bounds__(DK == 128 ? 512 : 256, DK == 128 ? 1 : 2) void edge
         const int sn = p.src[e], dn = p.dst[e];
         const float* gq = p.node + (size_t)sn * p.ld_node + p.gq_off + h * HID + 4 * hi;
         f32x16 lg[MO];
-#pragma unroll
-        for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {                  // b3[m], m = mo*32 + 8*r4 + 4*hi + c (zero past d_o)
-                f32x4 b = {0.f, 0.f, 0.f, 0.f};
-                if (mo * 32 + 8 * r4 < DOX) b = *reinterpret_cast<const f32x4*>(p.b3 + mo * 32 + 8 * r4 + 4 * hi);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) lg[mo][r4 * 4 + c] = b[c];
-            }
+        gate_bias<MO, DOX>(lg, p.b3, hi);
 #pragma unroll(DK == 128 ? 1 : TO)                        // (d_k = 128: one slice is 64 + 64 MFMAs; unrolled, the scheduler's appetite spills)
         for (int to = 0; to < TO; ++to) {
             f32x16 acc;
@@ -108,47 +83,10 @@ __global__ __launch_bounds__(DK == 128 ? 512 : 256, DK == 128 ? 1 : 2) void edge
                 }
             }
         }
-        // softmax over the d_o channels m = mo*32 + crow32(r, hi) (+ the other 16 of a block in lane^32)
-        float mx = -INFINITY;
-#pragma unroll
-        for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (mo * 32 + 8 * (r >> 2) < DOX) mx = fmaxf(mx, lg[mo][r]);       // (a group of four channels is in or out as a whole)
-        mx = half_max(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (mo * 32 + 8 * (r >> 2) < DOX) {
-                    lg[mo][r] = __expf(lg[mo][r] - mx);
-                    sum += lg[mo][r];
-                }
-        sum = half_sum(sum);
-        const float inv = 1.f / sum;
-        if (valid) {
-            const float* vrow = p.node + (size_t)dn * p.ld_node + p.v_off + h * DOX + 4 * hi;
-            float* grow = p.gated + (size_t)e * A + h * DOX + 4 * hi;
-#pragma unroll
-            for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    if (mo * 32 + 8 * r4 >= DOX) continue;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(vrow + mo * 32 + 8 * r4);
-                    f32x4 o;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) o[c] = lg[mo][r4 * 4 + c] * inv * v[c];
-                    *reinterpret_cast<f32x4*>(grow + mo * 32 + 8 * r4) = o;
-                }
-            if (p.prob) {                      // test tap in the reference's [E, d_o, H] order
-#pragma unroll
-                for (int mo = 0; mo < MO; ++mo)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if (mo * 32 + 8 * (r >> 2) < DOX) p.prob[(size_t)e * A + (mo * 32 + crow32(r, hi)) * n_heads + h] = lg[mo][r] * inv;
-            }
-        }
+        const float inv = gate_softmax<MO, DOX>(lg);
+        if (valid)
+            gate_store<MO, DOX>(lg, inv, p.node + (size_t)dn * p.ld_node + p.v_off + h * DOX + 4 * hi, p.gated + (size_t)e * A + h * DOX + 4 * hi,
+                                p.prob, (size_t)e * A, n_heads, h, hi);
     }
 }
 
@@ -163,18 +101,10 @@ int run(const GateArgs& a, int n_heads, hipStream_t s) {
 
 }  // namespace
 
-// 1 = geometry not built here (the caller falls back to the VALU kernel)
-int launch_edge_gate_heads(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s) {
-    if (a.n_edges <= 0) return 0;
-    if ((a.ld_node & 3) || (a.gq_off & 3) || (a.v_off & 3)) return fail(-1, "edge_gate: ld_node/gq_off/v_off must be multiples of 4");
-    if (n_heads * dk != 512) return 1;
-    int r = 1;
-#define VLSAT_GH(DK, DOX) if (dk == DK && dox == DOX) r = run<DK, DOX>(a, n_heads, s)
-    VLSAT_GH(32, 8); VLSAT_GH(32, 16); VLSAT_GH(32, 32);
-    VLSAT_GH(64, 16); VLSAT_GH(64, 32); VLSAT_GH(64, 64);
-    VLSAT_GH(128, 32); VLSAT_GH(128, 64); VLSAT_GH(128, 128);
+int launch_gate_f32_heads(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s) {
+#define VLSAT_GH(DK, DOX) if (dk == DK && dox == DOX) run<DK, DOX>(a, n_heads, s);
+    VLSAT_GATE_HEAD_GEOMETRIES(VLSAT_GH)
 #undef VLSAT_GH
-    if (r) return r;
     VLSAT_LAUNCH_CHECK("edge_gate_heads");
     return 0;
 }

@@ -673,29 +673,14 @@ int vlsat_k_edge_gate(const float* kproj, const float* node, int32_t ld_node, in
     GateArgs g{};
     g.kproj = kproj; g.node = node; g.ld_node = ld_node; g.gq_off = gq_off; g.v_off = v_off; g.src = src; g.dst = dst;
     g.w0k = w0k; g.w3 = w3; g.b3 = b3; g.gated = gated; g.prob = prob; g.n_edges = n_edges; g.use_edge = use_edge != 0;
-    const bool def = n_heads == 8 && dk == 64 && dox == 32;
-    switch (variant) {
-        case 0:                                                  // what the fp32 forward launches for this geometry
-            if (def) return launch_edge_gate(g, s);
-            {
-                const int r = launch_edge_gate_heads(g, n_heads, dk, dox, s);
-                if (r <= 0) return r;
-            }
-            return launch_edge_gate_generic(g, n_heads, dk, dox, s);
-        case 1: return launch_edge_gate_generic(g, n_heads, dk, dox, s);
-        case 2: {
-            const int r = launch_edge_gate_heads(g, n_heads, dk, dox, s);
-            return r > 0 ? fail(VLSAT_EINVAL, "edge_gate: head geometry not built on the MFMA template") : r;
-        }
-        case 3: case 4: {
-            const int terms = variant == 3 ? 3 : 1;
-            if (def) return launch_edge_gate_bf16(g, terms, 0, s);
-            if (!edge_gate_bf16_heads_supports(dk, dox, terms)) return fail(VLSAT_EINVAL, "edge_gate: head geometry / terms not built on the bf16 template");
-            const int r = launch_edge_gate_bf16_heads(g, n_heads, dk, dox, terms, 0, s);
-            return r > 0 ? fail(VLSAT_EINVAL, "edge_gate: head geometry not built on the bf16 template") : r;
-        }
-        default: return fail(VLSAT_EINVAL, "edge_gate: variant 0..4");
-    }
+    if (variant < 0 || variant > 4) return fail(VLSAT_EINVAL, "edge_gate: variant 0..4");
+    // 0: what the fp32 forward launches for this geometry; 1: the VALU kernel; 2: the fp32 template; 3 | 4: the split-bf16 | single-rounded
+    // bf16 kernel of this geometry
+    const int terms = variant == 3 ? 3 : variant == 4 ? 1 : 0;
+    const GateChoice gc = variant == 1 ? gate_choice(GATE_VALU) : gate_select(n_heads, dk, dox, terms, true, variant == 2 ? 2 : 1, true);
+    if (variant == 2 && gc.kernel != GATE_F32_HEADS) return fail(VLSAT_EINVAL, "edge_gate: head geometry not built on the MFMA template");
+    if (terms && !gc.bits16()) return fail(VLSAT_EINVAL, "edge_gate: head geometry / terms not built on the bf16 template");
+    return launch_gate(gc.kernel, g, n_heads, dk, dox, terms, 0, s);
 }
 
 int vlsat_k_aggregate(const float* gated, int32_t n_ch, const int64_t* index_host, int64_t n_edges, int32_t n_nodes, int32_t aggr,

@@ -33,6 +33,23 @@ static int split_fmt(const vlsat_ctx* h) {
     return h->gate_bf16 && h->half_fmt ? 2 : 1;
 }
 
+// the gate kernel of this handle (kernels.h gate_select: the only place that decides it), and the arguments its launch takes
+static GateChoice gate_of(const vlsat_ctx* h) {
+    return gate_select(h->H, h->D / h->H, h->A / h->H, h->prec_edge == 0 ? 0 : h->prec_edge == 3 ? 3 : 1, h->gate_bf16 != 0, h->gate_heads_mfma,
+                       h->gate_heads_bf16 != 0);
+}
+static int gate_launch(vlsat_ctx* h, const GateChoice& gc, const GateArgs& g, hipStream_t s, const GateArgs* twin = nullptr) {
+    const int S = gc.bits16() ? split_fmt(h) : 0;        // (the fp32 gate kernels read plain fp32)
+    return launch_gate(gc.kernel, g, h->H, h->D / h->H, h->A / h->H, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s, twin);
+}
+// whether the max aggregation runs inside the gate kernel: GCN_AGGR = max on a kernel that implements it, no debug tap
+// (fp32: measured neutral -- 2196-2201 vs 2195 scenes/s -- and it moves waiting time into the GEMM class of the two-stream
+//  profile, so the exact-fp32 mode keeps the separate aggregate launch unless "gate_fuse_agg" is 2)
+static bool gate_fuses_agg(const vlsat_ctx* h, const GateChoice& gc, const GateArgs& g) {
+    return gc.fuse_agg && (h->gate_fuse_agg == 2 || (h->gate_fuse_agg == 1 && gc.bits16())) && h->d.gcn_aggr == 0 && !g.prob && h->debug_stop < 0 &&
+           g.row_map && g.n_edges > 0;
+}
+
 // ---- profiling helpers ----
 hipEvent_t next_event(vlsat_ctx* h) {
     if (h->ev_used == h->ev_pool.size()) {
@@ -205,9 +222,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, float
     const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
     if (!node_done) RUN(gcn_node_project(h, p, s, w, x, sc));
     const int S = split_fmt(h);
-    const bool gate16 = h->prec_edge && h->gate_bf16 && default_heads(h);
-    const bool gate16h = h->prec_edge && h->gate_bf16 && (!default_heads(h) || h->gate_heads_mfma == 2) && h->gate_heads_mfma && h->gate_heads_bf16 &&
-                         edge_gate_bf16_heads_supports(D / h->H, A / h->H, h->prec_edge == 3 ? 3 : 1);   // other head geometries, bf16 kernel
+    const GateChoice gc = gate_of(h);
     GemmArgs e1 = G(e, D, w.we1, D, sc.Hbig, 2 * D, E, 2 * D, nullptr, ACT_RELU);
     e1.relu_a = e_relu_pending;
     e1.a_split = S; e1.c_split = S;
@@ -219,7 +234,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, float
         GemmArgs kp = G(e, D, w.wpe, D, sc.KP, D, E, D, w.bpe);
         kp.relu_a = e_relu_pending;
         kp.a_split = S;
-        kp.c_split = (gate16 || gate16h) ? S : 0;      // (the fp32 gate kernels read plain fp32)
+        kp.c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
         RUN(gemm(h, s, kp));
     }
     bool fused_agg = false;
@@ -230,29 +245,17 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, float
         GateArgs g{};
         g.kproj = sc.KP; g.node = sc.NP; g.ld_node = NPC; g.gq_off = 4 * D; g.v_off = 6 * D;    // Gq spans H * 2 d_k = 2 D columns
         g.src = p->d_src; g.dst = p->d_dst; g.w0k = w.w0k; g.w3 = w.w3; g.b3 = w.b3; g.gated = sc.G;
-        g.prob = p->prob; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = h->gate_row_map;
+        g.prob = p->prob; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = gc.row_map0 ? h->gate_row_map : 1;
         const double dk = D / h->H, dox = A / h->H;
-        // the gate at 8 x (64, 32) in any precision, max aggregation, no debug tap: the aggregation happens inside the gate kernel (no [E, 256]
-        // tensor of gated messages, no aggregate launch); the start values go in first
-        const bool shipped_kernel = !gate16h && default_heads(h) && !(h->gate_heads_mfma == 2 && !gate16);     // edge_gate.hip / edge_gate_bf16.hip
-        // (fp32: measured neutral -- 2196-2201 vs 2195 scenes/s -- and it moves waiting time into the GEMM class of the two-stream
-        //  profile, so the exact-fp32 mode keeps the separate aggregate launch unless "gate_fuse_agg" is 2)
-        fused_agg = shipped_kernel && (h->gate_fuse_agg == 2 || (h->gate_fuse_agg == 1 && gate16)) && h->d.gcn_aggr == 0 && !g.prob && h->debug_stop < 0 && h->gate_row_map && E > 0;
+        // fused: no [E, A] tensor of gated messages, no aggregate launch; the start values go in first
+        fused_agg = gate_fuses_agg(h, gc, g);
         if (fused_agg) {
             Scope scope(h, s, PC_AGGREGATE, 0);
             RUN(launch_agg_init(p->d_rowptr, N, A, x + D, LDX, s));
             g.agg = x + D; g.ld_agg = LDX;
         }
         Scope scope(h, s, PC_GATE, (double)E * h->H * (2.0 * dk * 2 * dk + 2.0 * 2 * dk * dox));
-        if (gate16h) {
-            RUN(launch_edge_gate_bf16_heads(g, h->H, D / h->H, A / h->H, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s));
-        } else if (!default_heads(h) || (h->gate_heads_mfma == 2 && !gate16)) {     // (2: the shipped geometry on the template as well -- A/B)
-            int r = h->gate_heads_mfma ? launch_edge_gate_heads(g, h->H, D / h->H, A / h->H, s) : 1;
-            if (r < 0) return r;
-            if (r) RUN(launch_edge_gate_generic(g, h->H, D / h->H, A / h->H, s));
-        }
-        else if (gate16) RUN(launch_edge_gate_bf16(g, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s));
-        else RUN(launch_edge_gate(g, s));
+        RUN(gate_launch(h, gc, g, s));
     }
     if (!fused_agg) {
         Scope scope(h, s, PC_AGGREGATE, 0);
@@ -301,12 +304,12 @@ int obj_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const float* x, const
 // ---- the paired schedule of one-scene plans (round 6): gcn_3ds[l] and gcn_2ds[l], the two relation heads, the two object heads and
 // the two relation encoders as launches of TWO problems each (gemm2, twin gate / aggregate launches).  Stage by stage the same
 // kernels on the same operands as gcn_block / rel_head / obj_head above: bit-identical outputs.
-// Shipped gate kernels only (default head geometry, no probability tap); the caller checks.
+// Only with a gate kernel that takes a twin (gate_select) and no probability tap; the caller checks.
 int gcn_block_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w3, const GcnW& w2, float* x3, float* x2, float* e3, float* e2,
                    int e3_relu_pending, int out_relu, const Scratch& sc3, const Scratch& sc2) {
     const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
     const int S = split_fmt(h);
-    const bool gate16 = h->prec_edge && h->gate_bf16;
+    const GateChoice gc = gate_of(h);
     {
         GemmArgs n3 = G(x3, LDX, w3.wnode, D, sc3.NP, NPC, N, NPC, w3.bnode), n2 = G(x2, LDX, w2.wnode, D, sc2.NP, NPC, N, NPC, w2.bnode);
         if (gather_f16_on(h)) n3.c_f16_cols = n2.c_f16_cols = 4 * D;
@@ -327,7 +330,7 @@ int gcn_block_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w3,
             GemmArgs kp = G(e, D, w.wpe, D, sc.KP, D, E, D, w.bpe);
             kp.relu_a = relu;
             kp.a_split = S;
-            kp.c_split = gate16 ? S : 0;
+            kp.c_split = gc.bits16() ? S : 0;
             return kp;
         };
         RUN(gemm2(h, s, kp_of(w3, e3, e3_relu_pending, sc3), kp_of(w2, e2, 0, sc2)));
@@ -338,16 +341,16 @@ int gcn_block_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w3,
         return g;
     };
     RUN(gemm2(h, s, e2_of(w3, e3, sc3), e2_of(w2, e2, sc2)));
-    auto gate_of = [&](const GcnW& w, const Scratch& sc) {
+    auto gate_args = [&](const GcnW& w, const Scratch& sc) {
         GateArgs g{};
         g.kproj = sc.KP; g.node = sc.NP; g.ld_node = NPC; g.gq_off = 4 * D; g.v_off = 6 * D;
         g.src = p->d_src; g.dst = p->d_dst; g.w0k = w.w0k; g.w3 = w.w3; g.b3 = w.b3; g.gated = sc.G;
-        g.prob = nullptr; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = h->gate_row_map;
+        g.prob = nullptr; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = gc.row_map0 ? h->gate_row_map : 1;
         return g;
     };
-    GateArgs g3 = gate_of(w3, sc3), g2 = gate_of(w2, sc2);
+    GateArgs g3 = gate_args(w3, sc3), g2 = gate_args(w2, sc2);
     const double dk = D / h->H, dox = A / h->H;
-    const bool fused_agg = (h->gate_fuse_agg == 2 || (h->gate_fuse_agg == 1 && gate16)) && h->d.gcn_aggr == 0 && h->gate_row_map && E > 0;
+    const bool fused_agg = gate_fuses_agg(h, gc, g3);
     if (fused_agg) {
         Scope scope(h, s, PC_AGGREGATE, 0);
         RUN(launch_agg_init(p->d_rowptr, N, A, x3 + D, LDX, s, x2 + D));
@@ -356,8 +359,7 @@ int gcn_block_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w3,
     }
     {
         Scope scope(h, s, PC_GATE, 2.0 * (double)E * h->H * (2.0 * dk * 2 * dk + 2.0 * 2 * dk * dox));
-        if (gate16) RUN(launch_edge_gate_bf16(g3, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s, &g2));
-        else RUN(launch_edge_gate(g3, s, &g2));
+        RUN(gate_launch(h, gc, g3, s, &g2));
     }
     if (!fused_agg) {
         Scope scope(h, s, PC_AGGREGATE, 0);
@@ -524,8 +526,8 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     // (relation encoders, gcn_3ds | gcn_2ds, both head pairs) have the same shapes, so each pair becomes ONE launch of two problems
     // on the caller's stream; the second lane keeps the only chain without a twin, the edge cross-attention of layer l, which runs
     // under the node attentions of layer l + 1.  Same kernels on the same operands as the other schedules: bit-identical outputs.
-    const bool pair = dual && h->pair_twins && p->E > 0 && p->E <= h->pair_max_edges && !h->d.feature_transform && default_heads(h) &&
-                      !p->prob && !(h->gate_heads_mfma == 2 && !(h->prec_edge && h->gate_bf16)) && h->sched != 1;
+    const bool pair = dual && h->pair_twins && p->E > 0 && p->E <= h->pair_max_edges && !h->d.feature_transform && gate_of(h).twin &&
+                      !p->prob && h->sched != 1;
     // (default: exact for the bf16 modes on plans that fill the chip by themselves.  One-scene plans keep two streams: with K replicas
     //  in flight on K host threads the third stream of every replica competes for the few hardware queues -- 551 vs 926-953 scenes/s at
     //  four in flight in bf16_mixed, profiles/r05_probes/val_loop_bf16_mixed_three_lanes.txt)

@@ -165,49 +165,84 @@ int launch_pts_conv1_rows(const float* pts, int n_obj, int P, int cin, const flo
 int launch_rowmax(const float* x, int ld, int n_obj, int P, int cols, float* out, int ldo, hipStream_t s);
 int launch_apply_stn(const float* h, int ldh, const float* T, size_t rows, int P, float* out, int ldo, hipStream_t s);
 
-// ---- 'fat' edge gate: per (edge, head) MLP 128->128->32, softmax over 32, times value ----
+// ---- 'fat' edge gate: per (edge, head) MLP 2 d_k -> 2 d_k -> d_o, softmax over d_o, times value (gate_core.h) ----
+// H heads, d_k = 512 / H query / edge channels and d_o = DIM_ATTEN / H output channels per head (shipped: 8 x (64, 32))
 struct GateArgs {
-    const float* kproj;      // [E, 512] head-major: kproj[e, h*64 + c]
+    const float* kproj;      // [E, 512] head-major: kproj[e, h*d_k + c]; fp32, or the 16-bit kernels' `kproj_split` formats
     const float* node;       // node-side buffer, row pitch ld_node
     int ld_node;
-    int gq_off;              // column offset of Gq[h*128 + o] (layer-1 node part incl. bias)
-    int v_off;               // column offset of value[h*32 + m]  (head-major, see edge_gate.hip)
+    int gq_off;              // column offset of Gq[h*2 d_k + o] (layer-1 node part incl. bias)
+    int v_off;               // column offset of value[h*d_o + m]  (head-major, see gate_core.h)
     const int32_t* src;      // [E]
     const int32_t* dst;      // [E]
-    const float* w0k;        // [128, 64]  layer-1 weights acting on the edge half
-    const float* w3;         // [32, 128]
-    const float* b3;         // [32]
-    float* gated;            // [E, 256]  gated[e, h*32 + m]
-    float* prob;             // optional [E, 32, 8] tap (tests) or nullptr
+    const float* w0k;        // [2 d_k, d_k]  layer-1 weights acting on the edge half
+    const float* w3;         // [d_o, 2 d_k]
+    const float* b3;         // [d_o]
+    float* gated;            // [E, H d_o]  gated[e, h*d_o + m]
+    float* prob;             // optional [E, d_o, H] tap (tests) or nullptr
     int n_edges;
     int use_edge = 1;        // MODEL.USE_GCN_EDGE: 0 -> the gate MLP sees the query alone (kproj / w0k unused)
-    int grid_cap = 0;        // debug: persistent grid size (0 = 3 blocks per CU; vlsat_debug_option "gate_grid")
+    int grid_cap = 0;        // debug: persistent grid size (0 = the kernel's own; vlsat_debug_option "gate_grid")
     // Fused max aggregation (Aggre_Index with GCN_AGGR = max, reference network_util.py:64-73): when `agg` is set the gated rows
     // are not stored; every wave reduces its 32 rows by source node through LDS and folds the partial maxima into
-    // agg[src, h*32 + m] (row pitch ld_agg) with integer-ordered atomic max -- exact and order-independent.  `agg` must have been
+    // agg[src, h*d_o + m] (row pitch ld_agg) with integer-ordered atomic max -- exact and order-independent.  `agg` must have been
     // initialised by launch_agg_init (-inf for nodes with out-edges, 0 for the others: torch_scatter's empty segment).
     float* agg = nullptr;
     int ld_agg = 0;
     int row_map = 1;         // rows of a wave: 1 = 32 edges of one head, 0 = 4 edges x 8 heads (vlsat_debug_option "gate_row_map")
 };
-int launch_edge_gate(const GateArgs& a, hipStream_t s, const GateArgs* twin = nullptr);     // twin: a second gate on the same edge list in the same launch (one-scene plans)
+// The five gate kernels, and the ONE place that says which of them runs and what it can do besides the plain gate.
+enum GateKernel {
+    GATE_VALU,          // any geometry, plain VALU (edge_gate.hip)
+    GATE_F32,           // fp32 MFMA, the shipped 8 x (64, 32) (edge_gate.hip)
+    GATE_F32_HEADS,     // fp32 MFMA, the template of the other head geometries (edge_gate_heads.hip)
+    GATE_16,            // bf16 / fp16 MFMA, the shipped geometry (edge_gate_bf16.hip)
+    GATE_16_HEADS       // bf16 / fp16 MFMA, the template (edge_gate_bf16_heads.hip)
+};
+struct GateChoice {
+    GateKernel kernel;
+    bool fuse_agg;      // implements GateArgs::agg
+    bool twin;          // takes a second problem on the same edge list in the same launch (one-scene plans)
+    bool row_map0;      // implements GateArgs::row_map = 0
+    bool bits16() const { return kernel == GATE_16 || kernel == GATE_16_HEADS; }      // reads the 16-bit kproj formats
+};
+// only the two kernels of the shipped geometry implement the extras; launch_gate refuses them on the others
+inline GateChoice gate_choice(GateKernel k) {
+    const bool shipped = k == GATE_F32 || k == GATE_16;
+    return {k, shipped, shipped, shipped};
+}
+// (d_k, d_o) the two head templates are instantiated for: MODEL.NUM_HEADS in {4, 8, 16} x DIM_ATTEN in {128, 256, 512}
+#define VLSAT_GATE_HEAD_GEOMETRIES(X) X(32, 8) X(32, 16) X(32, 32) X(64, 16) X(64, 32) X(64, 64) X(128, 32) X(128, 64) X(128, 128)
+inline bool gate_heads_built(int n_heads, int dk, int dox) {
+#define VLSAT_GH(DK, DOX) || (dk == DK && dox == DOX)
+    return n_heads * dk == 512 && (false VLSAT_GATE_HEAD_GEOMETRIES(VLSAT_GH));
+#undef VLSAT_GH
+}
+// terms: 0 = fp32 operands, 3 = split-bf16, 1 = single-rounded bf16 / fp16 (precision of the edge rows); gate_bf16, heads_mfma,
+// heads_bf16: the vlsat_debug_option switches "gate_bf16" (0: fp32 kernels in every mode), "gate_heads_mfma" (0: VALU kernel for the
+// other head geometries, 2: the templates for the shipped geometry as well -- A/B) and "gate_heads_bf16" (0: fp32 template).
+inline GateChoice gate_select(int n_heads, int dk, int dox, int terms, bool gate_bf16, int heads_mfma, bool heads_bf16) {
+    const bool shipped = n_heads == 8 && dk == 64 && dox == 32 && heads_mfma != 2;
+    const bool want16 = terms != 0 && gate_bf16;
+    if (shipped) return gate_choice(want16 ? GATE_16 : GATE_F32);
+    if (!heads_mfma || !gate_heads_built(n_heads, dk, dox)) return gate_choice(GATE_VALU);
+    // (two plane sets of d_k = 128 do not fit the LDS: split-bf16 stays on the fp32 template there)
+    if (want16 && heads_bf16 && !(terms == 3 && dk == 128)) return gate_choice(GATE_16_HEADS);
+    if (want16 && n_heads == 8 && dk == 64 && dox == 32) return gate_choice(GATE_16);     // (2 with "gate_heads_bf16" off)
+    return gate_choice(GATE_F32_HEADS);
+}
+// kernel: what gate_select (or a test that names a kernel) chose.  terms (1 | 3) and kproj_split (format of kproj: 0 fp32, 1 split-pair
+// words of common.h pack_split, 2 bf16 half rows, 3 fp16 half rows -- 2 and 3 with terms = 1 only) are read by the 16-bit kernels.
+// twin: a second gate on the same edge list with the same options in the same launch.  An `agg`, a twin or a row_map = 0 handed to a
+// kernel that does not implement it is refused, as is a geometry the kernel is not built for.
+int launch_gate(GateKernel kernel, const GateArgs& a, int n_heads, int dk, int dox, int terms, int kproj_split, hipStream_t s,
+                const GateArgs* twin = nullptr);
 // agg[n, 0:n_ch] = rowptr[n+1] > rowptr[n] ? -inf : 0   (start values of the fused max aggregation)
 int launch_agg_init(const int32_t* rowptr, int n_nodes, int n_ch, float* agg, int ld_agg, hipStream_t s, float* agg2 = nullptr);
 // p[0:n] = 0 with a kernel of the library (16-byte stores when n and p allow): the forward path does not use hipMemsetAsync
 int launch_zero_f32(float* p, size_t n, hipStream_t s);
 // dst[r, 0:cols] = src[r, 0:cols], r < rows (pitches in floats; 16-byte accesses when sizes and pointers allow)
 int launch_copy_rows(float* dst, size_t dst_ld, const float* src, size_t src_ld, int cols, size_t rows, hipStream_t s);
-// any head geometry (dk query / edge channels per head, dox output channels per head): plain VALU
-int launch_edge_gate_generic(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s);
-// the head geometries of MODEL.NUM_HEADS in {4, 8, 16} x DIM_ATTEN in {128, 256, 512} on the fp32 matrix cores
-// (edge_gate_heads.hip); returns 1 when (dk, dox) is not one of them (-> the VALU kernel)
-int launch_edge_gate_heads(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s);
-// ... and on the bf16 matrix cores (edge_gate_bf16_heads.hip); split-bf16 (terms = 3) not at dk = 128
-bool edge_gate_bf16_heads_supports(int dk, int dox, int terms);
-int launch_edge_gate_bf16_heads(const GateArgs& a, int n_heads, int dk, int dox, int terms, int kproj_split, hipStream_t s);
-// the same on the bf16 matrix cores (edge_gate_bf16.hip): terms = 3 split-bf16 | 1 single-rounded; kproj_split = 1: kproj is
-// in the split-pair format of the bf16 modes (common.h pack_split)
-int launch_edge_gate_bf16(const GateArgs& a, int terms, int kproj_split, hipStream_t s, const GateArgs* twin = nullptr);
 
 // ---- scatter aggregation by source node over a CSR (rowptr[N+1], order[E]) ----
 // out[n, col0 + c] = reduce_{k in rowptr[n]..rowptr[n+1]} gated[order[k], c]; empty -> 0

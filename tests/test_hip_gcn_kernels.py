@@ -143,6 +143,57 @@ def test_edge_gate_ragged_sizes(lib):
         _gate_case(lib, 8, 256, "bf16x3", "random", seed=e, n=9, e=e)
 
 
+def test_gate_kernels_refuse_what_they_do_not_implement():
+    """A fused aggregation, a twin problem or row_map = 0 handed to the VALU kernel or to a head-geometry template is an error with a
+    message, not a launch that ignores it (the gated messages would be neither stored nor aggregated).  vlsat_k_edge_gate cannot
+    pass these arguments, so a host program calls launch_gate itself (tests/gate_host_check.cpp); the checks precede any launch, and
+    the program runs with no device visible."""
+    import gate_host
+    rows = gate_host.run("refuse")
+    assert len(rows) == 18 and {l.split()[0] for l, _ in rows} == {"valu", "f32_heads", "16_heads"}
+    for left, right in rows:
+        code, msg = right.split(" | ", 1)
+        assert int(code) == -1 and msg.startswith("edge_gate: this kernel"), (left, right)
+        assert {"agg": "fused aggregation", "twin": "twin launch", "row_map0": "row map"}[left.split()[1]] in msg, (left, right)
+
+
+@pytest.fixture(scope="module")
+def ragged_forward():
+    """two scenes of 9 and 5 objects x 64 points (E = 72 + 20 = 92: no multiple of 32), and the fp64 oracle's outputs per geometry"""
+    from vlsat_amd import VLSATConfig, synth
+    b = synth.collate([synth.make_scene(9, 64, 5100), synth.make_scene(5, 64, 5101)])
+    c = {k: torch.from_numpy(v) for k, v in b.items()}
+    ref = {}
+
+    def get(H, A):
+        cfg = VLSATConfig(N_LAYERS=2, NUM_HEADS=H, DIM_ATTEN=A)
+        if (H, A) not in ref:
+            w = synth.make_weights(cfg)
+            ref[H, A] = (w, O.forward(O.to_torch(w, F64), cfg, c["obj_points"].double(), c["obj_2d_feats"].double(), c["edge_indices"],
+                                      c["descriptor"].double(), c["batch_ids"]))
+        return (cfg, b) + ref[H, A]
+    return get
+
+
+# the gate's kproj formats that only whole forwards produce: split-pair words (bf16x3), bf16 half rows (bf16_mixed), fp16 half rows
+# (fp16_mixed); tolerances of these modes against the fp64 oracle as in test_hip_round3.py / test_hip_round6.py
+@pytest.mark.parametrize("H,A", [(8, 256), (16, 128)])
+@pytest.mark.parametrize("mode,tol", [("bf16x3", 1e-3), ("bf16_mixed", 1e-2), ("fp16_mixed", 2e-3)])
+def test_gate_kproj_formats_in_a_ragged_forward_vs_oracle(lib, ragged_forward, H, A, mode, tol):
+    from vlsat_amd.model import VLSATModel
+    cfg, b, w, ref = ragged_forward(H, A)
+    m = VLSATModel(cfg, DEV).load_state(w).eval().set_gemm_precision(mode)
+    try:
+        d = {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
+        out = m(d["obj_points"], d["obj_2d_feats"], d["edge_indices"], d["descriptor"], d["batch_ids"])
+        torch.cuda.synchronize()
+        errs = [float((g.cpu() - r.float()).abs().max()) for g, r in zip(out, ref)]
+        print(H, A, mode, [f"{e:.2e}" for e in errs])
+        assert all(g.shape == r.shape for g, r in zip(out, ref)) and max(errs) < tol, (H, A, mode, errs, tol)
+    finally:
+        m.close()
+
+
 # ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("aggr", ["max", "add", "mean"])
 @pytest.mark.parametrize("n_ch", [128, 256, 512])

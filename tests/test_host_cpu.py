@@ -151,6 +151,37 @@ def test_c_abi_argument_validation_without_gpu(L):
     lib.vlsat_destroy(h)
 
 
+# Which gate kernel runs, written out by hand from the if-chain gcn_block had before gate_select existed (kernels.h).  "want16": the edge rows
+# are in a 16-bit precision (terms 1 | 3) and "gate_bf16" is on.  Keys: (want16, gate_heads_mfma, gate_heads_bf16).
+_GATE_SHIPPED_GEOMETRY = {           # 8 heads x DIM_ATTEN 256
+    (0, 0, 0): "f32", (0, 0, 1): "f32", (0, 1, 0): "f32", (0, 1, 1): "f32", (0, 2, 0): "f32_heads", (0, 2, 1): "f32_heads",
+    (1, 0, 0): "16", (1, 0, 1): "16", (1, 1, 0): "16", (1, 1, 1): "16", (1, 2, 0): "16", (1, 2, 1): "16_heads"}
+_GATE_OTHER_GEOMETRIES = {
+    (0, 0, 0): "valu", (0, 0, 1): "valu", (0, 1, 0): "f32_heads", (0, 1, 1): "f32_heads", (0, 2, 0): "f32_heads", (0, 2, 1): "f32_heads",
+    (1, 0, 0): "valu", (1, 0, 1): "valu", (1, 1, 0): "f32_heads", (1, 1, 1): "16_heads", (1, 2, 0): "f32_heads", (1, 2, 1): "16_heads"}
+
+
+def test_gate_select_chooses_what_the_forward_chose_before_it(L):
+    """gate_select over every head geometry x precision x debug switch: the kernel of the hand-written tables above (with the one
+    exception they do not show: no split-bf16 template at d_k = 128, so 4 heads with terms = 3 stay on the fp32 template), and only
+    the two kernels of the shipped geometry offer the fused aggregation, a twin launch and row_map = 0.  Host code only: no device."""
+    import gate_host
+    rows = gate_host.run("select")
+    assert len(rows) == 3 * 3 * 3 * 2 * 3 * 2
+    seen = set()
+    for left, right in rows:
+        H, A, terms, bf16, hm, hb = (int(x) for x in left.split())
+        kernel, fuse, twin, map0 = right.split()
+        table = _GATE_SHIPPED_GEOMETRY if (H, A) == (8, 256) else _GATE_OTHER_GEOMETRIES
+        want = table[int(terms != 0 and bf16 == 1), hm, hb]
+        if want == "16_heads" and H == 4 and terms == 3:
+            want = "f32_heads"
+        assert kernel == want, (left, kernel, want)
+        assert fuse == twin == map0 == ("1" if kernel in ("f32", "16") else "0"), (left, right)
+        seen.add(kernel)
+    assert seen == {"valu", "f32", "f32_heads", "16", "16_heads"}
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "cvpr2023-vlsat_amd")
     for dp, _, fs in os.walk(pkg):
