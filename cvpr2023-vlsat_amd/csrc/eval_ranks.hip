@@ -110,8 +110,10 @@ __global__ __launch_bounds__(256) void rel_rank_kernel(const float* __restrict__
 // ranks -- are bit-exact functions of the inputs, equal to the brute-force count whatever the tie order of the sort.
 // (Round 5's kernel walked the C^2 pairs of every edge with a pruning bound: 3.8 ms per branch on the 64-scene batch.)
 
-// sorted[n, 0:K] = the K largest entries of probs[n, :] in descending order; one wave per node, rank by counting
-__global__ __launch_bounds__(256) void sort_probs_kernel(const float* __restrict__ probs, int N, int C, int K, float* __restrict__ sorted) {
+// sorted[n, 0:K] = the K largest entries of probs[n, :] in descending order and -- si given -- si[n, 0:K] = their class indices (equal
+// values in ascending class order); one wave per node, rank by counting
+__global__ __launch_bounds__(256) void sort_probs_kernel(const float* __restrict__ probs, int N, int C, int K, float* __restrict__ sorted,
+                                                         int32_t* __restrict__ si) {
     extern __shared__ float s_row[];                               // [4][C]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = blockIdx.x * 4 + w;
     float* row = s_row + (size_t)w * C;
@@ -126,7 +128,10 @@ __global__ __launch_bounds__(256) void sort_probs_kernel(const float* __restrict
             const float x = row[q];
             r += (x > v) || (x == v && q < c);
         }
-        if (r < K) sorted[(size_t)n * K + r] = v;
+        if (r < K) {
+            sorted[(size_t)n * K + r] = v;
+            if (si) si[(size_t)n * K + r] = c;
+        }
     }
 }
 
@@ -482,9 +487,9 @@ int launch_eval_triplet_split(const int32_t* tri_rank3, const int32_t* tri_rank2
     return 0;
 }
 
-int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s) {
+int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s, int32_t* si) {
     if (N <= 0) return 0;
-    hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, probs, N, C, K, sorted);
+    hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, probs, N, C, K, sorted, si);
     VLSAT_LAUNCH_CHECK("sort_probs");
     return 0;
 }
@@ -514,7 +519,8 @@ int launch_eval_ranks(const float* obj_logits, const float* obj_probs, const flo
             return fail(-1, "eval_ranks: min(n_obj_class, topk_triplet) must be at most 1008");
         hipLaunchKernelGGL(rel_rank_kernel, dim3((E + 7) / 8), dim3(256), 0, s, rel, gt_rel, E, R, topk_rel, thr, rel_rank, cnt);
         VLSAT_LAUNCH_CHECK("rel_rank");
-        hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, obj_probs, N, C, K, sorted_probs);
+        hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, obj_probs, N, C, K, sorted_probs,
+                           (int32_t*)nullptr);
         VLSAT_LAUNCH_CHECK("sort_probs");
         hipLaunchKernelGGL(tri_rank_kernel, dim3((E + 7) / 8), dim3(256), (size_t)16 * K * sizeof(float) + 256 * sizeof(int), s, obj_probs, sorted_probs, rel, gt_cls,
                            gt_rel, edges, E, C, R, K, topk_tri, thr, tri_rank);

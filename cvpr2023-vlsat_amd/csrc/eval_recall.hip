@@ -8,8 +8,9 @@
 // largest candidate of the scene that is c >= T_K; the candidate condition is c >= max of e for GC and implied by c >= T_K for NGC
 // (K <= topk_each).  The conditions are monotone in c, so only an edge's best correct entry g_e matters:
 //   PredCls  g = max_{k in gt} r_k                      SGCls  g = fl(fl(s_gt * o_gt) * max_{k in gt} r_k)
-// Three launches after the per-node sort of eval_ranks.hip, values compared as order-preserving 32-bit keys (never indices):
-//   scene_ptr_kernel   edge offsets of every scene (edges arrive grouped by scene in ascending order)
+// Three launches after the per-node sort of eval_ranks.hip, values compared as order-preserving 32-bit keys (never indices; key,
+// bisection and tie rule: select_core.h):
+//   launch_scene_edge_ptr  (scene_graph.hip) edge offsets of every scene (edges arrive grouped by scene in ascending order)
 //   recall_edge_kernel one wave per edge: its gt mask, g keys, sorted predicate keys and -- SGCls NGC -- its top 100 products.
 //                      An entry at sorted position (i, j, k) of (s, o, r) is dominated by (i+1)(j+1)(k+1) - 1 others, so the top
 //                      100 lie in the 1 365 triples with (i+1)(j+1)(k+1) <= 100 (k < 32): evaluated, the 100th largest selected by
@@ -20,6 +21,7 @@
 // Integer / latency-bound work: no MFMA.
 #include "common.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace vlsat {
 
@@ -29,59 +31,11 @@ constexpr int RK_TOP = 100;                      // topk_each of the NGC variant
 constexpr int RK_MAX_R = 32;
 constexpr int RK_SCENE_THREADS = 1024;
 
-constexpr int tri_count() {
-    int n = 0;
-    for (int a = 1; a <= RK_TOP; ++a)
-        for (int b = 1; a * b <= RK_TOP; ++b)
-            for (int c = 1; c <= RK_MAX_R && a * b * c <= RK_TOP; ++c) ++n;
-    return n;
-}
-constexpr int RK_NT = tri_count();               // 1 365
+constexpr int RK_NT = tri_count(RK_TOP, RK_MAX_R);   // 1 365
 constexpr int RK_PER = (RK_NT + 63) / 64;        // triples per lane
-
-struct TriTable {
-    uint32_t v[RK_NT];
-};
-constexpr TriTable make_tri() {
-    TriTable t{};
-    int n = 0;
-    for (int a = 1; a <= RK_TOP; ++a)
-        for (int b = 1; a * b <= RK_TOP; ++b)
-            for (int c = 1; c <= RK_MAX_R && a * b * c <= RK_TOP; ++c) t.v[n++] = (uint32_t)((a - 1) | ((b - 1) << 8) | ((c - 1) << 16));
-    return t;
-}
-__constant__ TriTable c_tri = make_tri();
-
-// order-preserving key of a float (no NaN): key(x) < key(y) <=> x < y; every real value has a key > 0, so 0 pads a list
-__device__ __forceinline__ uint32_t fkey(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ int clampi(int64_t x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : (int)x; }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+__constant__ TriTable<RK_TOP, RK_MAX_R> c_tri = make_tri<RK_TOP, RK_MAX_R>();
 
 }  // namespace
-
-// ptr[q] = first edge of scene q, ptr[n_scenes] = E (thread t = E closes the list)
-__global__ __launch_bounds__(256) void scene_ptr_kernel(const int64_t* __restrict__ edges, const int64_t* __restrict__ batch_ids, int N,
-                                                        int E, int n_scenes, int32_t* __restrict__ ptr) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t > E) return;
-    auto scene = [&](int e) {
-        const int a = clampi(edges[2 * (size_t)e], 0, N - 1);
-        return batch_ids ? clampi(batch_ids[a], 0, n_scenes - 1) : 0;
-    };
-    const int s0 = t > 0 ? scene(t - 1) : -1, s1 = t < E ? scene(t) : n_scenes;
-    for (int q = s0 + 1; q <= s1; ++q) ptr[q] = t;
-}
 
 // one wave per edge, 4 edges per block
 __global__ __launch_bounds__(256) void recall_edge_kernel(const float* __restrict__ probs, const float* __restrict__ sorted, int Ks,
@@ -105,11 +59,7 @@ __global__ __launch_bounds__(256) void recall_edge_kernel(const float* __restric
         const float rv = lane < R ? rel[(size_t)e * R + lane] : -INFINITY;
         const bool is_gt = lane < R && gt_rel[(size_t)e * R + lane] == 1;
         mask = (unsigned)__ballot(is_gt);
-        int rk = 0;
-        for (int q = 0; q < R; ++q) {
-            const float x = __shfl(rv, q);
-            rk += x > rv || (x == rv && q < lane);
-        }
+        const int rk = rank_desc_in_wave(rv, lane, R);
         gr = wave_max(is_gt ? rv : -INFINITY);    // best gt predicate score (-inf: no gt relation)
         if (lane < R) {
             s_rs[w][rk] = rv;
@@ -145,25 +95,12 @@ __global__ __launch_bounds__(256) void recall_edge_kernel(const float* __restric
         }
         v[t] = key;
     }
-    // T = the 100th largest key (0 when the edge has fewer than 100 entries): the largest T with #{v >= T} >= 100
-    uint32_t T = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t trial = T | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int t = 0; t < RK_PER; ++t) c += v[t] >= trial;
-        if (wave_sum_int(c) >= RK_TOP) T = trial;
-    }
+    const uint32_t T = wave_kth_largest(v, RK_TOP);                // the 100th largest key (0 when the edge has fewer than 100 entries)
     // the (< 100) keys above T, compacted in lane order
     int mine = 0;
 #pragma unroll
     for (int t = 0; t < RK_PER; ++t) mine += v[t] > T;
-    int off = mine;                                // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(off, o);
-        if (lane >= o) off += x;
-    }
+    int off = wave_scan_incl(mine, lane);
     const int above = __shfl(off, 63);
     off -= mine;
 #pragma unroll
@@ -185,17 +122,6 @@ __global__ __launch_bounds__(256) void recall_edge_kernel(const float* __restric
             out[i] = T;                            // ties of T fill the list up to 100
         }
     }
-}
-
-// #{entries >= t} of a descending list
-__device__ __forceinline__ int count_ge(const uint32_t* __restrict__ p, int len, uint32_t t) {
-    if (p[0] < t) return 0;                        // (most lists, once the trial is near the scene's top: one load)
-    int lo = 1, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (p[mid] >= t) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // block (scene s, variant v); row layout of counts_out: see launch_eval_recallk
@@ -234,7 +160,7 @@ __global__ __launch_bounds__(RK_SCENE_THREADS) void recall_scene_kernel(const in
             }
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
-                c[q] = wave_sum_int(c[q]);
+                c[q] = wave_sum_i(c[q]);
                 if (lane == 0) s_red[q][wv] = c[q];
             }
             __syncthreads();
@@ -275,9 +201,9 @@ __global__ __launch_bounds__(RK_SCENE_THREADS) void recall_scene_kernel(const in
 
 size_t eval_recallk_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes) {
     const int64_t Ks = C < RK_TOP ? C : RK_TOP;
-    return align256((size_t)N * Ks * sizeof(float)) + align256((size_t)(n_scenes + 1) * sizeof(int32_t)) +
-           4 * align256((size_t)E * sizeof(uint32_t)) + align256((size_t)E * R * sizeof(uint32_t)) +
-           align256((size_t)E * RK_TOP * sizeof(uint32_t));
+    return align_up((size_t)N * Ks * sizeof(float), 256) + align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256) +
+           4 * align_up((size_t)E * sizeof(uint32_t), 256) + align_up((size_t)E * R * sizeof(uint32_t), 256) +
+           align_up((size_t)E * RK_TOP * sizeof(uint32_t), 256);
 }
 
 int launch_eval_recallk(const float* obj_probs, const float* rel, const int64_t* gt_cls, const int64_t* gt_rel, const int64_t* edges,
@@ -289,17 +215,17 @@ int launch_eval_recallk(const float* obj_probs, const float* rel, const int64_t*
     if (n_scenes == 0) return 0;
     const int Ks = C < RK_TOP ? C : RK_TOP;
     char* p = static_cast<char*>(scratch);
-    float* sorted = reinterpret_cast<float*>(p);                 p += align256((size_t)N * Ks * sizeof(float));
-    int32_t* ptr = reinterpret_cast<int32_t*>(p);                p += align256((size_t)(n_scenes + 1) * sizeof(int32_t));
-    uint32_t* gtmask = reinterpret_cast<uint32_t*>(p);           p += align256((size_t)E * sizeof(uint32_t));
-    uint32_t* gkey_p = reinterpret_cast<uint32_t*>(p);           p += align256((size_t)E * sizeof(uint32_t));
-    uint32_t* gkey_s = reinterpret_cast<uint32_t*>(p);           p += align256((size_t)E * sizeof(uint32_t));
-    uint32_t* mkey_s = reinterpret_cast<uint32_t*>(p);           p += align256((size_t)E * sizeof(uint32_t));
-    uint32_t* plist = reinterpret_cast<uint32_t*>(p);            p += align256((size_t)E * R * sizeof(uint32_t));
+    float* sorted = reinterpret_cast<float*>(p);                 p += align_up((size_t)N * Ks * sizeof(float), 256);
+    int32_t* ptr = reinterpret_cast<int32_t*>(p);                p += align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256);
+    uint32_t* gtmask = reinterpret_cast<uint32_t*>(p);           p += align_up((size_t)E * sizeof(uint32_t), 256);
+    uint32_t* gkey_p = reinterpret_cast<uint32_t*>(p);           p += align_up((size_t)E * sizeof(uint32_t), 256);
+    uint32_t* gkey_s = reinterpret_cast<uint32_t*>(p);           p += align_up((size_t)E * sizeof(uint32_t), 256);
+    uint32_t* mkey_s = reinterpret_cast<uint32_t*>(p);           p += align_up((size_t)E * sizeof(uint32_t), 256);
+    uint32_t* plist = reinterpret_cast<uint32_t*>(p);            p += align_up((size_t)E * R * sizeof(uint32_t), 256);
     uint32_t* slist = reinterpret_cast<uint32_t*>(p);
     const int do_sg = (vmask & 12) != 0, do_ngc = (vmask & 8) != 0;
-    hipLaunchKernelGGL(scene_ptr_kernel, dim3(E / 256 + 1), dim3(256), 0, s, edges, batch_ids, N, E, n_scenes, ptr);
-    VLSAT_LAUNCH_CHECK("recallk scene_ptr");
+    const int rp = launch_scene_edge_ptr(edges, batch_ids, nullptr, N, E, n_scenes, ptr, s);
+    if (rp) return rp;
     if (E > 0) {
         if (do_sg) {
             const int rc = launch_sort_probs(obj_probs, N, C, Ks, sorted, s);

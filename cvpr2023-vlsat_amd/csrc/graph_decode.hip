@@ -8,7 +8,8 @@
 //                     nodes (two roundings, no FMA: the convention of scene_graph.hip and eval_recall.hip)
 //   gd_node_kernel    one wave per node: n_labels rounds of a wave-wide arg-max (value descending, class ascending)
 //   gd_edge_kernel    32 lanes per edge, lane = predicate: the COMPACTION pass -- the asserted predicates of an edge, ordered by
-//                     (score descending, predicate ascending), as order-preserving keys into the edge's slots, and their number
+//                     (score descending, predicate ascending), as order-preserving keys (select_core.h; 0 = "not asserted") into
+//                     the edge's slots, and their number
 //   gd_scene_kernel   one block per scene: n_total by a block sum; when the cap bites, the max_rel-th largest key by bisection on
 //                     the key bits over the per-edge sorted lists (asserted pairs only); a gather of the keys above it plus the
 //                     first ones equal to it in (edge, predicate) order, by two block scans; a bitonic sort of <= 4096 rows in LDS
@@ -21,6 +22,7 @@
 // Integer / latency-bound work: no MFMA.
 #include "common.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace vlsat {
 
@@ -32,21 +34,6 @@ constexpr int GD_MAX_LABELS = 8;
 constexpr int GD_MAX_REL = 4096;                 // largest max_rel: rows of the LDS sort
 constexpr int GD_SCENE_THREADS = 1024;
 constexpr int GD_PER_LANE = GD_MAX_C / 64;       // classes per lane of the node wave
-
-// order-preserving key of a float (no NaN): key(x) < key(y) <=> x < y; every real value has a key > 0 (0 = "not asserted")
-__device__ __forceinline__ uint32_t gd_fkey(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float gd_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
-
-__device__ __forceinline__ int gd_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ int gd_clamp(int64_t x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : (int)x; }
 
 // the decision of lane k (< 32) about predicate k of its edge; r = rel[e, k] (any value for k >= R); all 32 lanes of the group call
 __device__ __forceinline__ bool gd_asserted(float r, int k, int R, const float* __restrict__ thr, int multi) {
@@ -66,8 +53,6 @@ __device__ __forceinline__ bool gd_asserted(float r, int k, int R, const float* 
     }
     return pass && k == bi && k != 0;
 }
-
-size_t gd_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -124,10 +109,10 @@ __global__ __launch_bounds__(256) void gd_edge_kernel(const float* __restrict__ 
     const bool on = gd_asserted(r, k, R, thr, multi);
     float sc = r;
     if (score_mode == 1) {
-        const int a = gd_clamp(edges[2 * el], 0, N - 1), b = gd_clamp(edges[2 * el + 1], 0, N - 1);
+        const int a = clampi(edges[2 * el], 0, N - 1), b = clampi(edges[2 * el + 1], 0, N - 1);
         sc = __fmul_rn(__fmul_rn(top[(size_t)a * ldt], top[(size_t)b * ldt]), r);
     }
-    const uint32_t key = on ? gd_fkey(sc) : 0u;
+    const uint32_t key = on ? fkey(sc) : 0u;
     int rank = 0, n = 0;
     for (int q = 0; q < R; ++q) {
         const uint32_t kq = __shfl(key, q, 32);
@@ -142,17 +127,6 @@ __global__ __launch_bounds__(256) void gd_edge_kernel(const float* __restrict__ 
     if (k == 0) cnt[e] = n;
 }
 
-// #{entries >= t} of a descending list of len entries
-__device__ __forceinline__ int gd_count_ge(const uint32_t* __restrict__ p, int len, uint32_t t) {
-    if (len == 0 || p[0] < t) return 0;
-    int lo = 1, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (p[mid] >= t) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // block = scene; thread = edge while selecting, = row while sorting and writing.  A row of the sort is
 // key << 32 | ~(edge << 5 | predicate): descending rows = (score descending, edge ascending, predicate ascending); 0 = padding.
 __global__ __launch_bounds__(GD_SCENE_THREADS) void gd_scene_kernel(const int32_t* __restrict__ ptr, const uint32_t* __restrict__ keys,
@@ -164,77 +138,21 @@ __global__ __launch_bounds__(GD_SCENE_THREADS) void gd_scene_kernel(const int32_
     __shared__ unsigned long long s_row[GD_MAX_REL];
     __shared__ int s_red[NW];
     __shared__ unsigned long long s_scan[NW];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int e0 = gd_clamp(ptr[s], 0, E), e1 = max(e0, gd_clamp(ptr[s + 1], 0, E));
-    auto block_sum = [&](int c) {
-        c = gd_wave_sum(c);
-        if (lane == 0) s_red[wv] = c;
-        __syncthreads();
-        int tot = 0;
-        for (int i = 0; i < NW; ++i) tot += s_red[i];
-        __syncthreads();
-        return tot;
-    };
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int e0 = clampi(ptr[s], 0, E), e1 = max(e0, clampi(ptr[s + 1], 0, E));
     int c = 0;
     for (int e = e0 + tid; e < e1; e += GD_SCENE_THREADS) c += cnt[e];
-    const int total = block_sum(c);                // n_total (the launcher bounds E * R by INT32_MAX)
+    const int total = block_sum<GD_SCENE_THREADS>(c, s_red);               // n_total (the launcher bounds E * R by INT32_MAX)
     const int Kk = total < K ? total : K;          // n_valid
     int P = 1;                                     // rows of the sort: the power of two >= Kk
     while (P < Kk) P <<= 1;
     if (Kk > 0) {                                  // (uniform)
-        uint32_t T = 0;                            // the Kk-th largest key: the largest T with #{key >= T} >= Kk; 0 when all are kept
-        if (total > K)
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t trial = T | (1u << bit);
-                int g = 0;
-                for (int e = e0 + tid; e < e1; e += GD_SCENE_THREADS) g += gd_count_ge(keys + (size_t)e * R, cnt[e], trial);
-                if (block_sum(g) >= Kk) T = trial;
-            }
-        c = 0;
-        if (T != 0xFFFFFFFFu)
-            for (int e = e0 + tid; e < e1; e += GD_SCENE_THREADS) c += gd_count_ge(keys + (size_t)e * R, cnt[e], T + 1);
-        const int above = block_sum(c), need = Kk - above;         // above <= Kk
-        // gather: keys above T in (edge, slot) order, then the first `need` keys equal to T in (edge, slot) order -- equal keys
-        // of one edge lie in ascending predicate order, so that is (edge, predicate) order
-        long long base = 0;                        // #above | #equal << 32 of the edges before this chunk
-        for (int c0 = e0; c0 < e1; c0 += GD_SCENE_THREADS) {
-            const int e = c0 + tid;
-            int g = 0, q = 0;
-            const size_t row = (size_t)(e < e1 ? e : e0) * R;
-            const uint32_t* p = keys + row;
-            if (e < e1) {
-                const int len = cnt[e];
-                g = T != 0xFFFFFFFFu ? gd_count_ge(p, len, T + 1) : 0;
-                q = gd_count_ge(p, len, T) - g;
-            }
-            const long long mine = (long long)g | ((long long)q << 32);
-            long long off = mine;                  // inclusive scan over the wave, then over the block's waves
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long x = __shfl_up(off, o);
-                if (lane >= o) off += x;
-            }
-            if (lane == 63) s_scan[wv] = (unsigned long long)off;
-            __syncthreads();
-            long long pre = base, all = 0;
-            for (int i = 0; i < NW; ++i) {
-                if (i < wv) pre += (long long)s_scan[i];
-                all += (long long)s_scan[i];
-            }
-            __syncthreads();
-            off += pre - mine;
-            const int oa = (int)(off & 0xffffffffll);
-            const long long oq = off >> 32;
-            for (int j = 0; j < g; ++j) {
-                const int pos = oa + j;
-                if (pos < Kk) s_row[pos] = ((unsigned long long)p[j] << 32) | (0xFFFFFFFFu - (((uint32_t)e << 5) | preds[row + j]));
-            }
-            for (int j = 0; j < q && oq + j < need; ++j) {
-                const int pos = above + (int)(oq + j);
-                if (pos < Kk) s_row[pos] = ((unsigned long long)p[g + j] << 32) | (0xFFFFFFFFu - (((uint32_t)e << 5) | preds[row + g + j]));
-            }
-            base += all;
-        }
+        // the Kk largest keys (all of them when the cap does not bite: no bisection); equal keys of one edge lie in ascending
+        // predicate order, so the (edge, slot) order of the ties is (edge, predicate) order
+        select_topk_lists<GD_SCENE_THREADS>(keys, R, [&](int e) { return cnt[e]; }, e0, e1, Kk, total > K, s_red, s_scan, [&](int pos, int e, int j) {
+            const size_t i = (size_t)e * R + j;
+            s_row[pos] = ((unsigned long long)keys[i] << 32) | (0xFFFFFFFFu - (((uint32_t)e << 5) | preds[i]));
+        });
         for (int i = Kk + tid; i < P; i += GD_SCENE_THREADS) s_row[i] = 0;
         __syncthreads();
         for (int k = 2; k <= P; k <<= 1)           // bitonic sort, descending (rows are pairwise distinct)
@@ -264,7 +182,7 @@ __global__ __launch_bounds__(GD_SCENE_THREADS) void gd_scene_kernel(const int32_
             const uint32_t id = 0xFFFFFFFFu - (uint32_t)x;
             orow[2 * i] = (int32_t)(id >> 5);
             orow[2 * i + 1] = (int32_t)(id & 31);
-            osc[i] = gd_unkey((uint32_t)(x >> 32));
+            osc[i] = unkey((uint32_t)(x >> 32));
         } else {                                   // rows past n_valid
             orow[2 * i] = orow[2 * i + 1] = -1;
             osc[i] = 0.f;
@@ -349,16 +267,16 @@ int graph_decode_check_args(int C, int R, int multi, int score_mode, int n_label
 }
 
 size_t graph_decode_scratch_bytes(int64_t E, int R, int n_scenes) {
-    return gd_align((size_t)(n_scenes + 1) * sizeof(int32_t)) + gd_align((size_t)E * sizeof(int32_t)) +
-           gd_align((size_t)E * R * sizeof(uint32_t)) + gd_align((size_t)E * R);
+    return align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256) + align_up((size_t)E * sizeof(int32_t), 256) +
+           align_up((size_t)E * R * sizeof(uint32_t), 256) + align_up((size_t)E * R, 256);
 }
 
 GraphDecodeWs graph_decode_carve(void* scratch, int64_t E, int R, int n_scenes) {
     char* p = static_cast<char*>(scratch);
     GraphDecodeWs w;
-    w.ptr = reinterpret_cast<int32_t*>(p);     p += gd_align((size_t)(n_scenes + 1) * sizeof(int32_t));
-    w.cnt = reinterpret_cast<int32_t*>(p);     p += gd_align((size_t)E * sizeof(int32_t));
-    w.keys = reinterpret_cast<uint32_t*>(p);   p += gd_align((size_t)E * R * sizeof(uint32_t));
+    w.ptr = reinterpret_cast<int32_t*>(p);     p += align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256);
+    w.cnt = reinterpret_cast<int32_t*>(p);     p += align_up((size_t)E * sizeof(int32_t), 256);
+    w.keys = reinterpret_cast<uint32_t*>(p);   p += align_up((size_t)E * R * sizeof(uint32_t), 256);
     w.preds = reinterpret_cast<uint8_t*>(p);
     return w;
 }

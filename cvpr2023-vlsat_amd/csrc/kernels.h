@@ -6,6 +6,8 @@
 
 namespace vlsat {
 
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }     // a: a power of two (scratch carving)
+
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
 
 // C[M,N] = act(rowscale[m]*(reluA?(A) . W^T) + bias[n] + resid_scale*resid[m,n] + g0[gi0[m],n] + g1[gi1[m],n])
@@ -262,8 +264,9 @@ int launch_eval_ranks(const float* obj_logits, const float* obj_probs, const flo
 // columns of the per-node sorted-probability scratch of launch_eval_ranks ([N, K] floats): only the topk largest matter
 inline int eval_ranks_sorted_k(int C, int topk_tri) { return C < topk_tri ? C : topk_tri; }
 
-// sorted[n, 0:K] = the K largest entries of probs[n, :] (C <= 1024), descending
-int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s);
+// sorted[n, 0:K] = the K largest entries of probs[n, :] (C <= 1024), descending; si: optional [N, K] class indices of the entries
+// (equal values in ascending class order)
+int launch_sort_probs(const float* probs, int N, int C, int K, float* sorted, hipStream_t s, int32_t* si = nullptr);
 // Recall@K / mR@K counts per scene (eval_recall.hip): counts [n_scenes][1 + R + 4 (3 + 3 R)] int64, every field written
 size_t eval_recallk_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes);
 int launch_eval_recallk(const float* obj_probs, const float* rel, const int64_t* gt_cls, const int64_t* gt_rel, const int64_t* edges,
@@ -332,6 +335,10 @@ int launch_sample_objects(const int32_t* instances, int64_t n_points, const int3
                           int32_t* id_map, int map_size, int32_t* scratch, int32_t* choice, int32_t* counts, hipStream_t s);
 int launch_fc_edges(const int32_t* node_ptr, const int64_t* edge_ptr, int n_scenes, int64_t n_nodes, int64_t n_edges,
                     int64_t* edges, int64_t* batch_ids, hipStream_t s);
+// id -> slot map (prep.hip): id_map[0:map_size] = -1; id_map[ids[i]] = i for the ids in range (one thread per entry; unchecked launches:
+// the caller's launch check covers them)
+void launch_id_map_clear(int32_t* id_map, int map_size, hipStream_t s);
+void launch_id_map_set(const int32_t* ids, int n, int32_t* id_map, int map_size, hipStream_t s);
 
 // ---- proximity-pruned edge lists (proximity.hip; the rule is stated in include/vlsat.h) ----
 int proximity_lds_boxes();
@@ -363,5 +370,16 @@ int launch_merge_segments(const float* obj_probs, const float* rel_probs, const 
                           int32_t* root, int32_t* object, int32_t* n_objects, int32_t* totals, int32_t* member_ptr, int32_t* members,
                           float* out_probs, float* out_weight, int64_t* obj_batch_ids, int32_t* edge_to_pair, int64_t* pair_edges,
                           int32_t* pair_count, float* pair_probs, hipStream_t s);
+// the three steps merge_segments shares with fuse_splits (scene_split.hip), defined in segment_merge.hip: a contract-off source.
+// Unchecked launches: the caller's launch check covers them.
+//   scan     out[0..n] = exclusive scan of in[0..n-1] by one block of 1024; *total = *total2 = out[n] (either may be null)
+//   members  one wave per object o < totals[0]: the rows n >= obj_root[o] with root[n] == obj_root[o], ascending, into
+//            members[member_ptr[o] ..]; bid given: the walk ends with the root's scene
+//   pool     one wave per object, members in order: s = fl(s + fl(w p)), W = fl(W + w), out_probs = fl(s / W), out_weight = W
+void launch_scan_i32(const int32_t* in, int n, int32_t* out, int32_t* total, int32_t* total2, hipStream_t s);
+void launch_members(const int32_t* root, const int32_t* obj_root, const int32_t* member_ptr, const int64_t* bid, const int32_t* totals, int n,
+                    int32_t* members, hipStream_t s);
+void launch_pool_members(const float* probs, const float* weights, const int32_t* members, const int32_t* member_ptr, const int32_t* totals,
+                         int n, int C, float* out_probs, float* out_weight, hipStream_t s);
 
 }  // namespace vlsat

@@ -4,7 +4,7 @@
 //                  d2 = (dx dx + dy dy) + dz dz in fp32, every operation rounded on its own (this file is compiled with -ffp-contract=off,
 //                  like proximity.hip, so numpy float32 restates d2 bit for bit).  Exact: a uniform grid over the finite reference points
 //                  with cell edge >= sqrt(max_sq_dist) (1/64 wider, see nn_params_kernel) and a search of the 27 cells around the query.
-//   nn_bbox_kernel     bounding box of the finite points: wave reduction, then integer atomics on the order-preserving code of proximity.hip
+//   nn_bbox_kernel     bounding box of the finite points: wave reduction, then integer atomics on the order-preserving key of select_core.h
 //   nn_params_kernel   one thread: cell edge, cells per axis (at most NN_AXIS_CELLS each, NN_MAX_CELLS in all: the edge grows until they fit)
 //   nn_zero_kernel     counts[0 .. n_cells] = 0
 //   nn_hist_kernel     cell of every point (kept), counts[cell] += 1 (int32 atomics)
@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace vlsat {
 
@@ -33,11 +34,6 @@ struct NnGrid {
     int n_cells;
 };
 
-__device__ __forceinline__ unsigned nn_code(float x) {                // unsigned order = float order (as proximity.hip's f32_code)
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float nn_decode(unsigned c) { return __uint_as_float((c & 0x80000000u) ? (c & 0x7fffffffu) : ~c); }
 __device__ __forceinline__ bool nn_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // cell coordinate on one axis: monotone in x, clamped to [0, n).  A NaN product (an overflowed difference times inv_h = 0) gives 0.
@@ -48,17 +44,17 @@ __device__ __forceinline__ int nn_cell_axis(float x, float lo, float inv_h, int 
 }
 
 __global__ void nn_init_kernel(unsigned* __restrict__ box) {
-    if (threadIdx.x < 3) box[threadIdx.x] = nn_code(INFINITY);
-    else if (threadIdx.x < 6) box[threadIdx.x] = nn_code(-INFINITY);
+    if (threadIdx.x < 3) box[threadIdx.x] = fkey(INFINITY);
+    else if (threadIdx.x < 6) box[threadIdx.x] = fkey(-INFINITY);
 }
 
 __global__ __launch_bounds__(NN_THREADS) void nn_bbox_kernel(const float* __restrict__ ref, int n_ref, unsigned* __restrict__ box) {
-    unsigned lo[3] = {nn_code(INFINITY), nn_code(INFINITY), nn_code(INFINITY)};
-    unsigned hi[3] = {nn_code(-INFINITY), nn_code(-INFINITY), nn_code(-INFINITY)};
+    unsigned lo[3] = {fkey(INFINITY), fkey(INFINITY), fkey(INFINITY)};
+    unsigned hi[3] = {fkey(-INFINITY), fkey(-INFINITY), fkey(-INFINITY)};
     for (int64_t i = (int64_t)blockIdx.x * NN_THREADS + threadIdx.x; i < n_ref; i += (int64_t)gridDim.x * NN_THREADS) {
         const float x = ref[i * 3], y = ref[i * 3 + 1], z = ref[i * 3 + 2];
         if (!nn_finite3(x, y, z)) continue;
-        const unsigned c[3] = {nn_code(x), nn_code(y), nn_code(z)};
+        const unsigned c[3] = {fkey(x), fkey(y), fkey(z)};
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], c[a]); hi[a] = max(hi[a], c[a]); }
     }
@@ -89,7 +85,7 @@ __global__ void nn_params_kernel(const unsigned* __restrict__ box, float max_sq_
     bool any = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float lo = nn_decode(box[a]), hi = nn_decode(box[3 + a]);
+        const float lo = unkey(box[a]), hi = unkey(box[3 + a]);
         any = any && lo <= hi;
         r.lo[a] = lo <= hi ? lo : 0.0f;
         r.n[a] = 1;
@@ -233,11 +229,10 @@ __global__ void nn_none_kernel(int n_query, int32_t* __restrict__ nn_index, floa
 }
 
 // scratch: sorted float4 [n_ref] | grid (64 bytes) | box u32 [8] | cell i32 [n_ref] | counts = cursor i32 [NN_MAX_CELLS + 1] | start i32 [NN_MAX_CELLS + 1]
-static size_t nn_round16(size_t b) { return (b + 15) & ~(size_t)15; }
 size_t nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref) {
     (void)n_query;
     const size_t g = (size_t)(n_ref > 0 ? n_ref : 0);
-    return g * 16 + 64 + 32 + nn_round16(g * 4) + 2 * nn_round16((size_t)(NN_MAX_CELLS + 1) * 4);
+    return g * 16 + 64 + 32 + align_up(g * 4, 16) + 2 * align_up((size_t)(NN_MAX_CELLS + 1) * 4, 16);
 }
 
 int launch_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
@@ -256,8 +251,8 @@ int launch_nearest_points(const float* query, int64_t n_query, const float* ref,
     float4* sorted = reinterpret_cast<float4*>(p);            p += (size_t)G * 16;
     NnGrid* grid = reinterpret_cast<NnGrid*>(p);               p += 64;
     unsigned* box = reinterpret_cast<unsigned*>(p);            p += 32;
-    int32_t* cell = reinterpret_cast<int32_t*>(p);             p += nn_round16((size_t)G * 4);
-    int32_t* counts = reinterpret_cast<int32_t*>(p);           p += nn_round16((size_t)(NN_MAX_CELLS + 1) * 4);
+    int32_t* cell = reinterpret_cast<int32_t*>(p);             p += align_up((size_t)G * 4, 16);
+    int32_t* counts = reinterpret_cast<int32_t*>(p);           p += align_up((size_t)(NN_MAX_CELLS + 1) * 4, 16);
     int32_t* start = reinterpret_cast<int32_t*>(p);
     const dim3 rgrid((unsigned)std::min<int64_t>((n_ref + NN_THREADS - 1) / NN_THREADS, 2048));
     hipLaunchKernelGGL(nn_init_kernel, dim3(1), dim3(64), 0, s, box);

@@ -116,11 +116,12 @@ __global__ void fc_edges_kernel(const int32_t* __restrict__ node_ptr, const int6
 // this one bit for bit.  Integer work, HBM-bound (4 B per point read twice, 4 B written).
 constexpr int SMP_CHUNK = 1024;      // points per block of the compaction (one wave walks them in 16 steps of 64)
 
-__global__ void smp_map_kernel(int32_t* __restrict__ id_map, int map_size) {
+// id -> slot maps (also of proximity.hip and scene_split.hip): every entry -1, then id_map[ids[i]] = i
+__global__ void id_map_clear_kernel(int32_t* __restrict__ id_map, int map_size) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < map_size) id_map[i] = -1;
 }
-__global__ void smp_map_set_kernel(const int32_t* __restrict__ ids, int n_obj, int32_t* __restrict__ id_map, int map_size) {
+__global__ void id_map_set_kernel(const int32_t* __restrict__ ids, int n_obj, int32_t* __restrict__ id_map, int map_size) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_obj && ids[i] >= 0 && ids[i] < map_size) id_map[ids[i]] = i;      // (duplicate ids: the last writer wins; callers pass a set)
 }
@@ -194,6 +195,14 @@ __global__ void smp_draw_kernel(const int32_t* __restrict__ list, const int32_t*
     choice[t] = cnt ? list[(size_t)offset[obj] + k] : 0;       // (an instance without points: counts[obj] == 0 tells the caller)
 }
 
+// (the caller checks the launch)
+void launch_id_map_clear(int32_t* id_map, int map_size, hipStream_t s) {
+    hipLaunchKernelGGL(id_map_clear_kernel, dim3((map_size + 255) / 256), dim3(256), 0, s, id_map, map_size);
+}
+void launch_id_map_set(const int32_t* ids, int n, int32_t* id_map, int map_size, hipStream_t s) {
+    hipLaunchKernelGGL(id_map_set_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ids, n, id_map, map_size);
+}
+
 size_t sample_objects_scratch_ints(int64_t n_points, int n_obj) {
     const size_t n_blocks = (size_t)((n_points + SMP_CHUNK - 1) / SMP_CHUNK);
     return n_blocks * (size_t)n_obj + (size_t)n_obj + (size_t)n_points;
@@ -208,8 +217,8 @@ int launch_sample_objects(const int32_t* instances, int64_t n_points, const int3
     int32_t* block_cnt = scratch;
     int32_t* offset = scratch + (size_t)n_blocks * n_obj;
     int32_t* list = offset + n_obj;
-    hipLaunchKernelGGL(smp_map_kernel, dim3((map_size + 255) / 256), dim3(256), 0, s, id_map, map_size);
-    hipLaunchKernelGGL(smp_map_set_kernel, dim3((n_obj + 255) / 256), dim3(256), 0, s, ids, n_obj, id_map, map_size);
+    launch_id_map_clear(id_map, map_size, s);
+    launch_id_map_set(ids, n_obj, id_map, map_size, s);
     hipLaunchKernelGGL(smp_scan_kernel<0>, dim3(n_blocks), dim3(64), n_obj * sizeof(int32_t), s, instances, n_points, id_map, map_size, n_obj,
                        block_cnt, offset, list);
     hipLaunchKernelGGL(smp_prefix_kernel, dim3((n_obj + 255) / 256), dim3(256), 0, s, block_cnt, n_blocks, n_obj, counts, offset);

@@ -22,6 +22,7 @@
 // reads them from global memory otherwise; the arithmetic is the same function in both branches.
 #include "common.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace vlsat {
 
@@ -33,20 +34,8 @@ constexpr unsigned long long PROX_ALL = ~0ull;
 int proximity_lds_boxes() { return PROX_LDS_BOXES; }
 
 // ---- per-instance boxes -------------------------------------------------------------------------------------------------------
-// min / max are order independent, so integer atomics on an order-preserving code of the float give the exact result:
-// code(x) = bits ^ 0x80000000 for x >= 0, ~bits for x < 0  (unsigned order = float order, -0 < +0).
-__device__ __forceinline__ unsigned f32_code(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_decode(unsigned c) {
-    return __uint_as_float((c & 0x80000000u) ? (c & 0x7fffffffu) : ~c);
-}
-
-__global__ void prox_map_clear_kernel(int32_t* __restrict__ id_map, int map_size) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < map_size) id_map[i] = -1;
-}
+// min / max are order independent, so integer atomics on the order-preserving key of the float (select_core.h fkey: unsigned order =
+// float order, -0 < +0) give the exact result.
 __global__ void prox_map_set_kernel(const int32_t* __restrict__ ids, int n_obj, int32_t* __restrict__ id_map, int map_size,
                                     unsigned* __restrict__ codes) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,8 +43,8 @@ __global__ void prox_map_set_kernel(const int32_t* __restrict__ ids, int n_obj, 
     if (ids[i] >= 0 && ids[i] < map_size) id_map[ids[i]] = i;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        codes[(size_t)i * 6 + a] = f32_code(INFINITY);
-        codes[(size_t)i * 6 + 3 + a] = f32_code(-INFINITY);
+        codes[(size_t)i * 6 + a] = fkey(INFINITY);
+        codes[(size_t)i * 6 + 3 + a] = fkey(-INFINITY);
     }
 }
 constexpr int BOX_CHUNK = 4096;           // points per block
@@ -66,7 +55,7 @@ __global__ __launch_bounds__(256) void prox_boxes_kernel(const int32_t* __restri
                                                          const int32_t* __restrict__ id_map, int map_size, int n_obj,
                                                          unsigned* __restrict__ codes) {
     __shared__ unsigned tab[TABLE ? PROX_LDS_BOXES * 6 : 1];
-    const unsigned lo0 = f32_code(INFINITY), hi0 = f32_code(-INFINITY);
+    const unsigned lo0 = fkey(INFINITY), hi0 = fkey(-INFINITY);
     if (TABLE) {
         for (int t = threadIdx.x; t < n_obj * 6; t += 256) tab[t] = (t % 6) < 3 ? lo0 : hi0;
         __syncthreads();
@@ -82,7 +71,7 @@ __global__ __launch_bounds__(256) void prox_boxes_kernel(const int32_t* __restri
         unsigned* dst = TABLE ? tab + slot * 6 : codes + (size_t)slot * 6;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const unsigned v = f32_code(pts[i * 3 + a]);
+            const unsigned v = fkey(pts[i * 3 + a]);
             atomicMin(dst + a, v);
             atomicMax(dst + 3 + a, v);
         }
@@ -98,7 +87,7 @@ __global__ __launch_bounds__(256) void prox_boxes_kernel(const int32_t* __restri
 }
 __global__ void prox_boxes_decode_kernel(unsigned* __restrict__ codes, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) codes[i] = __float_as_uint(f32_decode(codes[i]));
+    if (i < n) codes[i] = __float_as_uint(unkey(codes[i]));
 }
 
 int launch_instance_boxes(const int32_t* instances, const float* scene_points, int64_t n_points, const int32_t* ids, int n_obj,
@@ -106,7 +95,7 @@ int launch_instance_boxes(const int32_t* instances, const float* scene_points, i
     if (n_obj <= 0) return 0;
     if (n_points < 0 || n_points > 0x7fffffff || map_size <= 0) return fail(-1, "instance_boxes: bad sizes");
     unsigned* codes = reinterpret_cast<unsigned*>(boxes);
-    hipLaunchKernelGGL(prox_map_clear_kernel, dim3((map_size + 255) / 256), dim3(256), 0, s, id_map, map_size);
+    launch_id_map_clear(id_map, map_size, s);
     hipLaunchKernelGGL(prox_map_set_kernel, dim3((n_obj + 255) / 256), dim3(256), 0, s, ids, n_obj, id_map, map_size, codes);
     if (n_points > 0) {
         const unsigned blocks = (unsigned)((n_points + BOX_CHUNK - 1) / BOX_CHUNK);

@@ -5,8 +5,9 @@
 //                 roundings, no FMA: the reference's two einsums, as eval_recall.hip scores them)
 //   rels mode     conf(e; k) = r_k, subject / object class reported as -1
 // The candidates of a scene are, per edge, its L = min(topk_each, #entries) largest entries.  eval_recall.hip selects the same
-// candidates as values only; here every value carries its class triple:
-//   sg_node_argsort_kernel  per node the min(C, 100) largest probabilities, descending, with their class indices (stable by class)
+// candidates as values only; here every value carries its class triple (key, bisection and tie rule: select_core.h):
+//   launch_sort_probs       (eval_ranks.hip) per node the min(C, 100) largest probabilities, descending, with their class indices
+//                           (stable by class)
 //   sg_scene_ptr_kernel     edge offsets of every scene (edges arrive grouped by scene in ascending order)
 //   sg_edge_kernel          one wave per edge: predicates sorted with indices; triplet mode: the products over the dominance table
 //                           (an entry at sorted position (i, j, k) is dominated by (i+1)(j+1)(k+1) - 1 others, so the L largest lie
@@ -21,6 +22,7 @@
 // Integer / latency-bound work: no MFMA.
 #include "common.h"
 #include "kernels.h"
+#include "select_core.h"
 
 namespace vlsat {
 
@@ -31,48 +33,12 @@ constexpr int SG_MAX_R = 32;
 constexpr int SG_MAX_K = 1024;                   // largest top_k = threads of the scene block (one row per thread)
 constexpr int SG_SCENE_THREADS = 1024;
 
-constexpr int sg_tri_count() {
-    int n = 0;
-    for (int a = 1; a <= SG_EACH; ++a)
-        for (int b = 1; a * b <= SG_EACH; ++b)
-            for (int c = 1; c <= SG_MAX_R && a * b * c <= SG_EACH; ++c) ++n;
-    return n;
-}
-constexpr int SG_NT = sg_tri_count();            // 1 365
+constexpr int SG_NT = tri_count(SG_EACH, SG_MAX_R);   // 1 365
 constexpr int SG_PER = (SG_NT + 63) / 64;        // table entries per lane
-
-struct SgTriTable {
-    uint32_t v[SG_NT];
-};
-constexpr SgTriTable sg_make_tri() {
-    SgTriTable t{};
-    int n = 0;
-    for (int a = 1; a <= SG_EACH; ++a)
-        for (int b = 1; a * b <= SG_EACH; ++b)
-            for (int c = 1; c <= SG_MAX_R && a * b * c <= SG_EACH; ++c) t.v[n++] = (uint32_t)((a - 1) | ((b - 1) << 8) | ((c - 1) << 16));
-    return t;
-}
-__constant__ SgTriTable c_sg_tri = sg_make_tri();
-
-// order-preserving key of a float (no NaN): key(x) < key(y) <=> x < y; every real value has a key > 0
-__device__ __forceinline__ uint32_t sg_fkey(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float sg_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
+__constant__ TriTable<SG_EACH, SG_MAX_R> c_tri = make_tri<SG_EACH, SG_MAX_R>();
 
 // class triple of a slot: subject class (10 bits) | object class (10 bits) | predicate (5 bits); ascending = (sub, obj, pred) ascending
 __device__ __forceinline__ uint32_t sg_pack(int sub, int obj, int pred) { return ((uint32_t)sub << 15) | ((uint32_t)obj << 5) | (uint32_t)pred; }
-
-__device__ __forceinline__ int sg_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ int sg_clamp(int64_t x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : (int)x; }
-
-size_t sg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // slots per edge: min(topk_each, #entries of an edge)
 int sg_slots(int C, int R, int mode, int each) {
@@ -82,31 +48,6 @@ int sg_slots(int C, int R, int mode, int each) {
 
 }  // namespace
 
-// sv[n, 0:K] / si[n, 0:K] = the K largest entries of probs[n, :] in descending order and their class indices (equal values in
-// ascending class order); one wave per node, rank by counting
-__global__ __launch_bounds__(256) void sg_node_argsort_kernel(const float* __restrict__ probs, int N, int C, int K, float* __restrict__ sv,
-                                                              int32_t* __restrict__ si) {
-    extern __shared__ float s_row[];                               // [4][C]
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = blockIdx.x * 4 + w;
-    float* row = s_row + (size_t)w * C;
-    if (n < N)
-        for (int c = lane; c < C; c += 64) row[c] = probs[(size_t)n * C + c];
-    __syncthreads();
-    if (n >= N) return;
-    for (int c = lane; c < C; c += 64) {
-        const float v = row[c];
-        int r = 0;
-        for (int q = 0; q < C; ++q) {
-            const float x = row[q];
-            r += (x > v) || (x == v && q < c);
-        }
-        if (r < K) {
-            sv[(size_t)n * K + r] = v;
-            si[(size_t)n * K + r] = c;
-        }
-    }
-}
-
 // ptr[q] = first edge of scene q, ptr[n_scenes] = E (thread t = E closes the list).  The scene of an edge is that of its first
 // node: batch_ids[node], or -- node_ptr given -- the scene whose node range holds it, or 0.
 __global__ __launch_bounds__(256) void sg_scene_ptr_kernel(const int64_t* __restrict__ edges, const int64_t* __restrict__ batch_ids,
@@ -115,8 +56,8 @@ __global__ __launch_bounds__(256) void sg_scene_ptr_kernel(const int64_t* __rest
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t > E) return;
     auto scene = [&](int e) {
-        const int a = sg_clamp(edges[2 * (size_t)e], 0, N - 1);
-        if (batch_ids) return sg_clamp(batch_ids[a], 0, n_scenes - 1);
+        const int a = clampi(edges[2 * (size_t)e], 0, N - 1);
+        if (batch_ids) return clampi(batch_ids[a], 0, n_scenes - 1);
         if (!node_ptr) return 0;
         int lo = 0, hi = n_scenes;                                 // #{q <= n_scenes: node_ptr[q] <= a} - 1
         while (lo < hi) {
@@ -147,17 +88,13 @@ __global__ __launch_bounds__(256) void sg_edge_kernel(const float* __restrict__ 
     const bool live = e < E;                       // (no early return: the block synchronises twice)
     if (live) {
         const float rv = lane < R ? rel[(size_t)e * R + lane] : -INFINITY;
-        int rk = 0;
-        for (int q = 0; q < R; ++q) {
-            const float x = __shfl(rv, q);
-            rk += x > rv || (x == rv && q < lane);
-        }
+        const int rk = rank_desc_in_wave(rv, lane, R);
         if (lane < R) {
             s_rs[w][rk] = rv;
             s_ri[w][rk] = lane;
         }
         if (mode == 0) {
-            const int a = sg_clamp(edges[2 * (size_t)e], 0, N - 1), b = sg_clamp(edges[2 * (size_t)e + 1], 0, N - 1);
+            const int a = clampi(edges[2 * (size_t)e], 0, N - 1), b = clampi(edges[2 * (size_t)e + 1], 0, N - 1);
             for (int i = lane; i < Ks; i += 64) {
                 s_a[w][i] = sv[(size_t)a * Ks + i];
                 s_ai[w][i] = si[(size_t)a * Ks + i];
@@ -171,14 +108,14 @@ __global__ __launch_bounds__(256) void sg_edge_kernel(const float* __restrict__ 
     uint32_t* opk = packs + (size_t)(live ? e : 0) * L;
     if (mode == 1) {                               // (uniform) the L largest predicates
         if (live && lane < L) {
-            okey[lane] = sg_fkey(s_rs[w][lane]);
+            okey[lane] = fkey(s_rs[w][lane]);
             opk[lane] = (uint32_t)s_ri[w][lane];
         }
         return;
     }
     if (L == 1) {                                  // (uniform) graph constraint: the entry at sorted position (0, 0, 0)
         if (live && lane == 0) {
-            okey[0] = sg_fkey(__fmul_rn(__fmul_rn(s_a[w][0], s_b[w][0]), s_rs[w][0]));
+            okey[0] = fkey(__fmul_rn(__fmul_rn(s_a[w][0], s_b[w][0]), s_rs[w][0]));
             opk[0] = sg_pack(s_ai[w][0], s_bi[w][0], s_ri[w][0]);
         }
         return;
@@ -189,32 +126,19 @@ __global__ __launch_bounds__(256) void sg_edge_kernel(const float* __restrict__ 
         const int idx = lane + 64 * t;
         uint32_t key = 0;
         if (live && idx < SG_NT) {
-            const uint32_t tr = c_sg_tri.v[idx];
+            const uint32_t tr = c_tri.v[idx];
             const int i = tr & 0xff, j = (tr >> 8) & 0xff, k = tr >> 16;
             if (i < Ks && j < Ks && k < R && (i + 1) * (j + 1) * (k + 1) <= L)
-                key = sg_fkey(__fmul_rn(__fmul_rn(s_a[w][i], s_b[w][j]), s_rs[w][k]));
+                key = fkey(__fmul_rn(__fmul_rn(s_a[w][i], s_b[w][j]), s_rs[w][k]));
         }
         v[t] = key;
     }
-    // T = the L-th largest key: the largest T with #{v >= T} >= L (at least L table positions are in range, so T > 0)
-    uint32_t T = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t trial = T | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int t = 0; t < SG_PER; ++t) c += v[t] >= trial;
-        if (sg_wave_sum(c) >= L) T = trial;
-    }
+    const uint32_t T = wave_kth_largest(v, L);     // the L-th largest key (at least L table positions are in range, so T > 0)
     // the (< L) entries above T, then entries equal to T until L are gathered, both in lane order
     int mine = 0;                                  // #above | #equal << 16
 #pragma unroll
     for (int t = 0; t < SG_PER; ++t) mine += (v[t] > T) + ((v[t] == T) << 16);
-    int off = mine;                                // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(off, o);
-        if (lane >= o) off += x;
-    }
+    int off = wave_scan_incl(mine, lane);
     const int above = __shfl(off, 63) & 0xffff, need = L - above;
     off -= mine;
     int oa = off & 0xffff, oq = off >> 16;
@@ -228,7 +152,7 @@ __global__ __launch_bounds__(256) void sg_edge_kernel(const float* __restrict__ 
             ++oq;
         }
         if (pos >= 0 && pos < L) {
-            const uint32_t tr = c_sg_tri.v[lane + 64 * t];
+            const uint32_t tr = c_tri.v[lane + 64 * t];
             s_key[w][pos] = key;
             s_pk[w][pos] = sg_pack(s_ai[w][tr & 0xff], s_bi[w][(tr >> 8) & 0xff], s_ri[w][tr >> 16]);
         }
@@ -247,17 +171,6 @@ __global__ __launch_bounds__(256) void sg_edge_kernel(const float* __restrict__ 
     }
 }
 
-// #{entries >= t} of a descending list
-__device__ __forceinline__ int sg_count_ge(const uint32_t* __restrict__ p, int len, uint32_t t) {
-    if (p[0] < t) return 0;                        // (most lists, once the trial is near the scene's top: one load)
-    int lo = 1, hi = len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (p[mid] >= t) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // block = scene; thread = edge while selecting, = output row while sorting and writing
 __global__ __launch_bounds__(SG_SCENE_THREADS) void sg_scene_kernel(const int32_t* __restrict__ ptr, const uint32_t* __restrict__ keys,
                                                                    const uint32_t* __restrict__ packs, int E, int L, int K, int mode,
@@ -267,77 +180,16 @@ __global__ __launch_bounds__(SG_SCENE_THREADS) void sg_scene_kernel(const int32_
     __shared__ uint32_t s_k[SG_MAX_K], s_e[SG_MAX_K], s_p[SG_MAX_K];
     __shared__ int s_red[NW];
     __shared__ unsigned long long s_scan[NW];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int e0 = sg_clamp(ptr[s], 0, E), e1 = max(e0, sg_clamp(ptr[s + 1], 0, E));
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int e0 = clampi(ptr[s], 0, E), e1 = max(e0, clampi(ptr[s + 1], 0, E));
     const long long total = (long long)(e1 - e0) * L;
     const int Kk = total < K ? (int)total : K;     // n_valid
-    auto block_sum = [&](int c) {
-        c = sg_wave_sum(c);
-        if (lane == 0) s_red[wv] = c;
-        __syncthreads();
-        int tot = 0;
-        for (int i = 0; i < NW; ++i) tot += s_red[i];
-        __syncthreads();
-        return tot;
-    };
-    if (Kk > 0) {                                  // (uniform)
-        uint32_t T = 0;                            // the Kk-th largest key of the scene: the largest T with #{key >= T} >= Kk
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t trial = T | (1u << bit);
-            int c = 0;
-            for (int e = e0 + tid; e < e1; e += SG_SCENE_THREADS) c += sg_count_ge(keys + (size_t)e * L, L, trial);
-            if (block_sum(c) >= Kk) T = trial;
-        }
-        int c = 0;
-        if (T != 0xFFFFFFFFu)
-            for (int e = e0 + tid; e < e1; e += SG_SCENE_THREADS) c += sg_count_ge(keys + (size_t)e * L, L, T + 1);
-        const int above = block_sum(c), need = Kk - above;        // above < Kk
-        // gather: slots above T in (edge, slot) order, then the first `need` slots equal to T in (edge, slot) order
-        long long base = 0;                        // #above | #equal << 32 of the edges before this chunk
-        for (int c0 = e0; c0 < e1; c0 += SG_SCENE_THREADS) {
-            const int e = c0 + tid;
-            int g = 0, q = 0;
-            const uint32_t* p = keys + (size_t)(e < e1 ? e : e0) * L;
-            if (e < e1) {
-                g = T != 0xFFFFFFFFu ? sg_count_ge(p, L, T + 1) : 0;
-                q = sg_count_ge(p, L, T) - g;
-            }
-            const long long mine = (long long)g | ((long long)q << 32);
-            long long off = mine;                  // inclusive scan over the wave, then over the block's waves
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long x = __shfl_up(off, o);
-                if (lane >= o) off += x;
-            }
-            if (lane == 63) s_scan[wv] = (unsigned long long)off;
-            __syncthreads();
-            long long pre = base, all = 0;
-            for (int i = 0; i < NW; ++i) {
-                if (i < wv) pre += (long long)s_scan[i];
-                all += (long long)s_scan[i];
-            }
-            __syncthreads();
-            off += pre - mine;
-            const int oa = (int)(off & 0xffffffffll);
-            const long long oq = off >> 32;
-            const uint32_t* pp = packs + (size_t)(e < e1 ? e : e0) * L;
-            for (int j = 0; j < g; ++j) {
-                const int pos = oa + j;
-                if (pos < Kk) {                    // (always: above < Kk)
-                    s_k[pos] = p[j];
-                    s_e[pos] = (uint32_t)e;
-                    s_p[pos] = pp[j];
-                }
-            }
-            for (int j = 0; j < q && oq + j < need; ++j) {
-                const int pos = above + (int)(oq + j);
-                s_k[pos] = p[g + j];
-                s_e[pos] = (uint32_t)e;
-                s_p[pos] = pp[g + j];
-            }
-            base += all;
-        }
-    }
+    if (Kk > 0)                                    // (uniform) the Kk largest slots of the scene, unordered
+        select_topk_lists<SG_SCENE_THREADS>(keys, L, [&](int) { return L; }, e0, e1, Kk, true, s_red, s_scan, [&](int pos, int e, int j) {
+            s_k[pos] = keys[(size_t)e * L + j];
+            s_e[pos] = (uint32_t)e;
+            s_p[pos] = packs[(size_t)e * L + j];
+        });
     __syncthreads();
     if (tid == 0) nvalid[s] = Kk;
     if (tid >= K) return;
@@ -359,14 +211,14 @@ __global__ __launch_bounds__(SG_SCENE_THREADS) void sg_scene_kernel(const int32_
     o[1] = mode == 1 ? -1 : (int32_t)(px >> 15);
     o[2] = mode == 1 ? -1 : (int32_t)((px >> 5) & 1023);
     o[3] = (int32_t)(px & 31);
-    osc[rank] = sg_unkey(x);
+    osc[rank] = unkey(x);
 }
 
 size_t scene_graph_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes, int each) {
     const int64_t Ks = C < SG_EACH ? C : SG_EACH;
     const int L = sg_slots(C, R, 0, each);
-    return 2 * sg_align((size_t)N * Ks * sizeof(float)) + sg_align((size_t)(n_scenes + 1) * sizeof(int32_t)) +
-           2 * sg_align((size_t)E * L * sizeof(uint32_t));
+    return 2 * align_up((size_t)N * Ks * sizeof(float), 256) + align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256) +
+           2 * align_up((size_t)E * L * sizeof(uint32_t), 256);
 }
 
 SceneGraphWs scene_graph_carve(void* scratch, int64_t N, int64_t E, int C, int R, int n_scenes, int each) {
@@ -374,10 +226,10 @@ SceneGraphWs scene_graph_carve(void* scratch, int64_t N, int64_t E, int C, int R
     const int L = sg_slots(C, R, 0, each);
     char* p = static_cast<char*>(scratch);
     SceneGraphWs w;
-    w.sv = reinterpret_cast<float*>(p);        p += sg_align((size_t)N * Ks * sizeof(float));
-    w.si = reinterpret_cast<int32_t*>(p);      p += sg_align((size_t)N * Ks * sizeof(float));
-    w.ptr = reinterpret_cast<int32_t*>(p);     p += sg_align((size_t)(n_scenes + 1) * sizeof(int32_t));
-    w.keys = reinterpret_cast<uint32_t*>(p);   p += sg_align((size_t)E * L * sizeof(uint32_t));
+    w.sv = reinterpret_cast<float*>(p);        p += align_up((size_t)N * Ks * sizeof(float), 256);
+    w.si = reinterpret_cast<int32_t*>(p);      p += align_up((size_t)N * Ks * sizeof(float), 256);
+    w.ptr = reinterpret_cast<int32_t*>(p);     p += align_up((size_t)(n_scenes + 1) * sizeof(int32_t), 256);
+    w.keys = reinterpret_cast<uint32_t*>(p);   p += align_up((size_t)E * L * sizeof(uint32_t), 256);
     w.packs = reinterpret_cast<uint32_t*>(p);
     return w;
 }
@@ -417,9 +269,8 @@ int launch_scene_graph_topk(const float* obj_probs, const float* rel, const int6
     if (rp) return rp;
     if (E > 0) {
         if (mode == 0) {
-            hipLaunchKernelGGL(sg_node_argsort_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, obj_probs, N, C, Ks,
-                               ws.sv, ws.si);
-            VLSAT_LAUNCH_CHECK("scene_graph node_argsort");
+            const int rs = launch_sort_probs(obj_probs, N, C, Ks, ws.sv, s, ws.si);
+            if (rs) return rs;
         }
         hipLaunchKernelGGL(sg_edge_kernel, dim3((E + 3) / 4), dim3(256), 0, s, ws.sv, ws.si, Ks, rel, edges, N, E, R, mode, L, ws.keys,
                            ws.packs);

@@ -15,10 +15,10 @@
 // sets bit (group, segment slot) by atomicOr (after a relaxed load: most bits are set already); sg_count_kernel counts a group's bits.
 //
 // Fusion.  Rows of several splits that carry the same instance id are one object; objects are numbered by ascending id through an
-// id -> slot table (presence flags, exclusive scan); members and pooled probabilities as in segment_merge.hip (one wave per object,
-// rows ascending, fl(s + fl(w p)), fl(s / W)); an edge sets bit (a, b) of an [N, ceil(N / 32)] table, the pairs of a source object are
-// counted by popcount, scanned, and an edge's pair number is base[a] + the set bits below b: pairs come out sorted by (a, b) with no
-// sort; pair probabilities by atomicMax on the float bits (values >= 0).
+// id -> slot table (presence flags, exclusive scan); scan, members and pooled probabilities BY the kernels of segment_merge.hip
+// (launch_scan_i32, launch_members, launch_pool_members: one wave per object, rows ascending, fl(s + fl(w p)), fl(s / W)); an edge
+// sets bit (a, b) of an [N, ceil(N / 32)] table, the pairs of a source object are counted by popcount, scanned, and an edge's pair
+// number is base[a] + the set bits below b: pairs come out sorted by (a, b) with no sort; pair probabilities by atomicMax on the float bits (values >= 0).
 // Nothing depends on the order blocks run in.  Integer atomics only.  build.py compiles THIS file with -ffp-contract=off
 // (PER_SOURCE_FLAGS): the squared distance and the pooled sum round every product and sum on their own.
 #include <algorithm>
@@ -34,7 +34,6 @@ constexpr int SS_CHUNK = 1024;                          // vertices per block of
 constexpr int SS_PICK_THREADS = 1024;
 constexpr int SG_TILE = 512;                            // seed boxes in LDS at a time: 512 * 6 doubles = 24 KB
 constexpr int FS_THREADS = 256;
-constexpr int FS_SCAN_THREADS = 1024;
 constexpr int FS_NONE = 0x7fffffff;
 // state words of vlsat_split_seeds
 enum { SS_COUNT = 0, SS_STATUS = 1, SS_DONE = 2, SS_CUR = 3 };
@@ -189,10 +188,6 @@ __global__ void sg_clear_kernel(int32_t* __restrict__ id_map, int map_size, unsi
     for (int64_t i = t0; i < map_size; i += stride) id_map[i] = -1;
     for (int64_t i = t0; i < n_words; i += stride) mask[i] = 0u;
 }
-__global__ void sg_map_set_kernel(const int32_t* __restrict__ ids, int n, int32_t* __restrict__ id_map, int map_size) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && ids[i] >= 0 && ids[i] < map_size) id_map[ids[i]] = i;
-}
 
 __global__ __launch_bounds__(256) void sg_hit_kernel(const float* __restrict__ points, const int32_t* __restrict__ segments, int64_t n_points,
                                                      const int32_t* __restrict__ id_map, int map_size, const int32_t* __restrict__ seeds,
@@ -276,33 +271,6 @@ __global__ __launch_bounds__(FS_THREADS) void fs_flag_kernel(const int32_t* __re
     if (i < map_size) flag[i] = first[i] != FS_NONE;
 }
 
-// out[0..n] = exclusive scan of in[0..n-1]; *total = out[n].  One block; a thread owns a contiguous run.
-__global__ __launch_bounds__(FS_SCAN_THREADS) void fs_scan_kernel(const int32_t* __restrict__ in, int n, int32_t* __restrict__ out,
-                                                                  int32_t* __restrict__ total, int32_t* __restrict__ total2) {
-    __shared__ int part[FS_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    const int per = (n + FS_SCAN_THREADS - 1) / FS_SCAN_THREADS;
-    const int b = (int)min((int64_t)tid * per, (int64_t)n), e = (int)min((int64_t)b + per, (int64_t)n);
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += in[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid < 64) {
-        int v[FS_SCAN_THREADS / 64], s = 0;
-#pragma unroll
-        for (int k = 0; k < FS_SCAN_THREADS / 64; ++k) { v[k] = part[tid * (FS_SCAN_THREADS / 64) + k]; s += v[k]; }
-        int incl = s;
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (tid >= o) incl += t; }
-        int acc = incl - s;
-#pragma unroll
-        for (int k = 0; k < FS_SCAN_THREADS / 64; ++k) { part[tid * (FS_SCAN_THREADS / 64) + k] = acc; acc += v[k]; }
-        if (tid == 63) { out[n] = incl; if (total) *total = incl; if (total2) *total2 = incl; }
-    }
-    __syncthreads();
-    int acc = part[tid];
-    for (int i = b; i < e; ++i) { const int v = in[i]; out[i] = acc; acc += v; }
-}
-
 __global__ __launch_bounds__(FS_THREADS) void fs_object_kernel(const int32_t* __restrict__ row_instance, int n, int map_size,
                                                                const int32_t* __restrict__ first, const int32_t* __restrict__ rows,
                                                                const int32_t* __restrict__ num, int32_t* __restrict__ root,
@@ -318,51 +286,6 @@ __global__ __launch_bounds__(FS_THREADS) void fs_object_kernel(const int32_t* __
     root[i] = r;
     object[i] = o;
     if (r == i) { cnt[o] = rows[id]; obj_root[o] = i; obj_bid[o] = 0; obj_ids[o] = id; }
-}
-
-// one wave per object: its rows from the root on, compacted in ascending order by ballot prefixes
-__global__ __launch_bounds__(FS_THREADS) void fs_members_kernel(const int32_t* __restrict__ object, const int32_t* __restrict__ obj_root,
-                                                                const int32_t* __restrict__ member_ptr, const int32_t* __restrict__ totals, int n,
-                                                                int32_t* __restrict__ members) {
-    const int o = blockIdx.x * (FS_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= n || o >= totals[0]) return;
-    const int r = obj_root[o];
-    if (r < 0 || r >= n) return;
-    int pos = member_ptr[o];
-    const int end = member_ptr[o + 1];
-    for (int n0 = r; n0 < n && pos < end; n0 += 64) {
-        const int i = n0 + lane;
-        const bool mine = i < n && object[i] == o;
-        const unsigned long long m = __ballot(mine);
-        const int p = pos + (int)__popcll(m & ((1ull << lane) - 1));
-        if (mine && p >= 0 && p < end && p < n) members[p] = i;
-        pos += (int)__popcll(m);
-    }
-}
-
-__global__ __launch_bounds__(FS_THREADS) void fs_pool_kernel(const float* __restrict__ probs, const float* __restrict__ weights,
-                                                             const int32_t* __restrict__ members, const int32_t* __restrict__ member_ptr,
-                                                             const int32_t* __restrict__ totals, int n, int C, float* __restrict__ out_probs,
-                                                             float* __restrict__ out_weight) {
-    const int o = blockIdx.x * (FS_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (o >= n || o >= totals[0]) return;
-    const int m0 = max(member_ptr[o], 0), m1 = min(member_ptr[o + 1], n);
-    float W = 0.0f;
-    for (int k = m0; k < m1; ++k) {
-        const int i = members[k];
-        if (i < 0 || i >= n) continue;
-        W = __fadd_rn(W, weights ? weights[i] : 1.0f);
-    }
-    for (int c = lane; c < C; c += 64) {
-        float s = 0.0f;
-        for (int k = m0; k < m1; ++k) {
-            const int i = members[k];
-            if (i < 0 || i >= n) continue;
-            s = __fadd_rn(s, __fmul_rn(weights ? weights[i] : 1.0f, probs[(size_t)i * C + c]));
-        }
-        out_probs[(size_t)o * C + c] = __fdiv_rn(s, W);
-    }
-    if (lane == 0) out_weight[o] = W;
 }
 
 struct FsPair { int a, b; bool ok; };                   // ok: both rows in range, both with an object, two different objects
@@ -429,20 +352,19 @@ __global__ __launch_bounds__(FS_THREADS) void fs_pair_emit_kernel(const float* _
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static size_t ss_round16(size_t b) { return (b + 15) & ~(size_t)15; }
 static dim3 ss_blocks(int64_t n, int threads) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + threads - 1) / threads, 4096))); }
 
 // scratch of the seeds: dmin2 f64 [V] | block_cnt i32 [ceil(V / 1024)]
 static size_t split_seeds_scratch_bytes(int64_t V) {
     if (V < 1 || V > 0x7fffffff) return 0;
-    return ss_round16((size_t)V * 8) + ss_round16((size_t)((V + SS_CHUNK - 1) / SS_CHUNK) * 4);
+    return align_up((size_t)V * 8, 16) + align_up((size_t)((V + SS_CHUNK - 1) / SS_CHUNK) * 4, 16);
 }
 
 static int launch_split_seeds(const float* points, int64_t V, double distance, unsigned long long seed, const int64_t* ranks, int64_t n_ranks,
                               int max_seeds, void* scratch, int32_t* seeds, int32_t* state, hipStream_t s) {
     const int n_blocks = (int)((V + SS_CHUNK - 1) / SS_CHUNK);
     double* dmin2 = static_cast<double*>(scratch);
-    int32_t* block_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + ss_round16((size_t)V * 8));
+    int32_t* block_cnt = reinterpret_cast<int32_t*>(static_cast<char*>(scratch) + align_up((size_t)V * 8, 16));
     const double d2 = distance * distance;
     hipLaunchKernelGGL(ss_init_kernel, dim3(1), dim3(64), 0, s, V, seed, ranks, n_ranks, max_seeds, seeds, state);
     for (int k = 0; k < max_seeds; ++k) {
@@ -460,7 +382,7 @@ static int launch_split_groups(const float* points, const int32_t* segments, int
     const int words = (n_seg + 31) / 32;
     const int64_t n_words = (int64_t)n_seeds * words;
     hipLaunchKernelGGL(sg_clear_kernel, ss_blocks(std::max<int64_t>(map_size, n_words), 256), dim3(256), 0, s, id_map, map_size, mask, n_words);
-    if (n_seg > 0) hipLaunchKernelGGL(sg_map_set_kernel, dim3((n_seg + 255) / 256), dim3(256), 0, s, segment_ids, n_seg, id_map, map_size);
+    if (n_seg > 0) launch_id_map_set(segment_ids, n_seg, id_map, map_size, s);
     if (n_seeds > 0 && n_seg > 0 && V > 0)
         hipLaunchKernelGGL(sg_hit_kernel, ss_blocks(V, 256), dim3(256), 0, s, points, segments, V, (const int32_t*)id_map, map_size, seeds, n_seeds, bbox,
                            words, mask);
@@ -484,8 +406,8 @@ static int fuse_splits_check_args(int64_t N, int64_t E, int C, int R, int map_si
 static size_t fuse_splits_scratch_bytes(int64_t N, int64_t E, int map_size) {
     (void)E;
     const size_t n = (size_t)N, m = (size_t)map_size, big = n > m ? n : m, words = (n + 31) / 32;
-    return 2 * ss_round16(m * 4) + ss_round16(big * 4) + ss_round16((big + 1) * 4) + 2 * ss_round16(n * 4) + ss_round16((n + 1) * 4) +
-           ss_round16(n * words * 4);
+    return 2 * align_up(m * 4, 16) + align_up(big * 4, 16) + align_up((big + 1) * 4, 16) + 2 * align_up(n * 4, 16) + align_up((n + 1) * 4, 16) +
+           align_up(n * words * 4, 16);
 }
 
 static int launch_fuse_splits(const float* probs, const float* rel_probs, const int64_t* edges, const int32_t* row_instance, const float* weights,
@@ -496,40 +418,40 @@ static int launch_fuse_splits(const float* probs, const float* rel_probs, const 
     const int words = (N + 31) / 32;
     const int64_t bit_words = (int64_t)N * words;
     char* p = static_cast<char*>(scratch);
-    int32_t* first = reinterpret_cast<int32_t*>(p);     p += ss_round16(m * 4);
-    int32_t* rows = reinterpret_cast<int32_t*>(p);      p += ss_round16(m * 4);
-    int32_t* flag = reinterpret_cast<int32_t*>(p);      p += ss_round16(big * 4);
-    int32_t* num = reinterpret_cast<int32_t*>(p);       p += ss_round16((big + 1) * 4);
-    int32_t* cnt = reinterpret_cast<int32_t*>(p);       p += ss_round16(n * 4);
-    int32_t* obj_root = reinterpret_cast<int32_t*>(p);  p += ss_round16(n * 4);
-    int32_t* base = reinterpret_cast<int32_t*>(p);      p += ss_round16((n + 1) * 4);
+    int32_t* first = reinterpret_cast<int32_t*>(p);     p += align_up(m * 4, 16);
+    int32_t* rows = reinterpret_cast<int32_t*>(p);      p += align_up(m * 4, 16);
+    int32_t* flag = reinterpret_cast<int32_t*>(p);      p += align_up(big * 4, 16);
+    int32_t* num = reinterpret_cast<int32_t*>(p);       p += align_up((big + 1) * 4, 16);
+    int32_t* cnt = reinterpret_cast<int32_t*>(p);       p += align_up(n * 4, 16);
+    int32_t* obj_root = reinterpret_cast<int32_t*>(p);  p += align_up(n * 4, 16);
+    int32_t* base = reinterpret_cast<int32_t*>(p);      p += align_up((n + 1) * 4, 16);
     unsigned* bits = reinterpret_cast<unsigned*>(p);
 
     auto exact = [](int64_t k) { return dim3((unsigned)((k + FS_THREADS - 1) / FS_THREADS)); };
-    const dim3 block(FS_THREADS), one(1), scan(FS_SCAN_THREADS);
+    const dim3 block(FS_THREADS);
     const int64_t most = std::max<int64_t>(std::max<int64_t>((int64_t)N * C, (int64_t)E * R), std::max<int64_t>(map_size, bit_words));
     hipLaunchKernelGGL(fs_clear_kernel, ss_blocks(most, FS_THREADS), block, 0, s, N, E, C, R, map_size, bit_words, first, rows, cnt, bits, root, object,
                        n_objects, totals, members, out_probs, out_weight, obj_bid, obj_ids, edge_to_pair, pair_edges, pair_count, pair_probs);
     if (N == 0) {                                                     // no row: no object, no pair; member_ptr = [0]
-        hipLaunchKernelGGL(fs_scan_kernel, one, scan, 0, s, (const int32_t*)cnt, 0, member_ptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        launch_scan_i32(cnt, 0, member_ptr, nullptr, nullptr, s);
         VLSAT_LAUNCH_CHECK("fuse_splits");
         return 0;
     }
     hipLaunchKernelGGL(fs_first_kernel, exact(N), block, 0, s, row_instance, N, map_size, first, rows);
     hipLaunchKernelGGL(fs_flag_kernel, exact(map_size), block, 0, s, (const int32_t*)first, map_size, flag);
-    hipLaunchKernelGGL(fs_scan_kernel, one, scan, 0, s, (const int32_t*)flag, map_size, num, totals, n_objects);
+    launch_scan_i32(flag, map_size, num, totals, n_objects, s);
     hipLaunchKernelGGL(fs_object_kernel, exact(N), block, 0, s, row_instance, N, map_size, (const int32_t*)first, (const int32_t*)rows,
                        (const int32_t*)num, root, object, cnt, obj_root, obj_bid, obj_ids);
-    hipLaunchKernelGGL(fs_scan_kernel, one, scan, 0, s, (const int32_t*)cnt, N, member_ptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    launch_scan_i32(cnt, N, member_ptr, nullptr, nullptr, s);
+    // members: root[i] == obj_root[o] exactly when object[i] == o (fs_object_kernel writes both or neither, and distinct ids have
+    // distinct first rows), so the kernel of segment_merge.hip without scenes lists the rows of an object
+    launch_members(root, obj_root, member_ptr, nullptr, totals, N, members, s);
+    launch_pool_members(probs, weights, members, member_ptr, totals, N, C, out_probs, out_weight, s);
     const dim3 waves((unsigned)((N + FS_THREADS / 64 - 1) / (FS_THREADS / 64)));
-    hipLaunchKernelGGL(fs_members_kernel, waves, block, 0, s, (const int32_t*)object, (const int32_t*)obj_root, (const int32_t*)member_ptr,
-                       (const int32_t*)totals, N, members);
-    hipLaunchKernelGGL(fs_pool_kernel, waves, block, 0, s, probs, weights, (const int32_t*)members, (const int32_t*)member_ptr, (const int32_t*)totals,
-                       N, C, out_probs, out_weight);
     if (E > 0) {
         hipLaunchKernelGGL(fs_pair_mark_kernel, exact(E), block, 0, s, edges, (const int32_t*)object, N, E, words, bits);
         hipLaunchKernelGGL(fs_row_count_kernel, waves, block, 0, s, (const unsigned*)bits, N, words, flag);
-        hipLaunchKernelGGL(fs_scan_kernel, one, scan, 0, s, (const int32_t*)flag, N, base, totals + 1, (int32_t*)nullptr);
+        launch_scan_i32(flag, N, base, totals + 1, nullptr, s);
         hipLaunchKernelGGL(fs_pair_index_kernel, exact(E), block, 0, s, edges, (const int32_t*)object, (const unsigned*)bits, (const int32_t*)base, N, E,
                            words, edge_to_pair, pair_edges, pair_count);
         hipLaunchKernelGGL(fs_pair_emit_kernel, exact((int64_t)E * R), block, 0, s, rel_probs, (const int32_t*)edge_to_pair, E, R,

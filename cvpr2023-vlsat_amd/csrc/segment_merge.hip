@@ -159,9 +159,9 @@ __global__ __launch_bounds__(SM_THREADS) void sm_flatten_kernel(const int32_t* _
     flag[n] = r == n;
 }
 
-// out[0..n] = exclusive scan of in[0..n-1]; *total = out[n].  One block; a thread owns a contiguous run.
+// out[0..n] = exclusive scan of in[0..n-1]; *total = *total2 = out[n] (either may be null).  One block; a thread owns a contiguous run.
 __global__ __launch_bounds__(SM_SCAN_THREADS) void sm_scan_kernel(const int32_t* __restrict__ in, int n, int32_t* __restrict__ out,
-                                                                  int32_t* __restrict__ total) {
+                                                                  int32_t* __restrict__ total, int32_t* __restrict__ total2) {
     __shared__ int part[SM_SCAN_THREADS];
     const int tid = threadIdx.x;
     const int per = (n + SM_SCAN_THREADS - 1) / SM_SCAN_THREADS;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void sm_scan_kernel(const int32_t*
         int acc = incl - s;
 #pragma unroll
         for (int k = 0; k < SM_SCAN_THREADS / 64; ++k) { part[tid * (SM_SCAN_THREADS / 64) + k] = acc; acc += v[k]; }
-        if (tid == 63) { out[n] = incl; if (total) *total = incl; }
+        if (tid == 63) { out[n] = incl; if (total) *total = incl; if (total2) *total2 = incl; }
     }
     __syncthreads();
     int acc = part[tid];
@@ -205,7 +205,8 @@ __global__ __launch_bounds__(SM_THREADS) void sm_object_kernel(const int32_t* __
     }
 }
 
-// ---- members and pooled probabilities: one wave per object ----------------------------------------------------------------------
+// ---- members and pooled probabilities: one wave per object (fuse_splits of scene_split.hip runs the same two kernels: there root[n]
+// is the first row of n's instance id and bid is null, so "root[n] == r" selects the rows of the object and no scene ends the walk) ----
 __global__ __launch_bounds__(SM_THREADS) void sm_members_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ obj_root,
                                                                 const int32_t* __restrict__ member_ptr, const int64_t* __restrict__ bid,
                                                                 const int32_t* __restrict__ totals, int n_nodes, int32_t* __restrict__ members) {
@@ -305,7 +306,20 @@ __global__ __launch_bounds__(SM_THREADS) void sm_pair_emit_kernel(const float* _
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static size_t sm_round16(size_t b) { return (b + 15) & ~(size_t)15; }
+// (the three launchers below leave the launch check to their caller, which names the entry point)
+void launch_scan_i32(const int32_t* in, int n, int32_t* out, int32_t* total, int32_t* total2, hipStream_t s) {
+    hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, in, n, out, total, total2);
+}
+static dim3 sm_waves(int n) { return dim3((unsigned)((n + SM_THREADS / 64 - 1) / (SM_THREADS / 64))); }
+void launch_members(const int32_t* root, const int32_t* obj_root, const int32_t* member_ptr, const int64_t* bid, const int32_t* totals, int n,
+                    int32_t* members, hipStream_t s) {
+    hipLaunchKernelGGL(sm_members_kernel, sm_waves(n), dim3(SM_THREADS), 0, s, root, obj_root, member_ptr, bid, totals, n, members);
+}
+void launch_pool_members(const float* probs, const float* weights, const int32_t* members, const int32_t* member_ptr, const int32_t* totals,
+                         int n, int C, float* out_probs, float* out_weight, hipStream_t s) {
+    hipLaunchKernelGGL(sm_pool_kernel, sm_waves(n), dim3(SM_THREADS), 0, s, probs, weights, members, member_ptr, totals, n, C, out_probs, out_weight);
+}
+
 static int64_t sm_capacity(int64_t E) {
     int64_t cap = 64;
     while (cap < 2 * E) cap <<= 1;
@@ -324,7 +338,7 @@ int merge_segments_check_args(int64_t N, int64_t E, int C, int R, int n_scenes) 
 size_t merge_segments_scratch_bytes(int64_t N, int64_t E, int C, int R, int n_scenes) {
     (void)C; (void)R; (void)n_scenes;
     const size_t n = (size_t)N, e = (size_t)E, cap = (size_t)sm_capacity(E), big = n > e ? n : e;
-    return cap * 8 + sm_round16(cap * 4) + 3 * sm_round16(n * 4) + sm_round16(e * 4) + sm_round16(big * 4) + sm_round16((big + 1) * 4);
+    return cap * 8 + align_up(cap * 4, 16) + 3 * align_up(n * 4, 16) + align_up(e * 4, 16) + align_up(big * 4, 16) + align_up((big + 1) * 4, 16);
 }
 
 int launch_merge_segments(const float* obj_probs, const float* rel_probs, const int64_t* edges, const int64_t* batch_ids, const float* weights,
@@ -338,12 +352,12 @@ int launch_merge_segments(const float* obj_probs, const float* rel_probs, const 
     const size_t big = (size_t)std::max(N, E);
     char* p = static_cast<char*>(scratch);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(p);  p += (size_t)cap * 8;
-    int32_t* slot_min = reinterpret_cast<int32_t*>(p);                    p += sm_round16((size_t)cap * 4);
-    int32_t* parent = reinterpret_cast<int32_t*>(p);                      p += sm_round16((size_t)N * 4);
-    int32_t* cnt = reinterpret_cast<int32_t*>(p);                         p += sm_round16((size_t)N * 4);
-    int32_t* obj_root = reinterpret_cast<int32_t*>(p);                    p += sm_round16((size_t)N * 4);
-    int32_t* slot_of = reinterpret_cast<int32_t*>(p);                     p += sm_round16((size_t)E * 4);
-    int32_t* flag = reinterpret_cast<int32_t*>(p);                        p += sm_round16(big * 4);
+    int32_t* slot_min = reinterpret_cast<int32_t*>(p);                    p += align_up((size_t)cap * 4, 16);
+    int32_t* parent = reinterpret_cast<int32_t*>(p);                      p += align_up((size_t)N * 4, 16);
+    int32_t* cnt = reinterpret_cast<int32_t*>(p);                         p += align_up((size_t)N * 4, 16);
+    int32_t* obj_root = reinterpret_cast<int32_t*>(p);                    p += align_up((size_t)N * 4, 16);
+    int32_t* slot_of = reinterpret_cast<int32_t*>(p);                     p += align_up((size_t)E * 4, 16);
+    int32_t* flag = reinterpret_cast<int32_t*>(p);                        p += align_up(big * 4, 16);
     int32_t* num = reinterpret_cast<int32_t*>(p);
 
     auto blocks = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + SM_THREADS - 1) / SM_THREADS, 4096))); };
@@ -353,7 +367,7 @@ int launch_merge_segments(const float* obj_probs, const float* rel_probs, const 
     hipLaunchKernelGGL(sm_clear_kernel, blocks(most), block, 0, s, N, E, C, R, n_scenes, parent, cnt, slot_of, root, object, n_objects, totals,
                        members, out_probs, out_weight, obj_batch_ids, edge_to_pair, pair_edges, pair_count, pair_probs);
     if (N == 0) {                                                     // no node: no object, no pair; member_ptr = [0]
-        hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, (const int32_t*)cnt, 0, member_ptr, (int32_t*)nullptr);
+        launch_scan_i32(cnt, 0, member_ptr, nullptr, nullptr, s);
         VLSAT_LAUNCH_CHECK("merge_segments");
         return 0;
     }
@@ -369,20 +383,17 @@ int launch_merge_segments(const float* obj_probs, const float* rel_probs, const 
         }
     }
     hipLaunchKernelGGL(sm_flatten_kernel, exact(N), block, 0, s, (const int32_t*)parent, N, root, flag);
-    hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, (const int32_t*)flag, N, num, totals);
+    launch_scan_i32(flag, N, num, totals, nullptr, s);
     hipLaunchKernelGGL(sm_object_kernel, exact(N), block, 0, s, (const int32_t*)root, (const int32_t*)num, batch_ids, N, n_scenes, object, cnt,
                        obj_root, obj_batch_ids, n_objects);
-    hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, (const int32_t*)cnt, N, member_ptr, (int32_t*)nullptr);
-    const dim3 waves((unsigned)((N + SM_THREADS / 64 - 1) / (SM_THREADS / 64)));
-    hipLaunchKernelGGL(sm_members_kernel, waves, block, 0, s, (const int32_t*)root, (const int32_t*)obj_root, (const int32_t*)member_ptr, batch_ids,
-                       (const int32_t*)totals, N, members);
-    hipLaunchKernelGGL(sm_pool_kernel, waves, block, 0, s, obj_probs, weights, (const int32_t*)members, (const int32_t*)member_ptr,
-                       (const int32_t*)totals, N, C, out_probs, out_weight);
+    launch_scan_i32(cnt, N, member_ptr, nullptr, nullptr, s);
+    launch_members(root, obj_root, member_ptr, batch_ids, totals, N, members, s);
+    launch_pool_members(obj_probs, weights, members, member_ptr, totals, N, C, out_probs, out_weight, s);
     if (E > 0) {
         hipLaunchKernelGGL(sm_table_clear_kernel, blocks(cap), block, 0, s, keys, slot_min, cap);
         hipLaunchKernelGGL(sm_pair_insert_kernel, exact(E), block, 0, s, edges, batch_ids, (const int32_t*)object, N, E, keys, slot_min, mask, slot_of);
         hipLaunchKernelGGL(sm_pair_flag_kernel, exact(E), block, 0, s, (const int32_t*)slot_of, (const int32_t*)slot_min, E, flag);
-        hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, (const int32_t*)flag, E, num, totals + 1);
+        launch_scan_i32(flag, E, num, totals + 1, nullptr, s);
         hipLaunchKernelGGL(sm_pair_emit_kernel, exact((int64_t)E * R), block, 0, s, rel_probs, edges, (const int32_t*)object, (const int32_t*)slot_of,
                            (const int32_t*)slot_min, (const int32_t*)num, E, R, edge_to_pair, pair_edges, pair_count,
                            reinterpret_cast<unsigned*>(pair_probs));

@@ -76,3 +76,16 @@ def check_contract(graph, probs, rp, edges, scene_of_edge, n_scenes, top_k, each
 
 def graphs_equal(a, b):
     return all(torch.equal(getattr(a, k), getattr(b, k)) for k in ("edge", "sub_cls", "obj_cls", "pred", "score", "n_valid"))
+
+
+def three_valued_scene(p50, p75, seed=0, n=34, r=26, c=12):
+    """(probs [n, c], rel [E, r], edges [E, 2]) of one fully connected scene of 34 objects -- E = 1 122: one 1024-edge chunk of the
+    scene kernels plus 98 edges -- whose relation scores are 0.75 (probability p75), 0.5 (p50) or 0.25 only, so that equal scores
+    lie on both sides of edge 1024 and a cap falls inside a run of them."""
+    g = torch.Generator().manual_seed(seed)
+    edges = torch.tensor([(a, b) for a in range(n) for b in range(n) if a != b])
+    u = torch.rand(edges.shape[0], r, generator=g)
+    rel = torch.full_like(u, 0.25)
+    rel[u < p50 + p75] = 0.5
+    rel[u < p75] = 0.75
+    return torch.softmax(torch.randn(n, c, generator=g), -1), rel, edges

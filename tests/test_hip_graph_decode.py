@@ -12,6 +12,7 @@ import vlsat_amd  # noqa: F401
 from vlsat_amd import evaluate as EV, lib as L, metrics as M
 
 from graph_decode_checks import SG_GOLD, assert_equal, brute, case, indicator
+from scene_graph_checks import three_valued_scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -105,6 +106,26 @@ def test_hip_ties_at_the_cap_follow_the_total_order(multi):
             assert_equal(got, brute(probs, rp, edges, np.zeros(70, np.int64), 1, 0.5, multi, score, 2, max_rel))
             n_v = int(got.n_valid[0])
             assert n_v == max_rel and torch.equal(got.edge[0, :n_v].cpu(), full.edge[0, :n_v])
+
+
+@pytest.mark.parametrize("max_rel", [1024, 4096])
+def test_hip_equal_scores_across_the_cap_and_the_edge_chunk(max_rel):
+    """Ties that straddle both the cap and the 1024-edge chunk of the scene kernel's gather (select_core.h select_topk_lists).
+    Multi-label at threshold 0.5 on scores 0.25 / 0.5 / 0.75, 1 122 edges, about 0.95 asserted pairs per edge: n_total is a
+    little above 1024 while the first 1024 edges assert fewer than 1024 pairs, so at max_rel = 1024 the kept pairs equal to the
+    boundary value 0.5 run past edge 1024 and stop short of the last one; at 4096 nothing is cut (no bisection) and the pairs
+    of the second chunk land behind the first chunk's.  Equal to the host statement field for field."""
+    _need_gpu()
+    probs, rp, edges = three_valued_scene(p50=0.0245, p75=0.012)
+    got, want = _both(probs, rp, edges, None, 1, True, 0.5, "rel", 3, max_rel)
+    n_t, n_v = int(want.n_total[0]), int(want.n_valid[0])
+    assert n_t > 1024 and n_v == min(n_t, max_rel)
+    t = want.score[0, n_v - 1]                                               # the boundary value
+    assert bool((rp[:1024] == t).any()) and bool((rp[1024:] == t).any())
+    if max_rel == 1024:
+        kept = want.edge[0, :n_v][want.score[0, :n_v] == t]
+        assert float(t) == 0.5 and int(kept.max()) >= 1024 and int((kept >= 1024).sum()) < int((rp[1024:] == t).sum())
+    assert_equal(got, want, max_rel)
 
 
 def test_hip_threshold_vector():

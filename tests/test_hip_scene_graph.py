@@ -11,7 +11,7 @@ import torch
 import vlsat_amd  # noqa: F401
 from vlsat_amd import evaluate as EV, lib as L, metrics as M
 
-from scene_graph_checks import check_contract, edge_candidates, graphs_equal
+from scene_graph_checks import check_contract, edge_candidates, graphs_equal, three_valued_scene
 from test_scene_graph_cpu import GOLD, VARIANTS, assert_golden, golden_case, golden_probs, golden_rows, hits_from_graph, tie_cases
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +147,30 @@ def test_hip_ties_and_odd_graphs(evaluate):
     # no edge at all
     g = M.scene_graph_topk(probs, rel[:0], edges[:0], None, 1, True, 5, 5, evaluate, obj_probs=probs)
     assert int(g.n_valid[0]) == 0 and int(g.edge.max()) == -1
+
+
+@pytest.mark.parametrize("top_k", [100, 1024])
+@pytest.mark.parametrize("each", [1, 3])
+def test_hip_equal_scores_across_the_cap_and_the_edge_chunk(each, top_k):
+    """Ties that straddle both the cap and the 1024-edge chunk of the scene kernel's gather (select_core.h select_topk_lists: the
+    running base of a chunk meets the number of ties still needed).  Scores 0.25 / 0.5 / 0.75 only, 1 122 edges.  P(edge has a
+    0.75) = 0.30 and P(edge has a score >= 0.5) = 0.93, so with topk_each = 1 and top_k = 1024 about 337 candidates lie above the
+    boundary value 0.5 and the first 1024 edges hold fewer ties (about 645) than are still needed: the kept ties run past edge
+    1024 and stop short of the last one.  Equal to the host statement field for field."""
+    _need_gpu()
+    probs, rel, edges = three_valued_scene(p50=0.0836, p75=0.0136)
+    want = M.scene_graph_topk_host(probs, rel, edges, None, 1, True, top_k, each, "rels", obj_probs=probs)
+    n_v = int(want.n_valid[0])
+    cand = edge_candidates(probs, rel, edges, "rels", each)
+    t = want.score[0, n_v - 1]                                               # the boundary value
+    assert cand.numel() > top_k and n_v == top_k
+    assert bool((cand[:1024] == t).any()) and bool((cand[1024:] == t).any())
+    if (each, top_k) == (1, 1024):
+        kept = want.edge[0, :n_v][want.score[0, :n_v] == t]
+        assert float(t) == 0.5 and int(kept.max()) >= 1024 and int((kept >= 1024).sum()) < int((cand[1024:] == t).sum())
+    got = M.scene_graph_topk(probs.to(DEV), rel.to(DEV), edges.to(DEV), None, 1, True, top_k, each, "rels", obj_probs=probs.to(DEV))
+    for k in ("edge", "sub_cls", "obj_cls", "pred", "score", "n_valid"):
+        assert torch.equal(getattr(got, k).cpu(), getattr(want, k)), (each, top_k, k)
 
 
 def test_hip_arguments_out_of_range_are_refused_with_a_message():

@@ -182,6 +182,19 @@ def test_gate_select_chooses_what_the_forward_chose_before_it(L):
     assert seen == {"valu", "f32", "f32_heads", "16", "16_heads"}
 
 
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_select_core_integer_helpers_on_the_host(sanitize):
+    """csrc/select_core.h compiled by g++: the float key round-trips bit for bit, is strictly monotone and positive over
+    -inf .. +inf (denormals and both zeros included) and equals the formula proximity.hip / label_transfer.hip carried; count_ge
+    equals a linear count on descending lists with repeats of lengths 0, 1, 2, 31, 32, 33; the dominance table of (100, 32) holds
+    exactly the 1 365 triples with a b c <= 100, c <= 32.  The second case is the same stand-alone binary under ASan + UBSan."""
+    import select_host
+    rows = dict(select_host.run(sanitize))
+    assert set(rows) == {"keys", "count_ge", "triples", "clampi"}, rows
+    assert all(v.split()[0] == "ok" for v in rows.values()), rows
+    assert rows["triples"] == "ok 1365"
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "cvpr2023-vlsat_amd")
     for dp, _, fs in os.walk(pkg):
