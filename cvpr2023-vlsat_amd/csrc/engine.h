@@ -5,6 +5,39 @@
 //   engine_api.hip      kernel-level C entry points and debug hooks
 // The public surface is include/vlsat.h.
 #pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace vlsat {
+
+// The evaluation scratch of a plan (vlsat_plan_s::ev_f / ev_i; vlsat_process_val_counts, vlsat_forward_scene_graph, vlsat_forward_graph):
+// ONE statement of its layout -- engine_plan.hip sizes the arena with eval_scratch_floats / _ints, the entry points take their
+// pointers from eval_scratch_carve.  N nodes, E edges (edge tables keep one row when E = 0), C object classes, R predicate classes.
+struct EvalScratch {
+    float *obj3, *obj2, *prob3, *prob2;     // [N, C] each: the object logits and their softmax
+    float *rel3, *rel2;                     // [max(E, 1), R] each: the predicate outputs
+    float* sorted;                          // [N, <= C]: the rankings' per-node sorted probabilities
+    int32_t *or3, *or2;                     // [N] each: object ranks
+    int32_t *rr3, *rr2, *tr3, *tr2;         // [max(E, 1), R] each: predicate and triplet ranks
+    int32_t *cn3, *cn2;                     // [max(E, 1)] each: ground-truth predicates per edge
+};
+inline size_t eval_scratch_edge_rows(size_t E) { return E > 0 ? E : 1; }
+inline size_t eval_scratch_floats(size_t N, size_t E, size_t C, size_t R) { return 5 * N * C + 2 * eval_scratch_edge_rows(E) * R; }
+inline size_t eval_scratch_ints(size_t N, size_t E, size_t R) { return 2 * N + (4 * R + 2) * eval_scratch_edge_rows(E); }
+inline EvalScratch eval_scratch_carve(float* f, int32_t* i, size_t N, size_t E, size_t C, size_t R) {
+    const size_t Es = eval_scratch_edge_rows(E);
+    EvalScratch v;
+    v.obj3 = f;                v.obj2 = v.obj3 + N * C;   v.prob3 = v.obj2 + N * C;  v.prob2 = v.prob3 + N * C;
+    v.rel3 = v.prob2 + N * C;  v.rel2 = v.rel3 + Es * R;  v.sorted = v.rel2 + Es * R;
+    v.or3 = i;                 v.or2 = v.or3 + N;
+    v.rr3 = v.or2 + N;         v.rr2 = v.rr3 + Es * R;    v.tr3 = v.rr2 + Es * R;    v.tr2 = v.tr3 + Es * R;
+    v.cn3 = v.tr2 + Es * R;    v.cn2 = v.cn3 + Es;
+    return v;
+}
+
+}  // namespace vlsat
+
+#ifndef VLSAT_EVAL_SCRATCH_ONLY      // (tests/eval_scratch_check.cpp, a host-only program without the HIP headers, takes the layout above alone)
 #include <map>
 #include <string>
 #include <utility>
@@ -222,3 +255,5 @@ void give_event(vlsat_ctx* h, hipEvent_t e);
 void release_plan_resources(vlsat_ctx* h);       // frees pools (vlsat_destroy)
 
 }  // namespace vlsat
+
+#endif  // VLSAT_EVAL_SCRATCH_ONLY

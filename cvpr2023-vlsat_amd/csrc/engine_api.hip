@@ -208,8 +208,19 @@ int vlsat_k_pointnet(const float* pts, int32_t n_obj, int32_t n_points, const fl
     return launch_pointnet(pts, n_obj, n_points, 3, w1, b1, w2, b2, w3, b3, n_out, out, static_cast<hipStream_t>(stream));
 }
 
-int vlsat_k_flash_attn(const float* Q, const float* K, const float* V, float* O, int32_t ld, const int64_t* tok_ptr,
-                       int32_t n_scenes, int32_t n_heads, float scale, void* stream) {
+namespace {
+struct DevTable {                       // a host table copied to the device for the duration of one call
+    void* d = nullptr;
+    ~DevTable() { if (d) hipFree(d); }
+    int put(const void* host, size_t bytes) {
+        if (!bytes) return 0;
+        VLSAT_HIP_CHECK(hipMalloc(&d, bytes));
+        VLSAT_HIP_CHECK(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+// the FLASH_BQ-query tiles (scene start, scene tokens, first query, head) of a test call's attention, uploaded; *n = their count
+static int flash_tiles(const int64_t* tok_ptr, int n_scenes, int n_heads, DevTable& d, int* n) {
     if (!tok_ptr || n_scenes <= 0) return fail(VLSAT_EINVAL, "flash_attn: bad scene table");
     std::vector<int4> tiles;
     for (int s = 0; s < n_scenes; ++s) {
@@ -217,37 +228,35 @@ int vlsat_k_flash_attn(const float* Q, const float* K, const float* V, float* O,
         for (int hh = 0; hh < n_heads; ++hh)
             for (int64_t q0 = 0; q0 < T; q0 += FLASH_BQ) tiles.push_back(make_int4((int)tok_ptr[s], (int)T, (int)q0, hh));
     }
-    if (tiles.empty()) return 0;
-    int4* d = nullptr;
+    *n = (int)tiles.size();
+    return d.put(tiles.data(), tiles.size() * sizeof(int4));
+}
+}  // namespace
+
+int vlsat_k_flash_attn(const float* Q, const float* K, const float* V, float* O, int32_t ld, const int64_t* tok_ptr,
+                       int32_t n_scenes, int32_t n_heads, float scale, void* stream) {
+    DevTable d;
+    int n = 0;
+    RUN(flash_tiles(tok_ptr, n_scenes, n_heads, d, &n));
+    if (!n) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), tiles.size() * sizeof(int4)));
-    VLSAT_HIP_CHECK(hipMemcpy(d, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice));
-    int r = launch_flash_attn(Q, ld, K, V, ld, O, ld, d, (int)tiles.size(), scale * 1.4426950408889634f, st);
+    int r = launch_flash_attn(Q, ld, K, V, ld, O, ld, static_cast<const int4*>(d.d), n, scale * 1.4426950408889634f, st);
     hipStreamSynchronize(st);     // test entry point only: the tile table is freed right away
-    hipFree(d);
     return r;
 }
 
 int vlsat_k_flash_attn_bf16(const float* Q, const float* K, const float* V, float* O, int32_t ld, const int64_t* tok_ptr,
                             int32_t n_scenes, int32_t n_heads, float scale, int32_t terms, int32_t use_tr, void* stream) {
-    if (!tok_ptr || n_scenes <= 0) return fail(VLSAT_EINVAL, "flash_attn: bad scene table");
-    std::vector<int4> tiles;
-    for (int s = 0; s < n_scenes; ++s) {
-        const int64_t T = tok_ptr[s + 1] - tok_ptr[s];
-        for (int hh = 0; hh < n_heads; ++hh)
-            for (int64_t q0 = 0; q0 < T; q0 += FLASH_BQ) tiles.push_back(make_int4((int)tok_ptr[s], (int)T, (int)q0, hh));
-    }
-    if (tiles.empty()) return 0;
-    int4* d = nullptr;
+    DevTable d;
+    int n = 0;
+    RUN(flash_tiles(tok_ptr, n_scenes, n_heads, d, &n));
+    if (!n) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), tiles.size() * sizeof(int4)));
-    VLSAT_HIP_CHECK(hipMemcpy(d, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice));
     FlashSplit sp;                              // (no split keys; rows = the tensors' rows: lets the half-row variant take its LDS-direct staging)
     sp.rows = (int)tok_ptr[n_scenes];
-    int r = launch_flash_attn_bf16(Q, ld, K, V, ld, O, ld, d, (int)tiles.size(), scale * 1.4426950408889634f, terms, use_tr != 0,
+    int r = launch_flash_attn_bf16(Q, ld, K, V, ld, O, ld, static_cast<const int4*>(d.d), n, scale * 1.4426950408889634f, terms, use_tr != 0,
                                    use_tr == 2 ? 1 : use_tr == 3 ? 2 : 0, st, &sp);
     hipStreamSynchronize(st);     // test entry point only: the tile table is freed right away
-    hipFree(d);
     return r;
 }
 
@@ -426,25 +435,19 @@ static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_poi
     const int N = (int)p->N, E = (int)p->E, C = h->d.n_obj_class, R = h->d.n_rel_class;
     if (E > 0 && (!gt_rel || !edges_e2)) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: null edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    float* f = p->ev_f;
-    float *obj3 = f, *obj2 = f + (size_t)N * C, *prob3 = f + (size_t)2 * N * C, *prob2 = f + (size_t)3 * N * C;
-    float *rel3 = f + (size_t)4 * N * C, *rel2 = rel3 + (size_t)std::max(E, 1) * R;
-    float* sorted = rel2 + (size_t)std::max(E, 1) * R;          // [N, min(C, 101)]: the ranking's per-node sorted probabilities
-    int32_t* i = p->ev_i;
-    int32_t *or3 = i, *or2 = i + N, *rr3 = i + 2 * (size_t)N, *rr2 = rr3 + (size_t)std::max(E, 1) * R, *tr3 = rr2 + (size_t)std::max(E, 1) * R,
-            *tr2 = tr3 + (size_t)std::max(E, 1) * R, *cn3 = tr2 + (size_t)std::max(E, 1) * R, *cn2 = cn3 + std::max(E, 1);
-    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, obj3, obj2, rel3, rel2, stream));
+    const EvalScratch v = eval_scratch_carve(p->ev_f, p->ev_i, N, E, C, R);        // (sorted: [N, min(C, 101)] of it)
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, v.obj2, v.rel3, v.rel2, stream));
     for (int br = 0; br < 2; ++br) {
-        const float* lg = br ? obj2 : obj3;
-        float* pr = br ? prob2 : prob3;
+        const float* lg = br ? v.obj2 : v.obj3;
+        float* pr = br ? v.prob2 : v.prob3;
         RUN(launch_softmax_rows(lg, C, N, C, pr, 0, s));
-        RUN(launch_eval_ranks(lg, pr, br ? rel2 : rel3, gt_class, gt_rel, edges_e2, N, E, C, R, 11, 6, 101, 0.5f, br ? or2 : or3, br ? rr2 : rr3,
-                              br ? tr2 : tr3, br ? cn2 : cn3, sorted, s));
+        RUN(launch_eval_ranks(lg, pr, br ? v.rel2 : v.rel3, gt_class, gt_rel, edges_e2, N, E, C, R, 11, 6, 101, 0.5f, br ? v.or2 : v.or3,
+                              br ? v.rr2 : v.rr3, br ? v.tr2 : v.tr3, br ? v.cn2 : v.cn3, v.sorted, s));
     }
-    RUN(launch_eval_counts(or3, or2, rr3, rr2, tr3, tr2, cn3, gt_class, gt_rel, edges_e2, N, E, R, n_scenes,
+    RUN(launch_eval_counts(v.or3, v.or2, v.rr3, v.rr2, v.tr3, v.tr2, v.cn3, gt_class, gt_rel, edges_e2, N, E, R, n_scenes,
                            reinterpret_cast<unsigned long long*>(counts), s));
     if (split_counts)
-        RUN(launch_eval_triplet_split(tr3, tr2, cn3, gt_class, gt_rel, edges_e2, split_table, E, C, R,
+        RUN(launch_eval_triplet_split(v.tr3, v.tr2, v.cn3, gt_class, gt_rel, edges_e2, split_table, E, C, R,
                                       reinterpret_cast<unsigned long long*>(split_counts), s));
     VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the counting)
     return 0;
@@ -514,24 +517,22 @@ int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan p, const float* obj_poi
         return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null output");
     if (E > 0 && !edges_e2) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    float* f = p->ev_f;
-    float *obj3 = f, *obj2 = f + (size_t)N * C, *prob3 = f + (size_t)2 * N * C, *prob2 = f + (size_t)3 * N * C;
-    float *rel3 = f + (size_t)4 * N * C, *rel2 = rel3 + (size_t)std::max(E, 1) * R;
-    float* sorted = rel2 + (size_t)std::max(E, 1) * R;          // [N, min(C, 100)] of the [N, C] the plan holds
-    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, obj3, obj2, rel3, rel2, stream));
+    const EvalScratch v = eval_scratch_carve(p->ev_f, p->ev_i, N, E, C, R);
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, v.obj2, v.rel3, v.rel2, stream));
     for (int br = 0; br < 2; ++br) {
-        float* lg = br ? obj2 : obj3;
-        float* rl = br ? rel2 : rel3;
-        RUN(launch_softmax_rows(lg, C, N, C, br ? prob2 : prob3, 0, s));
+        float* lg = br ? v.obj2 : v.obj3;
+        float* pr = br ? v.prob2 : v.prob3;
+        float* rl = br ? v.rel2 : v.rel3;
+        RUN(launch_softmax_rows(lg, C, N, C, pr, 0, s));
         if (!h->d.multi_rel_outputs) RUN(launch_exp(rl, rl, (size_t)E * R, s));
         SceneGraphWs ws;
-        ws.sv = sorted;
+        ws.sv = v.sorted;                                       // ([N, min(C, 100)] of the [N, C] the plan holds)
         ws.si = reinterpret_cast<int32_t*>(lg);                 // (the logits are dead behind the softmax)
-        ws.ptr = p->ev_i;                                       // (S + 1 <= 2 max(N, 1) entries)
+        ws.ptr = v.or3;                                         // (the rank scratch from its start: S + 1 <= 2 max(N, 1) entries)
         ws.keys = reinterpret_cast<uint32_t*>(p->Hbig);         // (2 x E x <= 100 of the E x 1024 words)
         ws.packs = ws.keys + (size_t)std::max(E, 1) * 100;
-        RUN(launch_scene_graph_topk(br ? prob2 : prob3, rl, edges_e2, nullptr, p->d_scene_ptr, N, E, C, R, n_scenes, mode, top_k, topk_each,
-                                    ws, br ? triplets_2d : triplets_3d, br ? scores_2d : scores_3d, br ? n_valid_2d : n_valid_3d, s));
+        RUN(launch_scene_graph_topk(pr, rl, edges_e2, nullptr, p->d_scene_ptr, N, E, C, R, n_scenes, mode, top_k, topk_each, ws,
+                                    br ? triplets_2d : triplets_3d, br ? scores_2d : scores_3d, br ? n_valid_2d : n_valid_3d, s));
     }
     VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the selection)
     return 0;
@@ -604,20 +605,18 @@ int vlsat_forward_graph(vlsat_handle h, vlsat_plan p, const float* obj_points, c
         return fail(VLSAT_EINVAL, "vlsat_forward_graph: obj_2d_feats and the six 2D outputs go together (all, or none for 3D-only)");
     if (!thresholds || (E > 0 && !edges_e2)) return fail(VLSAT_EINVAL, "vlsat_forward_graph: null thresholds or edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t Es = (size_t)std::max(E, 1);
-    float* f = p->ev_f;
-    float *obj3 = f, *obj2 = f + (size_t)N * C, *prob3 = f + (size_t)2 * N * C, *prob2 = f + (size_t)3 * N * C;
-    float *rel3 = f + (size_t)4 * N * C, *rel2 = rel3 + Es * R;
-    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, obj3, do2d ? obj2 : nullptr, rel3, do2d ? rel2 : nullptr, stream));
-    GraphDecodeWs ws;
-    ws.ptr = p->ev_i;                                           // (S + 1 <= 2 max(N, 1) entries)
-    ws.cnt = p->ev_i + 2 * (size_t)N;
+    const size_t Es = eval_scratch_edge_rows(E);
+    const EvalScratch v = eval_scratch_carve(p->ev_f, p->ev_i, N, E, C, R);
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, do2d ? v.obj2 : nullptr, v.rel3, do2d ? v.rel2 : nullptr, stream));
+    GraphDecodeWs ws;                                           // in the rank scratch:
+    ws.ptr = v.or3;                                             // its node part (S + 1 <= 2 max(N, 1) entries)
+    ws.cnt = v.rr3;                                             // its edge part: E counts, E x R keys, E x R predicates
     ws.keys = reinterpret_cast<uint32_t*>(ws.cnt + Es);
     ws.preds = reinterpret_cast<uint8_t*>(ws.keys + Es * R);
     for (int br = 0; br < (do2d ? 2 : 1); ++br) {
-        float* pr = br ? prob2 : prob3;
-        float* rl = br ? rel2 : rel3;
-        RUN(launch_softmax_rows(br ? obj2 : obj3, C, N, C, pr, 0, s));
+        float* pr = br ? v.prob2 : v.prob3;
+        float* rl = br ? v.rel2 : v.rel3;
+        RUN(launch_softmax_rows(br ? v.obj2 : v.obj3, C, N, C, pr, 0, s));
         if (!h->d.multi_rel_outputs) RUN(launch_exp(rl, rl, (size_t)E * R, s));
         RUN(launch_graph_decode(pr, rl, edges_e2, nullptr, p->d_scene_ptr, thresholds, N, E, C, R, n_scenes, multi_label, score_mode,
                                 n_labels, max_rel, ws, br ? labels_2d : labels_3d, br ? label_probs_2d : label_probs_3d,
@@ -633,16 +632,6 @@ int vlsat_forward_graph(vlsat_handle h, vlsat_plan p, const float* obj_points, c
 // test entry points like vlsat_k_flash_attn -- small index tables are built on the host, uploaded, and the call
 // synchronises before it frees them.
 namespace {
-struct DevTable {                       // a host table copied to the device for the duration of one call
-    void* d = nullptr;
-    ~DevTable() { if (d) hipFree(d); }
-    int put(const void* host, size_t bytes) {
-        if (!bytes) return 0;
-        VLSAT_HIP_CHECK(hipMalloc(&d, bytes));
-        VLSAT_HIP_CHECK(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-};
 // node offsets of the scenes (int64 host, like batch_ids run lengths) -> int32 scene_ptr, int64 bias_ptr, largest scene
 static int scene_tables(const int64_t* node_ptr, int n_scenes, int n_heads, std::vector<int32_t>& sp, std::vector<int64_t>& bp, int* max_n) {
     if (!node_ptr || n_scenes <= 0) return fail(VLSAT_EINVAL, "bad scene table");

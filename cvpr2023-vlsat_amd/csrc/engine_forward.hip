@@ -208,209 +208,243 @@ int kv_project(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, con
     return gemm(h, s, G(xkv, ldx_of(h), w.wkv, D, kv, 2 * D, N, 2 * D, w.bkv));
 }
 
+// ---- the stages that exist on the 3D and on the 2D branch ----
+// Each stage below is ONE body over nb problems.  nb = 1: one branch on its lane.  nb = 2: the 3D / 2D twins of a one-scene plan as
+// launches of two problems each on the caller's stream (the paired schedule of round 6: gemm2, twin gate / aggregate launches).
+// Every GemmArgs / GateArgs of a stage is therefore written once, and the schedules launch the same kernels on the same operands by
+// construction: their outputs are bit-identical.
+int gemm_n(vlsat_ctx* h, hipStream_t s, const GemmArgs* a, int nb) { return nb == 2 ? gemm2(h, s, a[0], a[1]) : gemm(h, s, a[0]); }
+
+// one branch's operands of a GraphEdgeAttenNetwork block / a relation head / an object head
+struct GcnSide { const GcnW* w; float* x; float* e; int e_relu_pending; const Scratch* sc; };
+struct RelSide { const RelHeadW* w; const float* e; int relu_a; float* out; const Scratch* sc; };
+struct ObjSide { const float *x, *w, *b; float* out; const Scratch* sc; };
+// conv2 / conv3 of a relation encoder (+BN folded): rel_encoder_3d (br 0) or rel_encoder_2d (br 1)
+struct RelEncW { const float *w2, *b2, *w3, *b3; };
+RelEncW rel_enc_w(const vlsat_ctx* h, int br) {
+    return br ? RelEncW{h->re2_w2, h->re2_b2, h->re2_w3, h->re2_b3} : RelEncW{h->re3_w2, h->re3_b2, h->re3_w3, h->re3_b3};
+}
+
 // node side of a GraphEdgeAttenNetwork block: NP [N, 6D + A] = [P_i | P_j | Gq | value]
+GemmArgs node_project_args(const vlsat_ctx* h, const vlsat_plan_s* p, const GcnW& w, const float* x, const Scratch& sc) {
+    const int NPC = npc_of(h);
+    GemmArgs np = G(x, ldx_of(h), w.wnode, h->D, sc.NP, NPC, (int)p->N, NPC, w.bnode);
+    if (gather_f16_on(h)) np.c_f16_cols = 4 * h->D;             // [P_i | P_j] as fp16 half rows (what nn_edge.0 gathers per edge: half the bytes)
+    return np;
+}
 int gcn_node_project(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, const float* x, const Scratch& sc) {
-    const int N = (int)p->N, D = h->D, NPC = npc_of(h);
-    GemmArgs np = G(x, ldx_of(h), w.wnode, D, sc.NP, NPC, N, NPC, w.bnode);
-    if (gather_f16_on(h)) np.c_f16_cols = 4 * D;                 // [P_i | P_j] as fp16 half rows (what nn_edge.0 gathers per edge: half the bytes)
-    return gemm(h, s, np);
+    return gemm(h, s, node_project_args(h, p, w, x, sc));
+}
+// nn_edge.0 on the edge part `we` of its weight: Hbig = relu(e . we^T + P_i[src] + P_j[dst]); the node columns (with the bias) were made
+// on N rows by the node-side projection.  g_f16: they are fp16 half rows (never for triplet_projector_2d's first Linear, the other caller)
+GemmArgs nn_edge0_args(const vlsat_ctx* h, const vlsat_plan_s* p, const float* we, const float* e, int relu_a, const Scratch& sc, bool g_f16) {
+    const int D = h->D, NPC = npc_of(h), S = split_fmt(h);
+    GemmArgs e1 = G(e, D, we, D, sc.Hbig, 2 * D, (int)p->E, 2 * D, nullptr, ACT_RELU);
+    e1.relu_a = relu_a;
+    e1.a_split = S; e1.c_split = S;
+    e1.g0 = sc.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
+    e1.g_f16 = g_f16;
+    e1.g1 = sc.NP + (g_f16 ? D : 2 * D); e1.gi1 = p->d_dst; e1.ldg1 = NPC;       // (fp16 half rows: P_j starts at byte 2 * 2D of the row)
+    return e1;
 }
 
 // node_done: sc.NP has already been filled by gcn_node_project (on another lane; the caller has ordered this lane behind it)
-int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, float* x, float* e, int e_relu_pending,
-              int out_relu, const Scratch& sc, bool node_done = false) {
+int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side, int nb, int out_relu, bool node_done = false) {
     const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
-    if (!node_done) RUN(gcn_node_project(h, p, s, w, x, sc));
     const int S = split_fmt(h);
     const GateChoice gc = gate_of(h);
-    GemmArgs e1 = G(e, D, w.we1, D, sc.Hbig, 2 * D, E, 2 * D, nullptr, ACT_RELU);
-    e1.relu_a = e_relu_pending;
-    e1.a_split = S; e1.c_split = S;
-    e1.g0 = sc.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
-    e1.g_f16 = gather_f16_on(h);
-    e1.g1 = sc.NP + (e1.g_f16 ? D : 2 * D); e1.gi1 = p->d_dst; e1.ldg1 = NPC;       // (fp16 half rows: P_j starts at byte 2 * 2D of the row)
-    RUN(gemm(h, s, e1));
+    GemmArgs a[2];
+    GateArgs g[2] = {};
+    if (!node_done) {
+        for (int i = 0; i < nb; ++i) a[i] = node_project_args(h, p, *side[i].w, side[i].x, *side[i].sc);
+        RUN(gemm_n(h, s, a, nb));
+    }
+    for (int i = 0; i < nb; ++i) a[i] = nn_edge0_args(h, p, side[i].w->we1, side[i].e, side[i].e_relu_pending, *side[i].sc, gather_f16_on(h));
+    RUN(gemm_n(h, s, a, nb));
     if (h->d.use_gcn_edge) {              // proj_edge feeds only the gate MLP (reference network_MMG.py:98-102)
-        GemmArgs kp = G(e, D, w.wpe, D, sc.KP, D, E, D, w.bpe);
-        kp.relu_a = e_relu_pending;
-        kp.a_split = S;
-        kp.c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
-        RUN(gemm(h, s, kp));
-    }
-    bool fused_agg = false;
-    GemmArgs e2 = G(sc.Hbig, 2 * D, w.we2, 2 * D, e, D, E, D, w.be2);       // e <- nn_edge output (pre-activation)
-    e2.a_split = S; e2.c_split = S;
-    RUN(gemm(h, s, e2));
-    {
-        GateArgs g{};
-        g.kproj = sc.KP; g.node = sc.NP; g.ld_node = NPC; g.gq_off = 4 * D; g.v_off = 6 * D;    // Gq spans H * 2 d_k = 2 D columns
-        g.src = p->d_src; g.dst = p->d_dst; g.w0k = w.w0k; g.w3 = w.w3; g.b3 = w.b3; g.gated = sc.G;
-        g.prob = p->prob; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = gc.row_map0 ? h->gate_row_map : 1;
-        const double dk = D / h->H, dox = A / h->H;
-        // fused: no [E, A] tensor of gated messages, no aggregate launch; the start values go in first
-        fused_agg = gate_fuses_agg(h, gc, g);
-        if (fused_agg) {
-            Scope scope(h, s, PC_AGGREGATE, 0);
-            RUN(launch_agg_init(p->d_rowptr, N, A, x + D, LDX, s));
-            g.agg = x + D; g.ld_agg = LDX;
+        for (int i = 0; i < nb; ++i) {
+            const GcnSide& b = side[i];
+            a[i] = G(b.e, D, b.w->wpe, D, b.sc->KP, D, E, D, b.w->bpe);
+            a[i].relu_a = b.e_relu_pending;
+            a[i].a_split = S;
+            a[i].c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
         }
-        Scope scope(h, s, PC_GATE, (double)E * h->H * (2.0 * dk * 2 * dk + 2.0 * 2 * dk * dox));
-        RUN(gate_launch(h, gc, g, s));
+        RUN(gemm_n(h, s, a, nb));
     }
-    if (!fused_agg) {
-        Scope scope(h, s, PC_AGGREGATE, 0);
-        RUN(launch_aggregate(sc.G, A, p->d_rowptr, p->d_order, N, h->d.gcn_aggr, x, LDX, D, s));
+    for (int i = 0; i < nb; ++i) {
+        const GcnSide& b = side[i];
+        a[i] = G(b.sc->Hbig, 2 * D, b.w->we2, 2 * D, b.e, D, E, D, b.w->be2);       // e <- nn_edge output (pre-activation)
+        a[i].a_split = S; a[i].c_split = S;
     }
-    RUN(gemm(h, s, G(x, LDX, w.wp0, D + A, sc.T768, D + A, N, D + A, w.bp0, ACT_RELU)));
-    RUN(gemm(h, s, G(sc.T768, D + A, w.wp2, D + A, x, LDX, N, D, w.bp2, out_relu ? ACT_RELU : ACT_NONE)));
-    return 0;
-}
-
-int rel_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const RelHeadW& w, const float* e, int relu_a, float* out,
-             const Scratch& sc) {
-    const int E = (int)p->E, D = h->D, R = h->d.n_rel_class;
-    const int S = split_fmt(h);
-    GemmArgs a = G(e, D, w.w1, D, sc.R1, 512, E, 512, w.b1, ACT_RELU);
-    a.relu_a = relu_a;
-    a.a_split = S; a.c_split = S;
-    RUN(gemm(h, s, a));
-    GemmArgs b = G(sc.R1, 512, w.w2, 512, sc.R2, 256, E, 256, w.b2, ACT_RELU);
-    b.a_split = S; b.c_split = S;
-    RUN(gemm(h, s, b));
-    // multi_rel_outputs: sigmoid (PointNetRelClsMulti) or log_softmax over the R classes (PointNetRelCls)
-    GemmArgs c = G(sc.R2, 256, w.w3, 256, out, R, E, R, w.b3, h->d.multi_rel_outputs ? ACT_SIGMOID : ACT_NONE);
-    c.a_split = S;
-    RUN(gemm(h, s, c));
-    if (!h->d.multi_rel_outputs) {
-        Scope scope(h, s, PC_MISC, 0);
-        RUN(launch_softmax_rows(out, R, E, R, out, 1, s));
+    RUN(gemm_n(h, s, a, nb));
+    for (int i = 0; i < nb; ++i) {
+        const GcnSide& b = side[i];
+        g[i].kproj = b.sc->KP; g[i].node = b.sc->NP; g[i].ld_node = NPC; g[i].gq_off = 4 * D; g[i].v_off = 6 * D;    // Gq spans H * 2 d_k = 2 D columns
+        g[i].src = p->d_src; g[i].dst = p->d_dst; g[i].w0k = b.w->w0k; g[i].w3 = b.w->w3; g[i].b3 = b.w->b3; g[i].gated = b.sc->G;
+        g[i].prob = nb == 1 ? p->prob : nullptr;     // (the probability tap: single launches only)
+        g[i].n_edges = E; g[i].use_edge = h->d.use_gcn_edge; g[i].grid_cap = h->gate_grid; g[i].row_map = gc.row_map0 ? h->gate_row_map : 1;
     }
-    return 0;
-}
-
-int obj_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const float* x, const float* w, const float* b, float* out,
-             const Scratch& sc) {
-    const int N = (int)p->N, D = h->D, C = h->d.n_obj_class;
-    {
-        Scope scope(h, s, PC_MISC, 0);
-        RUN(launch_row_invnorm(x, ldx_of(h), N, D, std::exp(h->d.obj_logit_scale), sc.rs, s));
-    }
-    GemmArgs a = G(x, ldx_of(h), w, D, out, C, N, C, b);
-    a.rowscale = sc.rs;
-    RUN(gemm(h, s, a));
-    return 0;
-}
-
-// ---- the paired schedule of one-scene plans (round 6): gcn_3ds[l] and gcn_2ds[l], the two relation heads, the two object heads and
-// the two relation encoders as launches of TWO problems each (gemm2, twin gate / aggregate launches).  Stage by stage the same
-// kernels on the same operands as gcn_block / rel_head / obj_head above: bit-identical outputs.
-// Only with a gate kernel that takes a twin (gate_select) and no probability tap; the caller checks.
-int gcn_block_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w3, const GcnW& w2, float* x3, float* x2, float* e3, float* e2,
-                   int e3_relu_pending, int out_relu, const Scratch& sc3, const Scratch& sc2) {
-    const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
-    const int S = split_fmt(h);
-    const GateChoice gc = gate_of(h);
-    {
-        GemmArgs n3 = G(x3, LDX, w3.wnode, D, sc3.NP, NPC, N, NPC, w3.bnode), n2 = G(x2, LDX, w2.wnode, D, sc2.NP, NPC, N, NPC, w2.bnode);
-        if (gather_f16_on(h)) n3.c_f16_cols = n2.c_f16_cols = 4 * D;
-        RUN(gemm2(h, s, n3, n2));
-    }
-    auto e1_of = [&](const GcnW& w, float* e, int relu, const Scratch& sc) {
-        GemmArgs e1 = G(e, D, w.we1, D, sc.Hbig, 2 * D, E, 2 * D, nullptr, ACT_RELU);
-        e1.relu_a = relu;
-        e1.a_split = S; e1.c_split = S;
-        e1.g0 = sc.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
-        e1.g_f16 = gather_f16_on(h);
-        e1.g1 = sc.NP + (e1.g_f16 ? D : 2 * D); e1.gi1 = p->d_dst; e1.ldg1 = NPC;
-        return e1;
-    };
-    RUN(gemm2(h, s, e1_of(w3, e3, e3_relu_pending, sc3), e1_of(w2, e2, 0, sc2)));
-    if (h->d.use_gcn_edge) {
-        auto kp_of = [&](const GcnW& w, float* e, int relu, const Scratch& sc) {
-            GemmArgs kp = G(e, D, w.wpe, D, sc.KP, D, E, D, w.bpe);
-            kp.relu_a = relu;
-            kp.a_split = S;
-            kp.c_split = gc.bits16() ? S : 0;
-            return kp;
-        };
-        RUN(gemm2(h, s, kp_of(w3, e3, e3_relu_pending, sc3), kp_of(w2, e2, 0, sc2)));
-    }
-    auto e2_of = [&](const GcnW& w, float* e, const Scratch& sc) {
-        GemmArgs g = G(sc.Hbig, 2 * D, w.we2, 2 * D, e, D, E, D, w.be2);
-        g.a_split = S; g.c_split = S;
-        return g;
-    };
-    RUN(gemm2(h, s, e2_of(w3, e3, sc3), e2_of(w2, e2, sc2)));
-    auto gate_args = [&](const GcnW& w, const Scratch& sc) {
-        GateArgs g{};
-        g.kproj = sc.KP; g.node = sc.NP; g.ld_node = NPC; g.gq_off = 4 * D; g.v_off = 6 * D;
-        g.src = p->d_src; g.dst = p->d_dst; g.w0k = w.w0k; g.w3 = w.w3; g.b3 = w.b3; g.gated = sc.G;
-        g.prob = nullptr; g.n_edges = E; g.use_edge = h->d.use_gcn_edge; g.grid_cap = h->gate_grid; g.row_map = gc.row_map0 ? h->gate_row_map : 1;
-        return g;
-    };
-    GateArgs g3 = gate_args(w3, sc3), g2 = gate_args(w2, sc2);
-    const double dk = D / h->H, dox = A / h->H;
-    const bool fused_agg = gate_fuses_agg(h, gc, g3);
+    // fused: no [E, A] tensor of gated messages, no aggregate launch; the start values go in first
+    const bool fused_agg = gate_fuses_agg(h, gc, g[0]);
     if (fused_agg) {
         Scope scope(h, s, PC_AGGREGATE, 0);
-        RUN(launch_agg_init(p->d_rowptr, N, A, x3 + D, LDX, s, x2 + D));
-        g3.agg = x3 + D; g3.ld_agg = LDX;
-        g2.agg = x2 + D; g2.ld_agg = LDX;
+        RUN(launch_agg_init(p->d_rowptr, N, A, side[0].x + D, LDX, s, nb == 2 ? side[1].x + D : nullptr));
+        for (int i = 0; i < nb; ++i) { g[i].agg = side[i].x + D; g[i].ld_agg = LDX; }
     }
     {
-        Scope scope(h, s, PC_GATE, 2.0 * (double)E * h->H * (2.0 * dk * 2 * dk + 2.0 * 2 * dk * dox));
-        RUN(gate_launch(h, gc, g3, s, &g2));
+        const double dk = D / h->H, dox = A / h->H;
+        Scope scope(h, s, PC_GATE, nb * ((double)E * h->H * (2.0 * dk * 2 * dk + 2.0 * 2 * dk * dox)));
+        RUN(gate_launch(h, gc, g[0], s, nb == 2 ? &g[1] : nullptr));
     }
     if (!fused_agg) {
         Scope scope(h, s, PC_AGGREGATE, 0);
-        RUN(launch_aggregate(sc3.G, A, p->d_rowptr, p->d_order, N, h->d.gcn_aggr, x3, LDX, D, s, sc2.G, x2));
+        RUN(launch_aggregate(side[0].sc->G, A, p->d_rowptr, p->d_order, N, h->d.gcn_aggr, side[0].x, LDX, D, s, nb == 2 ? side[1].sc->G : nullptr,
+                             nb == 2 ? side[1].x : nullptr));
     }
-    RUN(gemm2(h, s, G(x3, LDX, w3.wp0, D + A, sc3.T768, D + A, N, D + A, w3.bp0, ACT_RELU), G(x2, LDX, w2.wp0, D + A, sc2.T768, D + A, N, D + A, w2.bp0, ACT_RELU)));
-    RUN(gemm2(h, s, G(sc3.T768, D + A, w3.wp2, D + A, x3, LDX, N, D, w3.bp2, out_relu ? ACT_RELU : ACT_NONE),
-              G(sc2.T768, D + A, w2.wp2, D + A, x2, LDX, N, D, w2.bp2, out_relu ? ACT_RELU : ACT_NONE)));
-    return 0;
+    for (int i = 0; i < nb; ++i) a[i] = G(side[i].x, LDX, side[i].w->wp0, D + A, side[i].sc->T768, D + A, N, D + A, side[i].w->bp0, ACT_RELU);
+    RUN(gemm_n(h, s, a, nb));
+    for (int i = 0; i < nb; ++i) a[i] = G(side[i].sc->T768, D + A, side[i].w->wp2, D + A, side[i].x, LDX, N, D, side[i].w->bp2, out_relu ? ACT_RELU : ACT_NONE);
+    return gemm_n(h, s, a, nb);
 }
 
-int rel_head_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const float* e3, int relu3, float* out3, const float* e2, float* out2,
-                  const Scratch& sc3, const Scratch& sc2) {
+int rel_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const RelSide* side, int nb) {
     const int E = (int)p->E, D = h->D, R = h->d.n_rel_class;
     const int S = split_fmt(h);
-    auto fc1 = [&](const RelHeadW& w, const float* e, int relu, const Scratch& sc) {
-        GemmArgs a = G(e, D, w.w1, D, sc.R1, 512, E, 512, w.b1, ACT_RELU);
-        a.relu_a = relu; a.a_split = S; a.c_split = S;
-        return a;
-    };
-    auto fc2 = [&](const RelHeadW& w, const Scratch& sc) {
-        GemmArgs b = G(sc.R1, 512, w.w2, 512, sc.R2, 256, E, 256, w.b2, ACT_RELU);
-        b.a_split = S; b.c_split = S;
-        return b;
-    };
-    auto fc3 = [&](const RelHeadW& w, const Scratch& sc, float* out) {
-        GemmArgs c = G(sc.R2, 256, w.w3, 256, out, R, E, R, w.b3, h->d.multi_rel_outputs ? ACT_SIGMOID : ACT_NONE);
-        c.a_split = S;
-        return c;
-    };
-    RUN(gemm2(h, s, fc1(h->rel3, e3, relu3, sc3), fc1(h->rel2, e2, 0, sc2)));
-    RUN(gemm2(h, s, fc2(h->rel3, sc3), fc2(h->rel2, sc2)));
-    RUN(gemm2(h, s, fc3(h->rel3, sc3, out3), fc3(h->rel2, sc2, out2)));
+    GemmArgs a[2];
+    for (int i = 0; i < nb; ++i) {
+        const RelSide& b = side[i];
+        a[i] = G(b.e, D, b.w->w1, D, b.sc->R1, 512, E, 512, b.w->b1, ACT_RELU);
+        a[i].relu_a = b.relu_a;
+        a[i].a_split = S; a[i].c_split = S;
+    }
+    RUN(gemm_n(h, s, a, nb));
+    for (int i = 0; i < nb; ++i) {
+        const RelSide& b = side[i];
+        a[i] = G(b.sc->R1, 512, b.w->w2, 512, b.sc->R2, 256, E, 256, b.w->b2, ACT_RELU);
+        a[i].a_split = S; a[i].c_split = S;
+    }
+    RUN(gemm_n(h, s, a, nb));
+    // multi_rel_outputs: sigmoid (PointNetRelClsMulti) or log_softmax over the R classes (PointNetRelCls)
+    for (int i = 0; i < nb; ++i) {
+        const RelSide& b = side[i];
+        a[i] = G(b.sc->R2, 256, b.w->w3, 256, b.out, R, E, R, b.w->b3, h->d.multi_rel_outputs ? ACT_SIGMOID : ACT_NONE);
+        a[i].a_split = S;
+    }
+    RUN(gemm_n(h, s, a, nb));
     if (!h->d.multi_rel_outputs) {
         Scope scope(h, s, PC_MISC, 0);
-        RUN(launch_softmax_rows(out3, R, E, R, out3, 1, s));
-        RUN(launch_softmax_rows(out2, R, E, R, out2, 1, s));
+        for (int i = 0; i < nb; ++i) RUN(launch_softmax_rows(side[i].out, R, E, R, side[i].out, 1, s));
     }
     return 0;
 }
 
-int obj_head_pair(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, float* out3, float* out2, const Scratch& sc3, const Scratch& sc2) {
+int obj_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const ObjSide* side, int nb) {
     const int N = (int)p->N, D = h->D, C = h->d.n_obj_class;
     {
         Scope scope(h, s, PC_MISC, 0);
-        RUN(launch_row_invnorm(p->X3, ldx_of(h), N, D, std::exp(h->d.obj_logit_scale), sc3.rs, s, p->X2, sc2.rs));
+        RUN(launch_row_invnorm(side[0].x, ldx_of(h), N, D, std::exp(h->d.obj_logit_scale), side[0].sc->rs, s, nb == 2 ? side[1].x : nullptr,
+                               nb == 2 ? side[1].sc->rs : nullptr));
     }
-    GemmArgs a = G(p->X3, ldx_of(h), h->obj3_w, D, out3, C, N, C, h->obj3_b), b = G(p->X2, ldx_of(h), h->obj2_w, D, out2, C, N, C, h->obj2_b);
-    a.rowscale = sc3.rs;
-    b.rowscale = sc2.rs;
-    return gemm2(h, s, a, b);
+    GemmArgs a[2];
+    for (int i = 0; i < nb; ++i) {
+        a[i] = G(side[i].x, ldx_of(h), side[i].w, D, side[i].out, C, N, C, side[i].b);
+        a[i].rowscale = side[i].sc->rs;
+    }
+    return gemm_n(h, s, a, nb);
+}
+
+// conv2 / conv3 of the relation encoders br0 .. br0 + nb - 1 on the edge embedding H1 [E, 64 | 64] -> E3 / E2
+int rel_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, int br0, int nb, const Scratch* const* sc) {
+    const int E = (int)p->E, D = h->D, S = split_fmt(h);
+    GemmArgs a[2];
+    for (int i = 0, br = br0; i < nb; ++i, ++br) {
+        a[i] = G(p->H1 + 64 * br, 128, rel_enc_w(h, br).w2, 64, sc[br]->H2, 128, E, 128, rel_enc_w(h, br).b2, ACT_RELU);
+        a[i].c_split = S;
+    }
+    RUN(gemm_n(h, s, a, nb));
+    for (int i = 0, br = br0; i < nb; ++i, ++br) {
+        a[i] = G(sc[br]->H2, 128, rel_enc_w(h, br).w3, 128, br ? p->E2 : p->E3, D, E, D, rel_enc_w(h, br).b3, ACT_RELU);
+        a[i].a_split = S; a[i].c_split = S;
+    }
+    return gemm_n(h, s, a, nb);
+}
+
+// ---- edge cross-attention (reference network_MMG.py:231): q = 2D edges, k = v = 3D edges (pre-activation), E2 <- LayerNorm(E2 + out) ----
+// Four steps -- query projection, key | value projection, attention, out-projection + residual + LayerNorm -- each on the lane the
+// caller gives it: the schedule (which lane, which events between the steps) is forward_body's.
+// The formats of a handle's edge attention, the same for every layer of a forward:
+struct EdgeAttnFmt {
+    int S;           // format of the chain tensors E3 / E2 (split_fmt)
+    int PA;          // operand precision of this block (mode 4: single rounding here, split-bf16 everywhere else -- the 3D outputs, which
+                     // never see this block, keep the split-bf16 accuracy; profiles/r05_probes/precision_mix_study.txt)
+    int dh;          // head dim
+    bool fa16;       // the bf16 attention kernel is built for this head dim and mode
+    int SA;          // format of Q / K|V / O: that of the chain with the bf16 attention kernel, else fp32
+    bool ln_resid;   // the residual is added by the LayerNorm kernel, not by the out-projection
+    bool o16;        // the out-projection writes fp16 half rows for the LayerNorm
+    float qscale;    // 1/sqrt(d_k) * log2(e): the attention works in exp2
+};
+EdgeAttnFmt edge_attn_fmt(const vlsat_ctx* h) {
+    EdgeAttnFmt f;
+    const int S = f.S = split_fmt(h), PA = f.PA = h->prec_attn, dh = f.dh = h->D / h->H;
+    f.fa16 = PA && h->flash_bf16 && (dh == 64 || (h->flash_heads_bf16 && S && flash_attn_bf16_supports(dh, PA == 3 ? 3 : 1, h->flash_tr, S)));
+    // (mode 4: the chain tensors are split pairs, but Q / K|V / O feed a single-rounded attention only -- they travel as half rows,
+    //  which puts the attention on its LDS-direct kernel and the out-projection on the 8-phase one)
+    f.SA = f.fa16 ? ((PA == 1 && S == 1 && h->half_fmt && dh == 64) ? 2 : S) : 0;
+    // Split-pair mode: the residual is added by the LayerNorm kernel (as an accumulator init it made the out-projection 60 % slower
+    // there -- 397 vs 243 us at the bench size -- against +1 KB per row in the LayerNorm).  Half rows: the same (the 8-phase GEMM has no
+    // fast accumulator-init path).
+    f.ln_resid = ((S == 1 || (S == 2 && !h->gemm_no_p8)) && h->ln_resid) || (S == 2 && h->half_f16);      // (mode 5: always -- no GEMM reads an fp16 residual)
+    // single-rounded attention (half-row O): the out-projection's result has one reader, the LayerNorm -- fp16 half rows instead of fp32 (2^-12 in
+    // front of a normalisation whose output is rounded to bf16 / split pairs: not visible in the mode's error; half the bytes both ways)
+    f.o16 = f.ln_resid && f.SA == 2 && h->outproj_f16 != 0 && h->D % 256 == 0;
+    f.qscale = (1.f / std::sqrt((float)dh)) * 1.4426950408889634f;
+    return f;
+}
+int edge_attn_q(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f) {
+    const int E = (int)p->E, D = h->D;
+    GemmArgs gq = G(p->E2, D, w.wq, D, p->Qe, D, E, D, w.bq);
+    gq.a_split = f.S; gq.c_split = f.SA;
+    if (f.SA) gq.c_scale = f.qscale;                                 // the split-format attention takes Q pre-scaled
+    return gemm(h, s, gq, f.PA);
+}
+int edge_attn_kv(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f, float* kve) {
+    const int E = (int)p->E, D = h->D;
+    GemmArgs gkv = G(p->E3, D, w.wkv, D, kve, 2 * D, E, 2 * D, w.bkv);
+    gkv.a_split = f.S; gkv.c_split = f.SA;
+    return gemm(h, s, gkv, f.PA);
+}
+int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAttnFmt& f, const float* kve) {
+    const int E = (int)p->E, D = h->D, dh = f.dh, SA = f.SA;
+    Scope sc(h, s, PC_FLASH, p->flash_flops);
+    FlashSplit sp;
+    sp.ablate = h->flash_ablate;
+    sp.parts = p->fa_parts; sp.krange = p->d_krange; sp.o_part = p->fa_opart; sp.m_part = p->fa_m;
+    sp.l_part = p->fa_l; sp.part_stride = (size_t)E * D; sp.rows = E; sp.heads = h->H;
+    if (dh != 32 && dh != 64 && dh != 128)   // any other head dim: VALU attention over the scenes' edge ranges (no bias)
+        return launch_node_attn(p->Qe, D, kve, 2 * D, kve + D, 2 * D, p->Oe, D, nullptr, p->d_edge_ptr32, nullptr, h->edge_scope == 1 ? 1 : p->S,
+                                h->edge_scope == 1 ? E : p->max_e, h->H, dh, 1.f / std::sqrt((float)dh), s, h->node_attn_split);
+    if (!f.fa16) return launch_flash_attn(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, s, &sp, dh);   // (head dims 32 / 128: NUM_HEADS 16 / 4)
+    const bool big = SA == 2 && dh == 64 && p->n_tiles_big && h->flash_tr && h->flash_dma == 1 && h->flash_bq_big;
+    if (big) sp.bq = FLASH_BQ_BIG;
+    sp.qg = h->flash_qg;
+    return launch_flash_attn_bf16(p->Qe, D, kve, kve + (SA == 2 ? D / 2 : D), 2 * D, p->Oe, D, big ? p->d_tiles_big : p->d_tiles, big ? p->n_tiles_big : p->n_tiles,
+                                  f.qscale, f.PA == 3 ? 3 : 1, h->flash_tr ? (h->flash_dma >= 3 ? h->flash_dma : h->flash_dma ? 1 : 2) : 0,
+                                  (SA == 2 && h->half_f16) ? 3 : SA, s, &sp, h->flash_pv_terms, dh);    // (half rows: V starts at byte 2 D)
+}
+// out-projection + residual, then LayerNorm (+ inter-layer ReLU).  Split format: the GEMM reads O and the residual as hi/lo pairs and
+// writes plain fp32 into the (now dead) Q buffer; the LayerNorm packs E2 again.
+int edge_attn_out(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f, int relu) {
+    const int E = (int)p->E, D = h->D, S = f.S;
+    float* pre_ln = S ? p->Qe : p->E2;
+    GemmArgs o = G(p->Oe, D, w.wo, D, pre_ln, D, E, D, w.bo);
+    if (!f.ln_resid) { o.resid = p->E2; o.ldr = D; o.r_split = S; }
+    o.a_split = f.SA;
+    if (f.o16) o.c_f16_cols = D;
+    RUN(gemm(h, s, o, f.PA));
+    Scope sc(h, s, PC_LAYERNORM, 0);
+    const int SL = (S == 2 && h->half_f16) ? 4 : S;          // (mode 5: the half rows the LayerNorm reads and writes hold fp16)
+    return launch_layernorm_to(pre_ln, D, p->E2, D, E, D, w.lng, w.lnb, relu, SL, s, f.ln_resid ? p->E2 : nullptr, D, SL, f.o16 ? 1 : 0);
 }
 
 int stn_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const StnW& w, const float* h1, int ldh, size_t R, int P,
@@ -525,7 +559,7 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     // of the chip idle, and a loop with several scenes in flight is bound by the SUM of their durations.  The 3D / 2D twin stages
     // (relation encoders, gcn_3ds | gcn_2ds, both head pairs) have the same shapes, so each pair becomes ONE launch of two problems
     // on the caller's stream; the second lane keeps the only chain without a twin, the edge cross-attention of layer l, which runs
-    // under the node attentions of layer l + 1.  Same kernels on the same operands as the other schedules: bit-identical outputs.
+    // under the node attentions of layer l + 1.  The stages are the same bodies with nb = 2 (see gemm_n): bit-identical outputs.
     const bool pair = dual && h->pair_twins && p->E > 0 && p->E <= h->pair_max_edges && !h->d.feature_transform && gate_of(h).twin &&
                       !p->prob && h->sched != 1;
     // (default: exact for the bf16 modes on plans that fill the chip by themselves.  One-scene plans keep two streams: with K replicas
@@ -576,7 +610,6 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     auto fork = [&]() { return (exact || pair) ? 0 : order(s, t); };     // (round-4 schedule only)
     auto join = [&]() { return (exact || pair) ? 0 : order(t, s); };
     const Scratch sc3 = scratch_of(p, 0), sc2 = scratch_of(p, dual ? 1 : 0);
-    const int S = split_fmt(h);            // edge tensors in the split-pair format (bf16 modes)
     if (exact) RUN(order(s, u));           // u starts where the forward starts (behind whatever the caller enqueued before it)
     if (pair) RUN(order(s, t));            // (paired schedule: so does t -- the adapter, then the edge cross-attention of every layer)
 
@@ -624,36 +657,25 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
         Scope sc(h, s, PC_MISC, 0);
         RUN(launch_edge_embed(desc, p->d_src, p->d_dst, E, h->re_w1cat, h->re_b1cat, p->H1, s));
     }
-    hipEvent_t h1_ready = nullptr;
-    if (!pair) {
+    const Scratch* const scs[2] = {&sc3, &sc2};
+    if (pair) {                                                             // conv2 / conv3 of both relation encoders, two problems per launch
+        RUN(rel_encoder(h, p, s, 0, 2, scs));
+    } else {
+        hipEvent_t h1_ready;
         RUN(after(s, &h1_ready));
         RUN(wait(t, h1_ready));                                             // t: 2D relation encoder (old schedule: + adapter)
-    }
-    if (pair) {                                                             // conv2 / conv3 of both relation encoders, two problems per launch
-        GemmArgs c2a = G(p->H1, 128, h->re3_w2, 64, sc3.H2, 128, E, 128, h->re3_b2, ACT_RELU), c2b = G(p->H1 + 64, 128, h->re2_w2, 64, sc2.H2, 128, E, 128, h->re2_b2, ACT_RELU);
-        c2a.c_split = S; c2b.c_split = S;
-        RUN(gemm2(h, s, c2a, c2b));
-        GemmArgs c3a = G(sc3.H2, 128, h->re3_w3, 128, p->E3, D, E, D, h->re3_b3, ACT_RELU), c3b = G(sc2.H2, 128, h->re2_w3, 128, p->E2, D, E, D, h->re2_b3, ACT_RELU);
-        c3a.a_split = S; c3a.c_split = S; c3b.a_split = S; c3b.c_split = S;
-        RUN(gemm2(h, s, c3a, c3b));
-    } else if (!ft) {
-        for (int br = 0; br < (do2d ? 2 : 1); ++br) {          // conv2 / conv3 of rel_encoder_3d (on s) and rel_encoder_2d (on t)
-            const Scratch& sc = br ? sc2 : sc3;
-            GemmArgs c2 = G(p->H1 + 64 * br, 128, br ? h->re2_w2 : h->re3_w2, 64, sc.H2, 128, E, 128, br ? h->re2_b2 : h->re3_b2, ACT_RELU);
-            c2.c_split = S;
-            RUN(gemm(h, br ? t : s, c2));
-            GemmArgs c3 = G(sc.H2, 128, br ? h->re2_w3 : h->re3_w3, 128, br ? p->E2 : p->E3, D, E, D, br ? h->re2_b3 : h->re3_b3, ACT_RELU);
-            c3.a_split = S; c3.c_split = S;
-            RUN(gemm(h, br ? t : s, c3));
+        if (!ft) {                                                          // rel_encoder_3d on s, rel_encoder_2d on t
+            RUN(rel_encoder(h, p, s, 0, 1, scs));
+            if (do2d) RUN(rel_encoder(h, p, t, 1, 1, scs));
+        } else if (E > 0) {   // P = 1: one row per edge; both encoders share the scratch, so they run one after the other on s
+            for (int br = 0; br < (do2d ? 2 : 1); ++br) {
+                const RelEncW w = rel_enc_w(h, br);
+                float* out = nullptr;
+                RUN(stn_encoder(h, p, s, br ? h->stn_re2 : h->stn_re3, p->H1 + 64 * br, 128, (size_t)E, 1, w.w2, w.b2, w.w3, w.b3, D, &out));
+                RUN(launch_copy_rows(br ? p->E2 : p->E3, (size_t)D, out, (size_t)D, D, (size_t)E, s));
+            }
+            if (dual) { hipEvent_t e; RUN(after(s, &e)); RUN(wait(t, e)); }    // (E2 was written on s)
         }
-    } else if (E > 0) {   // P = 1: one row per edge; both encoders share the scratch, so they run one after the other on s
-        for (int br = 0; br < (do2d ? 2 : 1); ++br) {
-            float* out = nullptr;
-            RUN(stn_encoder(h, p, s, br ? h->stn_re2 : h->stn_re3, p->H1 + 64 * br, 128, (size_t)E, 1, br ? h->re2_w2 : h->re3_w2,
-                            br ? h->re2_b2 : h->re3_b2, br ? h->re2_w3 : h->re3_w3, br ? h->re2_b3 : h->re3_b3, D, &out));
-            RUN(launch_copy_rows(br ? p->E2 : p->E3, (size_t)D, out, (size_t)D, D, (size_t)E, s));
-        }
-        if (dual) { hipEvent_t e; RUN(after(s, &e)); RUN(wait(t, e)); }    // (E2 was written on s)
     }
     STAGE(3);
     // a-6 adapter -> X2[:, 0:512]   (lane u: it depends on the inputs only -- u was forked where the forward began)
@@ -676,6 +698,7 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     int e3_pending_relu = 0;
     hipEvent_t flash_done[2] = {nullptr, nullptr};            // the edge attention that read KVe slot i has completed
     hipEvent_t edge_done = nullptr;                           // (paired schedule) the edge cross-attention of the previous layer has written E2 and is done with E3
+    const EdgeAttnFmt ef = edge_attn_fmt(h);
     for (int l = 0; l < L; ++l) {
         const int inter = (l < L - 1 || L == 1) ? 1 : 0;     // reference network_MMG.py:236
         const int base = 10 + 10 * l;
@@ -702,96 +725,44 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
             }
         }
         STAGE(base + 1);
-        if (pair) {                                           // :224-225 as launches of two problems each, behind the previous layer's edge attention
+        GcnSide gs[2] = {{&h->gcn3[l], p->X3, p->E3, e3_pending_relu, &sc3}, {}};      // :224 gcn_3ds[l], :225 gcn_2ds[l]
+        if (do2d) gs[1] = {&h->gcn2[l], p->X2, p->E2, 0, &sc2};
+        if (pair) {                                           // as launches of two problems each, behind the previous layer's edge attention
             RUN(wait(s, edge_done));
-            RUN(gcn_block_pair(h, p, s, h->gcn3[l], h->gcn2[l], p->X3, p->X2, p->E3, p->E2, e3_pending_relu, inter, sc3, sc2));
+            RUN(gcn_block(h, p, s, gs, 2, inter));
             RUN(order(s, t));                                 // t: this layer's edge cross-attention; s goes on with the next layer's node attentions
         } else {
-        RUN(fork());                                          // t: gcn_2ds + query projection; s: gcn_3ds + key/value projection
-        RUN(gcn_block(h, p, s, h->gcn3[l], p->X3, p->E3, e3_pending_relu, inter, sc3)); // :224
-        STAGE(base + 2);
-        if (do2d) {
-            RUN(wait(t, np2_ready));
-            RUN(gcn_block(h, p, t, h->gcn2[l], p->X2, p->E2, 0, inter, sc2, exact));      // :225
-            if (exact) RUN(after(t, &x2_ready));
-        }
+            RUN(fork());                                      // t: gcn_2ds + query projection; s: gcn_3ds + key/value projection
+            RUN(gcn_block(h, p, s, &gs[0], 1, inter));
+            STAGE(base + 2);
+            if (do2d) {
+                RUN(wait(t, np2_ready));
+                RUN(gcn_block(h, p, t, &gs[1], 1, inter, exact));
+                if (exact) RUN(after(t, &x2_ready));
+            }
         }
         STAGE(base + 3);
         if (do2d) {   // :231 edge cross-attention: q = 2D edges, k = v = 3D edges (pre-activation)
             const AttnW& w = h->cross_rel[l];
-            const float sc2e = (1.f / std::sqrt((float)(D / h->H))) * 1.4426950408889634f;   // 1/sqrt(d_k) * log2(e): the attention works in exp2
-            const int dh = D / h->H;
-            // format of Q / K|V / O: that of the chain when the bf16 attention kernel is built for this head dim and mode, else fp32
-            // PA: operand precision of this block (mode 4: single rounding here, split-bf16 everywhere else -- the 3D outputs, which
-            // never see this block, keep the split-bf16 accuracy; profiles/r05_probes/precision_mix_study.txt)
-            const int PA = h->prec_attn;
-            const bool fa16 = PA && h->flash_bf16 && (dh == 64 || (h->flash_heads_bf16 && S && flash_attn_bf16_supports(dh, PA == 3 ? 3 : 1, h->flash_tr, S)));
-            // (mode 4: the chain tensors are split pairs, but Q / K|V / O feed a single-rounded attention only -- they travel as half rows,
-            //  which puts the attention on its LDS-direct kernel and the out-projection on the 8-phase one)
-            const int SA = fa16 ? ((PA == 1 && S == 1 && h->half_fmt && dh == 64) ? 2 : S) : 0;
             // K | V of layer l go to slot l % 2 on the dependency-exact schedule (the 3D lane may be a layer ahead of the attention
             // that reads them: it waits for the reader of the slot's previous content only)
             const int slot = exact ? (l & 1) : 0;
             float* kve = slot ? p->KVe2 : p->KVe;
             hipStream_t fs = (exact || pair) ? t : s;         // lane of the attention itself
             hipStream_t kvs = pair ? t : s;                   // ... and of its key | value projection (paired schedule: the whole chain on t)
-            GemmArgs gq = G(p->E2, D, w.wq, D, p->Qe, D, E, D, w.bq);
-            gq.a_split = S; gq.c_split = SA;
-            if (SA) gq.c_scale = sc2e;                                 // the split-format attention takes Q pre-scaled
-            RUN(gemm(h, t, gq, PA));
+            RUN(edge_attn_q(h, p, t, w, ef));
             if (!pair) RUN(wait(s, flash_done[slot]));
-            GemmArgs gkv = G(p->E3, D, w.wkv, D, kve, 2 * D, E, 2 * D, w.bkv);
-            gkv.a_split = S; gkv.c_split = SA;
-            RUN(gemm(h, kvs, gkv, PA));
-            if (pair) {
-            } else if (exact) {
+            RUN(edge_attn_kv(h, p, kvs, w, ef, kve));
+            if (exact) {
                 hipEvent_t kve_ready;
                 RUN(after(s, &kve_ready));
                 RUN(wait(t, kve_ready));
             } else {
                 RUN(join());
             }
-            {
-                Scope sc(h, fs, PC_FLASH, p->flash_flops);
-                FlashSplit sp;
-                sp.ablate = h->flash_ablate;
-                sp.parts = p->fa_parts; sp.krange = p->d_krange; sp.o_part = p->fa_opart; sp.m_part = p->fa_m;
-                sp.l_part = p->fa_l; sp.part_stride = (size_t)E * D; sp.rows = E; sp.heads = h->H;
-                if (dh != 32 && dh != 64 && dh != 128)   // any other head dim: VALU attention over the scenes' edge ranges (no bias)
-                    RUN(launch_node_attn(p->Qe, D, kve, 2 * D, kve + D, 2 * D, p->Oe, D, nullptr, p->d_edge_ptr32, nullptr,
-                                         h->edge_scope == 1 ? 1 : p->S, h->edge_scope == 1 ? E : p->max_e, h->H, D / h->H,
-                                         1.f / std::sqrt((float)(D / h->H)), fs, h->node_attn_split));
-                else if (fa16) {
-                    const bool big = SA == 2 && dh == 64 && p->n_tiles_big && h->flash_tr && h->flash_dma == 1 && h->flash_bq_big;
-                    if (big) sp.bq = FLASH_BQ_BIG;
-                    sp.qg = h->flash_qg;
-                    RUN(launch_flash_attn_bf16(p->Qe, D, kve, kve + (SA == 2 ? D / 2 : D), 2 * D, p->Oe, D, big ? p->d_tiles_big : p->d_tiles, big ? p->n_tiles_big : p->n_tiles,
-                                               sc2e, PA == 3 ? 3 : 1, h->flash_tr ? (h->flash_dma >= 3 ? h->flash_dma : h->flash_dma ? 1 : 2) : 0, (SA == 2 && h->half_f16) ? 3 : SA, fs, &sp, h->flash_pv_terms, dh));    // (half rows: V starts at byte 2 D)
-                }
-                else
-                    RUN(launch_flash_attn(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, sc2e, fs, &sp, dh));   // (head dims 32 / 128: NUM_HEADS 16 / 4)
-            }
+            RUN(edge_attn_attend(h, p, fs, ef, kve));
             if (exact) RUN(after(t, &flash_done[slot]));
-            // out-projection + residual, then LayerNorm (+ inter-layer ReLU).  Split format: the GEMM reads O and the
-            // residual as hi/lo pairs and writes plain fp32 into the (now dead) Q buffer; the LayerNorm packs E2 again.
-            // Split-pair mode: the residual is added by the LayerNorm kernel instead (as an accumulator init it made the
-            // out-projection 60 % slower there -- 397 vs 243 us at the bench size -- against +1 KB per row in the LayerNorm).
-            float* pre_ln = S ? p->Qe : p->E2;
-            // Half rows: the same (the 8-phase GEMM has no fast accumulator-init path).
-            const bool ln_resid = ((S == 1 || (S == 2 && !h->gemm_no_p8)) && h->ln_resid) || (S == 2 && h->half_f16);      // (mode 5: always -- no GEMM reads an fp16 residual)
-            GemmArgs o = G(p->Oe, D, w.wo, D, pre_ln, D, E, D, w.bo);
-            if (!ln_resid) { o.resid = p->E2; o.ldr = D; o.r_split = S; }
-            o.a_split = SA;
-            // single-rounded attention (half-row O): pre_ln has one reader, the LayerNorm below -- fp16 half rows instead of fp32 (2^-12 in
-            // front of a normalisation whose output is rounded to bf16 / split pairs: not visible in the mode's error; half the bytes both ways)
-            const bool o16 = ln_resid && SA == 2 && h->outproj_f16 != 0 && D % 256 == 0;
-            if (o16) o.c_f16_cols = D;
-            RUN(gemm(h, fs, o, PA));
-            {
-                Scope sc(h, fs, PC_LAYERNORM, 0);
-                const int SL = (S == 2 && h->half_f16) ? 4 : S;          // (mode 5: the half rows the LayerNorm reads and writes hold fp16)
-                RUN(launch_layernorm_to(pre_ln, D, p->E2, D, E, D, w.lng, w.lnb, inter, SL, fs, ln_resid ? p->E2 : nullptr, D, SL, o16 ? 1 : 0));
-            }
+            RUN(edge_attn_out(h, p, fs, w, ef, inter));
             if (pair) RUN(after(t, &edge_done));
         }
         e3_pending_relu = inter;
@@ -799,35 +770,32 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     }
     if (tr && tr->edge_dis && E > 0) {
         // gcn_edge_feature_2d_dis = triplet_projector_2d(cat[x2[ei[0]], x2[ei[1]], e2]) (:259-264,319-322): node columns of
-        // its first Linear on N rows, gathered into the edge GEMM's accumulators like nn_edge.0
+        // its first Linear on N rows, gathered into the edge GEMM's accumulators like nn_edge.0 (fp32 tables, no ReLU pending)
         if (!h->trip.wnode) return fail(VLSAT_ESTATE, "forward(istrain=True): triplet_projector_2d weights were not loaded");
-        const int NPC = npc_of(h);
-        RUN(gemm(h, s, G(p->X2, LDX, h->trip.wnode, D, sc2.NP, NPC, N, 4 * D, h->trip.bnode)));
-        GemmArgs e1 = G(p->E2, D, h->trip.we, D, sc2.Hbig, 2 * D, E, 2 * D, nullptr, ACT_RELU);
-        e1.g0 = sc2.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
-        e1.g1 = sc2.NP + 2 * D; e1.gi1 = p->d_dst; e1.ldg1 = NPC;
-        e1.a_split = S; e1.c_split = S;
-        RUN(gemm(h, s, e1));
+        RUN(gemm(h, s, G(p->X2, LDX, h->trip.wnode, D, sc2.NP, npc_of(h), N, 4 * D, h->trip.bnode)));
+        RUN(gemm(h, s, nn_edge0_args(h, p, h->trip.we, p->E2, 0, sc2, false)));
         GemmArgs e2 = G(sc2.Hbig, 2 * D, h->trip.w2, 2 * D, tr->edge_dis, D, E, D, h->trip.b2);
-        e2.a_split = S;
+        e2.a_split = split_fmt(h);
         RUN(gemm(h, s, e2));
     }
     // a-15 relation heads, a-16 object heads
+    const RelSide rs[2] = {{&h->rel3, p->E3, e3_pending_relu, rel3d, &sc3}, {&h->rel2, p->E2, 0, rel2d, &sc2}};
+    const ObjSide os[2] = {{p->X3, h->obj3_w, h->obj3_b, obj3d, &sc3}, {p->X2, h->obj2_w, h->obj2_b, obj2d, &sc2}};
     if (pair) {                                               // both head pairs as launches of two problems each, behind the last edge attention
         RUN(wait(s, edge_done));
-        RUN(rel_head_pair(h, p, s, p->E3, e3_pending_relu, rel3d, p->E2, rel2d, sc3, sc2));
-        RUN(obj_head_pair(h, p, s, obj3d, obj2d, sc3, sc2));
+        RUN(rel_head(h, p, s, rs, 2));
+        RUN(obj_head(h, p, s, os, 2));
     } else {
-    RUN(fork());                                              // t: the 2D heads
-    if (E > 0) {
-        RUN(rel_head(h, p, s, h->rel3, p->E3, e3_pending_relu, rel3d, sc3));
-        if (do2d) RUN(rel_head(h, p, t, h->rel2, p->E2, 0, rel2d, sc2));
-    }
-    RUN(obj_head(h, p, s, p->X3, h->obj3_w, h->obj3_b, obj3d, sc3));
-    if (do2d) {
-        RUN(wait(u, x2_ready));
-        RUN(obj_head(h, p, u, p->X2, h->obj2_w, h->obj2_b, obj2d, sc2));
-    }
+        RUN(fork());                                          // t: the 2D heads
+        if (E > 0) {
+            RUN(rel_head(h, p, s, &rs[0], 1));
+            if (do2d) RUN(rel_head(h, p, t, &rs[1], 1));
+        }
+        RUN(obj_head(h, p, s, &os[0], 1));
+        if (do2d) {
+            RUN(wait(u, x2_ready));
+            RUN(obj_head(h, p, u, &os[1], 1));
+        }
     }
     if (dual) {                                               // every lane ends joined into the caller's stream
         profile_close(h, t);
