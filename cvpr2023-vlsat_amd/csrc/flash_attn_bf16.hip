@@ -21,6 +21,7 @@
 //   TR = false keeps a gather fallback for the V operand (eight ds_read_u16 per operand) -- the reference
 //   implementation the transpose-read path is tested against.
 // Split keys (plans that cannot fill the chip) and the output transpose through LDS are as in flash_attn_f32.hip.
+// Which instantiations exist and which one a launch gets: flash_pick.h; what each template argument does: the comment above the kernel.
 // Roofline: bf16 MFMA, 2.5 PF / TERMS; algorithmic work 4*T^2*64 flop per (scene, head).
 #include <type_traits>
 
@@ -576,110 +577,34 @@ __global__ __launch_bounds__(64 * BQW, 2) void flash_attn_bf16_kernel(
 }
 
 
-}  // namespace
+// one kernel pointer per row of the variant list (flash_pick.h), in its order: taking the address is what instantiates a row
+typedef void (*FlashKernel)(const float*, const float*, const float*, float*, int, int, int, const int4*, int, float, FlashSplit);
+#define VLSAT_FLASH_KERNEL(T, R, S, P, D, G, W, A, Q, O) flash_attn_bf16_kernel<T, R, S, P, D, G, W, A, Q, O>,
+constexpr FlashKernel kFlashKernels[] = {VLSAT_FLASH_BF16_VARIANTS(VLSAT_FLASH_KERNEL)};
+#undef VLSAT_FLASH_KERNEL
+static_assert(sizeof kFlashKernels / sizeof kFlashKernels[0] == kFlashVariantCount, "one kernel per row of the variant list");
 
-// head dims other than 64 exist for the tensor formats of the bf16 modes only (io_split 1 | 2, transpose read), and
-// split-bf16 (two LDS planes) not at 128, where the tile buffers of two blocks no longer fit a CU
-bool flash_attn_bf16_supports(int head_dim, int terms, int use_tr, int io_split) {
-    if (head_dim == 64) return true;
-    if (head_dim != 32 && head_dim != 128) return false;
-    if (!use_tr || !io_split) return false;
-    if (io_split >= 2 && terms != 1) return false;
-    return head_dim == 32 || terms == 1;
-}
+}  // namespace
 
 int launch_flash_attn_bf16(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
                            const int4* tiles, int n_tiles, float scale_log2e, int terms, int use_tr, int io_split,
                            hipStream_t s, const FlashSplit* split, int pv_terms, int head_dim) {
     if (n_tiles <= 0) return 0;
-    const int FB_D = head_dim;
-    if (!flash_attn_bf16_supports(head_dim, terms, use_tr, io_split)) return fail(-1, "flash_attn_bf16: head dim / format combination not built");
     if ((ldq | ldkv | ldo) & 3) return fail(-1, "flash_attn: leading dims must be multiples of 4");
-    if (terms != 1 && terms != 3) return fail(-1, "flash_attn_bf16: terms must be 1 or 3");
-    if (io_split == 3 && !(split && split->rows > 0 && (size_t)split->rows * (size_t)ldkv * 4 < (1ull << 32)))
-        return fail(-1, "flash_attn_bf16: fp16 half rows are built for scenes addressable with 32-bit offsets (the LDS-direct kernel)");
     FlashSplit sp{};
     if (split && split->parts > 1) {
         sp = *split;
-        if (!sp.krange || !sp.o_part || !sp.m_part || !sp.l_part || sp.heads * FB_D > ldo)
+        if (!sp.krange || !sp.o_part || !sp.m_part || !sp.l_part || sp.heads * head_dim > ldo)
             return fail(-1, "flash_attn: incomplete split-key workspace");
     }
     if (split) { sp.ablate = split->ablate; sp.bq = split->bq; sp.rows = split->rows; sp.qg = split->qg; }
-    if (sp.bq != FLASH_BQ && !(sp.bq == FLASH_BQ_BIG && FB_D == 64 && io_split >= 2 && use_tr == 1 && sp.parts <= 1 && sp.rows > 0 &&
-                               (size_t)sp.rows * (size_t)ldkv * 4 < (1ull << 32)))
-        return fail(-1, "flash_attn_bf16: 256-query tiles are built for half rows, head dim 64, the LDS-direct kernel, no key split");
-    // The LDS-direct K / V staging addresses a scene with 32-bit byte offsets (buffer descriptor of n_tok * ldkv * 4 bytes, row * ld4
-    // VGPR offsets): only where every scene's rows are known to span less than 4 GiB -- the caller states the rows of the whole
-    // tensor in FlashSplit::rows (an upper bound of any scene, and of the batch-wide attention of batch_mode 'reference').  Unknown
-    // or larger: the register-staged kernel, which addresses rows with size_t.
-    if (io_split == 2 && use_tr && use_tr != 2 && !(split && split->rows > 0 && (size_t)split->rows * (size_t)ldkv * 4 < (1ull << 32))) use_tr = 2;
-#define VLSAT_FA(T, R, S) hipLaunchKernelGGL((flash_attn_bf16_kernel<T, R, S>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp)
-#define VLSAT_FAD(T, S, P, D) hipLaunchKernelGGL((flash_attn_bf16_kernel<T, true, S, P, D>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp)
-    if (FB_D != 64) {          // 16 / 4 heads: the formats the forward uses (the transpose-read path; split-bf16 only at 32)
-        if (io_split == 3) {                         // fp16 half rows
-            if (use_tr == 2 || !use_tr || terms != 1) return fail(-1, "flash_attn_bf16: fp16 half rows are built for the LDS-direct single-rounding kernel only");
-            if (FB_D == 32) hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 3, 3, 32, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-            else hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 3, 3, 128, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        } else
-        if (io_split == 2 && use_tr != 2) {          // half rows: LDS-direct K/V staging, one tile ahead
-            if (FB_D == 32) hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 32, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-            else hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 128, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        } else if (FB_D == 32) {
-            if (io_split == 2) VLSAT_FAD(1, 2, 3, 32);
-            else if (terms == 3 && pv_terms == 2) VLSAT_FAD(3, 1, 2, 32);
-            else if (terms == 3) VLSAT_FAD(3, 1, 3, 32);
-            else VLSAT_FAD(1, 1, 3, 32);
-        } else {
-            if (io_split == 2) VLSAT_FAD(1, 2, 3, 128); else VLSAT_FAD(1, 1, 3, 128);
-        }
-    } else
-    if (io_split == 3) {                 // fp16 half rows (precision mode fp16_mixed): the two shipped forms of the LDS-direct kernel
-        if (!use_tr || terms != 1 || use_tr == 2 || use_tr >= 3) return fail(-1, "flash_attn_bf16: fp16 half rows are built for the LDS-direct single-rounding kernel only");
-        if (sp.bq == FLASH_BQ_BIG)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 3, 3, 64, 2, 8>), dim3(n_tiles), dim3(512), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 3, 3, 64, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-    } else
-    if (io_split == 2) {
-        if (!use_tr || terms != 1) return fail(-1, "flash_attn_bf16: half-row tensors need terms = 1 and the transpose-read path");
-        // LDS-direct K/V staging (scene-relative 32-bit byte offsets: checked above).  Measured on one box, interleaved (profiles/r04_probes/flash_bf16_dma_ab.txt): register-
-        // staged 596 TFLOP/s; ring of 3 buffers (3 blocks per CU) 745-773; ring of 4 (2 blocks per CU) 650-659; ring of 2 = one
-        // tile ahead with FOUR blocks per CU (34 KB of LDS, 120 VGPRs) 813-817: occupancy beats look-ahead depth.
-        if (use_tr == 3)            // (experiments: vlsat_debug_option "flash_dma" 3 | 4 = rings of three / four buffers)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 3>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr == 4)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 4>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-#ifdef VLSAT_EXPERIMENTS
-#define VLSAT_FA_ABL(A) else if (use_tr != 2 && sp.bq == FLASH_BQ_BIG && (sp.ablate & ~3) == (A)) \
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 8, A>), dim3(n_tiles), dim3(512), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        VLSAT_FA_ABL(4) VLSAT_FA_ABL(8) VLSAT_FA_ABL(16) VLSAT_FA_ABL(28) VLSAT_FA_ABL(32) VLSAT_FA_ABL(64) VLSAT_FA_ABL(96) VLSAT_FA_ABL(256) VLSAT_FA_ABL(124) VLSAT_FA_ABL(380)
-#undef VLSAT_FA_ABL
-#endif
-        else if (use_tr != 2 && sp.bq == FLASH_BQ_BIG && sp.qg == 1)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 4, 0, 2, 0>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr != 2 && sp.bq == FLASH_BQ_BIG && sp.qg == 2)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 4, 0, 2, 1>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr != 2 && sp.qg == 1 && sp.parts <= 1)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 2, 0, 2, 0>), dim3(n_tiles), dim3(128), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr != 2 && sp.qg == 2 && sp.parts <= 1)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 2, 0, 2, 1>), dim3(n_tiles), dim3(128), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr != 2 && sp.bq == FLASH_BQ_BIG)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2, 8>), dim3(n_tiles), dim3(512), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (use_tr != 2)       // (use_tr = 2: the register-staged kernel of round 3, for A/B -- "flash_dma" 0)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<1, true, 2, 3, 64, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else
-            VLSAT_FA(1, true, 2);
-    } else if (io_split) {
-        if (!use_tr) return fail(-1, "flash_attn_bf16: the split-pair format is built for the transpose-read path only");
-        if (terms == 3 && pv_terms == 2)
-            hipLaunchKernelGGL((flash_attn_bf16_kernel<3, true, 1, 2>), dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-        else if (terms == 3) VLSAT_FA(3, true, 1); else VLSAT_FA(1, true, 1);
-    } else if (terms == 3) { if (use_tr) VLSAT_FA(3, true, 0); else VLSAT_FA(3, false, 0); }
-    else                   { if (use_tr) VLSAT_FA(1, true, 0); else VLSAT_FA(1, false, 0); }
-#undef VLSAT_FA
-#undef VLSAT_FAD
+    // (FlashSplit::rows: the rows of the whole tensor, an upper bound of any scene and of the batch-wide attention of batch_mode 'reference')
+    const bool rows_fit_32bit = split && split->rows > 0 && (size_t)split->rows * (size_t)ldkv * 4 < (1ull << 32);
+    const FlashPick pick = flash_bf16_pick(head_dim, terms, use_tr, io_split, pv_terms, sp.bq, sp.qg, sp.parts, rows_fit_32bit, sp.ablate);
+    if (pick.index < 0) return fail(-1, pick.error);
+    hipLaunchKernelGGL(kFlashKernels[pick.index], dim3(n_tiles), dim3(64 * kFlashVariants[pick.index].bqw), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
     VLSAT_LAUNCH_CHECK("flash_attn_bf16");
-    if (sp.parts > 1) return launch_flash_merge(O, ldo, sp, s, io_split, FB_D);
+    if (sp.parts > 1) return launch_flash_merge(O, ldo, sp, s, io_split, head_dim);
     return 0;
 }
 

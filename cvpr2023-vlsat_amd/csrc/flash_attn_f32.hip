@@ -253,12 +253,8 @@ int launch_flash_attn(const float* Q, int ldq, const float* K, const float* V, i
             return fail(-1, "flash_attn: incomplete split-key workspace");
     }
     if (split) sp.ablate = split->ablate;
-    if (FA_D == 32)
-        hipLaunchKernelGGL(flash_attn_f32_kernel<32>, dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-    else if (FA_D == 64)
-        hipLaunchKernelGGL(flash_attn_f32_kernel<64>, dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
-    else
-        hipLaunchKernelGGL(flash_attn_f32_kernel<128>, dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
+    const auto kernel = FA_D == 32 ? flash_attn_f32_kernel<32> : FA_D == 64 ? flash_attn_f32_kernel<64> : flash_attn_f32_kernel<128>;
+    hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
     VLSAT_LAUNCH_CHECK("flash_attn_f32");
     if (sp.parts > 1) return launch_flash_merge(O, ldo, sp, s, 0, FA_D);
     return 0;

@@ -1,0 +1,107 @@
+// Which instantiation of flash_attn_bf16_kernel (flash_attn_bf16.hip) a launch gets: the list of the instantiations that are built and
+// the one function that picks among them.  No HIP header: tests/flash_pick_check.cpp compiles this with g++.  flash_bf16_pick works out
+// the ten template arguments a call asks for and looks them up, so what is not in the list is an error, never another kernel; the
+// kernel's static_asserts state the same rules on the device side, and a row that breaks them does not compile.
+#pragma once
+
+namespace vlsat {
+
+constexpr int FLASH_BQ = 128;       // queries per block
+constexpr int FLASH_BQ_BIG = 256;   // ... of the tile table for scenes of thousands of tokens (FlashSplit::bq)
+
+struct FlashVariant {               // the kernel's template arguments, in its order (what each one does: the comment above the kernel)
+    int terms; bool tr; int io, pvt, d, ring, bqw, abl, qg, ord;
+    constexpr bool operator==(const FlashVariant& o) const {
+        return terms == o.terms && tr == o.tr && io == o.io && pvt == o.pvt && d == o.d && ring == o.ring && bqw == o.bqw && abl == o.abl && qg == o.qg && ord == o.ord;
+    }
+};
+
+// X(TERMS, TR, IO, PVT, FB_D, RING, BQW, ABL, QG, ORD), one row per instantiation: flash_attn_bf16.hip makes its table of kernel pointers
+// from this list (which is what instantiates them), kFlashVariants below has the same rows at the same indices.
+// By line: fp32 tensors | split pairs at head dim 64, 32, 128 | bf16 half rows, register-staged and LDS-direct | the same with eight
+// waves (256-query tiles) and with 64 queries per wave (BQW 2 | 4 on 128- | 256-query tiles, ORD = flash_qg - 1) | fp16 half rows.
+#define VLSAT_FLASH_BF16_RELEASE(X)                                                                                                              \
+    X(3, true, 0, 3, 64, 0, 4, 0, 1, 0) X(3, false, 0, 3, 64, 0, 4, 0, 1, 0) X(1, true, 0, 3, 64, 0, 4, 0, 1, 0) X(1, false, 0, 3, 64, 0, 4, 0, 1, 0) \
+    X(3, true, 1, 3, 64, 0, 4, 0, 1, 0) X(3, true, 1, 2, 64, 0, 4, 0, 1, 0)  X(1, true, 1, 3, 64, 0, 4, 0, 1, 0)                                 \
+    X(3, true, 1, 3, 32, 0, 4, 0, 1, 0) X(3, true, 1, 2, 32, 0, 4, 0, 1, 0)  X(1, true, 1, 3, 32, 0, 4, 0, 1, 0) X(1, true, 1, 3, 128, 0, 4, 0, 1, 0) \
+    X(1, true, 2, 3, 64, 0, 4, 0, 1, 0) X(1, true, 2, 3, 32, 0, 4, 0, 1, 0)  X(1, true, 2, 3, 128, 0, 4, 0, 1, 0)                                \
+    X(1, true, 2, 3, 64, 2, 4, 0, 1, 0) X(1, true, 2, 3, 32, 2, 4, 0, 1, 0)  X(1, true, 2, 3, 128, 2, 4, 0, 1, 0)                                \
+    X(1, true, 2, 3, 64, 2, 8, 0, 1, 0) X(1, true, 2, 3, 64, 2, 2, 0, 2, 0)  X(1, true, 2, 3, 64, 2, 2, 0, 2, 1) X(1, true, 2, 3, 64, 2, 4, 0, 2, 0) X(1, true, 2, 3, 64, 2, 4, 0, 2, 1) \
+    X(1, true, 3, 3, 64, 2, 4, 0, 1, 0) X(1, true, 3, 3, 32, 2, 4, 0, 1, 0)  X(1, true, 3, 3, 128, 2, 4, 0, 1, 0) X(1, true, 3, 3, 64, 2, 8, 0, 1, 0)
+// Experiments build only (common.h), bf16 half rows at head dim 64: rings of 3 and 4 tile buffers ("flash_dma" 3 | 4), and the timing
+// ablations of the eight-wave kernel (ABL = FlashSplit::ablate without its bits 0, 1; results are GARBAGE).  The rings, measured on one
+// box, interleaved (profiles/r04_probes/flash_bf16_dma_ab.txt): register-staged 596 TFLOP/s; ring of 3 (3 blocks per CU) 745-773; ring of 4
+// (2 blocks per CU) 650-659; ring of 2 with FOUR blocks per CU (34 KB of LDS, 120 VGPRs) 813-817: occupancy beats look-ahead depth.
+#ifdef VLSAT_EXPERIMENTS
+#define VLSAT_FLASH_BF16_LAB(X)                                                                                                                  \
+    X(1, true, 2, 3, 64, 3, 4, 0, 1, 0)  X(1, true, 2, 3, 64, 4, 4, 0, 1, 0)  X(1, true, 2, 3, 64, 2, 8, 4, 1, 0)   X(1, true, 2, 3, 64, 2, 8, 8, 1, 0)   \
+    X(1, true, 2, 3, 64, 2, 8, 16, 1, 0) X(1, true, 2, 3, 64, 2, 8, 28, 1, 0) X(1, true, 2, 3, 64, 2, 8, 32, 1, 0)  X(1, true, 2, 3, 64, 2, 8, 64, 1, 0)  \
+    X(1, true, 2, 3, 64, 2, 8, 96, 1, 0) X(1, true, 2, 3, 64, 2, 8, 256, 1, 0) X(1, true, 2, 3, 64, 2, 8, 124, 1, 0) X(1, true, 2, 3, 64, 2, 8, 380, 1, 0)
+constexpr bool kFlashLab = true;
+#else
+#define VLSAT_FLASH_BF16_LAB(X)
+constexpr bool kFlashLab = false;
+#endif
+#define VLSAT_FLASH_BF16_VARIANTS(X) VLSAT_FLASH_BF16_RELEASE(X) VLSAT_FLASH_BF16_LAB(X)
+
+#define VLSAT_FLASH_ROW(T, R, S, P, D, G, W, A, Q, O) {T, R, S, P, D, G, W, A, Q, O},
+constexpr FlashVariant kFlashVariants[] = {VLSAT_FLASH_BF16_VARIANTS(VLSAT_FLASH_ROW)};
+#undef VLSAT_FLASH_ROW
+constexpr int kFlashVariantCount = (int)(sizeof kFlashVariants / sizeof kFlashVariants[0]);
+
+constexpr int flash_bf16_find(const FlashVariant& v) {
+    for (int i = 0; i < kFlashVariantCount; ++i)
+        if (kFlashVariants[i] == v) return i;
+    return -1;
+}
+
+struct FlashPick { int index; const char* error; };      // a row of kFlashVariants, or -1 and why
+
+// The kernel for head dim d; terms 1 | 3 (single rounding | split-bf16); use_tr 0 gather fallback | 1 transpose read, and LDS-direct K / V
+// staging where the format has it | 2 transpose read, register-staged | 3, 4 (experiments build) rings of 3 / 4; io 0 fp32 | 1 split pairs |
+// 2 bf16 half rows | 3 fp16 half rows; pv_terms (split-bf16 on split pairs) 3 | 2; bq, qg, ablate as in FlashSplit; parts > 1: split keys.
+// rows_fit_32bit: the caller has stated the rows of the tensors (FlashSplit::rows) and they span less than 4 GiB -- the LDS-direct staging
+// addresses a scene with 32-bit byte offsets (buffer descriptor of n_tok * ldkv * 4 bytes, row * ld4 VGPR offsets).
+inline FlashPick flash_bf16_pick(int d, int terms, int use_tr, int io, int pv_terms = 3, int bq = FLASH_BQ, int qg = 0, int parts = 1,
+                                 bool rows_fit_32bit = true, int ablate = 0) {
+    const bool big = bq == FLASH_BQ_BIG;
+    // head dims other than 64 exist for the tensor formats of the bf16 modes only (transpose read), and split-bf16 not at 128
+    if (d != 64 && !((d == 32 || d == 128) && use_tr && io && (io < 2 || terms == 1) && (d == 32 || terms == 1)))
+        return {-1, "flash_attn_bf16: head dim / format combination not built"};
+    if (terms != 1 && terms != 3) return {-1, "flash_attn_bf16: terms must be 1 or 3"};
+    if (io == 3 && !rows_fit_32bit)
+        return {-1, "flash_attn_bf16: fp16 half rows are built for scenes addressable with 32-bit offsets (the LDS-direct kernel)"};
+    if (bq != FLASH_BQ && !(big && d == 64 && io >= 2 && use_tr == 1 && parts <= 1 && rows_fit_32bit))
+        return {-1, "flash_attn_bf16: 256-query tiles are built for half rows, head dim 64, the LDS-direct kernel, no key split"};
+    if (io == 2 && use_tr && !rows_fit_32bit) use_tr = 2;      // unknown or larger: the register-staged kernel, which addresses rows with size_t
+    FlashVariant v{terms, use_tr != 0, io, 3, d, 0, big ? 8 : 4, 0, 1, 0};
+    if (io == 3) {
+        if (!use_tr || terms != 1 || use_tr == 2 || (d == 64 && use_tr >= 3))
+            return {-1, "flash_attn_bf16: fp16 half rows are built for the LDS-direct single-rounding kernel only"};
+        v.ring = 2;
+    } else if (io == 2) {
+        if (!use_tr || terms != 1) return {-1, "flash_attn_bf16: half-row tensors need terms = 1 and the transpose-read path"};
+        const int abl = ablate & ~3;
+        v.ring = use_tr == 2 ? 0 : (kFlashLab && d == 64 && (use_tr == 3 || use_tr == 4)) ? use_tr : 2;
+        if (v.ring == 2 && d == 64) {          // the forms of the shipped kernel
+            if (kFlashLab && big && abl && flash_bf16_find({1, true, 2, 3, 64, 2, 8, abl, 1, 0}) >= 0) {
+                v.abl = abl;
+            } else if ((qg == 1 || qg == 2) && (big || parts <= 1)) {      // 64 queries per wave
+                v.bqw = big ? 4 : 2; v.qg = 2; v.ord = qg - 1;
+            }
+        }
+    } else if (io) {
+        if (!use_tr) return {-1, "flash_attn_bf16: the split-pair format is built for the transpose-read path only"};
+        v.io = 1;
+        v.pvt = terms == 3 && pv_terms == 2 ? 2 : 3;
+    }
+    const int i = flash_bf16_find(v);
+    return i < 0 ? FlashPick{-1, "flash_attn_bf16: head dim / format combination not built"} : FlashPick{i, nullptr};
+}
+
+// which (head dim, format) combinations are built: the pick with 128-query tiles, 32 queries per wave, no key split, rows that fit
+inline bool flash_attn_bf16_supports(int head_dim, int terms, int use_tr, int io_split) {
+    return flash_bf16_pick(head_dim, terms, use_tr, io_split).index >= 0;
+}
+
+}  // namespace vlsat

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "flash_pick.h"
+
 namespace vlsat {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }     // a: a power of two (scratch carving)
@@ -118,17 +120,16 @@ struct FlashSplit {
 };
 int launch_flash_attn(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
                       const int4* tiles, int n_tiles, float scale_log2e, hipStream_t s, const FlashSplit* split = nullptr,
-                      int head_dim = 64);      // head_dim = 512 / NUM_HEADS: 32 | 64 | 128
+                      int head_dim = 64);      // head_dim = 512 / NUM_HEADS: 32 | 64 | 128, one instantiation each
 int launch_flash_merge(float* O, int ldo, const FlashSplit& sp, hipStream_t s, int out_split, int head_dim = 64);
 // the same attention on the bf16 matrix cores (flash_attn_bf16.hip): terms = 3 split-bf16 (~1e-5) | 1 single-rounded;
 // use_tr = 0 selects the gather fallback for the V operand instead of ds_read_b64_tr_b16 (tests); io_split = 1: Q (already
-// scaled), K, V and O are in the split-pair format of the bf16 modes (common.h pack_split)
+// scaled), K, V and O are in the split-pair format of the bf16 modes (common.h pack_split), 2 | 3: bf16 | fp16 half rows.
+// Which kernel a call gets, which calls are an error and flash_attn_bf16_supports (the (head dim, format) combinations that
+// are built) are all flash_bf16_pick of flash_pick.h, next to the list of the kernels that exist.
 int launch_flash_attn_bf16(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
                            const int4* tiles, int n_tiles, float scale_log2e, int terms, int use_tr, int io_split,
                            hipStream_t s, const FlashSplit* split = nullptr, int pv_terms = 3, int head_dim = 64);
-bool flash_attn_bf16_supports(int head_dim, int terms, int use_tr, int io_split);   // which (head dim, format) combinations are built
-constexpr int FLASH_BQ = 128;   // queries per block
-constexpr int FLASH_BQ_BIG = 256;   // ... of the eight-wave variant for scenes of thousands of tokens (FlashSplit::bq)
 
 // ---- node attention with distance bias (per scene, per head) ----
 // scene_ptr: device [n_scenes+1] node offsets; bias_ptr: device [n_scenes] offsets into bias

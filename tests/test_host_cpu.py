@@ -58,10 +58,20 @@ def test_library_exports_every_declared_symbol(L):
     assert b"gfx950" in lib.vlsat_version()
 
 
+def _flash_release_rows():
+    """the rows of the release part of the variant list of csrc/flash_pick.h, as tuples of the ten template arguments as nm prints them"""
+    import re
+    src = open(os.path.join(ROOT, "cvpr2023-vlsat_amd", "csrc", "flash_pick.h")).read()
+    body = src[src.index("#define VLSAT_FLASH_BF16_RELEASE(X)"):src.index("// Experiments build only")]
+    return [tuple(a.strip() for a in row.split(",")) for row in re.findall(r"\bX\(([^)]*)\)", body)]
+
+
 def test_release_library_carries_no_lab_code(L):
     """The in-tree build is the RELEASE library (csrc/common.h): no timing-ablation instantiation of the 8-phase GEMM (template
     argument ABL != 0 -- "results are garbage" by their own comment), and the lab switches of vlsat_debug_option are refused
-    (they exist in `build.py --experiments` -> tools/bin/libvlsat_hip_exp.so only)."""
+    (they exist in `build.py --experiments` -> tools/bin/libvlsat_hip_exp.so only).  The bf16 edge attention: the instantiations in the
+    library are exactly the release rows of the variant list of csrc/flash_pick.h (every row has a kernel, nothing else has), 26 of
+    them, none with ABL != 0 or a ring of more than 2 tile buffers."""
     import re
     import shutil
     import subprocess
@@ -70,6 +80,11 @@ def test_release_library_carries_no_lab_code(L):
     p8 = re.findall(r"gemm_p8_kernel<(\d+), (\d+), (?:true|false), (\d+), (\d+)>", out)
     assert p8, "nm shows no gemm_p8_kernel instantiation at all"
     assert all(abl == "0" for *_, abl in p8), sorted(set(p8))
+    fa = {tuple(a.split(", ")) for a in re.findall(r"flash_attn_bf16_kernel<([^>]*)>", out)}
+    rows = _flash_release_rows()
+    assert len(rows) == len(set(rows)) == 26 and all(len(r) == 10 for r in rows), rows
+    assert fa == set(rows), (sorted(fa - set(rows)), sorted(set(rows) - fa))
+    assert all(r[7] == "0" and int(r[5]) <= 2 for r in fa), sorted(fa)
     src = open(os.path.join(ROOT, "cvpr2023-vlsat_amd", "csrc", "engine_api.hip")).read()
     lab = src[src.index("#ifdef VLSAT_EXPERIMENTS"):src.index("#else", src.index("#ifdef VLSAT_EXPERIMENTS"))]
     assert "flash_ablate" in lab and "gate_grid" in lab           # the lab switches sit behind the macro, not in the release path
@@ -205,6 +220,27 @@ def test_evaluation_scratch_layout_on_the_host(sanitize):
     rows = dict(select_host.run(sanitize, "eval_scratch_check"))
     assert set(rows) == {"1 0 160 26", "2 2 160 26", "64 4032 160 26", "3 6 20 8"}, rows
     assert all(v == "ok" for v in rows.values()), rows
+
+
+@pytest.mark.parametrize("build", ["plain", "asan_ubsan", "experiments"])
+def test_flash_pick_chooses_what_the_cascade_chose_before_it(build):
+    """csrc/flash_pick.h compiled by g++ (tests/flash_pick_check.cpp): over head dim {32, 48, 64, 128} x terms {1, 2, 3} x use_tr 0..4 x
+    io_split 0..3 x pv_terms {2, 3} x bq {128, 256} x qg {0, 1, 2} x parts {1, 2} x rows that fit or not (11 520 calls) flash_bf16_pick
+    gives the ten template arguments and the block size, or the error text, of the if-cascade the launcher had before it (kept word
+    for word in the check program).  The one permitted difference: the 24 calls with use_tr 3 | 4 that reached the ring-of-3 / ring-of-4
+    kernels get the ring-of-2 kernel of use_tr 1 in the release list.  Every row of the list is reached, flash_attn_bf16_supports is
+    the pick with the defaults and answers the engine as the hand-written rule did, the block is 64 x BQW.  "asan_ubsan": the same
+    stand-alone binary under ASan + UBSan; "experiments": the list with the lab rows (12 more: rings of 3 and 4, ten ablations), the
+    ablation values enumerated too, no difference permitted."""
+    import select_host
+    lab = build == "experiments"
+    rows = dict(select_host.run(build == "asan_ubsan", "flash_pick_check", ("VLSAT_EXPERIMENTS",) if lab else ()))
+    assert set(rows) == {"legacy", "reachable", "supports", "block"}, rows
+    assert all(v.split()[0] == "ok" for v in rows.values()), rows
+    n = 13 if lab else 1
+    assert rows["legacy"] == f"ok {11520 * n} cases, {1104 * n} launches, {0 if lab else 24} ring-of-2 for ring-of-3/4"
+    assert rows["reachable"] == ("ok 38" if lab else "ok 26")
+    assert rows["block"] == f"ok {38 if lab else 26} rows, 26 without ABL or a ring above 2"
 
 
 def test_product_package_never_imports_the_oracle():
