@@ -561,103 +561,21 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmArgs p, int n_tiles
 
 }  // namespace
 
-// full rounds of a large-M launch on 256 x 256 tiles: half-row bf16 operands (prec 1), exact fp32 (prec 0) or split-bf16
-// on split-pair operands (prec 3); 1 = operand combination not built (the caller falls back to the older kernels); dry: decide only
-int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s, bool dry) {
-    const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
-    const bool f32 = a.prec == 0, x3 = a.prec == 3;
-    if (a.rowscale || a.act == ACT_SIGMOID || (add != 0 && add != 1 && add != 6)) return 1;
-    // the fp32 / split-bf16 epilogues read the bias as float4 (the half-row one as scalars): an unaligned bias pointer of a
-    // caller of vlsat_k_gemm goes to the older kernels, which have the scalar fallback
-    if ((f32 || x3) && a.bias && (reinterpret_cast<uintptr_t>(a.bias) & 15)) return 1;
-    // (round 4, measured and dropped: loading the accumulator inits of the wave tile's second row half one phase later, under
-    //  the MFMAs of phases 1 / 2 -- fp32 nn_edge.0 + gathered rows 923 vs 917 us, out-projection + residual 480 vs 483: the
-    //  cost of additive operands is not latency at the start of a tile; it is consistent with every CU pulling its 256-512 KB at the same
-    //  moment: 64-128 MB per round of tiles at what the memory system delivers)
-    if (f32 ? (a.a_split || a.c_split || a.r_split || a.c_scale != 1.f)
-            : x3 ? (a.a_split != 1 || a.c_split == 2 || !a.Wlo) : (a.prec != 1 || a.a_split != 2 || a.c_split == 1)) return 1;
-    const int kt = (f32 || x3) ? 32 : P8_BK;          // an output tile is an even number (>= 4) of K-tiles
-    // (M need not be a multiple of the tile: the last panel's rows past M are outside every buffer descriptor -- loads return zeros,
-    //  stores are dropped -- and tile_init clamps the row of an additive operand)
-    if (a.N % P8_BN || a.K % (2 * kt) || a.K < 4 * kt || n_tiles > (long)((a.M + P8_BM - 1) / P8_BM) * (a.N / P8_BN)) return 1;
-    const int nbn = a.N / P8_BN;
-    if (grid % 8 || (grid / 8) % nbn) return 1;      // the kernel keeps one column tile per block (bias registers)
-#define VLSAT_P8_K(...) do { if (!dry) hipLaunchKernelGGL((gemm_p8_kernel<__VA_ARGS__>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn); } while (0)
-#define VLSAT_P8(MODE, ADD, RELU, CF) VLSAT_P8_K(MODE, ADD, RELU, CF)
-#define VLSAT_P8_ABL(X) VLSAT_P8_K(0, 0, false, 2, X)
-    const bool c16 = a.c_f16_cols > 0;            // (the whole output as fp16 half rows: half-row launches only)
-    if (c16 && (a.c_f16_cols != a.N || f32 || x3 || a.c_split)) return 1;
-    if (a.half_f16 && (f32 || x3 || a.c_split)) return 1;         // (fp16 operands: half-row launches; their half-row outputs come as c_f16_cols == N)
-    const int key = add * 4 + (a.relu_a ? 2 : 0) + (a.c_split ? 1 : 0);
-    if (f32) {
-        switch (key) {
-            case 0: VLSAT_P8(1, 0, false, 0); break;
-            case 2: VLSAT_P8(1, 0, true, 0); break;
-            case 4: VLSAT_P8(1, 1, false, 0); break;
-            case 24: VLSAT_P8(1, 6, false, 0); break;
-            case 26: VLSAT_P8(1, 6, true, 0); break;
-            default: return 1;
-        }
-    } else if (x3) {
-        switch (key) {
-            case 0: VLSAT_P8(2, 0, false, 0); break;
-            case 1: VLSAT_P8(2, 0, false, 1); break;
-            case 2: VLSAT_P8(2, 0, true, 0); break;
-            case 3: VLSAT_P8(2, 0, true, 1); break;
-            case 4: VLSAT_P8(2, 1, false, 0); break;
-            case 25: VLSAT_P8(2, 6, false, 1); break;
-            case 27: VLSAT_P8(2, 6, true, 1); break;
-            default: return 1;
-        }
-#ifdef VLSAT_EXPERIMENTS
-    } else if (a.ablate && key == 27) {               // timing experiments on the gathered-row launch
-        switch (a.ablate) {
-            case 1: VLSAT_P8_K(0, 6, true, 2, 256); break;
-            default: VLSAT_P8_K(0, 6, true, 2, 512); break;
-        }
-    } else if (a.ablate && key == 1) {                // timing experiments (tools/p8_check.py --ablate)
-        switch (a.ablate) {
-            case 1: VLSAT_P8_ABL(1); break;
-            case 2: VLSAT_P8_ABL(2); break;
-            case 3: VLSAT_P8_ABL(3); break;
-            case 4: VLSAT_P8_ABL(4); break;
-            case 6: VLSAT_P8_ABL(6); break;
-            case 7: VLSAT_P8_ABL(7); break;
-            case 8: VLSAT_P8_ABL(8); break;
-            case 5: VLSAT_P8_ABL(5); break;
-            case 37: VLSAT_P8_ABL(37); break;
-            case 65: VLSAT_P8_ABL(65); break;
-            default: VLSAT_P8_ABL(15); break;
-        }
-#endif
-    } else {
-        if (a.half_f16) {                     // MODE 3: fp16 operands; output fp32 (CF 0) or fp16 half rows (CF 3)
-            switch (add * 4 + (a.relu_a ? 2 : 0) + (c16 ? 1 : 0)) {
-                case 0: VLSAT_P8(3, 0, false, 0); break;
-                case 1: VLSAT_P8(3, 0, false, 3); break;
-                case 2: VLSAT_P8(3, 0, true, 0); break;
-                case 3: VLSAT_P8(3, 0, true, 3); break;
-                case 25: VLSAT_P8(3, 6, false, 3); break;
-                case 27: VLSAT_P8(3, 6, true, 3); break;
-                default: return 1;
-            }
-        } else
-        switch (key) {
-            case 0: if (c16) VLSAT_P8(0, 0, false, 3); else VLSAT_P8(0, 0, false, 0); break;
-            case 1: VLSAT_P8(0, 0, false, 2); break;
-            case 2: VLSAT_P8(0, 0, true, 0); break;
-            case 3: VLSAT_P8(0, 0, true, 2); break;
-            case 4: VLSAT_P8(0, 1, false, 0); break;
-            case 5: VLSAT_P8(0, 1, false, 2); break;
-            case 25: VLSAT_P8(0, 6, false, 2); break;
-            case 27: VLSAT_P8(0, 6, true, 2); break;
-            default: return 1;
-        }
-    }
-#undef VLSAT_P8_ABL
-#undef VLSAT_P8
-#undef VLSAT_P8_K
-    if (dry) return 0;
+// one kernel pointer per row of the variant list (gemm_plan.h), in its order: taking the address is what instantiates a row
+typedef void (*P8Kernel)(GemmArgs, int, int);
+#define VLSAT_P8_KERNEL(...) gemm_p8_kernel<__VA_ARGS__>,
+constexpr P8Kernel kP8Kernels[] = {VLSAT_GEMM_P8_VARIANTS(VLSAT_P8_KERNEL)};
+#undef VLSAT_P8_KERNEL
+static_assert(sizeof kP8Kernels / sizeof kP8Kernels[0] == kGemmP8Count, "one kernel per row of the variant list");
+
+// full rounds of a large-M launch on 256 x 256 tiles: half-row bf16 / fp16 operands (prec 1), exact fp32 (prec 0) or split-bf16
+// on split-pair operands (prec 3).  Which launches come here, and as which row, is plan_gemm with gemm_p8_pick.
+// (round 4, measured and dropped: loading the accumulator inits of the wave tile's second row half one phase later, under
+//  the MFMAs of phases 1 / 2 -- fp32 nn_edge.0 + gathered rows 923 vs 917 us, out-projection + residual 480 vs 483: the
+//  cost of additive operands is not latency at the start of a tile; it is consistent with every CU pulling its 256-512 KB at the same
+//  moment: 64-128 MB per round of tiles at what the memory system delivers)
+int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    hipLaunchKernelGGL(kP8Kernels[p.variant], dim3(p.grid), dim3(512), 0, s, a, p.n_tiles, a.N / P8_BN);
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_p8");
     return 0;

@@ -303,45 +303,16 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(GemmArgs p, int n_til
 
 }  // namespace
 
-template <int T, int S, int ADD>
-static void ring_launch(bool wide, const GemmArgs& a, int n_tiles, int nbn, int grid, hipStream_t s) {
-    if constexpr (T == 1 && S >= 2) {          // half-row A, one plane: 64-wide slices whenever K allows
-        if (!wide && a.K % 128 == 0 && !a.ring_bk32 && !a.ring_nodb) {
-            hipLaunchKernelGGL((gemm_ring_kernel<T, S, ADD, 128, 64, true>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn);
-            return;
-        }
-        if (!wide && a.K % 64 == 0 && !a.ring_bk32) {
-            hipLaunchKernelGGL((gemm_ring_kernel<T, S, ADD, 128, 64>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn);
-            return;
-        }
-    }
-    if (!wide) hipLaunchKernelGGL((gemm_ring_kernel<T, S, ADD, 128>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn);
-    else hipLaunchKernelGGL((gemm_ring_kernel<T, S, ADD, 256>), dim3(grid), dim3(512), 0, s, a, n_tiles, nbn);
-}
+// one kernel pointer per row of the variant list (gemm_plan.h), in its order: taking the address is what instantiates a row
+typedef void (*RingKernel)(GemmArgs, int, int);
+#define VLSAT_RING_KERNEL(...) gemm_ring_kernel<__VA_ARGS__>,
+constexpr RingKernel kRingKernels[] = {VLSAT_GEMM_RING_VARIANTS(VLSAT_RING_KERNEL)};
+#undef VLSAT_RING_KERNEL
+static_assert(sizeof kRingKernels / sizeof kRingKernels[0] == kGemmRingCount, "one kernel per row of the variant list");
 
-// full rounds of a large-M bf16 launch; returns 1 if this operand combination is not built (the caller then uses the
-// 128 x 128 kernel for everything); dry: decide only
-int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s, bool dry) {
-    const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
-    if (a.rowscale || (add != 0 && add != 1 && add != 6)) return 1;
-    const bool wide = rbn == 256;
-    const int nbn = (a.N + rbn - 1) / rbn;
-#define VLSAT_RING(T, S, ADD) do { if (!dry) ring_launch<T, S, ADD>(wide, a, n_tiles, nbn, grid, s); } while (0)
-#define VLSAT_RING_ADD(T, S)                      \
-    switch (add) {                                \
-        case 0: VLSAT_RING(T, S, 0); break;       \
-        case 1: VLSAT_RING(T, S, 1); break;       \
-        default: VLSAT_RING(T, S, 6); break;      \
-    }
-    if (a.prec == 3) {
-        if (a.a_split == 2) return 1;
-        if (a.a_split) { VLSAT_RING_ADD(3, 1) } else { VLSAT_RING_ADD(3, 0) }
-    } else {
-        if (a.a_split == 2 && a.half_f16) { VLSAT_RING_ADD(1, 3) } else if (a.a_split == 2) { VLSAT_RING_ADD(1, 2) } else if (a.a_split) { VLSAT_RING_ADD(1, 1) } else { VLSAT_RING_ADD(1, 0) }
-    }
-#undef VLSAT_RING_ADD
-#undef VLSAT_RING
-    if (dry) return 0;
+// full rounds of a large-M bf16 launch; which launches come here, and as which row, is plan_gemm with gemm_ring_pick
+int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    hipLaunchKernelGGL(kRingKernels[p.variant], dim3(p.grid), dim3(512), 0, s, a, p.n_tiles, (a.N + p.bn - 1) / p.bn);
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_bf16_ring");
     return 0;

@@ -20,8 +20,6 @@
 
 namespace vlsat {
 
-constexpr int BK = 32;    // k-slice held in LDS per pipeline stage
-
 // residual element (ml, nl) of the tile whose first element is rbase = resid + m0 * ldr + n0, in the operand's format:
 // 0 fp32, 1 split-pair word, 2 half row (bf16 at byte 2 * column of the fp32-pitched row)
 // ---- accumulator-side access of the GEMM kernels -------------------------------------------------------------------------
@@ -779,30 +777,5 @@ template <int BM, int BN> struct PipeSel<BM, BN, 9> { using type = PipeSplitDma<
 template <int BM, int BN> struct PipeSel<BM, BN, 11> { using type = PipeSplitDma<BM, BN, 3, 1>; };
 template <int BM, int BN> struct PipeSel<BM, BN, 13> { using type = PipeSplitDma<BM, BN, 1, 2>; };  // ... A as half rows (bf16)
 template <int BM, int BN> struct PipeSel<BM, BN, 15> { using type = PipeSplitDma<BM, BN, 1, 3>; };  // ... A as half rows of fp16, fp16 weight plane
-
-// the byte offsets of rows [0, rows + 256) of an operand with a pitch of ld floats fit in 32 bits (LDS-direct loads, buffer descriptors)
-inline bool offsets32(size_t rows, size_t ld) { return (rows + 256) * ld * 4 < (1ull << 32); }
-
-// PipeSel code of the persistent (gemm_f32.hip) and split-K (gemm_splitk.hip) kernels for a launch's operands: exact fp32 without
-// ReLU-on-A and the bf16 modes take the LDS-direct pipes (codes 4..15) where the operands allow it; -1 = no pipe (*why: the reason).
-// relu_a: ReLU-on-A of the launch -- of either problem of a pair, which then both take the staging pipe (same products).
-// add_modes: the LDS-direct pipes only for the additive modes the persistent kernel instantiates them for (none, residual, both
-// gathered rows); the split-K kernel has every mode on every pipe.
-inline int gemm_pipe_prec(const GemmArgs& a, bool relu_a, bool add_modes, const char** why = nullptr) {
-    const int add = (a.resid ? 1 : 0) | (a.g0 ? 2 : 0) | (a.g1 ? 4 : 0);
-    const bool dma_ok = !a.no_dma && (!add_modes || add == 0 || add == 1 || add == 6) && offsets32(a.M, a.lda) && offsets32(a.N, a.ldw);
-    int prec = a.prec;
-    if (prec == 0 && dma_ok && !relu_a) prec = 4;
-    if (a.a_split == 2 && !(prec == 1 && dma_ok)) {
-        if (why) *why = "gemm: half-row A needs the single-rounding bf16 precision and the LDS-direct pipe";
-        return -1;
-    }
-    if ((prec == 1 || prec == 3) && dma_ok) return prec + (a.a_split == 2 ? (a.half_f16 ? 14 : 12) : a.a_split ? 8 : 4);   // bf16 modes: A split on the fragment-read side, so ReLU-on-A is fine
-    if (a.a_split) {
-        if (why) *why = "gemm: split-pair A needs a bf16 precision and the LDS-direct pipe";
-        return -1;
-    }
-    return prec;
-}
 
 }  // namespace vlsat

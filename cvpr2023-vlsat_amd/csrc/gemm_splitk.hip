@@ -11,7 +11,6 @@
 // (gemm_f32.hip): accumulator init from residual / gathered rows, row scale, bias, activation, scale, output format.
 // Soak: tools/splitk_soak.py (42 000 launches of six shapes, alone and next to a stream of large matmuls: every result
 // bit-identical to the first); kernel tests: tests/test_hip_kernels.py::test_gemm_splitk_*.
-#include <algorithm>
 #include "gemm_core.h"
 #include "kernels.h"
 
@@ -108,49 +107,19 @@ __global__ __launch_bounds__(256, 2) void gemm_splitk_kernel(GemmArgs pa, GemmAr
 
 }  // namespace
 
-// Decides whether the launch is one of the small ones this kernel is for: 0 = yes (p: its geometry), 1 = not applicable (the caller
-// falls through to the persistent kernel).
-int plan_gemm_splitk(const GemmArgs& a, int slots, GemmPlan& p) {
-    if (!a.sk_ws || !a.sk_counters) return 1;
-    const long nbm = (a.M + 63) / 64, nbn = (a.N + 63) / 64, T = nbm * nbn;
-    const int total = a.K / BK;                                      // k-slices
-    if (total < 4 || T > slots / 2 || (a.sk_max_tiles > 0 && T > a.sk_max_tiles)) return 1;      // at least two parts of >= 2 slices, and room for them
-    // as many parts as fill the resident slots once, each at least two slices (64 of K) long
-    int ks = (int)std::min<long>(total / 2, std::max<long>(1, slots / T));
-    ks = std::min(ks, 16);
-    if (ks < 2) return 1;
-    const int slices = (total + ks - 1) / ks;
-    ks = (total + slices - 1) / slices;                              // no empty parts
-    if ((size_t)T * ks * 4096 > a.sk_ws_floats || (size_t)T > a.sk_n_counters) return 1;
-    if (gemm_pipe_prec(a, a.relu_a, false) < 0) return 1;
-    p.family = GemmPlan::SPLITK;
-    p.rows = a.M;
-    p.bm = p.bn = 64;
-    p.ks = ks;
-    p.slices = slices;
-    p.n_tiles = (int)T;
-    p.grid = (int)((T + 7) / 8) * 8 * ks;
-    return 0;
-}
+// single and twin form of every row of the variant list (gemm_plan.h), in its order: taking the address is what instantiates them
+typedef void (*SplitkKernel)(GemmArgs, GemmArgs, int, int, int, int, float*, unsigned*, float*, unsigned*);
+#define VLSAT_SK_KERNELS(PREC) {gemm_splitk_kernel<PREC, false>, gemm_splitk_kernel<PREC, true>},
+constexpr SplitkKernel kSplitkKernels[][2] = {VLSAT_GEMM_SPLITK_VARIANTS(VLSAT_SK_KERNELS)};
+#undef VLSAT_SK_KERNELS
+static_assert(sizeof kSplitkKernels / sizeof kSplitkKernels[0] == kGemmSplitkCount, "one pair of kernels per row of the variant list");
 
-// twin: a second problem of the same shape and flags whose own plan is p (launch_gemm_pair has checked both), in the same launch:
-// each problem is computed as it would be alone.
+// twin: a second problem of the same shape and flags whose own plan is p (gemm_pair_plan has checked both, and that their workspaces
+// differ), in the same launch: each problem is computed as it would be alone.
 int launch_gemm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s, const GemmArgs* twin) {
-    if (twin && (twin->sk_ws == a.sk_ws || twin->sk_counters == a.sk_counters)) return 1;
     const GemmArgs& b = twin ? *twin : a;
-    const int nbn = (a.N + 63) / 64;
-    // (a pair takes the staging pipe that can apply ReLU to A if either needs it: same products)
-#define VLSAT_SK_CASE(PREC) \
-    case PREC: \
-        if (twin) hipLaunchKernelGGL((gemm_splitk_kernel<PREC, true>), dim3(p.grid, 2), dim3(256), 0, s, a, b, p.n_tiles, nbn, p.ks, p.slices, a.sk_ws, a.sk_counters, b.sk_ws, b.sk_counters); \
-        else hipLaunchKernelGGL((gemm_splitk_kernel<PREC, false>), dim3(p.grid), dim3(256), 0, s, a, a, p.n_tiles, nbn, p.ks, p.slices, a.sk_ws, a.sk_counters, a.sk_ws, a.sk_counters); \
-        break;
-    switch (gemm_pipe_prec(a, a.relu_a || b.relu_a, false)) {
-        VLSAT_SK_CASE(0) VLSAT_SK_CASE(1) VLSAT_SK_CASE(3) VLSAT_SK_CASE(4) VLSAT_SK_CASE(5) VLSAT_SK_CASE(7)
-        VLSAT_SK_CASE(9) VLSAT_SK_CASE(11) VLSAT_SK_CASE(13) VLSAT_SK_CASE(15)
-        default: return 1;
-    }
-#undef VLSAT_SK_CASE
+    hipLaunchKernelGGL(kSplitkKernels[p.variant][twin ? 1 : 0], dim3(p.grid, twin ? 2 : 1), dim3(256), 0, s, a, b, p.n_tiles, (a.N + 63) / 64, p.ks, p.slices,
+                       a.sk_ws, a.sk_counters, b.sk_ws, b.sk_counters);
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_splitk");
     return 0;

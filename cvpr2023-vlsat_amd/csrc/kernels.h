@@ -5,90 +5,21 @@
 #include <stdint.h>
 
 #include "flash_pick.h"
+#include "gemm_plan.h"
 
 namespace vlsat {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }     // a: a power of two (scratch carving)
 
-enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
-
-// C[M,N] = act(rowscale[m]*(reluA?(A) . W^T) + bias[n] + resid_scale*resid[m,n] + g0[gi0[m],n] + g1[gi1[m],n])
-struct GemmArgs {
-    const float* A = nullptr; int lda = 0;      // [M,K]
-    const float* W = nullptr; int ldw = 0;      // [N,K]  (nn.Linear layout)
-    float* C = nullptr;       int ldc = 0;      // [M,N]
-    int M = 0, N = 0, K = 0;
-    const float* bias = nullptr;                // [N]
-    const float* rowscale = nullptr;            // [M]
-    const float* resid = nullptr; int ldr = 0; float resid_scale = 1.f;
-    const float* g0 = nullptr; const int32_t* gi0 = nullptr; int ldg0 = 0;   // gathered row add
-    const float* g1 = nullptr; const int32_t* gi1 = nullptr; int ldg1 = 0;
-    int relu_a = 0;                             // apply ReLU to A while staging
-    int act = ACT_NONE;
-    // split-bf16 path: prec 0 = exact fp32 MFMA, 1 = bf16, 3 = bf16x3; weights pre-split [N,K] bf16 (ldw shared)
-    int prec = 0;
-    const uint16_t* Whi = nullptr;
-    const uint16_t* Wlo = nullptr;
-    long long* clock_probe = nullptr;           // optional [grid][4] DVFS probe buffer (vlsat_debug_gemm_clock_probe)
-    // storage format of A / the residual / C: 0 fp32, 1 split-pair words (common.h pack_split; split-bf16 mode),
-    // 2 half rows (bf16 values at byte 2 * column of an fp32-pitched row; single-rounding modes)
-    int a_split = 0, r_split = 0, c_split = 0;
-    float c_scale = 1.f;                        // final multiplier of C (after bias / activation)
-    int ablate = 0;                             // timing experiments on the ring kernel: bit 0 no operand loads after the first slices, bit 1 no MFMAs, bit 2 (8-phase kernel) no fragment reads (results are garbage)
-    int ring_nodb = 0;                          // experiment: half-row ring kernel without the double-buffered fragment sets
-    int ring_bk32 = 0;                          // experiment: half-row ring kernel with 32-wide k slices (default 64 where K allows)
-    int ring_wide = 0;                          // experiment: bf16 ring kernel with 128 x 256 tiles where N allows (measured equal)
-    int no_ring = 0;                            // debug: keep large bf16 launches on the two-stage 128 x 128 kernel
-    int no_p8 = 0;                              // debug: large launches skip the 256 x 256 8-phase kernel (gemm_bf16_p8.hip)
-    int p8_part_min = 0;                        // 8-phase kernel: tiles from which a remainder rides along as balanced rounds / a partial round (0: the built-in bound, 32 in bf16, 5/8 of a round otherwise)
-    int sk_max_tiles = 0;                       // split-K kernel only for launches of at most this many 64 x 64 tiles (0: half the resident slots, the rule of rounds 2-5)
-    int k_rot = 0;                              // A-B: the column tiles of a row panel walk their K-tiles rotated by tn * k_rot (8-phase kernel: siblings re-read the A panel out of step)
-    // fp16 additive tables (round 6; the single-rounding modes): the first c_f16_cols columns of C (a multiple of the block tile's width) are
-    // stored as fp16 HALF ROWS (element n at byte 2 n of the fp32-pitched row, values clamped to +-65504) -- what the node-side projection
-    // writes for [P_i | P_j]; g_f16: g0 / g1 are such half rows (launches without a residual).  Halves the bytes nn_edge.0 gathers per edge.
-    int c_f16_cols = 0, g_f16 = 0;
-    // fp16 half-row OPERANDS (precision mode "fp16_mixed"): A (a_split == 2) holds fp16 instead of bf16, Whi is an fp16 plane, the products run on
-    // v_mfma_f32_32x32x16_f16 (same rate as bf16 on CDNA4, 2^-12 instead of 2^-9 per operand); half-row outputs then go through c_f16_cols == N
-    int half_f16 = 0;
-    int force_tile = 0;                         // experiment (tools/gemm_tile_sweep.py): 1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 64x64 tiles of gemm_f32_kernel, whatever the heuristic says
-    int prefetch = -1;                          // bf16 LDS-direct pipe: slices of look-ahead of the A-panel prefetch (0 off, -1 default)
-    int no_dma = 0;                             // debug: VGPR-staged fp32 operands instead of LDS-direct (vlsat_debug_option "gemm_dma")
-    long* launches = nullptr;                   // optional host counter, +1 per kernel launched (profiling)
-    // split-K path of small launches (gemm_splitk.hip): partial-sum workspace + per-tile arrival counters (zero between
-    // launches), owned by the caller and private to the stream the launch goes to; null = never split
-    float* sk_ws = nullptr; size_t sk_ws_floats = 0;
-    unsigned* sk_counters = nullptr; size_t sk_n_counters = 0;
-};
+// ---- GEMM: GemmArgs, GemmPlan, the lists of the kernels that exist and the planner are gemm_plan.h (no HIP header) ----
 int launch_gemm(const GemmArgs& a, hipStream_t s);
-// The first launch of a GEMM as the planner of launch_gemm (gemm_f32.hip plan_gemm) chooses it: kernel family, geometry, and the
-// rows [0, rows) it covers -- the rows after them are planned again as a problem of their own (the tail).
-struct GemmPlan {
-    enum Family { SPLITK, P8, RING, TILED };
-    int family = TILED;
-    int rows = 0;
-    int bm = 64, bn = 64;           // output tile (8-phase: 256 x 256; ring: 32768 / bn x bn)
-    int ksl = 1, slot_mult = 2;     // persistent kernel: k-slices per pipeline step, resident blocks per CU its grid is sized for
-    int ks = 0, slices = 0;         // split-K: parts of the k range, k-slices per part
-    int n_tiles = 0, grid = 0;
-};
-// small launches: k range cut over several CUs, deterministic in-kernel reduction.  plan: 0 = this kernel takes the launch (p),
-// 1 = not applicable; launch: runs the plan, twin = a second problem whose own plan is p in the same launch (1 = not pairable)
-int plan_gemm_splitk(const GemmArgs& a, int slots, GemmPlan& p);
-int launch_gemm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s, const GemmArgs* twin = nullptr);
 // two problems of the same shape and flags in ONE launch (round 6: the 3D / 2D twins of a one-scene forward): 0 = launched,
-// 1 = not pairable: invalid or different problems, or plans of launch_gemm that are not the same single launch of a kernel with a
-// twin form (split-K, one round of 64 x 64 tiles at two k-slices per step).  The caller then launches them one after the other;
-// results are bit-identical either way
+// 1 = not pairable (gemm_pair_plan).  The caller then launches them one after the other; results are bit-identical either way
 int launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s);
-constexpr size_t SPLITK_WS_FLOATS = (size_t)768 * 4096;    // room for 768 partial 64 x 64 tiles (12 MB)
-constexpr size_t SPLITK_COUNTERS = 512;
-// bf16 modes, full rounds of large-M launches: 3-stage LDS ring, 256 x 128 tiles, one 8-wave block per CU
-// (gemm_bf16_ring.hip); returns 1 if the operand combination is not built.  dry: decide only (the planner), launch nothing
-int launch_gemm_ring(const GemmArgs& a, int rbn, int n_tiles, int grid, hipStream_t s, bool dry = false);   // rbn: tile width 128 | 256
-// full rounds of large-M launches, exact fp32 or single-rounding bf16 with half-row A: 256 x 256 tiles, 8-phase pipeline,
-// one 8-wave block per CU (gemm_bf16_p8.hip); needs N % 256 == 0, K % 128 == 0; returns 1 if the combination is not built.
-// dry: decide only (the planner), launch nothing
-int launch_gemm_p8(const GemmArgs& a, int n_tiles, int grid, hipStream_t s, bool dry = false);
+// the launch of a plan of that family on rows [0, a.M): table[p.variant]; twin: a second problem whose own plan is p, in the same launch
+int launch_gemm_splitk(const GemmArgs& a, const GemmPlan& p, hipStream_t s, const GemmArgs* twin = nullptr);
+int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 double gemm_flops(const GemmArgs& a);
 void gemm_set_clock_probe(long long* buf);
 

@@ -66,12 +66,26 @@ def _flash_release_rows():
     return [tuple(a.strip() for a in row.split(",")) for row in re.findall(r"\bX\(([^)]*)\)", body)]
 
 
+def _gemm_release_rows(macro):
+    """the rows of a release variant list of csrc/gemm_plan.h (the text between its #define and the next comment line), as tuples of strings"""
+    import re
+    src = open(os.path.join(ROOT, "cvpr2023-vlsat_amd", "csrc", "gemm_plan.h")).read()
+    body = src[src.index("#define " + macro + "(X)"):]
+    body = body[:body.index("\n//")]
+    rows = [tuple(a.strip() for a in row.split(",")) for row in re.findall(r"\bX\(([^)]*)\)", body)]
+    assert rows and len(rows) == len(set(rows)), (macro, rows)
+    return rows
+
+
 def test_release_library_carries_no_lab_code(L):
     """The in-tree build is the RELEASE library (csrc/common.h): no timing-ablation instantiation of the 8-phase GEMM (template
     argument ABL != 0 -- "results are garbage" by their own comment), and the lab switches of vlsat_debug_option are refused
     (they exist in `build.py --experiments` -> tools/bin/libvlsat_hip_exp.so only).  The bf16 edge attention: the instantiations in the
     library are exactly the release rows of the variant list of csrc/flash_pick.h (every row has a kernel, nothing else has), 26 of
-    them, none with ABL != 0 or a ring of more than 2 tile buffers."""
+    them, none with ABL != 0 or a ring of more than 2 tile buffers.  The GEMM: the instantiations of its four kernels are exactly the
+    release rows of the four lists of csrc/gemm_plan.h -- 27 of gemm_p8_kernel, 30 of gemm_ring_kernel (none on 128 x 256 tiles: those 18
+    are kernels of the experiments build), 193 of gemm_f32_kernel (34 rows on five tiles, 23 of them as a twin too), 20 of
+    gemm_splitk_kernel (10 rows, single and twin)."""
     import re
     import shutil
     import subprocess
@@ -80,6 +94,21 @@ def test_release_library_carries_no_lab_code(L):
     p8 = re.findall(r"gemm_p8_kernel<(\d+), (\d+), (?:true|false), (\d+), (\d+)>", out)
     assert p8, "nm shows no gemm_p8_kernel instantiation at all"
     assert all(abl == "0" for *_, abl in p8), sorted(set(p8))
+
+    def built(kernel):
+        return {tuple(a.split(", ")) for a in re.findall(kernel + r"<([^>]*)>", out)}
+    p8_rows = {r + ("0",) for r in _gemm_release_rows("VLSAT_GEMM_P8_RELEASE")}
+    ring_rows = set(_gemm_release_rows("VLSAT_GEMM_RING_RELEASE"))
+    tiled = _gemm_release_rows("VLSAT_GEMM_TILED_VARIANTS")
+    tiles = [("128", "128", "1"), ("128", "64", "1"), ("64", "128", "1"), ("64", "64", "1"), ("64", "64", "2")]
+    tiled_rows = {(bm, bn, add, prec, ksl, "false") for add, prec, _ in tiled for bm, bn, ksl in tiles}
+    tiled_rows |= {("64", "64", add, prec, "2", "true") for add, prec, twin in tiled if twin == "true"}
+    sk_rows = {(prec, twin) for (prec,) in _gemm_release_rows("VLSAT_GEMM_SPLITK_VARIANTS") for twin in ("false", "true")}
+    for kernel, rows, n in (("gemm_p8_kernel", p8_rows, 27), ("gemm_ring_kernel", ring_rows, 30), ("gemm_f32_kernel", tiled_rows, 193),
+                            ("gemm_splitk_kernel", sk_rows, 20)):
+        assert len(rows) == n, (kernel, len(rows))
+        assert built(kernel) == rows, (kernel, sorted(built(kernel) - rows), sorted(rows - built(kernel)))
+    assert all(r[3] == "128" for r in built("gemm_ring_kernel")), sorted(built("gemm_ring_kernel"))
     fa = {tuple(a.split(", ")) for a in re.findall(r"flash_attn_bf16_kernel<([^>]*)>", out)}
     rows = _flash_release_rows()
     assert len(rows) == len(set(rows)) == 26 and all(len(r) == 10 for r in rows), rows
@@ -241,6 +270,41 @@ def test_flash_pick_chooses_what_the_cascade_chose_before_it(build):
     assert rows["legacy"] == f"ok {11520 * n} cases, {1104 * n} launches, {0 if lab else 24} ring-of-2 for ring-of-3/4"
     assert rows["reachable"] == ("ok 38" if lab else "ok 26")
     assert rows["block"] == f"ok {38 if lab else 26} rows, 26 without ABL or a ring above 2"
+
+
+@pytest.mark.parametrize("build", ["plain", "asan_ubsan", "experiments"])
+def test_gemm_plan_chooses_what_the_launchers_chose_before_it(build):
+    """csrc/gemm_plan.h compiled by g++ (tests/gemm_plan_check.cpp, which keeps the planner and the four launcher dispatches the library
+    had before the lists word for word): whole launch sequences -- plan, tail, plan again -- of old and new code, compared launch by
+    launch in family, rows, tile, k-slices per step, slot multiplier, split-K parts and slices, tiles, grid, block, kernel arguments and
+    the kernel's template arguments; for refused problems the error text.  1 413 120 problems: G {512, 608, 8} x 12 M x 8 N x 8 K x two
+    pitches of A x 8 operand formats = 36 864 shapes and formats, each with every other switch of the enumeration varied one at a time
+    from the baseline (21 variations: 774 144); the switches that name a row varied together (additive mode 0..7 x ReLU-on-A x format of
+    C x fp16 columns x no_dma x no_p8 = 576) over 60 shapes x 8 formats (276 480); and the planner's thresholds from both sides (M at
+    every multiple of 64 up to 10 240 and one past it, around part_min / rem_min of each precision, N around the 64 x 128 rule's window,
+    K = 192: 362 496).  Pairs: 2 027 520 twins that differ in nothing, in ReLU-on-A only, in one shape field, or share a workspace.  No
+    difference is permitted.  Every row of every list is reached, and every twin form.  "asan_ubsan": the same stand-alone binary under
+    ASan + UBSan; "experiments": the lists with the lab rows (13 ablations of the 8-phase kernel, 18 ring rows on 128 x 256 tiles) and
+    ring_wide, ring_bk32, ring_nodb, force_tile 1..7 and ablate enumerated too.  The program also prints the launch sequences of the
+    bench batch's shapes (the planner section)."""
+    import select_host
+    lab = build == "experiments"
+    out = select_host.run(build == "asan_ubsan", "gemm_plan_check", ("VLSAT_EXPERIMENTS",) if lab else ())
+    rows = dict(r for r in out if len(r) == 2)
+    assert set(rows) == {"legacy", "pairs", "reachable", "lists", "bench"}, rows
+    assert all(v.split()[0] == "ok" for v in rows.values()), rows
+    if not lab:
+        assert rows["legacy"].startswith("ok 1413120 cases (774144 one switch at a time, 276480 operand products, 362496 thresholds)"), rows["legacy"]
+    assert rows["pairs"].startswith("ok 2027520 pairs, "), rows["pairs"]
+    assert rows["reachable"] == ("ok 8-phase 40, ring 48, persistent 34 (23 with a twin form), split-K 10" if lab else
+                                 "ok 8-phase 27, ring 30, persistent 34 (23 with a twin form), split-K 10")
+    assert rows["lists"] == ("ok 18 ring rows with 128 x 256 tiles, 13 ablations" if lab else "ok 0 ring rows with 128 x 256 tiles, 0 ablations")
+    table = [r[0] for r in out if len(r) == 1 and r[0].startswith("table |")]
+    assert len(table) == 3 * 9, table
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    if not lab:
+        for line in table:
+            assert line[len("table "):] in design, line          # the table in DESIGN.md is this program's output
 
 
 def test_product_package_never_imports_the_oracle():
