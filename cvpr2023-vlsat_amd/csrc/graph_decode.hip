@@ -21,6 +21,7 @@
 //                     64-bit global atomic per counter and block: exact and order-independent.
 // Integer / latency-bound work: no MFMA.
 #include "common.h"
+#include "decode_core.h"
 #include "kernels.h"
 #include "select_core.h"
 
@@ -40,17 +41,7 @@ __device__ __forceinline__ bool gd_asserted(float r, int k, int R, const float* 
     const bool in = k < R;
     const bool pass = in && r >= thr[in ? k : 0];
     if (multi) return pass;
-    float bv = in ? r : -INFINITY;                 // arg-max of the row, lowest index among equals
-    int bi = k;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 32);
-        const int oi = __shfl_xor(bi, o, 32);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
+    const int bi = gd_pick(r, k, R);               // arg-max of the row, lowest index among equals (every lane calls: shuffles)
     return pass && k == bi && k != 0;
 }
 
@@ -226,24 +217,8 @@ __global__ __launch_bounds__(256) void gd_counts_kernel(const float* __restrict_
     } else {
         int nodes = 0, hit = 0;
         for (int n = ((int)blockIdx.x - nbe) * 4 + (threadIdx.x >> 6); n < N; n += ((int)gridDim.x - nbe) * 4) {
-            float bv = -INFINITY;
-            int bi = INT32_MAX;
-            for (int c = lane; c < C; c += 64) {
-                const float v = probs[(size_t)n * C + c];
-                if (bi == INT32_MAX || v > bv) {
-                    bv = v;
-                    bi = c;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o);
-                const int oi = __shfl_xor(bi, o);
-                if (oi != INT32_MAX && (bi == INT32_MAX || ov > bv || (ov == bv && oi < bi))) {
-                    bv = ov;
-                    bi = oi;
-                }
-            }
+            float bv;
+            const int bi = gd_top1(probs + (size_t)n * C, C, lane, bv);
             ++nodes;
             hit += gt_cls[n] == bi;
         }

@@ -10,7 +10,7 @@ counts reproduce ``get_mean_recall`` (eva_utils_acc.py:224-237) and ``compute_me
 (model.py:364-388)."""
 from __future__ import annotations
 
-from typing import Dict, Iterable
+from typing import Dict, Iterable, Optional
 
 import numpy as np
 import torch
@@ -590,6 +590,129 @@ def graph_quality(counts, n_rel: int = N_REL) -> Dict[str, float]:
     for name, m, M_, p in zip(("precision", "recall", "f1"), micro, macro, per):
         out[f"micro_{name}"], out[f"macro_{name}"], out[f"per_class_{name}"] = float(m), M_, p
     return out
+
+
+def operating_points(tables, default: float = 0.5) -> Dict[str, object]:
+    """PR curves, average precision, per-predicate thresholds and the calibration of the object head, on the host, from the
+    (all-reduced) ``metrics.ScoreTables`` of ``metrics.score_histograms`` / ``calibrate``.  B = ``tables.bins``; threshold k / B.
+    Predicate head -- ``precision`` / ``recall`` / ``f1`` float64 [R, B] at every k (NaN where the denominator is 0);
+    ``k`` int64 [R] and ``threshold`` float32 [R] (a tensor ready for ``decode_graph(threshold=...)``): the k of the best F1, the
+    lowest k among equals; a predicate without ground truth keeps ``default`` (which must be a multiple of 1 / B in [0, 1): nothing
+    else can be read off the table); ``tp`` / ``fp`` / ``fn`` int64 [R] at that choice (``counts`` [3 R]: the same in
+    ``decode_counts`` order) -- ``decode_counts(threshold=threshold)`` over the same data reproduces them exactly;
+    ``ap`` float64 [R]: non-interpolated average precision at bin resolution, sum over k of (recall_k - recall_{k+1}) precision_k
+    with recall_B = 0 (NaN without ground truth), ``mean_ap`` over the predicates that occur; ``micro_f1`` / ``macro_f1`` at the
+    chosen vector beside ``micro_f1_default`` / ``macro_f1_default`` at ``default``, as ``graph_quality`` defines them (macro:
+    over the predicates with tp + fp + fn > 0, a value whose denominator is 0 counting as 0).
+    Object head -- ``obj_bin_count`` int64 [B] and ``obj_bin_acc`` float64 [B] (NaN for an empty bin): the reliability diagram of the
+    top-1 probability; ``ece`` = sum over the bins of count / total * |accuracy - (b + 0.5) / B|: the table holds counts and no sums of
+    confidences, so a bin's confidence is its MIDPOINT (off by at most 1 / (2 B) per bin; nodes whose top-1 probability is NaN
+    are left out); ``obj_acc``; ``per_class_acc`` float64 [C] (NaN for a class without nodes) and ``mean_class_acc`` over the classes
+    that occur; ``confusion`` int64 [C, C]."""
+    t = tables.cpu()
+    b, rel = t.bins, t.rel.numpy()
+    r = rel.shape[0]
+    kd = t.k_vector(float(default))[:1].item()
+    suf = t.suffix_sums().numpy().astype(np.float64)                                   # [R, 2, B]
+    tp, fp = suf[:, 1], suf[:, 0]
+    n_gt = rel[:, 1].sum(-1).astype(np.float64)
+    fn = n_gt[:, None] - tp
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prec, rec, f1 = tp / (tp + fp), tp / (tp + fn), 2 * tp / (2 * tp + fp + fn)
+        occurs = n_gt > 0
+        k = np.where(occurs, np.argmax(np.nan_to_num(f1, nan=-1.0), axis=1), kd).astype(np.int64)       # (argmax: the first maximum)
+        rec_next = np.concatenate([rec[:, 1:], np.zeros((r, 1))], 1)
+        ap = np.where(occurs, np.nan_to_num((rec - rec_next) * np.nan_to_num(prec)).sum(1), np.nan)
+        counts = t.counts_at(torch.from_numpy(k))
+        both = {"": counts, "_default": t.counts_at(kd)}
+        out = {"bins": b, "precision": prec, "recall": rec, "f1": f1, "k": k,
+               "threshold": torch.from_numpy(k.astype(np.float32) / np.float32(b)), "counts": counts,
+               "tp": counts[0::3].clone(), "fp": counts[1::3].clone(), "fn": counts[2::3].clone(), "ap": ap,
+               "mean_ap": float(ap[occurs].mean()) if occurs.any() else float("nan")}
+        for name, c in both.items():
+            q = graph_quality(torch.cat([c, torch.zeros(2, dtype=torch.int64)]), r)
+            out["micro_f1" + name], out["macro_f1" + name] = q["micro_f1"], q["macro_f1"]
+        obj = t.obj.numpy()[:, :b].astype(np.float64)
+        cnt = obj.sum(0)
+        acc = obj[1] / cnt
+        total = cnt.sum()
+        mid = (np.arange(b) + 0.5) / b
+        out["obj_bin_count"], out["obj_bin_acc"] = cnt.astype(np.int64), acc
+        out["ece"] = float((cnt[cnt > 0] / total * np.abs(acc - mid)[cnt > 0]).sum()) if total else float("nan")
+        cm = t.confusion.numpy()
+        per = cm.sum(1).astype(np.float64)
+        out["obj_acc"] = float(np.trace(cm) / per.sum()) if per.sum() else float("nan")
+        out["per_class_acc"] = np.diag(cm) / per
+        out["mean_class_acc"] = float(out["per_class_acc"][per > 0].mean()) if (per > 0).any() else float("nan")
+        out["confusion"] = cm
+    return out
+
+
+@torch.no_grad()
+def calibrate(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d: bool = True, bins: int = 1024,
+              multi_rel_outputs: Optional[bool] = None) -> Dict[str, object]:
+    """The score histograms of this rank's ``batches`` (the loader's dicts, with ``gt_class`` and ``gt_rel_cls``), all-reduced:
+    ``{"3d": metrics.ScoreTables, "2d": metrics.ScoreTables | None}`` -- what ``operating_points`` reads.  Per batch the forward
+    (``forward_3d`` with ``use_2d=False``: ``obj_2d_feats`` is not read and "2d" is None) and ``metrics.score_histograms`` per
+    branch are enqueued back to back; nothing is read back per batch.  workers = 0: one batch after the other on the current
+    stream.  workers >= 1: as ``decode`` -- every worker thread owns a replica of the model and a stream and takes the next batch;
+    all of them add into the same table per branch (integer atomics: the sums do not depend on the order).  ONE collective at the
+    end (``dist.allreduce_metrics`` over both branches' buffers); it sums in fp64, so the counts are exact as long as every entry of
+    the summed tables stays below 2^53.  ``multi_rel_outputs`` (default: the model's) selects the rule."""
+    import threading
+    from . import metrics as M
+    workers = int(workers)
+    if workers > 0 and device is None:
+        raise ValueError("calibrate(workers > 0) needs the device")
+    cfg = model.config
+    multi = bool(cfg.multi_rel_outputs if multi_rel_outputs is None else multi_rel_outputs)
+    dev = torch.device(model.device if device is None else device)
+    tabs = [M.ScoreTables(cfg.num_rel_class, cfg.num_obj_class, bins, dev) for _ in range(2 if use_2d else 1)]
+    it, lock, errors = iter(batches), threading.Lock(), []
+
+    def one(m, b):
+        edges = b["edge_indices"]
+        ei_t = edges.t() if b.get("fc_sizes") is not None else edges.t().contiguous()
+        if use_2d:
+            obj3, obj2, rel3, rel2 = m(b["obj_points"], b["obj_2d_feats"], ei_t, b["descriptor"], b.get("batch_ids"), istrain=False,
+                                       fc_sizes=b.get("fc_sizes"))
+            outs = ((obj3, rel3), (obj2, rel2))
+        else:
+            outs = (m.forward_3d(b["obj_points"], ei_t, b["descriptor"], b.get("batch_ids"), fc_sizes=b.get("fc_sizes")),)
+        for (obj, rel), t in zip(outs, tabs):
+            M.score_histograms(obj, rel, b["gt_class"], b["gt_rel_cls"], multi, bins, tables=t)
+
+    def work(k, models):
+        try:
+            torch.cuda.set_device(dev)
+            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
+            with torch.cuda.stream(stream):
+                while not errors:
+                    with lock:
+                        b = next(it, None)
+                    if b is None:
+                        break
+                    one(models[k], b)
+            stream.synchronize()
+        except BaseException as ex:             # (re-raised in the caller's thread)
+            errors.append(ex)
+
+    if workers <= 1:
+        work(0, [model])
+    else:
+        models = [model] + model.replicas(workers - 1)
+        torch.cuda.current_stream(dev).synchronize()      # the zeroed tables and the inputs are complete before the workers touch them
+        ts = [threading.Thread(target=work, args=(k, models), daemon=True) for k in range(workers)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise errors[0]
+    vec = vdist.allreduce_metrics(torch.cat([t.buffer for t in tabs]).double())
+    parts = vec.to(torch.int64).split([t.buffer.numel() for t in tabs])
+    out = [M.ScoreTables(cfg.num_rel_class, cfg.num_obj_class, bins, buffer=p.contiguous()) for p in parts]
+    return {"3d": out[0], "2d": out[1] if use_2d else None}
 
 
 @torch.no_grad()

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlsat_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
 SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
+CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
 
 
 class VlsatDims(C.Structure):
@@ -123,10 +124,16 @@ _SIGNATURES_SPLIT = {
     "vlsat_fuse_splits": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_vp] * 15 + [_vp]),
 }
 
+# include/vlsat_calib.h: score histograms against ground truth, for thresholds and calibration (csrc/calibration.hip)
+_SIGNATURES_CALIB = {
+    "vlsat_score_hist": (C.c_int, [_vp] * 4 + [_i32] * 6 + [_vp] * 3 + [_vp]),
+    "vlsat_score_hist_geometry": (None, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
-    built from (csrc/*.hip, csrc/*.h, include/vlsat.h, build flags) -- the GPU box has no .git, so the source digest is what a
+    built from (csrc/*.hip, csrc/*.h, include/*.h, build flags) -- the GPU box has no .git, so the source digest is what a
     profile summary and a later bench run can compare; the commit is added when the summary is published (tools/)."""
     import hashlib
     path = lib_path or LIB_PATH
@@ -136,7 +143,7 @@ def identity(lib_path: str = "") -> dict:
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -160,6 +167,11 @@ def declared_split_symbols() -> list:
     return _declared(SPLIT_HEADER_PATH)
 
 
+def declared_calib_symbols() -> list:
+    """Every function include/vlsat_calib.h declares."""
+    return _declared(CALIB_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -169,7 +181,7 @@ def load():
         raise VlsatError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

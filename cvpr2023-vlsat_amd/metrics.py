@@ -685,15 +685,23 @@ def _rel_probs(rel, rel_probs, multi_rel_outputs, exp):
     return rel.float().contiguous() if multi_rel_outputs else exp(rel)
 
 
+def _eligible(rp: torch.Tensor, multi_rel_outputs: bool) -> torch.Tensor:
+    """bool [E, R]: the cells the decode can assert at some threshold -- all of them for a multi-label model, the arg-max predicate
+    of the row unless it is class 0 for a single-label one."""
+    pick = torch.ones_like(rp, dtype=torch.bool)
+    if not multi_rel_outputs and rp.shape[0]:
+        best = rp.sort(dim=1, descending=True, stable=True).indices[:, 0]                # lowest index of the row maximum
+        pick = torch.zeros_like(pick)
+        pick[torch.arange(rp.shape[0], device=rp.device), best] = True
+        pick[:, 0] = False                                                            # class 0 = none
+    return pick
+
+
 def _asserted(rp: torch.Tensor, thr: torch.Tensor, multi_rel_outputs: bool) -> torch.Tensor:
     """bool [E, R]: the decisions of the decode on predicate probabilities ``rp``."""
     on = rp >= thr[None, :]
     if not multi_rel_outputs and rp.shape[0]:
-        best = rp.sort(dim=1, descending=True, stable=True).indices[:, 0]                # lowest index of the row maximum
-        pick = torch.zeros_like(on)
-        pick[torch.arange(rp.shape[0], device=rp.device), best] = True
-        pick[:, 0] = False                                                            # class 0 = none
-        on = on & pick
+        on = on & _eligible(rp, False)
     return on
 
 
@@ -798,6 +806,147 @@ def decode_counts_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs=True, 
     out[0:3 * r:3], out[1:3 * r:3], out[2:3 * r:3] = (on & hot).sum(0), (on & ~hot).sum(0), (hot & ~on).sum(0)
     top1 = probs.sort(dim=1, descending=True, stable=True).indices[:, 0] if n else torch.zeros(0, dtype=torch.int64, device=dev)
     out[3 * r], out[3 * r + 1] = n, (top1 == gt_cls.to(torch.int64).view(-1)).sum()
+    return out
+
+
+# ---- score histograms: the counts of every threshold k / bins at once (csrc/calibration.hip, include/vlsat_calib.h) ----
+CALIB_MIN_BINS, CALIB_MAX_BINS = 16, 4096
+
+
+def _check_bins(bins) -> int:
+    bins = int(bins)
+    if not CALIB_MIN_BINS <= bins <= CALIB_MAX_BINS or bins & (bins - 1):
+        raise L.VlsatError(f"score_histograms: bins must be a power of two in {CALIB_MIN_BINS}..{CALIB_MAX_BINS}")
+    return bins
+
+
+class ScoreTables:
+    """The additive int64 tables of ``score_histograms`` (rule: include/vlsat_calib.h), views of ONE contiguous ``buffer`` so that a
+    single all-reduce takes them whole: ``rel`` [R, 2, bins + 1] (predicate, ground truth not-hot / hot, column), ``obj``
+    [2, bins + 1] (top-1 wrong / right, column of the top-1 probability), ``confusion`` [C, C] ([gt_cls, top-1]).  Column b < bins
+    holds the scores in [b / bins, (b + 1) / bins) (the last one everything from there up); column ``bins`` the cells the decode
+    asserts at no threshold (NaN, negative, or not the pick of a single-label row)."""
+    __slots__ = ("buffer", "rel", "obj", "confusion", "bins")
+
+    def __init__(self, n_rel: int, n_obj: int, bins: int = 1024, device=None, buffer: torch.Tensor | None = None):
+        self.bins = _check_bins(bins)
+        w, n_rel, n_obj = self.bins + 1, int(n_rel), int(n_obj)
+        sizes = (n_rel * 2 * w, 2 * w, n_obj * n_obj)
+        if buffer is None:
+            buffer = torch.zeros(sum(sizes), dtype=torch.int64, device=device)
+        if buffer.dtype != torch.int64 or buffer.dim() != 1 or buffer.numel() != sum(sizes) or not buffer.is_contiguous():
+            raise L.VlsatError(f"ScoreTables: the buffer must be a contiguous int64 vector of {sum(sizes)} entries")
+        self.buffer = buffer
+        a, b, c = buffer.split(sizes)
+        self.rel, self.obj, self.confusion = a.view(n_rel, 2, w), b.view(2, w), c.view(n_obj, n_obj)
+
+    def cpu(self) -> "ScoreTables":
+        return ScoreTables(self.rel.shape[0], self.confusion.shape[0], self.bins, buffer=self.buffer.cpu())
+
+    def suffix_sums(self) -> torch.Tensor:
+        """int64 [R, 2, bins]: entry [r, h, k] = the cells of predicate r and ground truth h in columns k..bins - 1, i.e. the cells
+        the decode asserts at threshold k / bins (h = 1: tp, h = 0: fp)."""
+        return self.rel[:, :, :self.bins].flip(-1).cumsum(-1).flip(-1)
+
+    def k_vector(self, k_or_thresholds) -> torch.Tensor:
+        """``k_or_thresholds`` as the int64 [R] vector of columns (on the host): an integer k or one per predicate, or floating
+        point thresholds that are multiples of 1 / bins (anything else cannot be read off the table and raises)."""
+        r = self.rel.shape[0]
+        t = torch.as_tensor(k_or_thresholds).detach().cpu().reshape(-1)
+        if t.is_floating_point():
+            x = t.double() * self.bins
+            if not bool((x == x.round()).all()):
+                raise ValueError(f"ScoreTables: a threshold must be a multiple of 1 / {self.bins}")
+            t = x.round()
+        t = t.to(torch.int64)
+        if t.numel() == 1 and r != 1:
+            t = t.expand(r)
+        if t.numel() != r or not bool(((t >= 0) & (t < self.bins)).all()):
+            raise ValueError(f"ScoreTables: one column in 0..{self.bins - 1} (or threshold in [0, 1)) per predicate ({r})")
+        return t.contiguous()
+
+    def counts_at(self, k_or_thresholds) -> torch.Tensor:
+        """int64 [3 R], tp / fp / fn of predicate r at 3 r + {0, 1, 2}: exactly what ``decode_counts`` counts at threshold
+        k / bins (its first 3 R fields)."""
+        k = self.k_vector(k_or_thresholds).to(self.rel.device)
+        s = self.suffix_sums().gather(2, k[:, None, None].expand(-1, 2, 1))[:, :, 0]                # [R, 2]
+        tp, fp = s[:, 1], s[:, 0]
+        return torch.stack([tp, fp, self.rel[:, 1].sum(-1) - tp], 1).reshape(-1)
+
+
+def _score_columns(p: torch.Tensor, eligible, bins: int) -> torch.Tensor:
+    """int64 columns of fp32 scores ``p`` under the bin rule of include/vlsat_calib.h (one fp32 multiply, floor, clamp)."""
+    ok = (p >= 0) & eligible
+    x = torch.where(ok, p, torch.zeros_like(p)) * bins
+    return torch.where(ok, x.floor().clamp(max=bins - 1).to(torch.int64), torch.full_like(x, bins, dtype=torch.int64))
+
+
+def score_histograms(obj_logits: torch.Tensor, rel: torch.Tensor, gt_cls: torch.Tensor, gt_rel: torch.Tensor,
+                     multi_rel_outputs: bool = True, bins: int = 1024, obj_probs: torch.Tensor | None = None,
+                     rel_probs: torch.Tensor | None = None, tables: ScoreTables | None = None) -> ScoreTables:
+    """Histograms of a batch's scores against ground truth (``ScoreTables``): the tp / fp / fn of ``decode_counts`` at EVERY
+    threshold k / bins in one pass (``tables.counts_at(k)``, exact), the reliability table of the object head and its confusion
+    matrix.  ``bins``: a power of two in 16..4096.  Inputs exactly as for ``decode_counts``: ``rel`` holds log-probabilities for a
+    single-label model, ``rel_probs`` overrides it, ``gt_rel`` is the int64 multi-hot [E, R] target or int64 [E] (0 = none).  A node
+    whose ``gt_cls`` is outside [0, C) is in neither node table.  Additive: pass ``tables`` (zeroed once) to accumulate over batches,
+    from several streams if need be.  ``evaluate.operating_points`` turns the sums into PR curves, AP, per-predicate thresholds
+    and calibration figures.  Device tensors: the HIP kernel, asynchronous, no host round trip.  CPU tensors:
+    ``score_histograms_host``."""
+    bins = _check_bins(bins)
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    if tables is not None and (tables.bins != bins or tables.rel.shape[0] != r or tables.confusion.shape[0] != c
+                               or tables.buffer.device != obj_logits.device):
+        raise L.VlsatError("score_histograms: tables must have the call's bins, predicate and class counts and live on its device")
+    if not obj_logits.is_cuda:
+        out = score_histograms_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs, bins, obj_probs, rel_probs)
+        if tables is None:
+            return out
+        tables.buffer.add_(out.buffer)
+        return tables
+    lib = L.load()
+    if not 1 <= c <= 1024 or not 1 <= r <= 32:
+        raise L.VlsatError("score_histograms: 1..1024 object and 1..32 relation classes")
+    gt_rel = gt_rel.to(torch.int64).contiguous()
+    if gt_rel.shape != ((e, r) if multi_rel_outputs else (e,)):
+        raise L.VlsatError("score_histograms: gt_rel must be multi-hot [E,R] (multi-label) or [E] (single label)")
+    gt_cls = gt_cls.to(torch.int64).contiguous().view(-1)
+    if gt_cls.numel() != n:
+        raise L.VlsatError("score_histograms: gt_cls must hold one class per node")
+    r_probs = _rel_probs(rel, rel_probs, multi_rel_outputs, exp_probs)
+    obj_probs = softmax_rows(obj_logits.float()) if obj_probs is None else obj_probs.float().contiguous()
+    if tables is None:
+        tables = ScoreTables(r, c, bins, obj_logits.device)
+    L.check(lib.vlsat_score_hist(obj_probs.data_ptr(), r_probs.data_ptr(), gt_cls.data_ptr(), gt_rel.data_ptr(), n, e, c, r,
+                                 int(bool(multi_rel_outputs)), bins, tables.rel.data_ptr(), tables.obj.data_ptr(),
+                                 tables.confusion.data_ptr(), L.stream_ptr()))
+    return tables
+
+
+@torch.no_grad()
+def score_histograms_host(obj_logits, rel, gt_cls, gt_rel, multi_rel_outputs=True, bins=1024, obj_probs=None,
+                          rel_probs=None) -> ScoreTables:
+    """``score_histograms`` stated in PyTorch, with the ground truth (``_gt_hot``), the probabilities (``_rel_probs``) and the
+    single-label pick (``_eligible``) of the decode's own restatement."""
+    bins = _check_bins(bins)
+    n, c = obj_logits.shape
+    e, r = rel.shape
+    dev = obj_logits.device
+    w = bins + 1
+    rp = _rel_probs(rel, rel_probs, multi_rel_outputs, lambda x: x.float().exp())
+    probs = torch.softmax(obj_logits.float(), -1) if obj_probs is None else obj_probs.float()
+    hot = _gt_hot(gt_rel.to(torch.int64), e, r, multi_rel_outputs)
+    out = ScoreTables(r, c, bins, dev)
+    col = _score_columns(rp, _eligible(rp, multi_rel_outputs), bins)
+    cell = (torch.arange(r, device=dev)[None, :] * 2 + hot.to(torch.int64)) * w + col
+    out.rel.view(-1).add_(torch.bincount(cell.reshape(-1), minlength=r * 2 * w))
+    gt = gt_cls.to(torch.int64).view(-1)
+    top1 = probs.sort(dim=1, descending=True, stable=True).indices[:, 0]                 # lowest index of the row maximum
+    conf = probs.gather(1, top1[:, None])[:, 0]
+    valid = (gt >= 0) & (gt < c)
+    ocell = (top1 == gt).to(torch.int64) * w + _score_columns(conf, True, bins)
+    out.obj.view(-1).add_(torch.bincount(ocell[valid], minlength=2 * w))
+    out.confusion.view(-1).add_(torch.bincount((gt * c + top1)[valid], minlength=c * c))
     return out
 
 
