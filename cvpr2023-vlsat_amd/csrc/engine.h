@@ -1,6 +1,7 @@
 // Internal state of libvlsat_hip.so shared by the engine translation units:
 //   engine_weights.hip  handle life cycle, weight preparation (folding / hoisting / permutations), precision modes
-//   engine_plan.hip     graph plan: host-side graph analysis, one device arena, asynchronous index upload
+//   plan_graph.h        graph plan, the host-only part: graph analysis, attention tile tables, the list of the arena's buffers
+//   engine_plan.hip     graph plan, the HIP objects: arena pool, pinned staging, asynchronous index upload
 //   engine_forward.hip  the forward orchestration (vlsat_forward / vlsat_forward_train) and per-class profiling
 //   engine_api.hip      kernel-level C entry points and debug hooks
 // The public surface is include/vlsat.h.
@@ -11,7 +12,7 @@
 namespace vlsat {
 
 // The evaluation scratch of a plan (vlsat_plan_s::ev_f / ev_i; vlsat_process_val_counts, vlsat_forward_scene_graph, vlsat_forward_graph):
-// ONE statement of its layout -- engine_plan.hip sizes the arena with eval_scratch_floats / _ints, the entry points take their
+// ONE statement of its layout -- the buffer list of plan_graph.h sizes the arena with eval_scratch_floats / _ints, the entry points take their
 // pointers from eval_scratch_carve.  N nodes, E edges (edge tables keep one row when E = 0), C object classes, R predicate classes.
 struct EvalScratch {
     float *obj3, *obj2, *prob3, *prob2;     // [N, C] each: the object logits and their softmax
@@ -37,7 +38,9 @@ inline EvalScratch eval_scratch_carve(float* f, int32_t* i, size_t N, size_t E, 
 
 }  // namespace vlsat
 
-#ifndef VLSAT_EVAL_SCRATCH_ONLY      // (tests/eval_scratch_check.cpp, a host-only program without the HIP headers, takes the layout above alone)
+#include "plan_graph.h"
+
+#ifndef VLSAT_EVAL_SCRATCH_ONLY      // (the host-only programs tests/eval_scratch_check.cpp and plan_graph_check.cpp, built without the HIP headers, stop here)
 #include <map>
 #include <string>
 #include <utility>
@@ -81,7 +84,7 @@ struct vlsat_ctx {
     int dual_stream = 2;     // 2D twin stages on a second stream: 0 never, 1 launch-bound plans only (E <= 8192), 2 every plan
                              // (vlsat_debug_option "dual_stream").  A two-stream plan carries a second scratch set (NP2, Hbig2,
                              // KP2, G2, T768b, H2b: +7.3 KB per edge, 0.73 GB at the bench batch); plans whose workspace would pass
-                             // DUAL_WS_BUDGET with it fall back to one stream (engine_plan.hip).  The per-class profiling keeps the
+                             // DUAL_WS_BUDGET with it fall back to one stream (plan_graph.h).  The per-class profiling keeps the
                              // two streams unless "prof_dual" is 0.
     hipStream_t side = nullptr;          // lane 1: the 2D edge chain (two-stream schedule of round 4: every 2D twin stage)
     hipStream_t side2 = nullptr;         // lane 2: the 2D node chain of the dependency-exact schedule (adapter, node cross-attention, wnode, 2D object head)
@@ -181,6 +184,7 @@ struct vlsat_plan_s {
     std::vector<int32_t> node_ptr;          // [S+1]
     std::vector<int64_t> edge_ptr;          // [S+1]
     size_t ws_bytes = 0;
+    vlsat::WsParams ws;                     // what the arena was laid out for (plan_graph.h: the buffer list)
     char* arena = nullptr;
     size_t arena_bytes = 0;
     hipEvent_t uploaded = nullptr;          // index tables are in place (recorded on the handle's copy stream)
@@ -194,7 +198,7 @@ struct vlsat_plan_s {
     int64_t* d_bias_ptr;
     int4* d_tiles;
     int n_tiles = 0;
-    int4* d_tiles_big = nullptr;             // the same attention cut into FLASH_BQ_BIG-query tiles: only when every scene has >= 4096 edges (engine_plan.hip)
+    int4* d_tiles_big = nullptr;             // the same attention cut into FLASH_BQ_BIG-query tiles: only when every scene has >= 4096 edges (plan_graph.h)
     int n_tiles_big = 0;
     // split-key mode of the edge attention for plans with too few blocks to fill the chip (flash_attn_*.hip)
     int fa_parts = 1;
@@ -237,8 +241,6 @@ inline int npc_of(const vlsat_ctx* h) { return 6 * h->D + h->A; }
 // never in the exact-fp32 mode and never when the node rows run in fp32
 inline bool gather_f16_on(const vlsat_ctx* h) { return h->prec_edge != 0 && h->prec_node != 0 && (h->gather_f16 >= 0 ? h->gather_f16 != 0 : h->prec_edge == 1); }
 inline bool default_heads(const vlsat_ctx* h) { return h->H == 8 && h->A == 256; }
-// a plan whose workspace would exceed this with the second scratch set of the two-stream mode runs on one stream
-constexpr size_t DUAL_WS_BUDGET = size_t(48) << 30;
 
 #define RUN(expr)                  \
     do {                           \

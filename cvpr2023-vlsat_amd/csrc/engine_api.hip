@@ -222,14 +222,10 @@ struct DevTable {                       // a host table copied to the device for
 // the FLASH_BQ-query tiles (scene start, scene tokens, first query, head) of a test call's attention, uploaded; *n = their count
 static int flash_tiles(const int64_t* tok_ptr, int n_scenes, int n_heads, DevTable& d, int* n) {
     if (!tok_ptr || n_scenes <= 0) return fail(VLSAT_EINVAL, "flash_attn: bad scene table");
-    std::vector<int4> tiles;
-    for (int s = 0; s < n_scenes; ++s) {
-        const int64_t T = tok_ptr[s + 1] - tok_ptr[s];
-        for (int hh = 0; hh < n_heads; ++hh)
-            for (int64_t q0 = 0; q0 < T; q0 += FLASH_BQ) tiles.push_back(make_int4((int)tok_ptr[s], (int)T, (int)q0, hh));
-    }
+    std::vector<PlanTile> tiles;                 // (int4's size and alignment: engine_plan.hip)
+    for (int s = 0; s < n_scenes; ++s) append_tile_rows(tiles, tok_ptr[s], tok_ptr[s + 1] - tok_ptr[s], n_heads, FLASH_BQ);
     *n = (int)tiles.size();
-    return d.put(tiles.data(), tiles.size() * sizeof(int4));
+    return d.put(tiles.data(), tiles.size() * sizeof(PlanTile));
 }
 }  // namespace
 

@@ -1,5 +1,6 @@
 // Graph plan: everything about one (edge list, batch ids, point count) that does not depend on the tensors' values --
-// scene partition, CSR over sources, attention tile tables, one device arena carved into every workspace buffer.
+// scene partition, CSR over sources, attention tile tables, one device arena carved into every workspace buffer.  What of that is
+// host arithmetic (the analysis, the list of the arena's buffers and their layout) is plan_graph.h; here are the HIP objects.
 //
 // No device-wide synchronisation anywhere on this path: the index tables are packed into ONE pinned host
 // buffer and uploaded with ONE hipMemcpyAsync on the handle's copy stream; the first forward of the plan makes its
@@ -81,6 +82,15 @@ static int take_staging(vlsat_ctx* h, size_t bytes, Staging** out) {
     return 0;
 }
 
+static PlanCfg plan_cfg_of(const vlsat_ctx* h) {
+    PlanCfg c;
+    c.H = h->H; c.D = h->D; c.A = h->A;
+    c.edge_scope = h->edge_scope; c.fa_split = h->fa_split; c.flash_bq_big_min = h->flash_bq_big_min; c.dual_stream = h->dual_stream;
+    c.n_layers = h->d.n_layers; c.n_obj_class = h->d.n_obj_class; c.n_rel_class = h->d.n_rel_class; c.feature_transform = h->d.feature_transform;
+    return c;
+}
+static_assert(sizeof(PlanTile) == sizeof(int4) && alignof(PlanTile) == alignof(int4), "the tile tables are uploaded as bytes");
+
 }  // namespace vlsat
 
 extern "C" {
@@ -91,236 +101,34 @@ int vlsat_plan_create(vlsat_handle h, const int64_t* bid, const int64_t* edges, 
     if (!h->finalized) return fail(VLSAT_ESTATE, "weights not finalised");
     if (N <= 0 || E < 0 || P <= 0) return fail(VLSAT_EINVAL, "N, P must be positive and E non-negative");
     if (N > (1 << 28) || E > (1ll << 30)) return fail(VLSAT_EINVAL, "graph too large for 32-bit indices");
+    // ---- the graph, then the workspace it needs: host arithmetic alone (plan_graph.h) ----
+    const PlanCfg cfg = plan_cfg_of(h);
+    PlanGraph g = plan_graph_analyse(bid, edges, N, E, cfg);
+    if (g.code) return fail(g.code, g.error);
+    const WsLayout L = ws_layout(ws_params(cfg, g, N, E, P));
     std::unique_ptr<vlsat_plan_s> p(new vlsat_plan_s());
     p->h = h; p->N = N; p->E = E; p->P = P;
-    const int H = h->H, D = h->D;
-    const size_t LDX = (size_t)ldx_of(h), NPC = (size_t)npc_of(h), A = (size_t)h->A;
-    // ---- scenes: maximal runs of equal batch id (must not re-appear) ----
-    std::vector<int32_t> node_scene(N);
-    p->node_ptr.push_back(0);
-    {
-        std::map<int64_t, int> seen;
-        for (int64_t i = 0; i < N; ++i) {
-            if (i == 0 || bid[i] != bid[i - 1]) {
-                if (seen.count(bid[i])) return fail(VLSAT_EINVAL, "batch_ids: nodes of a scene must be contiguous");
-                seen[bid[i]] = 1;
-                if (i) p->node_ptr.push_back((int32_t)i);
-            }
-            node_scene[i] = (int32_t)p->node_ptr.size() - 1;
-        }
-        p->node_ptr.push_back((int32_t)N);
-    }
-    p->S = (int)p->node_ptr.size() - 1;
-    for (int s = 0; s < p->S; ++s) p->max_n = std::max(p->max_n, p->node_ptr[s + 1] - p->node_ptr[s]);
-    // ---- edges: same-scene endpoints, grouped by scene in node order ----
-    const size_t Es = (size_t)std::max<int64_t>(E, 1), Ns = (size_t)N;
-    std::vector<int32_t> src(Es), dst(Es);
-    p->edge_ptr.assign(p->S + 1, 0);
-    int cur = 0;
-    bool sorted_by_src = true;
-    for (int64_t e = 0; e < E; ++e) {
-        const int64_t a = edges[e], b = edges[E + e];
-        if (a < 0 || a >= N || b < 0 || b >= N) return fail(VLSAT_EINVAL, "edge index out of range");
-        const int sa = node_scene[a];
-        if (sa != node_scene[b]) return fail(VLSAT_EINVAL, "edge joins nodes of different scenes");
-        if (sa < cur) return fail(VLSAT_EGRAPH, "edges are not grouped by scene in node order");
-        while (cur < sa) p->edge_ptr[++cur] = e;
-        src[e] = (int32_t)a; dst[e] = (int32_t)b;
-        if (e && src[e] < src[e - 1]) sorted_by_src = false;
-    }
-    while (cur < p->S) p->edge_ptr[++cur] = E;
-    // ---- CSR over sources (stable counting sort) ----
-    std::vector<int32_t> rowptr(N + 1, 0), order(Es);
-    for (int64_t e = 0; e < E; ++e) rowptr[src[e] + 1]++;
-    for (int64_t i = 0; i < N; ++i) rowptr[i + 1] += rowptr[i];
-    {
-        std::vector<int32_t> fill(rowptr.begin(), rowptr.end() - 1);
-        for (int64_t e = 0; e < E; ++e) order[fill[src[e]]++] = (int32_t)e;
-    }
-    p->is_fc = sorted_by_src;
-    for (int s = 0; s < p->S && p->is_fc; ++s) {
-        const int64_t n = p->node_ptr[s + 1] - p->node_ptr[s];
-        if (p->edge_ptr[s + 1] - p->edge_ptr[s] != n * (n - 1)) p->is_fc = 0;
-    }
-    // ---- flash tiles: scene-major, head, q-tile (consecutive ids share K/V -> same XCD) ----
-    std::vector<int4> tiles;
-    std::vector<int64_t> bias_ptr(p->S);
-    int64_t bias_total = 0;
-    if (h->edge_scope == 1 && E > 0) {       // reference multi-scene call: one attention over all edges
-        for (int hh = 0; hh < H; ++hh)
-            for (int64_t q0 = 0; q0 < E; q0 += FLASH_BQ) tiles.push_back(make_int4(0, (int)E, (int)q0, hh));
-        p->flash_flops += 4.0 * (double)E * (double)E * D;
-    }
-    for (int s = 0; s < p->S; ++s) {
-        const int64_t T = p->edge_ptr[s + 1] - p->edge_ptr[s];
-        if (h->edge_scope == 0) {
-            for (int hh = 0; hh < H; ++hh)
-                for (int64_t q0 = 0; q0 < T; q0 += FLASH_BQ)
-                    tiles.push_back(make_int4((int)p->edge_ptr[s], (int)T, (int)q0, hh));
-            p->flash_flops += 4.0 * (double)T * (double)T * D;
-        }
-        const int64_t n = p->node_ptr[s + 1] - p->node_ptr[s];
-        bias_ptr[s] = bias_total;
-        bias_total += (int64_t)H * n * n;
-    }
-    // Many blocks (several rounds of the resident slots): the kernels map block b to tile xcd_remap(b) -- XCD b % 8 walks a
-    // contiguous range of tile ids in order -- and a scene's last query tile is usually mostly empty (1560 = 12 * 128 + 24:
-    // one wave of four has work).  Those light tiles go to the END of every XCD's range, so that the last, partly filled
-    // round of blocks is made of light work instead of ending on full tiles next to idle CUs.
-    if (tiles.size() >= 2048) {
-        std::vector<int4> full, part;
-        for (const int4& t : tiles) (t.z + FLASH_BQ <= t.y ? full : part).push_back(t);
-        if (!part.empty() && !full.empty()) {
-            const size_t n = tiles.size(), q = n / 8, r = n % 8;
-            std::vector<int4> out;
-            out.reserve(n);
-            size_t fi = 0, pi = 0;
-            for (size_t x = 0; x < 8; ++x) {
-                const size_t cnt = q + (x < r ? 1 : 0);
-                size_t np = part.size() * (x + 1) / 8 - part.size() * x / 8;          // this XCD's share of the light tiles
-                np = std::min(np, cnt);
-                size_t nf = std::min(cnt - np, full.size() - fi);
-                np = cnt - nf;                                                          // (whatever the full list cannot cover)
-                for (size_t i = 0; i < nf; ++i) out.push_back(full[fi++]);
-                for (size_t i = 0; i < np && pi < part.size(); ++i) out.push_back(part[pi++]);
-            }
-            while (fi < full.size()) out.push_back(full[fi++]);                         // (rounding leftovers, if any)
-            while (pi < part.size()) out.push_back(part[pi++]);
-            if (out.size() == n) tiles.swap(out);
-        }
-    }
-    // Few blocks (one scene alone: ceil(T/128)*8 ~ 100 for 256 CUs): cut every block's key range into `parts`
-    // pieces so that about two rounds of 512 resident blocks exist; each piece keeps at least two key tiles.
-    std::vector<int4> krange;
-    if (!tiles.empty() && tiles.size() < 512 && h->fa_split) {
-        int parts = (int)std::min<size_t>(16, 1024 / tiles.size());
-        if (parts > 1) {
-            std::vector<int4> split;
-            for (const int4& t : tiles) {
-                const int kt = (t.y + 31) / 32;
-                const int ps = std::max(1, std::min(parts, kt / 2));          // parts actually used by this scene
-                for (int q = 0; q < parts; ++q) {
-                    split.push_back(t);
-                    const int a = q < ps ? (int)((int64_t)kt * q / ps) : 0, b = q < ps ? (int)((int64_t)kt * (q + 1) / ps) : 0;
-                    krange.push_back(make_int4(a, b, q, 0));
-                }
-            }
-            tiles.swap(split);
-            p->fa_parts = parts;
-        }
-    }
-    p->n_tiles = (int)tiles.size();
-    // Scenes of thousands of edges (cfg 5: one of 39 800): 256 queries per block share every K / V tile -- half the L2 -> LDS bytes
-    // per query, and the partly filled last tile is < 1/16 of a scene.  Built only when EVERY scene is that large (one table, one
-    // block size per launch); the forward uses it for half rows at head dim 64 (engine_forward.hip).
-    std::vector<int4> tiles_big;
-    if (h->edge_scope == 0 && p->fa_parts <= 1 && E > 0 && E * (int64_t)(2 * D) * 4 < (int64_t)1 << 32) {
-        int64_t min_t = INT64_MAX;
-        for (int s = 0; s < p->S; ++s) { const int64_t T = p->edge_ptr[s + 1] - p->edge_ptr[s]; if (T > 0) min_t = std::min(min_t, T); }
-        if (min_t >= h->flash_bq_big_min && min_t != INT64_MAX)
-            for (int s = 0; s < p->S; ++s) {
-                const int64_t T = p->edge_ptr[s + 1] - p->edge_ptr[s];
-                for (int hh = 0; hh < H; ++hh)
-                    for (int64_t q0 = 0; q0 < T; q0 += FLASH_BQ_BIG) tiles_big.push_back(make_int4((int)p->edge_ptr[s], (int)T, (int)q0, hh));
-            }
-        if (tiles_big.size() < 1024) tiles_big.clear();          // (two rounds of the 512 resident blocks, as for the key split above)
-    }
-    p->n_tiles_big = (int)tiles_big.size();
-    // ---- one device arena; the index tables come first, in the order they are packed into the staging buffer ----
-    struct Item { void** dst; size_t bytes; const void* host; };
-    std::vector<Item> items;
-    auto want = [&](auto** ptr, size_t count, const void* host = nullptr) {
-        items.push_back({reinterpret_cast<void**>(ptr), count * sizeof(**ptr), host});
-    };
-    want(&p->d_src, Es, src.data()); want(&p->d_dst, Es, dst.data()); want(&p->d_order, Es, order.data());
-    want(&p->d_rowptr, Ns + 1, rowptr.data()); want(&p->d_scene_ptr, (size_t)p->S + 1, p->node_ptr.data());
-    want(&p->d_bias_ptr, (size_t)p->S, bias_ptr.data());
-    std::vector<int32_t> edge_ptr32(p->edge_ptr.begin(), p->edge_ptr.end());
-    if (h->edge_scope == 1) { edge_ptr32.assign((size_t)p->S + 1, (int32_t)E); edge_ptr32[0] = 0; }   // one range: the whole batch
-    for (int sc = 0; sc < p->S; ++sc) p->max_e = std::max<int>(p->max_e, (int)(p->edge_ptr[sc + 1] - p->edge_ptr[sc]));
-    want(&p->d_edge_ptr32, (size_t)p->S + 1, edge_ptr32.data());
-    want(&p->d_tiles, std::max<size_t>(tiles.size(), 1), tiles.empty() ? nullptr : tiles.data());
-    if (p->fa_parts > 1) want(&p->d_krange, krange.size(), krange.data());
-    if (!tiles_big.empty()) want(&p->d_tiles_big, tiles_big.size(), tiles_big.data());
-    const size_t n_index_items = items.size();
-    want(&p->F, Ns * 768); want(&p->X3, Ns * LDX); want(&p->X2, Ns * LDX); want(&p->NP, Ns * NPC);
-    want(&p->QKVn, Ns * 1536); want(&p->On, Ns * 512); want(&p->T256, Ns * 256); want(&p->T768, Ns * LDX);
-    want(&p->rs, Ns); want(&p->bias, (size_t)std::max<int64_t>(bias_total, 1));
-    want(&p->H1, Es * 128); want(&p->H2, Es * 128); want(&p->E3, Es * 512); want(&p->E2, Es * 512);
-    want(&p->Hbig, Es * 1024); want(&p->KP, Es * 512); want(&p->G, Es * A);
-    want(&p->Qe, Es * 512); want(&p->KVe, Es * 1024); want(&p->Oe, Es * 512);
-    want(&p->Q2n, Ns * 512); want(&p->On2, Ns * 512);
-    {   // evaluation scratch (vlsat_process_val_counts): 0.6 KB per edge, 2.6 KB per node
-        const size_t C = (size_t)h->d.n_obj_class, R = (size_t)h->d.n_rel_class;
-        want(&p->ev_f, eval_scratch_floats(Ns, (size_t)E, C, R));      // (the layout: engine.h EvalScratch)
-        want(&p->ev_i, eval_scratch_ints(Ns, (size_t)E, R));
-    }
-    // launch-bound plans (every edge GEMM fits one round of the grid): second scratch set for the 2D twin stages
-    p->dual = h->dual_stream && E > 0 && (h->dual_stream > 1 || E <= 8192);      // (dual_stream = 2: every plan)
-    if (p->dual) {                         // ... unless the second scratch set would take the plan past the budget
-        size_t base = 0;
-        for (auto& it : items) base += it.bytes;
-        const size_t extra = (Ns * (size_t)(NPC + LDX + 1 + 1024 * (size_t)h->d.n_layers) + Es * (size_t)(1024 + 512 + A + 128 + 1024)) * sizeof(float);
-        if (base + extra > DUAL_WS_BUDGET) p->dual = false;
-    }
-    if (p->dual) {
-        want(&p->NP2, Ns * NPC); want(&p->Hbig2, Es * 1024); want(&p->KP2, Es * 512); want(&p->G2, Es * A);
-        want(&p->T768b, Ns * LDX); want(&p->rs2, Ns); want(&p->H2b, Es * 128);
-        want(&p->KVe2, Es * 1024);
-        p->kvx_slots = std::max(1, (int)h->d.n_layers);
-    }
-    want(&p->KVx, Ns * 1024 * (size_t)p->kvx_slots);
-    if (h->d.feature_transform) {
-        // point rows R = N*P (objects) or E (relation encoders, P = 1), one phase at a time:
-        //   rows [R,64] h1, [R,64], [R,128], [R,1024] STN convs (the last two double as conv2/conv3 of the main chain),
-        //   [R,64] h1';  per object: 1024 + 512 + 256 + 4096
-        const size_t R = std::max<size_t>(Ns * (size_t)P, Es), O = std::max(Ns, Es);
-        p->stn_ws_floats = R * (64 + 64 + 128 + 1024 + 64) + O * (1024 + 512 + 256 + 4096);
-        want(&p->stn_ws, p->stn_ws_floats);
-    }
-    if (p->fa_parts > 1) {
-        want(&p->fa_opart, (size_t)p->fa_parts * Es * 512);
-        want(&p->fa_m, (size_t)p->fa_parts * Es * H); want(&p->fa_l, (size_t)p->fa_parts * Es * H);
-    }
-    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-    size_t total = 0, index_bytes = 0;
-    for (size_t i = 0; i < items.size(); ++i) {
-        total += pad(items[i].bytes);
-        if (i + 1 == n_index_items) index_bytes = total;
-    }
+    p->S = g.S; p->max_n = g.max_n; p->max_e = g.max_e; p->is_fc = g.is_fc;
+    p->n_tiles = (int)g.tiles.size(); p->n_tiles_big = (int)g.tiles_big.size(); p->fa_parts = g.fa_parts; p->flash_flops = g.flash_flops;
+    p->ws = L.w; p->dual = L.w.dual; p->kvx_slots = (int)L.w.kvx_slots();
+    p->stn_ws_floats = L.bytes[WS_stn_ws] / sizeof(float);
+    p->ws_bytes = L.total;
+    // ---- an arena: a pooled one that fits, else a fresh one of the next size class ----
     sweep_trash(h, false);
     hipEvent_t prev_use = nullptr;
-    {   // smallest pooled arena that fits (and is not absurdly larger), else a fresh allocation of the next SIZE CLASS
-        // (2^k or 1.5 * 2^k bytes): an evaluation loop sees a new graph size almost every scene, and with exact sizes
-        // nearly every plan would allocate and nearly every evicted one would end in hipFree (which waits for the device:
-        // profiles/r02_hip_api_trace.txt had 48 of them in 80 forwards before the classes)
-        int best = -1;
-        for (size_t i = 0; i < h->arena_pool.size(); ++i)
-            if (h->arena_pool[i].bytes >= total && h->arena_pool[i].bytes <= 4 * total + (64u << 20) &&
-                (best < 0 || h->arena_pool[i].bytes < h->arena_pool[best].bytes))
-                best = (int)i;
-        size_t cls = size_t(1) << 20;
-        while (cls < total) cls = (cls & (cls - 1)) ? (cls / 3) * 4 : cls + cls / 2;      // 1, 1.5, 2, 3, 4, 6, ... MiB
-        if (best >= 0) {
-            p->arena = h->arena_pool[best].p;
-            p->arena_bytes = h->arena_pool[best].bytes;
-            prev_use = h->arena_pool[best].last;
-            h->arena_pool.erase(h->arena_pool.begin() + best);
-        } else {
-            VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p->arena), cls));
-            p->arena_bytes = cls;
-        }
+    const int best = arena_pool_pick(h->arena_pool, L.total);
+    if (best >= 0) {
+        p->arena = h->arena_pool[best].p;
+        p->arena_bytes = h->arena_pool[best].bytes;
+        prev_use = h->arena_pool[best].last;
+        h->arena_pool.erase(h->arena_pool.begin() + best);
+    } else {
+        p->arena_bytes = arena_size_class(L.total);
+        VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p->arena), p->arena_bytes));
     }
-    size_t off = 0;
-    for (auto& it : items) {
-        *it.dst = p->arena + off;
-        off += pad(it.bytes);
-    }
-    p->R1 = p->Hbig;                 // relation-head hidden layers re-use the nn_edge hidden buffer
-    p->R2 = p->Hbig + Es * 512;
+    ws_carve(p.get(), p->arena, L);
     p->prob = nullptr;
-    p->ws_bytes = total;
-    // ---- pack + one asynchronous upload ----
+    // ---- pack the index tables + one asynchronous upload ----
     auto give_up = [&](int code, const std::string& msg) {
         h->arena_pool.push_back({p->arena, p->arena_bytes, prev_use});
         p->arena = nullptr;
@@ -329,17 +137,13 @@ int vlsat_plan_create(vlsat_handle h, const int64_t* bid, const int64_t* edges, 
     if (!h->copy && hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking) != hipSuccess)
         return give_up(VLSAT_EHIP, "plan: cannot create the copy stream");
     Staging* st = nullptr;
-    if (take_staging(h, index_bytes, &st)) return give_up(VLSAT_EHIP, std::string("plan staging: ") + vlsat_last_error());
-    off = 0;
-    for (size_t i = 0; i < n_index_items; ++i) {
-        if (items[i].host) std::memcpy(st->p + off, items[i].host, items[i].bytes);
-        off += pad(items[i].bytes);
-    }
+    if (take_staging(h, L.index_bytes, &st)) return give_up(VLSAT_EHIP, std::string("plan staging: ") + vlsat_last_error());
+    pack_index_tables(g, L, st->p);
     p->uploaded = take_event(h);
     p->last_use = take_event(h);
     hipError_t er = (p->uploaded && p->last_use) ? hipSuccess : hipErrorOutOfMemory;
     if (er == hipSuccess && prev_use) er = hipStreamWaitEvent(h->copy, prev_use, 0);     // the arena's previous owner is done
-    if (er == hipSuccess) er = hipMemcpyAsync(p->arena, st->p, index_bytes, hipMemcpyHostToDevice, h->copy);
+    if (er == hipSuccess) er = hipMemcpyAsync(p->arena, st->p, L.index_bytes, hipMemcpyHostToDevice, h->copy);
     if (er == hipSuccess) er = hipEventRecord(st->done, h->copy);
     if (er == hipSuccess) er = hipEventRecord(p->uploaded, h->copy);
     if (er != hipSuccess) {
@@ -348,6 +152,7 @@ int vlsat_plan_create(vlsat_handle h, const int64_t* bid, const int64_t* edges, 
     }
     give_event(h, prev_use);       // (stream-ordered: the wait above has been enqueued; the handle may re-record it later)
     p->upload_pending = true;
+    p->node_ptr = std::move(g.node_ptr); p->edge_ptr = std::move(g.edge_ptr);
     *out = p.release();
     return 0;
 }
@@ -406,16 +211,16 @@ int vlsat_plan_check_graph(vlsat_plan p, const int64_t* edges_dev, const int64_t
 // debug: device pointer / shape of a named workspace buffer of a plan
 int vlsat_debug_buffer(vlsat_plan p, const char* name, void** ptr, int64_t* rows, int32_t* cols, int32_t* ld) {
     if (!p || !name) return fail(VLSAT_EINVAL, "null argument");
-    struct B { const char* n; float* p; int64_t r; int c, ld; };
-    const int LDX = ldx_of(p->h), NPC = npc_of(p->h), A = p->h->A;
-    const B tab[] = {{"F", p->F, p->N, 768, 768},       {"X3", p->X3, p->N, 512, LDX},     {"X2", p->X2, p->N, 512, LDX},
-                     {"AGG3", p->X3 + 512, p->N, A, LDX}, {"AGG2", p->X2 + 512, p->N, A, LDX},
-                     {"E3", p->E3, p->E, 512, 512},     {"E2", p->E2, p->E, 512, 512},     {"G", p->G, p->E, A, A},
-                     {"H1", p->H1, p->E, 128, 128},     {"KP", p->KP, p->E, 512, 512},     {"NP", p->NP, p->N, NPC, NPC},
-                     {"Hbig", p->Hbig, p->E, 1024, 1024}, {"bias", p->bias, 1, 0, 0},      {"On", p->On, p->N, 512, 512},
-                     {"Oe", p->Oe, p->E, 512, 512},     {"Qe", p->Qe, p->E, 512, 512},     {"KVe", p->KVe, p->E, 1024, 1024}};
+    struct B { const char* n; void* p; int64_t r; int c, ld; };
+    const WsParams& w = p->ws;
+    const int LDX = (int)w.LDX, A = (int)w.A;
+    // the buffers whose row of the list states visible columns (a flat one shows as one row without columns), and two views of the aggregated message
+    auto n_rows = [&](WsRows r) { return r == WS_NODES ? p->N : r == WS_EDGES ? p->E : 1; };
+#define VLSAT_WS_DEBUG(m, T, r, per, when, cols) {#m, p->m, n_rows(r), cols, cols > 0 ? (int)(per) : 0},
+    const B tab[] = {VLSAT_WS_BUFFERS(VLSAT_WS_DEBUG){"AGG3", p->X3 + 512, p->N, A, LDX}, {"AGG2", p->X2 + 512, p->N, A, LDX}};
+#undef VLSAT_WS_DEBUG
     for (auto& b : tab)
-        if (!std::strcmp(b.n, name)) {
+        if (b.c >= 0 && !std::strcmp(b.n, name)) {
             if (ptr) *ptr = b.p;
             if (rows) *rows = b.r;
             if (cols) *cols = b.c;

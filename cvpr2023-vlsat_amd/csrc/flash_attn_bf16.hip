@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64 * BQW, 2) void flash_attn_bf16_kernel(
     const int4 t = tiles[tile_id];
     const int row_base = t.x, n_tok = t.y, q0 = t.z, head = t.w;
     const int n_kv_tiles = (n_tok + FB_KV - 1) / FB_KV;
-    // split mode: sp.krange[tile] = {first 32-key tile, end 32-key tile, part, -} (units of 32 keys, see engine_plan.hip)
+    // split mode: sp.krange[tile] = {first 32-key tile, end 32-key tile, part, -} (units of 32 keys, see split_keys, plan_graph.h)
     const int4 kr = sp.parts > 1 ? sp.krange[tile_id] : make_int4(0, 2 * n_kv_tiles, 0, 0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, hi = lane >> 5;

@@ -35,7 +35,7 @@ static void check_regions(const Region<T> (&r)[K], T* base, size_t total) {
 }
 
 static void check_case(size_t N, size_t E, size_t C, size_t R) {
-    const size_t Es = E > 0 ? E : 1;                     // engine_plan.hip: Ns = N, Es = max(E, 1)
+    const size_t Es = E > 0 ? E : 1;                     // plan_graph.h: Ns = N, Es = max(E, 1)
     const size_t nf = eval_scratch_floats(N, E, C, R), ni = eval_scratch_ints(N, E, R);
     check(nf == 4 * N * C + 2 * Es * R + N * C, "floats", (long long)nf);
     check(ni == 2 * N + 4 * Es * R + 2 * Es, "ints", (long long)ni);

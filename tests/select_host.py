@@ -1,7 +1,7 @@
 """Builds and runs the host-only check programs of tests/: select_host_check.cpp on the integer helpers of csrc/select_core.h (the float
 key, count_ge, the dominance-triple table), eval_scratch_check.cpp on the evaluation-scratch layout of csrc/engine.h, flash_pick_check.cpp
-on the kernel selector of csrc/flash_pick.h, gemm_plan_check.cpp on the GEMM planner and variant lists of csrc/gemm_plan.h.  g++ only: no HIP
-header, no library, no device."""
+on the kernel selector of csrc/flash_pick.h, gemm_plan_check.cpp on the GEMM planner and variant lists of csrc/gemm_plan.h, plan_graph_check.cpp
+on the graph analysis and the workspace list of csrc/plan_graph.h.  g++ only: no HIP header, no library, no device."""
 import functools
 import os
 import shutil

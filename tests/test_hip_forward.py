@@ -334,6 +334,36 @@ def test_cfg5_large_scene_stress(golden_dir):
     assert info["n_scenes"] == 1 and info["is_fc"] and info["workspace_bytes"] < 2 * 1024 ** 3   # O(E), not O(E^2)
 
 
+def test_plan_layout_is_the_host_checked_one_and_key_split_changes_nothing():
+    """The three graphs of tests/plan_cases.py: the library's plan has the workspace bytes that tests/plan_graph_check.cpp printed after
+    holding csrc/plan_graph.h against the old plan creation (so the layout on the device is the verified one), the scene count and is_fc.
+    An fp32 forward with "flash_split" 1 (the default: 16 key parts where there is an edge at all) is finite and equals the forward
+    with "flash_split" 0 -- compared as tests/test_hip_round6.py compares its forwards around "flash_split": torch.equal.  (No scene here
+    has more than three key tiles, so each uses one part of the plan's 16 and the merge multiplies by exp2(0) = 1.)"""
+    import plan_cases
+    cfg = VLSATConfig()
+    m = model_for(cfg)
+    for i, (name, sizes, ws_bytes) in enumerate(plan_cases.CASES):
+        d = _dev(synth.collate([synth.make_scene(n, plan_cases.POINTS, 8800 + 10 * i + j) for j, n in enumerate(sizes)]))
+        args = (d["obj_points"], d["obj_2d_feats"], d["edge_indices"], d["descriptor"], d["batch_ids"])
+        info = m.plan_info(d["edge_indices"], d["batch_ids"], sum(sizes), plan_cases.POINTS)
+        assert info == {"n_scenes": len(sizes), "workspace_bytes": ws_bytes, "is_fc": True}, (name, info)
+        def run():
+            out = m(*args)
+            torch.cuda.synchronize()
+            return [o.clone() for o in out]
+        split = run()
+        try:
+            m.debug_option("flash_split", 0)
+            whole = run()
+        finally:
+            m.debug_option("flash_split", 1)
+        for n, a, b in zip(NAMES, split, whole):
+            assert torch.isfinite(a).all(), (name, n)
+            print(name, n, float((a - b).abs().max()) if a.numel() else 0.0)
+            assert torch.equal(a, b), (name, n, float((a - b).abs().max()))
+
+
 def test_plan_cache_not_fooled_by_address_reuse():
     """Two different graphs with identical shapes: a plan must never be reused across them."""
     cfg = VLSATConfig(N_LAYERS=2)

@@ -251,6 +251,32 @@ def test_evaluation_scratch_layout_on_the_host(sanitize):
     assert all(v == "ok" for v in rows.values()), rows
 
 
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_plan_graph_analyses_and_lays_out_what_plan_creation_did_before_it(sanitize):
+    """csrc/plan_graph.h compiled by g++ (tests/plan_graph_check.cpp, which keeps the body vlsat_plan_create had before the header word for
+    word, from the scene loop to the offset loop and the packing of the staging buffer): on every graph and configuration old and new code
+    give the same packed index tables byte for byte, S, max_n, max_e, is_fc, fa_parts, tile counts, flash_flops (bit-equal), bias_total,
+    the same buffers at the same offsets with the same sizes, R1 / R2, total, index_bytes, two-stream decision, kvx_slots and stn_ws_floats,
+    and refuse the same graphs with the same code and text; no difference is permitted.  NUM_HEADS {4, 8, 16} x edge_scope x flash_split x
+    dual_stream {0, 1, 2} x feature transform x 1..3 layers (all 216 on the small graphs, 72 or 28 of them on the large ones) over fully
+    connected scenes of 1 .. 200 nodes, 9 + 40, the bench batch and E = 0; unsorted, pruned and one-edge-short lists; tile counts on both
+    sides of the light-tile threshold (2048), of the key split (512; 2, 4, 9 and 16 parts; 1 .. 4 key tiles) and of the 256-query table (a
+    scene one edge short of the minimum, 1016 / 1024 tiles, another minimum); nine refused graphs, four of them with two faults; one 64-node scene
+    just under and just over the two-stream budget (1 566 372 edges); size classes from 1 byte to 64 GiB around every boundary and the pool
+    pick on seven hand-made pools.  Small cases are carved in a host buffer of exactly `total` bytes and every region is written.  The
+    program's workspace bytes for the graphs of tests/plan_cases.py are the recorded ones (the GPU test holds the library to them).  The
+    second case is the same stand-alone binary under ASan + UBSan."""
+    import plan_cases
+    import select_host
+    out = select_host.run(sanitize, "plan_graph_check")
+    rows = dict(r for r in out if len(r) == 2)
+    assert set(rows) == {"fully connected", "not fully connected", "light tiles", "key split", "big tiles", "refused graphs", "budget", "size classes"}, rows
+    assert all(v.split()[0] == "ok" and int(v.split()[1]) > 0 for v in rows.values()), rows
+    assert rows["budget"] == "ok 2 cases, two streams up to 1566372 edges of one 64-node scene"
+    ws = [r[0] for r in out if len(r) == 1]
+    assert ws == [f"ws | {name} | {n}" for name, _, n in plan_cases.CASES], ws
+
+
 @pytest.mark.parametrize("build", ["plain", "asan_ubsan", "experiments"])
 def test_flash_pick_chooses_what_the_cascade_chose_before_it(build):
     """csrc/flash_pick.h compiled by g++ (tests/flash_pick_check.cpp): over head dim {32, 48, 64, 128} x terms {1, 2, 3} x use_tr 0..4 x
