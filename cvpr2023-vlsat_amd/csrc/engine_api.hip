@@ -212,6 +212,10 @@ namespace {
 struct DevTable {                       // a host table copied to the device for the duration of one call
     void* d = nullptr;
     ~DevTable() { if (d) hipFree(d); }
+    int alloc(size_t bytes) {           // (or scratch of one call, uninitialised)
+        VLSAT_HIP_CHECK(hipMalloc(&d, bytes));
+        return 0;
+    }
     int put(const void* host, size_t bytes) {
         if (!bytes) return 0;
         VLSAT_HIP_CHECK(hipMalloc(&d, bytes));
@@ -733,6 +737,75 @@ int vlsat_k_dist_bias(const float* desc, int32_t ld_desc, const int64_t* node_pt
 int vlsat_k_layernorm(float* x, int32_t ld, int32_t rows, int32_t dim, const float* gamma, const float* beta,
                       int32_t relu, void* stream) {
     return launch_layernorm(x, ld, rows, dim, gamma, beta, relu, static_cast<hipStream_t>(stream));
+}
+
+// -------------------------------------------------------------------------------------------
+// Test entry points of the kernels that otherwise run only inside a forward: every PointNet kernel and operand form, every
+// form of the LayerNorm kernel, and the glue kernels of small_ops.hip / stn.hip.  Each calls the launcher the forward calls.
+int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32_t cin, const float* w1, const float* b1,
+                        const float* w2, const float* b2, const float* w3, const float* b3, int32_t n_out, int32_t terms,
+                        float* out, void* stream) {
+    if (!pts || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return fail(VLSAT_EINVAL, "pointnet_ex: null argument");
+    if (terms < 0 || terms > 3) return fail(VLSAT_EINVAL, "pointnet_ex: terms 0 (fp32) | 1 (bf16) | 2 (fp16) | 3 (split-bf16)");
+    if (n_out <= 0) return fail(VLSAT_EINVAL, "pointnet_ex: n_out must be > 0");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (terms == 0) return launch_pointnet(pts, n_obj, n_points, cin, w1, b1, w2, b2, w3, b3, n_out, out, st);
+    const size_t n2 = 128 * 64, n3 = (size_t)n_out * 128;
+    DevTable planes;                            // [w2 hi | w2 lo | w3 hi | w3 lo], freed when the call returns
+    RUN(planes.alloc(2 * (n2 + n3) * sizeof(uint16_t)));
+    uint16_t* w2h = static_cast<uint16_t*>(planes.d);
+    uint16_t *w2l = w2h + n2, *w3h = w2l + n2, *w3l = w3h + n3;
+    int r;
+    if (terms == 2) {
+        r = launch_to_f16(w2, n2, w2h, st);
+        if (!r) r = launch_to_f16(w3, n3, w3h, st);
+    } else {
+        r = launch_split_bf16(w2, n2, w2h, w2l, st);
+        if (!r) r = launch_split_bf16(w3, n3, w3h, w3l, st);
+    }
+    if (!r) r = launch_pointnet_bf16(pts, n_obj, n_points, cin, w1, b1, w2h, w2l, b2, w3h, w3l, b3, n_out, terms, out, st);
+    hipStreamSynchronize(st);     // test entry point only: the planes are freed right away
+    return r;
+}
+
+int vlsat_k_layernorm_to(const float* x, int32_t ld, float* y, int32_t ldy, int32_t rows, int32_t dim, const float* gamma,
+                         const float* beta, int32_t relu, int32_t out_fmt, const float* resid, int32_t ldr, int32_t resid_fmt,
+                         int32_t x_f16, void* stream) {
+    if (!x || !y || !gamma || !beta) return fail(VLSAT_EINVAL, "layernorm_to: null argument");
+    return launch_layernorm_to(x, ld, y, ldy, rows, dim, gamma, beta, relu, out_fmt, static_cast<hipStream_t>(stream), resid, ldr, resid_fmt, x_f16);
+}
+
+int vlsat_k_edge_embed(const float* desc, const int32_t* src, const int32_t* dst, int32_t n_edges, const float* w1cat,
+                       const float* b1cat, float* h1, void* stream) {
+    return launch_edge_embed(desc, src, dst, n_edges, w1cat, b1cat, h1, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_k_desc_tail(const float* desc, int32_t n_nodes, float* x, int32_t ldx, int32_t col0, void* stream) {
+    return launch_desc_tail(desc, n_nodes, x, ldx, col0, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_k_row_invnorm(const float* x, int32_t ld, int32_t rows, int32_t dim, float scale, float* out, const float* x2,
+                        float* out2, void* stream) {
+    return launch_row_invnorm(x, ld, rows, dim, scale, out, static_cast<hipStream_t>(stream), x2, out2);
+}
+
+int vlsat_k_copy_rows(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int32_t cols, int64_t rows, void* stream) {
+    if (dst_ld < 0 || src_ld < 0 || rows < 0) return fail(VLSAT_EINVAL, "copy_rows: negative pitch or row count");
+    return launch_copy_rows(dst, (size_t)dst_ld, src, (size_t)src_ld, cols, (size_t)rows, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_k_pts_conv1_rows(const float* pts, int32_t n_obj, int32_t n_points, int32_t cin, const float* w1, const float* b1,
+                           float* rows, void* stream) {
+    return launch_pts_conv1_rows(pts, n_obj, n_points, cin, w1, b1, rows, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_k_rowmax(const float* x, int32_t ld, int32_t n_obj, int32_t n_points, int32_t cols, float* out, int32_t ldo, void* stream) {
+    return launch_rowmax(x, ld, n_obj, n_points, cols, out, ldo, static_cast<hipStream_t>(stream));
+}
+
+int vlsat_k_apply_stn(const float* h, int32_t ldh, const float* T, int64_t rows, int32_t n_points, float* out, int32_t ldo, void* stream) {
+    if (rows < 0) return fail(VLSAT_EINVAL, "apply_stn: negative row count");
+    return launch_apply_stn(h, ldh, T, (size_t)rows, n_points, out, ldo, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -171,6 +171,9 @@ int launch_layernorm_to(const float* x, int ld, float* y, int ldy, int rows, int
     if (rows <= 0) return 0;
     if (dim != 512 || (ld & 3) || (ldy & 3) || (resid && ((ldr & 3) || (r_split > 2 && r_split != 4))))
         return fail(-1, "layernorm: dim must be 512, ld a multiple of 4, residual fp32, split pairs or half rows");
+    if (out_split != 0 && out_split != 1 && out_split != 2 && out_split != 4)
+        return fail(-1, "layernorm: out_split must be 0 (fp32), 1 (split pairs), 2 (bf16 half rows) or 4 (fp16 half rows)");
+    if (x_f16 != 0 && x_f16 != 1) return fail(-1, "layernorm: x_f16 must be 0 or 1");
     hipLaunchKernelGGL(layernorm512_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ld, y, ldy, rows, gamma, beta, relu, out_split,
                        resid, ldr, r_split, x_f16);
     VLSAT_LAUNCH_CHECK("layernorm512");

@@ -69,6 +69,15 @@ _SIGNATURES = {
     "vlsat_k_aggregate": (C.c_int, [_vp, _i32, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp]),
     "vlsat_k_node_attn": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _i32, _vp]),
     "vlsat_k_dist_bias": (C.c_int, [_vp, _i32, _vp, _i32, _i32] + [_vp] * 10 + [_vp, _vp]),
+    "vlsat_k_pointnet_ex": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "vlsat_k_layernorm_to": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vlsat_k_edge_embed": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_k_desc_tail": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "vlsat_k_row_invnorm": (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "vlsat_k_copy_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i64, _vp]),
+    "vlsat_k_pts_conv1_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vlsat_k_rowmax": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "vlsat_k_apply_stn": (C.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
     "vlsat_prepare_objects": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vlsat_fc_edges": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
     "vlsat_sample_objects_scratch": (_sz, [_i64, _i32]),

@@ -284,6 +284,56 @@ int vlsat_k_dist_bias(const float* desc, int32_t ld_desc, const int64_t* node_pt
                       const float* b3, const float* ln5_w, const float* ln5_b, const float* w6, const float* b6,
                       float* bias, void* stream);
 
+/* vlsat_k_pointnet for every encoder kernel and operand form: pts [N,cin,P] with cin in {3, 6, 9} (W1 [64,cin]), n_out a
+ * multiple of 128 up to 768.  terms: 0 = the fp32 kernel; 1 / 2 / 3 = the matrix-core kernel of the 16-bit modes with conv2 /
+ * conv3 operands as single-rounded bf16 / single-rounded fp16 (clamped to +-65504) / split bf16 (hi + lo, three MFMAs per
+ * product); conv1, the biases, the ReLUs and the max stay fp32.  The planes of W2 / W3 are made on the spot from the fp32
+ * weights (terms != 0: allocates, synchronises). */
+int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32_t cin,
+                        const float* w1, const float* b1, const float* w2, const float* b2,
+                        const float* w3, const float* b3, int32_t n_out, int32_t terms, float* out, void* stream);
+
+/* vlsat_k_layernorm in every form the forward uses: y[r, :] = LN(x[r, :] + resid[r, :]) over rows of 512 (row pitches ld,
+ * ldy, ldr in floats, multiples of 4; y may be x or resid).  x_f16 = 1: the rows of x are fp16 half rows (fp16 values at
+ * byte 2 * column).  resid may be NULL; resid_fmt: 0 fp32, 1 split-pair words, 2 bf16 half rows, 4 fp16 half rows.
+ * out_fmt: 0 fp32, 1 split-pair words, 2 bf16 half rows, 4 fp16 half rows clamped to +-65504 (a half row fills the first
+ * 1024 bytes of the row of y).  Any other out_fmt or x_f16 is refused.  Asynchronous. */
+int vlsat_k_layernorm_to(const float* x, int32_t ld, float* y, int32_t ldy, int32_t rows, int32_t dim,
+                         const float* gamma, const float* beta, int32_t relu, int32_t out_fmt,
+                         const float* resid, int32_t ldr, int32_t resid_fmt, int32_t x_f16, void* stream);
+
+/* Gen_edge_descriptor (reference src/utils/op_utils.py:78-97, flow target_to_source) + conv1 of both relation encoders:
+ * ed = [desc[src, 0:6] - desc[dst, 0:6], log(desc[src, 6:11] / desc[dst, 6:11])], h1[e, c] = relu(w1cat[c, :] . ed + b1cat[c])
+ * with desc [N,11], src / dst int32 [E], w1cat [128,11] (rows 0..63 rel_encoder_3d.conv1, 64..127 rel_encoder_2d.conv1),
+ * h1 [E,128].  Asynchronous. */
+int vlsat_k_edge_embed(const float* desc, const int32_t* src, const int32_t* dst, int32_t n_edges,
+                       const float* w1cat, const float* b1cat, float* h1, void* stream);
+
+/* Spatial tail of the 3D node feature (reference SGFN_MMG/model.py:296-299):
+ * x[n, col0:col0+8] = [desc[n, 3:9], log desc[n, 9], log desc[n, 10]], row pitch ldx.  Asynchronous. */
+int vlsat_k_desc_tail(const float* desc, int32_t n_nodes, float* x, int32_t ldx, int32_t col0, void* stream);
+
+/* out[m] = scale / ||x[m, 0:512]||_2 (object heads, reference SGFN_MMG/model.py:327-330); x2 / out2 (both or neither): a
+ * second problem of the same shape in the same launch.  Asynchronous. */
+int vlsat_k_row_invnorm(const float* x, int32_t ld, int32_t rows, int32_t dim, float scale, float* out,
+                        const float* x2, float* out2, void* stream);
+
+/* dst[r, 0:cols] = src[r, 0:cols] for r < rows (pitches in floats): the forward's device-to-device copy; 16-byte accesses
+ * when cols, both pitches and both pointers allow, scalar ones otherwise.  Asynchronous. */
+int vlsat_k_copy_rows(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int32_t cols, int64_t rows,
+                      void* stream);
+
+/* The glue of MODEL.feature_transform (STNkd, reference network_PointNet.py:52-86,146-150):
+ * pts_conv1_rows: rows[n*P + p, c] = relu(b1[c] + sum_k w1[c,k] pts[n,k,p]), c < 64, cin in 1..9;
+ * rowmax: out[n, c] = max_{p < P} x[n*P + p, c] for c < cols (row pitches ld / ldo);
+ * apply_stn: out[r, j] = sum_i h[r, i] T[r / P][i, j] with T [n_obj,64,64].  Asynchronous. */
+int vlsat_k_pts_conv1_rows(const float* pts, int32_t n_obj, int32_t n_points, int32_t cin,
+                           const float* w1, const float* b1, float* rows, void* stream);
+int vlsat_k_rowmax(const float* x, int32_t ld, int32_t n_obj, int32_t n_points, int32_t cols, float* out, int32_t ldo,
+                   void* stream);
+int vlsat_k_apply_stn(const float* h, int32_t ldh, const float* T, int64_t rows, int32_t n_points, float* out,
+                      int32_t ldo, void* stream);
+
 /* -------- input preparation (the step BEFORE the path: the data loader, reference dataset_3dssg.py:279-294) --- */
 
 /* Per object n: gather P sampled points scene_points[choice[n, :]] ([Npts,3] fp32, choice int32 [N,P]),

@@ -132,7 +132,7 @@ def test_calib_header_symbols_are_bound_and_disjoint():
     assert names == set(L.declared_calib_symbols()) == set(L._SIGNATURES_CALIB)
     assert not names & set(L.declared_symbols()) and not names & set(L._SIGNATURES)
     assert not names & set(L.declared_split_symbols()) and not names & set(L._SIGNATURES_SPLIT)
-    assert len(L.declared_symbols()) == 72 and len(L.declared_split_symbols()) == 5
+    assert len(L.declared_symbols()) == 81 and len(L.declared_split_symbols()) == 5
     assert len(L._SIGNATURES_CALIB["vlsat_score_hist"][1]) == 14
     lib = L.load()
     assert all(hasattr(lib, n) for n in names)

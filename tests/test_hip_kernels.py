@@ -9,6 +9,7 @@ import torch
 
 import vlsat_amd  # noqa: F401
 from vlsat_amd import VLSATConfig, synth
+from quant_model import from_half_rows as _from_half_rows, pack_split as _pack_split, to_half_rows as _to_half_rows, unpack_split as _unpack_split
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -407,19 +408,6 @@ def test_flash_attn_bf16_forced_rescale(lib):
     assert err < 2e-4, f"{err:.3e}"
 
 
-def _pack_split(x):
-    """Host restatement of common.h pack_split: (bf16 rne(x) << 16) | bf16 rne(x - hi), as float32 bit patterns."""
-    hi = x.to(torch.bfloat16)
-    lo = (x - hi.float()).to(torch.bfloat16)
-    w = (hi.view(torch.int16).to(torch.int32) << 16) | (lo.view(torch.int16).to(torch.int32) & 0xFFFF)
-    return w.view(torch.float32)
-
-
-def _unpack_split(w):
-    u = w.view(torch.int32)
-    return (u & -65536).view(torch.float32) + (u << 16).view(torch.float32)
-
-
 def test_split_pair_format_gemm(lib):
     """The split-pair tensor format of the bf16 modes: A read as packed hi/lo words (ReLU on the packed word), residual
     decoded, C packed and scaled -- all against the plain-fp32 operand path of the same kernel on the same values."""
@@ -515,18 +503,6 @@ def test_gemm_bf16_ring_kernel(lib, M, N, K, fmt):
         ref = _ref_gemm(Af.to(DEV), W, **kw)
         err = float((run(prec, fmt, 0, 0, 0) - ref).abs().max())
         assert err < (1e-4 if prec == 3 else 3e-2) * math.sqrt(K / 64) + 2e-5, f"prec {prec}: {err:.3e}"
-
-
-def _to_half_rows(x):
-    """fp32-pitched rows carrying bf16 values at byte 2 * column (the half-row format of the single-rounding modes)."""
-    M, N = x.shape
-    out = torch.zeros(M, N, dtype=torch.float32)
-    out.view(torch.bfloat16).view(M, 2 * N)[:, :N] = x.to(torch.bfloat16)
-    return out
-
-
-def _from_half_rows(w, N):
-    return w.view(torch.bfloat16).view(w.shape[0], -1)[:, :N].float()
 
 
 def test_half_row_format_gemm_and_attention(lib):

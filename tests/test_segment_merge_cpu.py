@@ -192,5 +192,5 @@ def test_the_new_symbols_are_declared_and_bound():
     from vlsat_amd import build as B
     names = {"vlsat_merge_segments", "vlsat_merge_segments_scratch_bytes"}
     assert names <= set(L.declared_symbols()) and names <= set(L._SIGNATURES)
-    assert len(L._SIGNATURES["vlsat_merge_segments"][1]) == 28 and len(L.declared_symbols()) == 72
+    assert len(L._SIGNATURES["vlsat_merge_segments"][1]) == 28 and len(L.declared_symbols()) == 81
     assert "segment_merge.hip" in B.SOURCES and B.PER_SOURCE_FLAGS["segment_merge.hip"] == ["-ffp-contract=off"]
