@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libvlsat_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
 SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
 CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
+SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_segment.h")
 
 
 class VlsatDims(C.Structure):
@@ -139,6 +140,12 @@ _SIGNATURES_CALIB = {
     "vlsat_score_hist_geometry": (None, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
 }
 
+# include/vlsat_segment.h: an unlabelled mesh over-segmented into segments (csrc/mesh_segment.hip)
+_SIGNATURES_SEGMENT = {
+    "vlsat_segment_mesh_scratch_bytes": (_sz, [_i64, _i64]),
+    "vlsat_segment_mesh": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -152,7 +159,7 @@ def identity(lib_path: str = "") -> dict:
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -181,6 +188,11 @@ def declared_calib_symbols() -> list:
     return _declared(CALIB_HEADER_PATH)
 
 
+def declared_segment_symbols() -> list:
+    """Every function include/vlsat_segment.h declares."""
+    return _declared(SEGMENT_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -190,7 +202,8 @@ def load():
         raise VlsatError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
+            _SIGNATURES_SEGMENT.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -542,3 +542,163 @@ def split_groups(points: torch.Tensor, segments: torch.Tensor, segment_ids, seed
     host = out.cpu().numpy()                                                      # the one host wait
     mask = host[:k * words].view(np.uint32).reshape(k, words)
     return (*_unpack_groups(ids, mask, host[k * words:k * words + k], host[k * words + k:]), mask)
+
+
+# ---- an unlabelled mesh over-segmented into segments (csrc/mesh_segment.hip; the rule is stated in include/vlsat_segment.h) -------------
+SEG_MAX_VERTS = 1 << 24
+
+
+class MeshSegments:
+    """What ``segment_mesh`` found: ``labels`` int32 [V] (0 = dropped, else 1..S in the order of a segment's lowest vertex),
+    ``n_segments`` (an int when trimmed, else an int32 tensor [1] on the labels' device) and ``seg_size`` int32 ([S] when trimmed, else
+    [V] with zeros past S).  ``trimmed`` as in ``metrics.MergedGraph``."""
+    __slots__ = ("labels", "n_segments", "seg_size", "trimmed")
+
+    def __init__(self, labels, n_segments, seg_size, trimmed=False):
+        self.labels, self.n_segments, self.seg_size, self.trimmed = labels, n_segments, seg_size, bool(trimmed)
+
+    def trim(self) -> "MeshSegments":
+        """``seg_size`` cut to S entries.  Reads ``n_segments`` back: ONE host synchronisation."""
+        if self.trimmed:
+            return self
+        s = int(self.n_segments.reshape(-1)[0])
+        return MeshSegments(self.labels, s, self.seg_size[:s], True)
+
+    def __iter__(self):                      # labels, n_segments, seg_size = segment_mesh(...)
+        return iter((self.labels, self.n_segments, self.seg_size))
+
+    def __repr__(self):
+        return f"MeshSegments({int(self.labels.shape[0])} vertices, {self.n_segments if self.trimmed else '?'} segments)"
+
+
+def mesh_edges(faces):
+    """faces int [F,3] -> the three sides of every triangle, int32 [3 F, 2], in the faces' order: (v0, v1), (v1, v2), (v2, v0).  A
+    tensor in, a tensor on its device out; anything else goes through numpy.  Shared sides appear twice: the rule ignores duplicates."""
+    import numpy as np
+    if torch.is_tensor(faces):
+        if faces.dim() != 2 or faces.shape[1] != 3:
+            raise L.VlsatError("mesh_edges: faces must be [F,3]")
+        return faces.to(torch.int32)[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2).contiguous()
+    faces = np.asarray(faces)
+    if faces.ndim != 2 or faces.shape[1] != 3:
+        raise L.VlsatError("mesh_edges: faces must be [F,3]")
+    return np.ascontiguousarray(faces.astype(np.int32)[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2))
+
+
+def segment_rounds(min_verts: int) -> int:
+    """ceil(log2(min_verts)), 0 for min_verts <= 1: the absorb rounds of include/vlsat_segment.h (csrc/segment_core.h: seg_rounds)."""
+    r = 0
+    while (1 << r) < int(min_verts):
+        r += 1
+    return r
+
+
+def _segment_args(normals, edges, max_weight, min_verts):
+    import math
+    if len(normals.shape) != 2 or normals.shape[1] != 3 or not 1 <= normals.shape[0] <= SEG_MAX_VERTS:
+        raise L.VlsatError("segment_mesh: normals must be float32 [V,3] with 1 <= V <= 2^24")
+    if len(edges.shape) != 2 or edges.shape[1] != 2 or edges.shape[0] >= 1 << 31:
+        raise L.VlsatError("segment_mesh: edges must be int32 [M,2] with M < 2^31")
+    if math.isnan(float(max_weight)):
+        raise L.VlsatError("segment_mesh: max_weight is NaN")
+    if not -(1 << 31) <= int(min_verts) < 1 << 31:
+        raise L.VlsatError("segment_mesh: min_verts must fit an int32")
+
+
+def _seg_unite(parent, a, b):
+    """Union-find on numpy arrays: the pairs (a[i], b[i]) united, every tree left flat with its LOWEST member as root.  Each pass
+    hooks every root that still has a pair to another tree under the lowest root it sees (np.minimum.at: a set operation) and jumps
+    pointers until flat; the number of trees with such a pair at least halves per pass."""
+    import numpy as np
+    while len(a):
+        ra, rb = parent[a], parent[b]
+        live = ra != rb
+        if not live.any():
+            break
+        a, b, ra, rb = a[live], b[live], ra[live], rb[live]
+        low = np.minimum(ra, rb)
+        np.minimum.at(parent, ra, low)
+        np.minimum.at(parent, rb, low)
+        while True:
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent[:] = up
+    return parent
+
+
+def segment_weights_host(normals, a, b):
+    """w of include/vlsat_segment.h for the vertex pairs (a[i], b[i]) in numpy float32: every product and sum rounded on its own."""
+    import numpy as np
+    n = np.ascontiguousarray(normals, dtype=np.float32)
+    na, nb = n[a], n[b]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = (na[:, 0] * nb[:, 0] + na[:, 1] * nb[:, 1]) + na[:, 2] * nb[:, 2]
+        w = np.float32(1.0) - d
+        w = np.where(w < 0, np.float32(0.0), np.where(w > 2, np.float32(2.0), w)).astype(np.float32)
+    return np.where(np.isnan(d), np.float32(2.0), w).astype(np.float32)
+
+
+def segment_mesh_host(normals, edges, max_weight: float, min_verts: int = 20, trim: bool = True) -> MeshSegments:
+    """``segment_mesh`` stated in numpy with the kernels' operations: the rule of include/vlsat_segment.h, step by step -- equal labels,
+    count and sizes.  Returns CPU tensors."""
+    import numpy as np
+    n = np.ascontiguousarray(normals.cpu().numpy() if torch.is_tensor(normals) else normals, dtype=np.float32)
+    e = np.asarray(edges.cpu().numpy() if torch.is_tensor(edges) else edges).astype(np.int64)
+    e = e.reshape(0, 2) if e.size == 0 else e
+    _segment_args(n, e, max_weight, min_verts)
+    v, min_verts, max_weight = n.shape[0], int(min_verts), np.float32(max_weight)
+    ok = (e >= 0).all(1) & (e < v).all(1) & (e[:, 0] != e[:, 1])
+    a, b = e[ok, 0], e[ok, 1]
+    w = segment_weights_host(n, a, b)
+    parent = np.arange(v, dtype=np.int64)
+    link = w <= max_weight
+    _seg_unite(parent, a[link], b[link])                                           # step 2; parent is flat: parent[x] = root(x)
+    a2, b2 = np.concatenate([a, b]), np.concatenate([b, a])                        # both directions of every edge
+    bits = np.concatenate([w, w]).view(np.uint32).astype(np.uint64) << np.uint64(32)
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    for _ in range(segment_rounds(min_verts) if len(a) else 0):                    # step 3
+        size = np.bincount(parent, minlength=v)
+        ra, rb = parent[a2], parent[b2]
+        sel = (ra != rb) & (size[ra] < min_verts)
+        best = np.full(v, none, dtype=np.uint64)
+        np.minimum.at(best, ra[sel], bits[sel] | rb[sel].astype(np.uint64))
+        src = np.nonzero(best != none)[0]
+        _seg_unite(parent, src, (best[src] & np.uint64(0xFFFFFFFF)).astype(np.int64))
+    size = np.bincount(parent, minlength=v)
+    kept = (parent == np.arange(v)) & (size >= min_verts)                          # steps 4 and 5
+    num = np.where(kept, np.cumsum(kept), 0)
+    labels = num[parent].astype(np.int32)
+    s = int(kept.sum())
+    seg_size = np.zeros(v, dtype=np.int32)
+    seg_size[:s] = size[kept]
+    out = MeshSegments(torch.from_numpy(labels), torch.tensor([s], dtype=torch.int32), torch.from_numpy(seg_size))
+    return out.trim() if trim else out
+
+
+def segment_mesh(normals: torch.Tensor, edges: torch.Tensor, max_weight: float, min_verts: int = 20, trim: bool = True) -> MeshSegments:
+    """normals f32 [V,3], edges int32 [M,2] (``mesh_edges(faces)``, or any undirected edge list: kNN edges for a cloud without faces)
+    -> ``MeshSegments``: an over-segmentation by smoothness-constrained region growing (include/vlsat_segment.h, vlsat_segment_mesh).
+    Edges whose normals agree (w = 1 - dot <= ``max_weight``) link their ends into components; in ceil(log2(min_verts)) rounds
+    every component of fewer than ``min_verts`` vertices joins its neighbour across the lowest-weight edge (ties: the lower root); what
+    is still smaller has no neighbour and gets label 0; the rest is numbered 1..S by lowest vertex.  Device tensors: the HIP kernels,
+    asynchronous, 8 + 4 rounds launches and nothing read back to decide anything; ``trim=True`` then reads S back -- the ONE host
+    synchronisation -- and cuts ``seg_size``, ``trim=False`` reads nothing.  CPU tensors: ``segment_mesh_host``."""
+    if not normals.is_cuda:
+        return segment_mesh_host(normals, edges, max_weight, min_verts, trim)
+    lib = L.load()
+    if normals.dtype != torch.float32:
+        raise L.VlsatError("segment_mesh: normals must be float32 [V,3]")
+    _segment_args(normals, edges, max_weight, min_verts)
+    dev = normals.device
+    normals = normals.contiguous()
+    edges = edges.to(device=dev, dtype=torch.int32).contiguous()
+    v, m = normals.shape[0], edges.shape[0]
+    scratch = torch.empty(int(lib.vlsat_segment_mesh_scratch_bytes(v, m)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(v, dtype=torch.int32, device=dev)
+    seg_size = torch.empty(v, dtype=torch.int32, device=dev)
+    n_segments = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_segment_mesh(normals.data_ptr(), edges.data_ptr(), v, m, float(max_weight), int(min_verts), scratch.data_ptr(),
+                                   labels.data_ptr(), n_segments.data_ptr(), seg_size.data_ptr(), L.stream_ptr()))
+    out = MeshSegments(labels, n_segments, seg_size)
+    return out.trim() if trim else out

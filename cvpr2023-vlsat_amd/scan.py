@@ -9,7 +9,9 @@ class does on the host before ``Mmgnet.forward`` sees a scene, without trimesh -
 * ``scene_nodes`` / ``edge_list`` / ``ground_truth``   the node order, the edge list and the labels of
                                ``data_preparation`` (``dataset_3dssg.py:248-266,281-283,300-336``);
 * ``prepare_scan``             all of it + the per-object point selection, zero-mean, descriptor on the DEVICE (``prep.py``; reference
-                               ``:279-294``) -> one batch dict in the layout ``evaluate.validation`` and ``VLSATModel.forward`` take.
+                               ``:279-294``) -> one batch dict in the layout ``evaluate.validation`` and ``VLSATModel.forward`` take;
+* ``read_mesh`` / ``write_ply`` / ``vertex_normals`` / ``segment_scan``   a bare mesh with its faces, and the over-segmentation (on the
+                               DEVICE, ``prep.segment_mesh``) that stands in for the instance ids when nobody has made any.
 
 The union point sets (``rel_points``, ``:337-359``) are not produced: ``Mmgnet.forward`` never reads them.  The host-side
 functions are plain numpy; ``prepare_scan`` needs the GPU library.  Parity: PINNED to the reference's own dataset code --
@@ -467,3 +469,222 @@ def split_scan(mesh_or_path, distance: float = 1.0, bbox_distance: float = 0.75,
     seeds = seeds.cpu().numpy().astype(np.int32)
     kept = [k for k in range(len(seeds)) if keep[k]]
     return ScanSplits(groups=[groups[k] for k in kept], kept=kept, seeds=seeds, seed_points=pts[seeds], counts=counts)
+
+
+# ---- a bare mesh: faces, normals, and the segmentation every function above takes as given -------------------------------------------
+def _ply_header(f, path):
+    """-> (format, [[element name, count, [(property, dtype) | (property, (count dtype, item dtype)) for a list]]])"""
+    if f.readline().strip() != b"ply":
+        raise ScanError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ScanError(f"{path}: header without end_header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if not elements:
+                raise ScanError(f"{path}: property before any element")
+            types = tok[2:4] if tok[1] == "list" else tok[1:2]
+            if len(tok) < (5 if tok[1] == "list" else 3) or any(t not in _PLY_TYPES for t in types):
+                raise ScanError(f"{path}: unknown property type in {' '.join(tok)!r}")
+            elements[-1][2].append((tok[-1], tuple(_PLY_TYPES[t] for t in types) if tok[1] == "list" else _PLY_TYPES[types[0]]))
+        elif tok[0] == "end_header":
+            break
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ScanError(f"{path}: format {fmt!r} is not supported (ascii, binary_little_endian)")
+    return fmt, elements
+
+
+def _ply_rows(f, path, fmt, name, count, props):
+    """One element -> {property: column}; a list property becomes an int64 [count, 3] table (every row must hold three entries)."""
+    lists = [p for p, t in props if isinstance(t, tuple)]
+    if len(lists) > 1:
+        raise ScanError(f"{path}: element {name!r} has more than one list property")
+    if fmt == "ascii":
+        vals = b" ".join(f.readline() for _ in range(count)).split()
+        width = len(props) + (3 if lists else 0)
+        if len(vals) != count * width:
+            raise ScanError(f"{path}: {name} rows do not hold {count} x {width} values" + (" (triangles only)" if lists else ""))
+        try:
+            table = np.array(vals, dtype=np.float64).reshape(count, width)
+        except ValueError:
+            raise ScanError(f"{path}: a {name} value is not a number") from None
+        out, col = {}, 0
+        for p, t in props:
+            if isinstance(t, tuple):
+                if count and not (table[:, col] == 3).all():
+                    raise ScanError(f"{path}: a {name} row is not a triangle")
+                out[p] = table[:, col + 1:col + 4].astype(np.int64)
+                col += 4
+            else:                          # parsed INTO the declared type, as read_ply does
+                out[p] = table[:, col].astype(t) if t[0] == "f" else table[:, col].astype(np.int64).astype(t)
+                col += 1
+        return out
+    fields = []                            # a list row as (count, three items): rows of another length fail the count check below
+    for p, t in props:
+        fields += [("#" + p, "<" + t[0]), (p, "<" + t[1], (3,))] if isinstance(t, tuple) else [(p, "<" + t)]
+    dt = np.dtype(fields)
+    raw = f.read(dt.itemsize * count)
+    if len(raw) != dt.itemsize * count:
+        raise ScanError(f"{path}: {name} data truncated" + (" (triangles only)" if lists else ""))
+    rec = np.frombuffer(raw, dtype=dt, count=count)
+    if lists and count and not (rec["#" + lists[0]] == 3).all():
+        raise ScanError(f"{path}: a {name} row is not a triangle")
+    return {p: (rec[p].astype(np.int64) if isinstance(t, tuple) else rec[p]) for p, t in props}
+
+
+def read_mesh(path: str) -> Dict[str, Optional[np.ndarray]]:
+    """``read_ply`` plus the triangles: -> {"points", "colors", "normals", "instances", "faces": i32[F,3]}.  ASCII and
+    binary_little_endian; the face element's list property (``vertex_indices`` / ``vertex_index``, any integer count and index type:
+    ``uchar`` / ``int`` is the usual pair) must hold triangles.  A file without a face element has F = 0.  A vertex element without
+    ``objectId`` / ``label`` -- a plain reconstructed mesh -- is accepted: ``instances`` is all zeros, for ``segment_scan`` to fill."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        vert, faces = None, np.zeros((0, 3), dtype=np.int32)
+        for name, count, props in elements:
+            if name not in ("vertex", "face") and vert is not None and faces.size:
+                break
+            rows = _ply_rows(f, path, fmt, name, count, props)
+            if name == "vertex":
+                if any(isinstance(t, tuple) for _, t in props):
+                    raise ScanError(f"{path}: list property inside the vertex element")
+                vert = rows
+            elif name == "face":
+                lists = [p for p, t in props if isinstance(t, tuple)]
+                if not lists:
+                    raise ScanError(f"{path}: the face element has no list property")
+                faces = rows[lists[0]]
+    if vert is None:
+        raise ScanError(f"{path}: no vertex element")
+    for k in ("x", "y", "z"):
+        if k not in vert:
+            raise ScanError(f"{path}: vertex element has no {k}")
+    n = len(vert["x"])
+    if faces.size and (faces.min() < 0 or faces.max() >= n):
+        raise ScanError(f"{path}: a face names a vertex outside [0, {n})")
+    out = {"points": np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float64)}
+    out["colors"] = (np.stack([vert["red"], vert["green"], vert["blue"]], 1).astype(np.uint8)
+                     if all(k in vert for k in ("red", "green", "blue")) else None)
+    out["normals"] = (np.stack([vert["nx"], vert["ny"], vert["nz"]], 1).astype(np.float64)
+                      if all(k in vert for k in ("nx", "ny", "nz")) else None)
+    lab = vert["objectId"] if "objectId" in vert else vert.get("label")
+    out["instances"] = np.zeros(n, dtype=np.int64) if lab is None else np.asarray(lab).astype(np.int64).reshape(-1)
+    out["faces"] = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    return out
+
+
+def write_ply(path: str, mesh: Dict[str, Optional[np.ndarray]], ascii: bool = False) -> None:
+    """A minimal PLY writer (binary_little_endian, or ASCII): float x y z, float nx ny nz when ``mesh["normals"]`` is there, int
+    ``objectId`` from ``mesh["instances"]`` (zeros when absent) and, when ``mesh["faces"]`` holds any, ``property list uchar int
+    vertex_indices`` -- enough to save a segmentation, view it, and read it back with ``read_ply`` / ``read_mesh`` /
+    ``transfer_labels``.  Coordinates are stored as float32; ASCII prints them with nine significant digits, which reads back as the
+    same float32."""
+    pts = np.asarray(mesh["points"], dtype=np.float32).reshape(-1, 3)
+    nrm = mesh.get("normals")
+    cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    data = [pts[:, 0], pts[:, 1], pts[:, 2]]
+    if nrm is not None:
+        nrm = np.asarray(nrm, dtype=np.float32).reshape(-1, 3)
+        if len(nrm) != len(pts):
+            raise ScanError("write_ply: one normal per vertex")
+        cols += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        data += [nrm[:, 0], nrm[:, 1], nrm[:, 2]]
+    inst = mesh.get("instances")
+    inst = np.zeros(len(pts), dtype=np.int64) if inst is None else np.asarray(inst).astype(np.int64).reshape(-1)
+    if len(inst) != len(pts) or (len(inst) and (inst.min() < -(1 << 31) or inst.max() >= 1 << 31)):
+        raise ScanError("write_ply: one int32 instance id per vertex")
+    cols.append(("objectId", "<i4"))
+    data.append(inst)
+    faces = mesh.get("faces")
+    faces = np.zeros((0, 3), np.int32) if faces is None else np.asarray(faces).astype(np.int32).reshape(-1, 3)
+    header = ["ply", f"format {'ascii' if ascii else 'binary_little_endian'} 1.0", f"element vertex {len(pts)}"]
+    header += [f"property {'int' if t == '<i4' else 'float'} {p}" for p, t in cols]
+    if len(faces):
+        header += [f"element face {len(faces)}", "property list uchar int vertex_indices"]
+    header.append("end_header")
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        if ascii:
+            for row in zip(*data):
+                f.write((" ".join(str(int(x)) if isinstance(x, (int, np.integer)) else f"{float(x):.9g}" for x in row) + "\n").encode("ascii"))
+            for a, b, c in faces.tolist():
+                f.write(f"3 {a} {b} {c}\n".encode("ascii"))
+            return
+        rec = np.empty(len(pts), dtype=np.dtype(cols))
+        for (p, _), col in zip(cols, data):
+            rec[p] = col
+        f.write(rec.tobytes())
+        if len(faces):
+            frec = np.empty(len(faces), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+            frec["n"], frec["v"] = 3, faces
+            f.write(frec.tobytes())
+
+
+def vertex_normals(points: np.ndarray, faces: np.ndarray) -> np.ndarray:
+    """Area-weighted vertex normals f64 [V,3], on the host in float64, for meshes that carry none: the sum over a vertex's triangles of
+    (p1 - p0) x (p2 - p0) (twice the area times the face normal), normalised; a vertex of no triangle, or whose triangles cancel,
+    gets (0, 0, 0) -- its edges then weigh 1, as a right angle does."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    faces = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(pts)):
+        raise ScanError("vertex_normals: a face names a vertex outside the mesh")
+    cross = np.cross(pts[faces[:, 1]] - pts[faces[:, 0]], pts[faces[:, 2]] - pts[faces[:, 0]])
+    acc = np.zeros_like(pts)
+    for k in range(3):
+        np.add.at(acc, faces[:, k], cross)
+    length = np.linalg.norm(acc, axis=1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(length > 0, acc / length, 0.0)
+
+
+def segment_scan(mesh_or_path, max_angle_deg: float = 10.0, min_verts: int = 20, device="cuda:0") -> Dict[str, Optional[np.ndarray]]:
+    """A bare mesh over-segmented into segments on the device: -> a copy of the mesh dict with ``instances`` filled (int64 [V]: 0 =
+    dropped, else 1..S), ``n_segments`` = S and ``seg_size`` int32 [S].  ``mesh_or_path``: a PLY path (``read_mesh``) or a dict with
+    ``points``, ``faces`` and optionally ``normals`` (absent or None: ``vertex_normals``).  Vertices joined by a mesh edge whose normals
+    differ by at most ``max_angle_deg`` grow into regions; a region of fewer than ``min_verts`` vertices joins its most similar
+    neighbour (``prep.segment_mesh``; the rule is stated in include/vlsat_segment.h).  ``max_weight = np.float32(1 - cos(angle))`` is
+    computed once here, on the host.  ``device=None`` (or "cpu") runs the numpy restatement, which gives the same result.
+
+    The result is an OVER-segmentation -- a flat wall, a table top and each of its sides come out as separate segments -- which is what
+    ``merge_graph`` expects: feed it to ``prepare_scan(mesh, {i: "?" for i in range(1, S + 1)}, ["?"], [], relations, ...)``.  Both
+    defaults are starting values, not tuned operating points: no scan data and no checkpoint is available to this project, so the
+    accuracy of the rule on real reconstructions is unmeasured."""
+    import math
+
+    import torch
+
+    from . import prep
+
+    mesh = dict(read_mesh(mesh_or_path) if isinstance(mesh_or_path, (str, os.PathLike)) else mesh_or_path)
+    faces = mesh.get("faces")
+    if faces is None:
+        raise ScanError("segment_scan: the mesh has no faces (prep.segment_mesh takes any edge list, for a cloud with kNN edges)")
+    pts = np.asarray(mesh["points"])[:, :3]
+    if not 1 <= len(pts) <= prep.SEG_MAX_VERTS:
+        raise ScanError("segment_scan: 1 .. 2^24 vertices")
+    faces = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= len(pts)):
+        raise ScanError("segment_scan: a face names a vertex outside the mesh")
+    normals = mesh.get("normals")
+    if normals is None:
+        normals = mesh["normals"] = vertex_normals(pts, faces)
+    if not 0.0 <= float(max_angle_deg) <= 180.0:
+        raise ScanError("segment_scan: max_angle_deg must be in [0, 180]")
+    max_weight = np.float32(1.0 - math.cos(math.radians(float(max_angle_deg))))
+    on_host = device is None or torch.device(device).type == "cpu"
+    d_normals = torch.from_numpy(np.ascontiguousarray(np.asarray(normals)[:, :3], dtype=np.float32))
+    d_edges = torch.from_numpy(prep.mesh_edges(faces))
+    if not on_host:
+        d_normals, d_edges = d_normals.to(device), d_edges.to(device)
+    seg = prep.segment_mesh(d_normals, d_edges, float(max_weight), min_verts)      # trim=True: the one host wait
+    mesh["instances"] = seg.labels.cpu().numpy().astype(np.int64)
+    mesh["n_segments"] = int(seg.n_segments)
+    mesh["seg_size"] = seg.seg_size.cpu().numpy()
+    return mesh

@@ -169,3 +169,68 @@ def make_room(n_obj: int, pts_per_obj: int, seed: int, extent=(10.0, 10.0, 3.0))
     pts = (centre + g.uniform(-0.5, 0.5, (n_obj, pts_per_obj, 3)) * size).astype(np.float32)
     inst = np.repeat(np.arange(1, n_obj + 1, dtype=np.int32), pts_per_obj)
     return np.ascontiguousarray(pts.reshape(-1, 3)), inst
+
+
+def _grid_triangles(idx: np.ndarray, pts: np.ndarray, outward: np.ndarray) -> np.ndarray:
+    """Two triangles per cell of the vertex-index grid ``idx`` [A+1, B+1], wound so that their normal points along ``outward``."""
+    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
+    tri = np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)])
+    t0 = tri[0]
+    if np.dot(np.cross(pts[t0[1]] - pts[t0[0]], pts[t0[2]] - pts[t0[0]]), outward) < 0:
+        tri = tri[:, ::-1]
+    return tri
+
+
+def make_box_mesh(n_obj: int, step: float, seed: int, normal_noise: float = 0.0, extent=(10.0, 10.0)) -> dict:
+    """A room as a triangle MESH, for the mesh segmenter: a floor of ``extent`` metres plus ``n_obj`` closed axis-aligned boxes standing
+    on it (separate surfaces: nothing connects a box to the floor), every surface tessellated on a grid of spacing ``step``, two
+    triangles per cell.  A box is 0.4-1.2 m along each axis and at least 6 cells, so each of its faces has at least 25 interior
+    vertices.  The vertices on a box's edges and corners are SHARED between its faces and carry the normalised average of the faces'
+    normals, as a reconstruction's vertex normals do at a crease.  ``normal_noise`` > 0 adds that many standard normals to every
+    component of every normal and renormalises.
+
+    -> the dict of ``scan.read_mesh``: ``points`` f64 [V,3], ``normals`` f64 [V,3], ``colors`` None, ``faces`` i32 [F,3], ``instances``
+    i64 [V] = the GENERATING object (1 = floor, 2 + k = box k), plus ``plane`` i32 [V]: the planar face a vertex belongs to (0 = floor,
+    1 + 6 k + f = face f of box k in the order -x, +x, -y, +y, -z, +z) or -1 for a crease vertex, which belongs to several."""
+    g = np.random.default_rng([int(seed) & 0x7FFFFFFF, 0xB0C5])
+    step = float(step)
+    pts, nrm, plane, inst, faces = [], [], [], [], []
+    nx, ny = (max(2, int(round(e / step))) for e in extent)
+    ii, jj = np.meshgrid(np.arange(nx + 1), np.arange(ny + 1), indexing="ij")
+    floor = np.stack([ii.ravel() * step, jj.ravel() * step, np.zeros(ii.size)], 1)
+    pts.append(floor)
+    nrm.append(np.tile([0.0, 0.0, 1.0], (len(floor), 1)))
+    plane.append(np.zeros(len(floor), np.int32))
+    inst.append(np.ones(len(floor), np.int64))
+    faces.append(_grid_triangles(np.arange(len(floor)).reshape(nx + 1, ny + 1), floor, np.array([0.0, 0.0, 1.0])))
+    base = len(floor)
+    for k in range(n_obj):
+        cells = np.maximum(6, np.rint(g.uniform(0.4, 1.2, 3) / step).astype(np.int64))
+        origin = np.array([*(g.uniform(0.0, max(extent[d] - cells[d] * step, 0.0)) for d in range(2)), 0.0])
+        lat = np.stack(np.meshgrid(*(np.arange(c + 1) for c in cells), indexing="ij"), -1)           # [a+1, b+1, c+1, 3]
+        side = (lat == cells).astype(np.int64) - (lat == 0).astype(np.int64)                            # outward direction per axis
+        on = (side != 0).any(-1)
+        vid = np.full(on.shape, -1, np.int64)
+        vid[on] = base + np.arange(int(on.sum()))
+        s = side[on]
+        p = origin + lat[on] * step
+        n_faces_at = (s != 0).sum(1)
+        axis = np.argmax(s != 0, 1)
+        pl = np.where(n_faces_at == 1, 1 + 6 * k + 2 * axis + (s[np.arange(len(s)), axis] > 0), -1)
+        pts.append(p)
+        nrm.append(s / np.linalg.norm(s, axis=1, keepdims=True))
+        plane.append(pl.astype(np.int32))
+        inst.append(np.full(len(p), 2 + k, np.int64))
+        allp = np.concatenate(pts)
+        for d in range(3):
+            for end, sign in ((0, -1.0), (int(cells[d]), 1.0)):
+                out = np.zeros(3)
+                out[d] = sign
+                faces.append(_grid_triangles(np.take(vid, end, axis=d), allp, out))
+        base += len(p)
+    points, normals = np.concatenate(pts), np.concatenate(nrm)
+    if normal_noise > 0:
+        normals = normals + float(normal_noise) * g.standard_normal(normals.shape)
+        normals /= np.linalg.norm(normals, axis=1, keepdims=True)
+    return {"points": points, "colors": None, "normals": normals, "instances": np.concatenate(inst),
+            "faces": np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), "plane": np.concatenate(plane)}
