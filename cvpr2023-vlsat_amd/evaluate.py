@@ -10,6 +10,8 @@ counts reproduce ``get_mean_recall`` (eva_utils_acc.py:224-237) and ``compute_me
 (model.py:364-388)."""
 from __future__ import annotations
 
+import contextlib
+import itertools
 from typing import Dict, Iterable, Optional
 
 import numpy as np
@@ -247,12 +249,130 @@ def merge_batches(bs) -> dict:
     return out
 
 
+@contextlib.contextmanager
+def _worker_stream(dev, own: bool):
+    """What a worker of ``_run_pool`` runs its items in: the device set for its thread and a stream -- a new one (``own``) or the
+    thread's current one -- synchronised after the last item.  An exception leaves without the synchronise."""
+    torch.cuda.set_device(dev)
+    stream = torch.cuda.Stream(device=dev) if own else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(stream):
+        yield
+    stream.synchronize()
+
+
+def _run_pool(model, items, dev, workers: int, job, context=None):
+    """``job(k, model_k, item)`` for every item of the iterator ``items``, ``workers`` of them in flight: worker k owns a replica of
+    the model (its own library handle: a handle is driven by one host thread and one stream at a time; kept by the model:
+    building one uploads and prepares every weight) and a stream, and takes the next item under a lock until the iterator ends or
+    any worker has failed.  One worker runs in the caller's thread on its current stream; more run on daemon threads with a stream
+    each, after ONE synchronise of the caller's stream: what it produced -- inputs, zeroed tables -- is complete before they read
+    it.  The first exception of a job is re-raised here after every thread has joined.  ``context``: the ``_worker_stream`` of
+    a run without a GPU (the tests pass ``contextlib.nullcontext``)."""
+    import threading
+    models = [model] + model.replicas(workers - 1)
+    items, lock, errors, end = iter(items), threading.Lock(), [], object()
+
+    def work(k):
+        try:
+            with (context or _worker_stream)(dev, workers > 1):
+                while not errors:
+                    with lock:
+                        item = next(items, end)
+                    if item is end:
+                        break
+                    job(k, models[k], item)
+        except BaseException as ex:             # (re-raised in the caller's thread)
+            errors.append(ex)
+
+    if workers == 1:
+        work(0)
+    else:
+        if context is None:
+            torch.cuda.current_stream(dev).synchronize()
+        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+    if errors:
+        raise errors[0]
+
+
+def _in_order(model, batches, dev, workers: int, one, split):
+    """``split(one(model, b), b)`` of every batch, in input order.  workers <= 0: one batch after the other on the current stream,
+    batch i + 1 untouched before the scenes of batch i are out.  workers >= 1: every batch through ``_run_pool`` first."""
+    if workers <= 0:
+        for b in batches:
+            yield from split(one(model, b), b)
+        return
+    results = {}
+
+    def job(k, m, item):
+        results[item[0]] = one(m, item[1]), item[1]
+
+    _run_pool(model, enumerate(batches), torch.device(dev), workers, job)
+    for i in sorted(results):
+        yield from split(*results[i])
+
+
+def _scene_starts(b: dict, n_sc: int, nodes: bool = True):
+    """Where every scene of a batch starts: (first node row, first edge row), two lists of ``n_sc`` + 1 entries, the last the
+    end.  ``batch_ids`` ascend and the edges are grouped by scene, so both are a ``searchsorted`` -- a scene without edges gets an
+    empty range.  One read-back per list; ``nodes=False`` spares the first (None)."""
+    ids = b["batch_ids"].view(-1).contiguous()
+    arange = torch.arange(n_sc + 1, device=ids.device)
+    node = torch.searchsorted(ids, arange).tolist() if nodes else None
+    return node, torch.searchsorted(ids[b["edge_indices"][:, 0]].contiguous(), arange).tolist()
+
+
+def _split_scene_graphs(pair, b):
+    g3, g2 = pair
+    n_sc = g3.n_valid.numel()
+    if n_sc == 1:
+        yield g3, g2
+        return
+    _, start = _scene_starts(b, n_sc, nodes=False)
+    for s in range(n_sc):
+        yield g3.scene(s, start[s]), g2.scene(s, start[s])
+
+
+def _split_decoded(pair, b):
+    g3, g2 = pair
+    n_sc = g3.n_valid.numel()
+    if n_sc == 1:
+        yield g3, g2
+        return
+    node, start = _scene_starts(b, n_sc)
+    for s in range(n_sc):
+        nodes = (node[s], node[s + 1])
+        yield g3.scene(s, start[s], nodes), (None if g2 is None else g2.scene(s, start[s], nodes))
+
+
+def _split_merged(pairs, b):
+    n_sc = pairs[0][0].n_objects.numel()
+    if n_sc == 1:
+        yield pairs
+        return
+    _, start = _scene_starts(b, n_sc, nodes=False)
+    first = [None if pair is None else [0] + list(itertools.accumulate(pair[0].n_objects.tolist())) for pair in pairs]
+    for s in range(n_sc):
+        out = []
+        for pair, o in zip(pairs, first):                 # o: first object row of every scene of this branch
+            if pair is None:
+                out.append(None)
+                continue
+            g, d = pair
+            src = g.pair_edges[:, 0]
+            rows = ((src >= o[s]) & (src < o[s + 1])).nonzero().view(-1)
+            out.append((g.scene(s, (start[s], start[s + 1])), d.scene(s, int(rows[0]) if rows.numel() else 0, (o[s], o[s + 1]))))
+        yield tuple(out)
+
+
 @torch.no_grad()
 def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False,
                           zero_shot=None):
-    """The counts vector of this rank's batches with NO host round trip per batch and ``workers`` batches in flight:
-    every worker thread owns a replica of the model (its own library handle: a handle is driven by one host thread and one
-    stream at a time) and a stream; forward, ranking and counting of a batch are enqueued back to back
+    """The counts vector of this rank's batches with NO host round trip per batch and ``workers`` batches in flight
+    (``_run_pool``); forward, ranking and counting of a batch are enqueued back to back
     (``metrics.process_val_counts``) and the counts accumulate on the device with integer atomics.  One scene per batch --
     validation()'s own pattern (batch_size = 1, reference src/model/model.py:185,201-211) -- leaves most of the 256 CUs idle
     when scenes run one after the other (a 40-object forward is ~115 dependent kernels of 5-20 us); several in flight fill
@@ -262,45 +382,23 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     near-ties (a batched forward differs from a one-scene forward in the last bits: a rank may move by one).
     Returns the counts vector; with ``recall_k`` or ``zero_shot`` (the device uint8 table) the tuple (counts, recall vector or
     None, split vector or None)."""
-    import threading
     from . import metrics as M
     dev = torch.device(device)
-    models = [model] + model.replicas(workers - 1)        # (kept by the model: building one uploads and prepares every weight)
     counts = [torch.zeros(len(fields()), dtype=torch.int64, device=dev) for _ in range(workers)]
     recall = [torch.zeros(len(recall_fields()), dtype=torch.float64, device=dev) if recall_k else None for _ in range(workers)]
     split = [torch.zeros(len(split_fields()), dtype=torch.int64, device=dev) if zero_shot is not None else None for _ in range(workers)]
-    it, lock, errors = iter(batches), threading.Lock(), []
 
-    def work(k):
-        try:
-            torch.cuda.set_device(dev)
-            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
-            with torch.cuda.stream(stream):
-                while not errors:
-                    with lock:
-                        group = [b for b in (next(it, None) for _ in range(max(1, merge))) if b is not None]
-                    if not group:
-                        break
-                    b = merge_batches(group)
-                    M.process_val_counts(models[k], counts[k], b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"],
-                                         b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"),
-                                         recall=recall[k], split_table=zero_shot, split_counts=split[k])
-            stream.synchronize()
-        except BaseException as ex:             # (re-raised in the caller's thread)
-            errors.append(ex)
+    def groups(it, n):                          # (the pool takes an item under its lock: a whole group is read there)
+        while group := list(itertools.islice(it, n)):
+            yield group
 
-    if workers == 1:
-        work(0)
-    else:
-        cur = torch.cuda.current_stream(dev)
-        cur.synchronize()                       # inputs produced on the caller's stream are complete before the workers read them
-        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-    if errors:
-        raise errors[0]
+    def one(k, m, group):
+        b = merge_batches(group)
+        M.process_val_counts(m, counts[k], b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"],
+                             b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"),
+                             recall=recall[k], split_table=zero_shot, split_counts=split[k])
+
+    _run_pool(model, groups(iter(batches), max(1, merge)), dev, workers, one)
     vec = torch.stack(counts).sum(0).cpu().numpy().astype(np.float64)
     if recall_k or zero_shot is not None:
         return (vec, torch.stack(recall).sum(0).cpu().numpy() if recall_k else None,
@@ -315,63 +413,15 @@ def predict(model, batches: Iterable[dict], device=None, workers: int = 0, **gra
     edge list.  ``graph_args``: ``top_k``, ``topk_each``, ``evaluate`` of ``VLSATModel.predict_graph``.  workers = 0: one batch
     after the other on the current stream.  workers >= 1: as the pipelined validation loop -- every worker thread owns a replica
     of the model and a stream and takes the next batch; nothing is read back per batch."""
-    import threading
-    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
     workers = int(workers)
     if workers > 0 and device is None:
         raise ValueError("predict(workers > 0) needs the device")
 
     def one(m, b):
-        ids = b.get("batch_ids")
-        return m.predict_graph(b["obj_points"], b["obj_2d_feats"], b["edge_indices"].t(), b["descriptor"], ids,
-                               fc_sizes=b.get("fc_sizes"), **graph_args), b
+        return m.predict_graph(b["obj_points"], b["obj_2d_feats"], b["edge_indices"].t(), b["descriptor"], b.get("batch_ids"),
+                               fc_sizes=b.get("fc_sizes"), **graph_args)
 
-    def scenes(pair, b):
-        g3, g2 = pair
-        n_sc = g3.n_valid.numel()
-        if n_sc == 1:
-            yield g3, g2
-            return
-        first = b["batch_ids"].view(-1)[b["edge_indices"][:, 0]]                       # scene of every edge
-        start = torch.searchsorted(first.contiguous(), torch.arange(n_sc, device=first.device)).tolist()
-        for s in range(n_sc):
-            yield g3.scene(s, start[s]), g2.scene(s, start[s])
-
-    if workers <= 0:
-        for _, b in it:
-            yield from scenes(*one(model, b))
-        return
-    dev = torch.device(device)
-    models = [model] + model.replicas(workers - 1)
-
-    def work(k):
-        try:
-            torch.cuda.set_device(dev)
-            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
-            with torch.cuda.stream(stream):
-                while not errors:
-                    with lock:
-                        i, b = next(it, (None, None))
-                    if b is None:
-                        break
-                    results[i] = one(models[k], b)
-            stream.synchronize()
-        except BaseException as ex:             # (re-raised in the caller's thread)
-            errors.append(ex)
-
-    if workers == 1:
-        work(0)
-    else:
-        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
-        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-    if errors:
-        raise errors[0]
-    for i in sorted(results):
-        yield from scenes(*results[i])
+    yield from _in_order(model, batches, device, workers, one, _split_scene_graphs)
 
 
 @torch.no_grad()
@@ -382,65 +432,15 @@ def decode(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d
     the route of unlabelled scans.  ``decode_args``: ``threshold``, ``score``, ``n_labels``, ``max_rel``, ``multi_rel_outputs`` of
     ``VLSATModel.decode_graph``.  workers = 0: one batch after the other on the current stream.  workers >= 1: as ``predict`` --
     every worker thread owns a replica of the model and a stream and takes the next batch; nothing is read back per batch."""
-    import threading
-    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
     workers = int(workers)
     if workers > 0 and device is None:
         raise ValueError("decode(workers > 0) needs the device")
 
     def one(m, b):
         return m.decode_graph(b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["edge_indices"].t(), b["descriptor"],
-                              b.get("batch_ids"), fc_sizes=b.get("fc_sizes"), **decode_args), b
+                              b.get("batch_ids"), fc_sizes=b.get("fc_sizes"), **decode_args)
 
-    def scenes(pair, b):
-        g3, g2 = pair
-        n_sc = g3.n_valid.numel()
-        if n_sc == 1:
-            yield g3, g2
-            return
-        ids = b["batch_ids"].view(-1).contiguous()
-        arange = torch.arange(n_sc + 1, device=ids.device)
-        node = torch.searchsorted(ids, arange).tolist()                               # first node row of every scene
-        start = torch.searchsorted(ids[b["edge_indices"][:, 0]].contiguous(), arange).tolist()      # ... and first edge row
-        for s in range(n_sc):
-            nodes = (node[s], node[s + 1])
-            yield g3.scene(s, start[s], nodes), (None if g2 is None else g2.scene(s, start[s], nodes))
-
-    if workers <= 0:
-        for _, b in it:
-            yield from scenes(*one(model, b))
-        return
-    dev = torch.device(device)
-    models = [model] + model.replicas(workers - 1)
-
-    def work(k):
-        try:
-            torch.cuda.set_device(dev)
-            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
-            with torch.cuda.stream(stream):
-                while not errors:
-                    with lock:
-                        i, b = next(it, (None, None))
-                    if b is None:
-                        break
-                    results[i] = one(models[k], b)
-            stream.synchronize()
-        except BaseException as ex:             # (re-raised in the caller's thread)
-            errors.append(ex)
-
-    if workers == 1:
-        work(0)
-    else:
-        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
-        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-    if errors:
-        raise errors[0]
-    for i in sorted(results):
-        yield from scenes(*results[i])
+    yield from _in_order(model, batches, device, workers, one, _split_decoded)
 
 
 @torch.no_grad()
@@ -452,8 +452,6 @@ def merged(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d
     index of the "same part" predicate among the model's classes.  The weights of the pooled class probabilities are the batch's
     ``weights`` or, without, its ``points_per_instance`` (None: all 1).  workers as for ``decode``; the merge reads two totals back
     per batch and branch."""
-    import threading
-    results, it, lock, errors = {}, enumerate(batches), threading.Lock(), []
     workers = int(workers)
     if workers > 0 and device is None:
         raise ValueError("merged(workers > 0) needs the device")
@@ -462,66 +460,9 @@ def merged(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d
         w = b.get("weights", b.get("points_per_instance"))
         return m.merge_graph(b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["edge_indices"].t(), b["descriptor"],
                              b.get("batch_ids"), same_part=same_part, weights=w, threshold=threshold, mutual=mutual,
-                             fc_sizes=b.get("fc_sizes"), **decode_args), b
+                             fc_sizes=b.get("fc_sizes"), **decode_args)
 
-    def scenes(pairs, b):
-        n_sc = pairs[0][0].n_objects.numel()
-        if n_sc == 1:
-            yield pairs
-            return
-        ids = b["batch_ids"].view(-1).contiguous()
-        arange = torch.arange(n_sc + 1, device=ids.device)
-        start = torch.searchsorted(ids[b["edge_indices"][:, 0]].contiguous(), arange).tolist()      # first edge row of every scene
-        for s in range(n_sc):
-            out = []
-            for pair in pairs:
-                if pair is None:
-                    out.append(None)
-                    continue
-                g, d = pair
-                gs = g.scene(s, (start[s], start[s + 1]))
-                n_obj = g.n_objects.tolist()
-                o0 = sum(n_obj[:s])
-                src = g.pair_edges[:, 0]
-                rows = ((src >= o0) & (src < o0 + n_obj[s])).nonzero().view(-1)
-                out.append((gs, d.scene(s, int(rows[0]) if rows.numel() else 0, (o0, o0 + n_obj[s]))))
-            yield tuple(out)
-
-    if workers <= 0:
-        for _, b in it:
-            yield from scenes(*one(model, b))
-        return
-    dev = torch.device(device)
-    models = [model] + model.replicas(workers - 1)
-
-    def work(k):
-        try:
-            torch.cuda.set_device(dev)
-            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
-            with torch.cuda.stream(stream):
-                while not errors:
-                    with lock:
-                        i, b = next(it, (None, None))
-                    if b is None:
-                        break
-                    results[i] = one(models[k], b)
-            stream.synchronize()
-        except BaseException as ex:             # (re-raised in the caller's thread)
-            errors.append(ex)
-
-    if workers == 1:
-        work(0)
-    else:
-        torch.cuda.current_stream(dev).synchronize()      # inputs produced on the caller's stream are complete before the workers read them
-        ts = [threading.Thread(target=work, args=(k,), daemon=True) for k in range(workers)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-    if errors:
-        raise errors[0]
-    for i in sorted(results):
-        yield from scenes(*results[i])
+    yield from _in_order(model, batches, device, workers, one, _split_merged)
 
 
 def merge_quality(root, gt_of_segment) -> Dict[str, float]:
@@ -659,7 +600,6 @@ def calibrate(model, batches: Iterable[dict], device=None, workers: int = 0, use
     all of them add into the same table per branch (integer atomics: the sums do not depend on the order).  ONE collective at the
     end (``dist.allreduce_metrics`` over both branches' buffers); it sums in fp64, so the counts are exact as long as every entry of
     the summed tables stays below 2^53.  ``multi_rel_outputs`` (default: the model's) selects the rule."""
-    import threading
     from . import metrics as M
     workers = int(workers)
     if workers > 0 and device is None:
@@ -668,9 +608,8 @@ def calibrate(model, batches: Iterable[dict], device=None, workers: int = 0, use
     multi = bool(cfg.multi_rel_outputs if multi_rel_outputs is None else multi_rel_outputs)
     dev = torch.device(model.device if device is None else device)
     tabs = [M.ScoreTables(cfg.num_rel_class, cfg.num_obj_class, bins, dev) for _ in range(2 if use_2d else 1)]
-    it, lock, errors = iter(batches), threading.Lock(), []
 
-    def one(m, b):
+    def one(k, m, b):
         edges = b["edge_indices"]
         ei_t = edges.t() if b.get("fc_sizes") is not None else edges.t().contiguous()
         if use_2d:
@@ -682,33 +621,7 @@ def calibrate(model, batches: Iterable[dict], device=None, workers: int = 0, use
         for (obj, rel), t in zip(outs, tabs):
             M.score_histograms(obj, rel, b["gt_class"], b["gt_rel_cls"], multi, bins, tables=t)
 
-    def work(k, models):
-        try:
-            torch.cuda.set_device(dev)
-            stream = torch.cuda.Stream(device=dev) if workers > 1 else torch.cuda.current_stream(dev)
-            with torch.cuda.stream(stream):
-                while not errors:
-                    with lock:
-                        b = next(it, None)
-                    if b is None:
-                        break
-                    one(models[k], b)
-            stream.synchronize()
-        except BaseException as ex:             # (re-raised in the caller's thread)
-            errors.append(ex)
-
-    if workers <= 1:
-        work(0, [model])
-    else:
-        models = [model] + model.replicas(workers - 1)
-        torch.cuda.current_stream(dev).synchronize()      # the zeroed tables and the inputs are complete before the workers touch them
-        ts = [threading.Thread(target=work, args=(k, models), daemon=True) for k in range(workers)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-    if errors:
-        raise errors[0]
+    _run_pool(model, batches, dev, max(workers, 1), one)
     vec = vdist.allreduce_metrics(torch.cat([t.buffer for t in tabs]).double())
     parts = vec.to(torch.int64).split([t.buffer.numel() for t in tabs])
     out = [M.ScoreTables(cfg.num_rel_class, cfg.num_obj_class, bins, buffer=p.contiguous()) for p in parts]

@@ -516,6 +516,17 @@ class VLSATModel:
                                                                  split_counts.data_ptr(), L.stream_ptr()))
         return True
 
+    def _scene_plan(self, edge_indices, batch_ids, n, p, fc_sizes, grouped_for: Optional[str] = None):
+        """The head of the graph entry points, under their ``torch.cuda.device``: (the plan -- ONE ``_plan`` lookup --, its scene
+        count, the edge list as a contiguous [E,2] device tensor).  ``grouped_for``: the name of a method whose outputs count edge
+        rows per scene, so that a plan which had to sort the edges by scene is refused in its name."""
+        plan = self._plan(edge_indices, batch_ids, n, p, fc_sizes)
+        if grouped_for is not None and plan.perm is not None:
+            raise L.VlsatError(f"{grouped_for}: edge_indices must be grouped by scene in ascending scene order")
+        s = C.c_int32()
+        L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
+        return plan, s.value, edge_indices.to(self.device).t().contiguous()
+
     @torch.no_grad()
     def predict_graph(self, obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids=None, top_k: int = 100, topk_each: int = 100,
                       evaluate: str = "triplet", fc_sizes: Optional[Sequence[int]] = None):
@@ -529,15 +540,10 @@ class VLSATModel:
             raise NotImplementedError("evaluate type", evaluate)
         pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, edge_indices, descriptor)
         with torch.cuda.device(self.device):
-            plan = self._plan(edge_indices, batch_ids, n, p, fc_sizes)
-            if plan.perm is not None:
-                raise L.VlsatError("predict_graph: edge_indices must be grouped by scene in ascending scene order")
-            s = C.c_int32()
-            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
-            n_scenes, top_k, topk_each = s.value, int(top_k), int(topk_each)
+            plan, n_scenes, edges_e2 = self._scene_plan(edge_indices, batch_ids, n, p, fc_sizes, grouped_for="predict_graph")
+            top_k, topk_each = int(top_k), int(topk_each)
             if not 1 <= top_k <= M.SG_MAX_TOP_K or not 1 <= topk_each <= M.SG_MAX_EACH:
                 raise L.VlsatError(f"predict_graph: top_k must be in 1..{M.SG_MAX_TOP_K} and topk_each in 1..{M.SG_MAX_EACH}")
-            edges_e2 = edge_indices.to(self.device).t().contiguous()
             trip = torch.empty(2, n_scenes, top_k, 4, dtype=torch.int32, device=self.device)
             score = torch.empty(2, n_scenes, top_k, dtype=torch.float32, device=self.device)
             n_valid = torch.empty(2, n_scenes, dtype=torch.int32, device=self.device)
@@ -571,14 +577,9 @@ class VLSATModel:
             raise L.VlsatError(f"decode_graph: n_labels must be in 1..{M.GD_MAX_LABELS} and max_rel in 1..{M.GD_MAX_REL}")
         multi = bool(c.multi_rel_outputs if multi_rel_outputs is None else multi_rel_outputs)
         with torch.cuda.device(self.device):
-            plan = self._plan(edge_indices, batch_ids, n, p, fc_sizes)
-            if plan.perm is not None:
-                raise L.VlsatError("decode_graph: edge_indices must be grouped by scene in ascending scene order")
-            s = C.c_int32()
-            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
-            n_scenes, nb = s.value, 2 if use_2d else 1
+            plan, n_scenes, edges_e2 = self._scene_plan(edge_indices, batch_ids, n, p, fc_sizes, grouped_for="decode_graph")
+            nb = 2 if use_2d else 1
             thr = M.decode_thresholds(threshold, c.num_rel_class, self.device)
-            edges_e2 = edge_indices.to(self.device).t().contiguous()
             labels = torch.empty(nb, n, n_labels, dtype=torch.int32, device=self.device)
             label_probs = torch.empty(nb, n, n_labels, dtype=torch.float32, device=self.device)
             rels = torch.empty(nb, n_scenes, max_rel, 2, dtype=torch.int32, device=self.device)
@@ -635,15 +636,12 @@ class VLSATModel:
             obj3, obj2, rel3, rel2 = self.forward(obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids, fc_sizes=fc_sizes)
             branches = [(obj3, rel3), (obj2, rel2)]
         with torch.cuda.device(self.device):
-            plan = self._plan(edge_indices, batch_ids, obj3.shape[0], obj_points.shape[2], fc_sizes)
-            s = C.c_int32()
-            L.check(self._lib.vlsat_plan_info(plan.handle, C.byref(s), None, None))
-            edges_e2 = edge_indices.to(self.device).t().contiguous()
+            _, n_scenes, edges_e2 = self._scene_plan(edge_indices, batch_ids, obj3.shape[0], obj_points.shape[2], fc_sizes)
             ids = None if batch_ids is None else batch_ids.to(self.device).view(-1)
             w = None if weights is None else torch.as_tensor(weights).to(self.device)
             out = []
             for obj, rel in branches:
-                g = M.merge_segments(obj, rel, edges_e2, ids, s.value, same_part, threshold, mutual, w, multi)
+                g = M.merge_segments(obj, rel, edges_e2, ids, n_scenes, same_part, threshold, mutual, w, multi)
                 out.append((g, g.decode(multi, **decode_args)))
         return out[0], (out[1] if len(out) > 1 else None)
 

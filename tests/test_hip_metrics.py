@@ -328,6 +328,33 @@ def test_merged_validation_matches_the_one_scene_loop():
     check(EV._validation_pipelined(model, batches, DEV, 1, merge=5))
 
 
+def test_a_host_side_failure_in_a_worker_reaches_the_caller_and_leaves_the_replicas_usable():
+    """An item whose dict lacks ``descriptor`` fails in Python, in a worker thread, before any library call: nothing invalid is
+    enqueued.  The caller gets the KeyError from ``validation(workers=2)`` and from ``decode(workers=2)``; the same replicas and
+    fresh streams then give what the serial loops give on the valid items."""
+    _need_gpu()
+    from vlsat_amd import evaluate as EV
+    from vlsat_amd.model import VLSATModel
+    cfg, w, batches = _label_batches(8, 1, 31)
+    model = VLSATModel(cfg, DEV).load_state(w).eval()
+    bad = {k: v for k, v in batches[2].items() if k != "descriptor"}
+    items = batches[:2] + [bad] + batches[2:]
+    want = EV.validation(model, batches, device=DEV)
+    with pytest.raises(KeyError, match="descriptor"):
+        EV.validation(model, items, device=DEV, workers=2)
+    got = EV.validation(model, batches, device=DEV, workers=2)
+    assert got["scenes"] == 8 and got == want
+    with pytest.raises(KeyError, match="descriptor"):
+        list(EV.decode(model, items, device=DEV, workers=2, n_labels=2, max_rel=40))
+    serial = list(EV.decode(model, batches, n_labels=2, max_rel=40))
+    piped = list(EV.decode(model, batches, device=DEV, workers=2, n_labels=2, max_rel=40))
+    assert len(serial) == len(piped) == 8
+    for a, b in zip(serial, piped):
+        for ga, gb in zip(a, b):
+            for k in ga.__slots__:
+                assert torch.equal(getattr(ga, k), getattr(gb, k)), k
+
+
 @pytest.mark.parametrize("regime", ["flat", "peaked", "ties", "few_classes", "one_hot"])
 def test_triplet_staircase_counts_equal_the_brute_force_oracle(regime):
     """The triplet ranks come from a staircase walk over each node's sorted class probabilities (csrc/eval_ranks.hip) instead of

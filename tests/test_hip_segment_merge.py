@@ -113,6 +113,47 @@ def test_merge_graph_on_a_forwards_own_outputs():
     assert sum(int(s[0][0].totals[1]) for s in per_scene) == int(g0.totals[1])
 
 
+def test_evaluate_merged_pipelined_equals_the_serial_loop():
+    """EV.merged(workers=2) -- replicas, streams, results put back in input order, a two-scene item split per scene -- against the
+    serial loop: the same graphs, scene by scene and branch by branch."""
+    _need_gpu()
+    from vlsat_amd import VLSATConfig, synth
+    from vlsat_amd.model import VLSATModel
+    cfg = VLSATConfig(N_LAYERS=1)
+    m = VLSATModel(cfg, DEV).load_state(synth.make_weights(cfg)).eval()
+
+    def item(sizes, seed):
+        b = synth.collate([synth.make_scene(n, 32, seed + i) for i, n in enumerate(sizes)])
+        t = {k: torch.from_numpy(v).to(DEV) for k, v in b.items()}
+        n = t["obj_points"].shape[0]
+        return dict(t, edge_indices=t["edge_indices"].t().contiguous(), n_scenes=len(sizes),
+                    weights=torch.arange(1, n + 1, dtype=torch.float32) * 37.0)
+
+    items = [item([n], 40 + 10 * i) for i, n in enumerate((3, 11, 5, 8, 6))]
+    items.insert(3, item([7, 4], 100))
+    two = items[3]
+    same_part = 7
+    r3 = m(two["obj_points"], two["obj_2d_feats"], two["edge_indices"].t(), two["descriptor"], two["batch_ids"])[2]
+    kw = dict(same_part=same_part, threshold=float(r3[:, same_part].float().quantile(0.9)), n_labels=2, max_rel=50)
+    serial = list(EV.merged(m, items, **kw))
+    piped = list(EV.merged(m, items, device=DEV, workers=2, **kw))
+    assert len(serial) == len(piped) == 7
+    assert [s[0][0].root.numel() for s in piped] == [3, 11, 5, 7, 4, 8, 6]          # input order, the pair split in two
+    for want, got in zip(serial, piped):
+        for (gw, dw), (gg, dg) in zip(want, got):
+            assert_tables(gg, gw)
+            for k in dw.__slots__:
+                assert torch.equal(getattr(dg, k), getattr(dw, k)), k
+    only3 = list(EV.merged(m, items, device=DEV, workers=2, use_2d=False, **kw))
+    assert len(only3) == 7
+    for want, got in zip(serial, only3):
+        assert got[1] is None
+        assert_tables(got[0][0], want[0][0])
+        for k in want[0][1].__slots__:
+            assert torch.equal(getattr(got[0][1], k), getattr(want[0][1], k)), k
+    m.close()
+
+
 def test_bad_arguments_are_errors_not_faults():
     _need_gpu()
     lib = L.load()
