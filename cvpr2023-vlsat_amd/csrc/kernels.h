@@ -286,6 +286,10 @@ int launch_proximity_fill(const float* boxes, const int32_t* node_ptr, int n_sce
 
 // ---- annotation transfer onto a predicted segmentation (label_transfer.hip; the rule is stated in include/vlsat.h) ----
 size_t nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref);
+// the grid nearest_points searches, for other searches over the same cells (cloud.hip): nn_grid.h describes what comes back
+struct NnGridView;
+size_t nn_grid_scratch_bytes(int64_t n_ref);
+NnGridView launch_nn_grid(const float* ref, int64_t n_ref, float max_sq_dist, void* scratch, hipStream_t s);
 int launch_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
                           int32_t* nn_index, float* nn_sqdist, hipStream_t s);
 // id_maps: int32 [seg_map_size + gt_map_size] scratch (segment id -> slot, then instance id -> slot)

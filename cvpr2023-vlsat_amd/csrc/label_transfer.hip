@@ -17,31 +17,14 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "nn_grid.h"
 #include "select_core.h"
 
 namespace vlsat {
 
-constexpr int NN_AXIS_CELLS = 1024;            // cells per axis: keeps the rounding of a cell coordinate below 1/64 of a cell (nn_params_kernel)
-constexpr int NN_MAX_CELLS = 1 << 21;          // cells in all (the histogram and its scan are this long at most)
 constexpr int NN_THREADS = 256;
 constexpr int NN_SCAN_THREADS = 1024, NN_SCAN_PER = 4;
 constexpr unsigned long long NN_NONE = ~0ull;
-
-struct NnGrid {
-    float lo[3];
-    float inv_h;
-    int n[3];
-    int n_cells;
-};
-
-__device__ __forceinline__ bool nn_finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// cell coordinate on one axis: monotone in x, clamped to [0, n).  A NaN product (an overflowed difference times inv_h = 0) gives 0.
-__device__ __forceinline__ int nn_cell_axis(float x, float lo, float inv_h, int n) {
-    const float t = (x - lo) * inv_h;
-    if (!(t >= 0.0f)) return 0;
-    return min((int)fminf(t, (float)(NN_AXIS_CELLS - 1)), n - 1);
-}
 
 __global__ void nn_init_kernel(unsigned* __restrict__ box) {
     if (threadIdx.x < 3) box[threadIdx.x] = fkey(INFINITY);
@@ -229,24 +212,15 @@ __global__ void nn_none_kernel(int n_query, int32_t* __restrict__ nn_index, floa
 }
 
 // scratch: sorted float4 [n_ref] | grid (64 bytes) | box u32 [8] | cell i32 [n_ref] | counts = cursor i32 [NN_MAX_CELLS + 1] | start i32 [NN_MAX_CELLS + 1]
-size_t nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref) {
-    (void)n_query;
+size_t nn_grid_scratch_bytes(int64_t n_ref) {
     const size_t g = (size_t)(n_ref > 0 ? n_ref : 0);
     return g * 16 + 64 + 32 + align_up(g * 4, 16) + 2 * align_up((size_t)(NN_MAX_CELLS + 1) * 4, 16);
 }
 
-int launch_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
-                          int32_t* nn_index, float* nn_sqdist, hipStream_t s) {
-    if (n_query < 0 || n_ref < 0 || n_query > 0x7fffffff || n_ref > 0x7fffffff) return fail(-1, "nearest_points: bad sizes");
-    if (!(max_sq_dist >= 0.0f)) return fail(-1, "nearest_points: max_sq_dist must be >= 0 (it is a squared distance)");
-    if (n_query == 0) return 0;
-    const int Q = (int)n_query, G = (int)n_ref;
-    const dim3 qgrid((unsigned)((n_query + NN_THREADS - 1) / NN_THREADS));
-    if (G == 0) {
-        hipLaunchKernelGGL(nn_none_kernel, qgrid, dim3(NN_THREADS), 0, s, Q, nn_index, nn_sqdist);
-        VLSAT_LAUNCH_CHECK("nearest_points");
-        return 0;
-    }
+// The grid over ref[0 .. n_ref), 1 <= n_ref <= 2^31 - 1, built inside `scratch` (nn_grid_scratch_bytes): seven launches, no check of
+// its own -- the caller's VLSAT_LAUNCH_CHECK covers them.
+NnGridView launch_nn_grid(const float* ref, int64_t n_ref, float max_sq_dist, void* scratch, hipStream_t s) {
+    const int G = (int)n_ref;
     char* p = static_cast<char*>(scratch);
     float4* sorted = reinterpret_cast<float4*>(p);            p += (size_t)G * 16;
     NnGrid* grid = reinterpret_cast<NnGrid*>(p);               p += 64;
@@ -262,7 +236,28 @@ int launch_nearest_points(const float* query, int64_t n_query, const float* ref,
     hipLaunchKernelGGL(nn_hist_kernel, rgrid, dim3(NN_THREADS), 0, s, ref, G, grid, cell, counts);
     hipLaunchKernelGGL(nn_scan_kernel, dim3(1), dim3(NN_SCAN_THREADS), 0, s, grid, counts, start);
     hipLaunchKernelGGL(nn_fill_kernel, rgrid, dim3(NN_THREADS), 0, s, ref, G, cell, counts, sorted);
-    hipLaunchKernelGGL(nn_query_kernel, qgrid, dim3(NN_THREADS), 0, s, query, Q, G, max_sq_dist, grid, start, sorted, nn_index, nn_sqdist);
+    return NnGridView{sorted, grid, cell, start};
+}
+
+size_t nearest_points_scratch_bytes(int64_t n_query, int64_t n_ref) {
+    (void)n_query;
+    return nn_grid_scratch_bytes(n_ref);
+}
+
+int launch_nearest_points(const float* query, int64_t n_query, const float* ref, int64_t n_ref, float max_sq_dist, void* scratch,
+                          int32_t* nn_index, float* nn_sqdist, hipStream_t s) {
+    if (n_query < 0 || n_ref < 0 || n_query > 0x7fffffff || n_ref > 0x7fffffff) return fail(-1, "nearest_points: bad sizes");
+    if (!(max_sq_dist >= 0.0f)) return fail(-1, "nearest_points: max_sq_dist must be >= 0 (it is a squared distance)");
+    if (n_query == 0) return 0;
+    const int Q = (int)n_query, G = (int)n_ref;
+    const dim3 qgrid((unsigned)((n_query + NN_THREADS - 1) / NN_THREADS));
+    if (G == 0) {
+        hipLaunchKernelGGL(nn_none_kernel, qgrid, dim3(NN_THREADS), 0, s, Q, nn_index, nn_sqdist);
+        VLSAT_LAUNCH_CHECK("nearest_points");
+        return 0;
+    }
+    const NnGridView g = launch_nn_grid(ref, n_ref, max_sq_dist, scratch, s);
+    hipLaunchKernelGGL(nn_query_kernel, qgrid, dim3(NN_THREADS), 0, s, query, Q, G, max_sq_dist, g.grid, g.start, g.sorted, nn_index, nn_sqdist);
     VLSAT_LAUNCH_CHECK("nearest_points");
     return 0;
 }

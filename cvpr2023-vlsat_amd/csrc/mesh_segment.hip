@@ -25,7 +25,13 @@
 // all vertices) is read by many and written by none once it is the lowest vertex of its component; its size takes one add per wave and
 // distinct root, and no thread retries a CAS on it: a CAS is only ever aimed at the LARGER of two roots, which then stops being a root.
 // build.py compiles THIS file with -ffp-contract=off (PER_SOURCE_FLAGS): seg_weight rounds every product and sum on its own.
+//
+// vlsat_segment_cloud (include/vlsat_cloud.h) runs the same launches over a cloud's neighbour table: the edge loader and the weight are
+// template parameters of ms_link_kernel and ms_choose_kernel (MsEdgeList | MsNbrTable, signed | unsigned), and vlsat_segment_mesh
+// instantiates what it always ran.
+#include "../../include/vlsat_cloud.h"
 #include "../../include/vlsat_segment.h"
+#include "cloud_core.h"
 #include "common.h"
 #include "kernels.h"
 #include "segment_core.h"
@@ -62,18 +68,31 @@ __device__ __forceinline__ void ms_unite(int32_t* __restrict__ parent, int a, in
     }
 }
 
+// Where the edges come from -- a template parameter of the two kernels that read them: an explicit list (a mesh), or the neighbour
+// table of a cloud, whose edge e joins point e / K and nbr[e] (a -1 entry fails seg_edge_ok like any end out of range).
 struct MsEdge { int a, b; bool ok; };
-__device__ __forceinline__ MsEdge ms_edge(const int32_t* __restrict__ edges, int n_verts, int64_t e) {
-    const int a = edges[(size_t)e * 2], b = edges[(size_t)e * 2 + 1];
+__device__ __forceinline__ MsEdge ms_checked(int a, int b, int n_verts) {
     MsEdge r;
     r.ok = seg_edge_ok(a, b, n_verts);
     r.a = r.ok ? a : 0;
     r.b = r.ok ? b : 0;
     return r;
 }
+struct MsEdgeList {
+    const int32_t* edges;
+    __device__ __forceinline__ MsEdge load(int n_verts, int64_t e) const { return ms_checked(edges[(size_t)e * 2], edges[(size_t)e * 2 + 1], n_verts); }
+};
+struct MsNbrTable {
+    const int32_t* nbr;
+    int k;
+    __device__ __forceinline__ MsEdge load(int n_verts, int64_t e) const { return ms_checked((int)(e / k), nbr[e], n_verts); }
+};
+// UNSIGNED: the weight of unoriented normals, fl(1 - |d|) (cloud_core.h); else seg_weight.
+template <bool UNSIGNED>
 __device__ __forceinline__ float ms_weight(const float* __restrict__ normals, int a, int b) {
     const float* na = normals + (size_t)a * 3;
     const float* nb = normals + (size_t)b * 3;
+    if (UNSIGNED) return cloud_unsigned_weight(na[0], na[1], na[2], nb[0], nb[1], nb[2]);
     return seg_weight(na[0], na[1], na[2], nb[0], nb[1], nb[2]);
 }
 
@@ -86,12 +105,13 @@ __global__ __launch_bounds__(MS_THREADS) void ms_init_kernel(int n_verts, int32_
     seg_size[v] = 0;
 }
 
-__global__ __launch_bounds__(MS_THREADS) void ms_link_kernel(const float* __restrict__ normals, const int32_t* __restrict__ edges, int n_verts,
+template <class Edges, bool UNSIGNED>
+__global__ __launch_bounds__(MS_THREADS) void ms_link_kernel(const float* __restrict__ normals, const Edges edges, int n_verts,
                                                              int64_t n_edges, float max_weight, int32_t* __restrict__ parent) {
     const int64_t e = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
     if (e >= n_edges) return;
-    const MsEdge ed = ms_edge(edges, n_verts, e);
-    if (!ed.ok || !(ms_weight(normals, ed.a, ed.b) <= max_weight)) return;
+    const MsEdge ed = edges.load(n_verts, e);
+    if (!ed.ok || !(ms_weight<UNSIGNED>(normals, ed.a, ed.b) <= max_weight)) return;
     ms_unite(parent, ed.a, ed.b);
 }
 
@@ -130,18 +150,19 @@ __global__ __launch_bounds__(MS_THREADS) void ms_count_kernel(const int32_t* __r
     }
 }
 
-__global__ __launch_bounds__(MS_THREADS) void ms_choose_kernel(const float* __restrict__ normals, const int32_t* __restrict__ edges, int n_verts,
+template <class Edges, bool UNSIGNED>
+__global__ __launch_bounds__(MS_THREADS) void ms_choose_kernel(const float* __restrict__ normals, const Edges edges, int n_verts,
                                                                int64_t n_edges, int min_verts, const int32_t* __restrict__ root,
                                                                const int32_t* __restrict__ size, unsigned long long* __restrict__ key) {
     const int64_t e = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
     if (e >= n_edges) return;
-    const MsEdge ed = ms_edge(edges, n_verts, e);
+    const MsEdge ed = edges.load(n_verts, e);
     if (!ed.ok) return;
     const int ra = root[ed.a], rb = root[ed.b];
     if (ra == rb || ra < 0 || rb < 0 || ra >= n_verts || rb >= n_verts) return;
     const bool small_a = size[ra] < min_verts, small_b = size[rb] < min_verts;
     if (!small_a && !small_b) return;
-    const float w = ms_weight(normals, ed.a, ed.b);                   // symmetric: the edge stands for both of its directions
+    const float w = ms_weight<UNSIGNED>(normals, ed.a, ed.b);         // symmetric: the edge stands for both of its directions
     if (small_a) atomicMin(key + ra, seg_key(w, rb));
     if (small_b) atomicMin(key + rb, seg_key(w, ra));
 }
@@ -229,7 +250,8 @@ static int segment_mesh_check_args(int64_t V, int64_t M) {
     return 0;
 }
 
-static int launch_segment_mesh(const float* normals, const int32_t* edges, int64_t n_verts, int64_t n_edges, float max_weight, int min_verts,
+template <class Edges, bool UNSIGNED>
+static int launch_segment(const char* what, const float* normals, const Edges edges, int64_t n_verts, int64_t n_edges, float max_weight, int min_verts,
                                void* scratch, int32_t* labels, int32_t* n_segments, int32_t* seg_size, hipStream_t s) {
     const int V = (int)n_verts;
     const int64_t M = n_edges;
@@ -246,12 +268,12 @@ static int launch_segment_mesh(const float* normals, const int32_t* edges, int64
     const dim3 block(MS_THREADS), per_vertex((unsigned)((V + MS_THREADS - 1) / MS_THREADS)),
         per_edge((unsigned)((M + MS_THREADS - 1) / MS_THREADS)), per_tile((unsigned)lay.tiles);
     hipLaunchKernelGGL(ms_init_kernel, per_vertex, block, 0, s, V, parent, seg_size, n_segments);
-    if (M > 0) hipLaunchKernelGGL(ms_link_kernel, per_edge, block, 0, s, normals, edges, V, M, max_weight, parent);
+    if (M > 0) hipLaunchKernelGGL((ms_link_kernel<Edges, UNSIGNED>), per_edge, block, 0, s, normals, edges, V, M, max_weight, parent);
     hipLaunchKernelGGL(ms_flatten_kernel, per_vertex, block, 0, s, (const int32_t*)parent, V, root, size, key);
     const int rounds = M > 0 ? seg_rounds(min_verts) : 0;              // without an edge no component has a neighbour
     for (int r = 0; r < rounds; ++r) {
         hipLaunchKernelGGL(ms_count_kernel, per_vertex, block, 0, s, (const int32_t*)root, V, parent, size);
-        hipLaunchKernelGGL(ms_choose_kernel, per_edge, block, 0, s, normals, edges, V, M, min_verts, (const int32_t*)root, (const int32_t*)size, key);
+        hipLaunchKernelGGL((ms_choose_kernel<Edges, UNSIGNED>), per_edge, block, 0, s, normals, edges, V, M, min_verts, (const int32_t*)root, (const int32_t*)size, key);
         hipLaunchKernelGGL(ms_hook_kernel, per_vertex, block, 0, s, V, min_verts, (const int32_t*)root, (const int32_t*)size,
                            (const unsigned long long*)key, parent);
         hipLaunchKernelGGL(ms_flatten_kernel, per_vertex, block, 0, s, (const int32_t*)parent, V, root, size, key);
@@ -262,7 +284,7 @@ static int launch_segment_mesh(const float* normals, const int32_t* edges, int64
     hipLaunchKernelGGL(ms_number_kernel, per_tile, block, 0, s, (const int32_t*)root, (const int32_t*)size, V, min_verts,
                        (const int32_t*)block_first, num, seg_size);
     hipLaunchKernelGGL(ms_label_kernel, per_vertex, block, 0, s, (const int32_t*)root, (const int32_t*)num, V, labels);
-    VLSAT_LAUNCH_CHECK("segment_mesh");
+    VLSAT_LAUNCH_CHECK(what);
     return 0;
 }
 
@@ -283,8 +305,24 @@ int vlsat_segment_mesh(const float* normals, const int32_t* edges, int64_t n_ver
     if (max_weight != max_weight) return fail(VLSAT_EINVAL, "segment_mesh: max_weight is NaN");
     if (!normals || !scratch || !labels || !n_segments || !seg_size) return fail(VLSAT_EINVAL, "segment_mesh: null argument");
     if (n_edges > 0 && !edges) return fail(VLSAT_EINVAL, "segment_mesh: null edge list");
-    return launch_segment_mesh(normals, edges, n_verts, n_edges, max_weight, min_verts, scratch, labels, n_segments, seg_size,
-                               static_cast<hipStream_t>(stream));
+    return launch_segment<MsEdgeList, false>("segment_mesh", normals, MsEdgeList{edges}, n_verts, n_edges, max_weight, min_verts, scratch, labels,
+                                             n_segments, seg_size, static_cast<hipStream_t>(stream));
+}
+
+// include/vlsat_cloud.h: the same rules over the directed pairs (e / K, nbr[e]), e < V K
+int vlsat_segment_cloud(const float* normals, const int32_t* nbr, int64_t n_points, int32_t k, float max_weight, int32_t min_verts,
+                        int32_t unsigned_dot, void* scratch, int32_t* labels, int32_t* n_segments, int32_t* seg_size, void* stream) {
+    if (!cloud_sizes_ok(n_points, k)) return fail(VLSAT_EINVAL, "segment_cloud: 1 .. 2^24 points and 1 .. 32 neighbours");
+    if (max_weight != max_weight) return fail(VLSAT_EINVAL, "segment_cloud: max_weight is NaN");
+    if (!normals || !nbr || !scratch || !labels || !n_segments || !seg_size) return fail(VLSAT_EINVAL, "segment_cloud: null argument");
+    const int64_t n_edges = n_points * k;                              // at most 2^29
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const MsNbrTable table{nbr, (int)k};
+    if (unsigned_dot)
+        return launch_segment<MsNbrTable, true>("segment_cloud", normals, table, n_points, n_edges, max_weight, min_verts, scratch, labels,
+                                                n_segments, seg_size, s);
+    return launch_segment<MsNbrTable, false>("segment_cloud", normals, table, n_points, n_edges, max_weight, min_verts, scratch, labels,
+                                             n_segments, seg_size, s);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
 SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
 CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
 SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_segment.h")
+CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud.h")
 
 
 class VlsatDims(C.Structure):
@@ -146,6 +147,14 @@ _SIGNATURES_SEGMENT = {
     "vlsat_segment_mesh": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_cloud.h: a cloud without faces -- kNN table, normals and flatness (csrc/cloud.hip), segments over the table (csrc/mesh_segment.hip)
+_SIGNATURES_CLOUD = {
+    "vlsat_cloud_knn_scratch_bytes": (_sz, [_i64, _i32]),
+    "vlsat_cloud_knn": (C.c_int, [_vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "vlsat_cloud_normals": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "vlsat_segment_cloud": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -159,7 +168,8 @@ def identity(lib_path: str = "") -> dict:
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH,
+                                          os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -193,6 +203,11 @@ def declared_segment_symbols() -> list:
     return _declared(SEGMENT_HEADER_PATH)
 
 
+def declared_cloud_symbols() -> list:
+    """Every function include/vlsat_cloud.h declares."""
+    return _declared(CLOUD_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -203,7 +218,7 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()):
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

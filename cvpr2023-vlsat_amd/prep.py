@@ -5,7 +5,7 @@ The selection of an object's points (``np.where(instances == id)`` + ``np.random
 (``sample_objects``): its index lists are np.where's, its draws come from a documented counter-based generator, not numpy's."""
 from __future__ import annotations
 
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import torch
 
@@ -627,21 +627,22 @@ def _seg_unite(parent, a, b):
     return parent
 
 
-def segment_weights_host(normals, a, b):
-    """w of include/vlsat_segment.h for the vertex pairs (a[i], b[i]) in numpy float32: every product and sum rounded on its own."""
+def segment_weights_host(normals, a, b, unsigned: bool = False):
+    """w of include/vlsat_segment.h for the vertex pairs (a[i], b[i]) in numpy float32: every product and sum rounded on its own.
+    ``unsigned``: the weight of include/vlsat_cloud.h for normals without a meaningful sign, 1 - |d|."""
     import numpy as np
     n = np.ascontiguousarray(normals, dtype=np.float32)
     na, nb = n[a], n[b]
     with np.errstate(invalid="ignore", over="ignore"):
         d = (na[:, 0] * nb[:, 0] + na[:, 1] * nb[:, 1]) + na[:, 2] * nb[:, 2]
-        w = np.float32(1.0) - d
+        w = np.float32(1.0) - (np.abs(d) if unsigned else d)
         w = np.where(w < 0, np.float32(0.0), np.where(w > 2, np.float32(2.0), w)).astype(np.float32)
     return np.where(np.isnan(d), np.float32(2.0), w).astype(np.float32)
 
 
-def segment_mesh_host(normals, edges, max_weight: float, min_verts: int = 20, trim: bool = True) -> MeshSegments:
+def segment_mesh_host(normals, edges, max_weight: float, min_verts: int = 20, trim: bool = True, unsigned: bool = False) -> MeshSegments:
     """``segment_mesh`` stated in numpy with the kernels' operations: the rule of include/vlsat_segment.h, step by step -- equal labels,
-    count and sizes.  Returns CPU tensors."""
+    count and sizes.  ``unsigned`` selects the weight 1 - |d| of include/vlsat_cloud.h.  Returns CPU tensors."""
     import numpy as np
     n = np.ascontiguousarray(normals.cpu().numpy() if torch.is_tensor(normals) else normals, dtype=np.float32)
     e = np.asarray(edges.cpu().numpy() if torch.is_tensor(edges) else edges).astype(np.int64)
@@ -650,7 +651,7 @@ def segment_mesh_host(normals, edges, max_weight: float, min_verts: int = 20, tr
     v, min_verts, max_weight = n.shape[0], int(min_verts), np.float32(max_weight)
     ok = (e >= 0).all(1) & (e < v).all(1) & (e[:, 0] != e[:, 1])
     a, b = e[ok, 0], e[ok, 1]
-    w = segment_weights_host(n, a, b)
+    w = segment_weights_host(n, a, b, unsigned)
     parent = np.arange(v, dtype=np.int64)
     link = w <= max_weight
     _seg_unite(parent, a[link], b[link])                                           # step 2; parent is flat: parent[x] = root(x)
@@ -700,5 +701,249 @@ def segment_mesh(normals: torch.Tensor, edges: torch.Tensor, max_weight: float, 
     n_segments = torch.empty(1, dtype=torch.int32, device=dev)
     L.check(lib.vlsat_segment_mesh(normals.data_ptr(), edges.data_ptr(), v, m, float(max_weight), int(min_verts), scratch.data_ptr(),
                                    labels.data_ptr(), n_segments.data_ptr(), seg_size.data_ptr(), L.stream_ptr()))
+    out = MeshSegments(labels, n_segments, seg_size)
+    return out.trim() if trim else out
+
+
+# ---- a cloud without faces: kNN table, normals and flatness, segments (csrc/cloud.hip; the rules are stated in include/vlsat_cloud.h) ----
+CLOUD_MAX_K = 32
+CLOUD_SWEEPS = 6
+
+
+class KnnTable(NamedTuple):
+    """``knn_points``: ``index`` int32 [V,K] (-1 pads), ``sqdist`` f32 [V,K] (+inf pads), ``count`` int32 [V]."""
+    index: object
+    sqdist: object
+    count: object
+
+
+def _knn_args(shape, k, max_sq_dist):
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= SEG_MAX_VERTS:
+        raise L.VlsatError("knn_points: points must be float32 [V,3] with 1 <= V <= 2^24")
+    if not 1 <= int(k) <= CLOUD_MAX_K:
+        raise L.VlsatError("knn_points: 1 <= k <= 32")
+    if not float(max_sq_dist) >= 0:
+        raise L.VlsatError("knn_points: max_sq_dist must be >= 0 (it is a squared distance)")
+
+
+def knn_points_host(points, k: int, max_sq_dist: float, chunk: int = 256) -> KnnTable:
+    """The neighbour rule of include/vlsat_cloud.h in numpy, in the same fp32 operations (every index, distance bit and count is the
+    device's) -> ``KnnTable`` of numpy arrays.  A sweep along x like ``nearest_points_host``: per chunk of points in x order, the keys
+    (bits(d2) << 32) | j of the points within sqrt(max_sq_dist) in x, the point itself and everything beyond max_sq_dist struck out,
+    and the k smallest of them -- which do not depend on how the candidates were found."""
+    import numpy as np
+
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 3)
+    _knn_args(p.shape, k, max_sq_dist)
+    k, m = int(k), np.float32(max_sq_dist)
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    best = np.full((len(p), k), none, dtype=np.uint64)
+    idx = np.nonzero(np.isfinite(p).all(1))[0]
+    if len(idx):
+        idx = idx[np.argsort(p[idx, 0], kind="stable")]
+        ps, px = p[idx], p[idx, 0].astype(np.float64)
+        w = float(np.sqrt(np.float64(m))) * (1.0 + 2.0 ** -20) + 1e-20 if np.isfinite(m) else np.inf   # as in nearest_points_host
+        with np.errstate(over="ignore", invalid="ignore"):
+            for c0 in range(0, len(idx), chunk):
+                qi = idx[c0:c0 + chunk]
+                qc = p[qi]
+                a = np.searchsorted(px, float(qc[0, 0]) - w, "left")
+                b = np.searchsorted(px, float(qc[-1, 0]) + w, "right")
+                acc = np.full((len(qi), k), none, dtype=np.uint64)
+                for p0 in range(a, b, 8192):
+                    rp, ri = ps[p0:min(p0 + 8192, b)], idx[p0:min(p0 + 8192, b)]
+                    dx, dy, dz = (qc[:, None, c] - rp[None, :, c] for c in range(3))
+                    d2 = (dx * dx + dy * dy) + dz * dz
+                    key = (np.ascontiguousarray(d2).view(np.uint32).astype(np.uint64) << np.uint64(32)) | ri.astype(np.uint64)[None, :]
+                    key = np.where((d2 <= m) & (ri[None, :] != qi[:, None]), key, none)
+                    if key.shape[1] > 4 * k:
+                        key = np.partition(key, k - 1, axis=1)[:, :k]
+                    acc = np.sort(np.concatenate([acc, key], 1), axis=1)[:, :k]
+                best[qi] = acc
+    found = best != none
+    index = np.where(found, best & np.uint64(0xFFFFFFFF), 0).astype(np.int64).astype(np.int32)
+    index[~found] = -1
+    sqdist = np.where(found, (best >> np.uint64(32)).astype(np.uint32).view(np.float32), np.float32(np.inf)).astype(np.float32)
+    return KnnTable(index, sqdist, found.sum(1).astype(np.int32))
+
+
+def knn_points(points, k: int, max_sq_dist: float) -> KnnTable:
+    """points f32 [V,3] -> ``KnnTable``: per point its ``k`` (1 .. 32) nearest other points among those with
+    ``d2 = (dx*dx + dy*dy) + dz*dz <= max_sq_dist`` (fp32, every operation rounded on its own: the d2 of ``nearest_points``), nearest
+    first, ties to the lower index; fewer than k: the row is padded with -1 / +inf and ``count`` says how many there are
+    (include/vlsat_cloud.h, vlsat_cloud_knn).  ``max_sq_dist`` is a SQUARED distance.  A point with a non-finite coordinate has no
+    neighbours and is nobody's.  Exact and deterministic.  Device tensors run the HIP kernels (nothing is read back); CPU tensors or
+    arrays run ``knn_points_host`` and get CPU tensors."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        t = knn_points_host(points.numpy() if isinstance(points, torch.Tensor) else points, k, max_sq_dist)
+        return KnnTable(*(torch.from_numpy(x) for x in t))
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("knn_points: points must be float32 [V,3]")
+    _knn_args(points.shape, k, max_sq_dist)
+    dev, points, v, k = points.device, points.contiguous(), points.shape[0], int(k)
+    scratch = torch.empty(int(lib.vlsat_cloud_knn_scratch_bytes(v, k)), dtype=torch.uint8, device=dev)
+    index = torch.empty((v, k), dtype=torch.int32, device=dev)
+    sqdist = torch.empty((v, k), dtype=torch.float32, device=dev)
+    count = torch.empty(v, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_cloud_knn(points.data_ptr(), v, k, float(max_sq_dist), scratch.data_ptr(), index.data_ptr(), sqdist.data_ptr(),
+                                count.data_ptr(), L.stream_ptr()))
+    return KnnTable(index, sqdist, count)
+
+
+def _normals_args(points_shape, index_shape, count_shape, min_points, viewpoint):
+    import math
+    if len(points_shape) != 2 or points_shape[1] != 3 or not 1 <= points_shape[0] <= SEG_MAX_VERTS:
+        raise L.VlsatError("cloud_normals: points must be float32 [V,3] with 1 <= V <= 2^24")
+    if len(index_shape) != 2 or index_shape[0] != points_shape[0] or not 1 <= index_shape[1] <= CLOUD_MAX_K:
+        raise L.VlsatError("cloud_normals: knn_index must be int32 [V,K] with 1 <= K <= 32")
+    if tuple(count_shape) != (points_shape[0],):
+        raise L.VlsatError("cloud_normals: knn_count must be int32 [V]")
+    if int(min_points) < 3:
+        raise L.VlsatError("cloud_normals: min_points must be at least 3")
+    if viewpoint is not None and (len(viewpoint) != 3 or any(math.isnan(float(x)) for x in viewpoint)):
+        raise L.VlsatError("cloud_normals: the viewpoint is three numbers, none NaN")
+
+
+def _jacobi_rotate(np, app, aqq, apq, arp, arq, vp, vq):
+    """cloud_rotate of csrc/cloud_core.h on arrays: the same operations in the same order, the skipped pairs left as they are."""
+    live = apq != 0.0
+    theta = (aqq - app) / (2.0 * apq)
+    den = np.abs(theta) + np.sqrt(theta * theta + 1.0)
+    t = np.where(theta < 0.0, -1.0, 1.0) / den
+    c = 1.0 / np.sqrt(t * t + 1.0)
+    s = t * c
+    tap = t * apq
+    keep = lambda new, old: np.where(live, new, old)   # noqa: E731
+    out = [keep(app - tap, app), keep(aqq + tap, aqq), keep(0.0, apq), keep(c * arp - s * arq, arp), keep(s * arp + c * arq, arq)]
+    nvp = [keep(c * a - s * b, a) for a, b in zip(vp, vq)]
+    nvq = [keep(s * a + c * b, b) for a, b in zip(vp, vq)]
+    return (*out, nvp, nvq)
+
+
+def cloud_normals_host(points, knn_index, knn_count, min_points: int = 5, viewpoint=None, rounded: bool = True):
+    """The normal and flatness rule of include/vlsat_cloud.h in numpy float64, the same operations in the same order as
+    csrc/cloud_core.h -> (normals f32 [V,3], curvature f32 [V]) as numpy arrays, every bit the device's.  ``rounded=False`` returns the
+    float64 values before the last step, the rounding to fp32 (to compare the eigenvectors with another solver's)."""
+    import numpy as np
+
+    p32 = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 3)
+    nbr = np.asarray(knn_index).astype(np.int64)
+    cnt = np.asarray(knn_count).astype(np.int64).reshape(-1)
+    _normals_args(p32.shape, nbr.shape, cnt.shape, min_points, viewpoint)
+    v, k = nbr.shape
+    p = p32.astype(np.float64)
+    listed = np.clip(cnt, 0, k)
+    member = (np.arange(k)[None, :] < listed[:, None]) & (nbr >= 0) & (nbr < v)
+    safe = np.where(member, nbr, 0)
+    with np.errstate(all="ignore"):
+        s = p.copy()
+        for j in range(k):
+            s = np.where(member[:, j, None], s + p[safe[:, j]], s)
+        n = 1 + member.sum(1)
+        c = s / n[:, None].astype(np.float64)
+        a = {key: np.zeros(v) for key in ("00", "01", "02", "11", "12", "22")}
+
+        def add(a, q, on):
+            d = q - c
+            for key, (x, y) in (("00", (0, 0)), ("01", (0, 1)), ("02", (0, 2)), ("11", (1, 1)), ("12", (1, 2)), ("22", (2, 2))):
+                a[key] = np.where(on, a[key] + d[:, x] * d[:, y], a[key])
+
+        add(a, p, np.ones(v, bool))
+        for j in range(k):
+            add(a, p[safe[:, j]], member[:, j])
+        trace = (a["00"] + a["11"]) + a["22"]
+        have = (n >= int(min_points)) & (trace > 0.0)
+        one, zero = np.ones(v), np.zeros(v)
+        v0, v1, v2 = [one, zero, zero], [zero, one, zero], [zero, zero, one]      # columns of V: v0[r] = V[r][0]
+        a00, a11, a22, a01, a02, a12 = a["00"], a["11"], a["22"], a["01"], a["02"], a["12"]
+        for _ in range(CLOUD_SWEEPS):
+            a00, a11, a01, a02, a12, v0, v1 = _jacobi_rotate(np, a00, a11, a01, a02, a12, v0, v1)
+            a00, a22, a02, a01, a12, v0, v2 = _jacobi_rotate(np, a00, a22, a02, a01, a12, v0, v2)
+            a11, a22, a12, a01, a02, v1, v2 = _jacobi_rotate(np, a11, a22, a12, a01, a02, v1, v2)
+        lmin, nrm = a00, list(v0)
+        for lam, col in ((a11, v1), (a22, v2)):
+            lower = lam < lmin
+            lmin = np.where(lower, lam, lmin)
+            nrm = [np.where(lower, x, y) for x, y in zip(col, nrm)]
+        curv = np.where(lmin > 0.0, lmin, 0.0) / ((a00 + a11) + a22)
+        d = np.zeros(v)
+        if viewpoint is not None:
+            t = np.asarray([float(x) for x in viewpoint], dtype=np.float64)[None, :] - p
+            d = (nrm[0] * t[:, 0] + nrm[1] * t[:, 1]) + nrm[2] * t[:, 2]
+        big = nrm[0]
+        big = np.where(np.abs(nrm[1]) > np.abs(big), nrm[1], big)
+        big = np.where(np.abs(nrm[2]) > np.abs(big), nrm[2], big)
+        flip = np.where(d < 0.0, True, np.where(d > 0.0, False, big < 0.0))
+        nrm = np.stack([np.where(flip, -x, x) for x in nrm], 1)
+        normals = np.where(have[:, None], nrm, 0.0)
+        curvature = np.where(have, curv, 1.0)
+    return (normals.astype(np.float32), curvature.astype(np.float32)) if rounded else (normals, curvature)
+
+
+def cloud_normals(points, knn_index, knn_count, min_points: int = 5, viewpoint=None):
+    """points f32 [V,3] and the table of ``knn_points`` -> (normals f32 [V,3], curvature f32 [V]): per point the eigenvector of the
+    smallest eigenvalue of the covariance of the point and its neighbours, and the surface variation lambda_min / (l0 + l1 + l2) in
+    [0, 1/3] -- 0 on a plane, large at a crease (include/vlsat_cloud.h, vlsat_cloud_normals: fp64, six cyclic Jacobi sweeps).  Fewer than
+    ``min_points`` members (the point counts) or coincident members: normal (0, 0, 0), curvature 1.  ``viewpoint`` (x, y, z) turns every
+    normal towards it; without one the sign is a convention (largest component positive) and means nothing: segment with
+    ``unsigned=True``.  Device tensors run the HIP kernel; CPU tensors or arrays run ``cloud_normals_host`` and get CPU tensors."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x   # noqa: E731
+        n, c = cloud_normals_host(as_np(points), as_np(knn_index), as_np(knn_count), min_points, viewpoint)
+        return torch.from_numpy(n), torch.from_numpy(c)
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("cloud_normals: points must be float32 [V,3]")
+    _normals_args(points.shape, knn_index.shape, knn_count.shape, min_points, viewpoint)
+    dev, points = points.device, points.contiguous()
+    index = knn_index.to(device=dev, dtype=torch.int32).contiguous()
+    count = knn_count.to(device=dev, dtype=torch.int32).contiguous()
+    v, k = index.shape
+    normals = torch.empty((v, 3), dtype=torch.float32, device=dev)
+    curvature = torch.empty(v, dtype=torch.float32, device=dev)
+    vp = [float(x) for x in viewpoint] if viewpoint is not None else [0.0, 0.0, 0.0]
+    L.check(lib.vlsat_cloud_normals(points.data_ptr(), index.data_ptr(), count.data_ptr(), v, k, int(min_points), int(viewpoint is not None),
+                                    vp[0], vp[1], vp[2], normals.data_ptr(), curvature.data_ptr(), L.stream_ptr()))
+    return normals, curvature
+
+
+def knn_edges(knn_index):
+    """The neighbour table as an explicit edge list int32 [V K, 2]: edge e joins e // K and index[e]; the -1 pads stay and are ignored
+    by the rule.  ``segment_mesh`` on this list equals ``segment_cloud`` on the table."""
+    import numpy as np
+    if torch.is_tensor(knn_index):
+        v, k = knn_index.shape
+        a = torch.arange(v, dtype=torch.int32, device=knn_index.device).repeat_interleave(k)
+        return torch.stack([a, knn_index.to(torch.int32).reshape(-1)], 1).contiguous()
+    idx = np.asarray(knn_index).astype(np.int32)
+    v, k = idx.shape
+    return np.ascontiguousarray(np.stack([np.repeat(np.arange(v, dtype=np.int32), k), idx.reshape(-1)], 1))
+
+
+def segment_cloud(normals: torch.Tensor, knn_index: torch.Tensor, max_weight: float, min_verts: int = 20, unsigned: bool = True,
+                  trim: bool = True) -> MeshSegments:
+    """normals f32 [V,3] and the neighbour table int32 [V,K] of ``knn_points`` -> ``MeshSegments``: the rule of ``segment_mesh`` over
+    the pairs (i, index[i, j]) instead of mesh edges (include/vlsat_cloud.h, vlsat_segment_cloud).  ``unsigned=True`` weighs an edge
+    1 - |dot|, for normals whose sign is a convention (``cloud_normals`` without a viewpoint); ``unsigned=False`` is the mesh's
+    1 - dot.  A zero normal weighs 1 against everyone: it links to nobody and is absorbed by a neighbour.  Device tensors: the HIP
+    kernels, asynchronous, ``trim`` as in ``segment_mesh``.  CPU tensors: ``segment_mesh_host`` on ``knn_edges(knn_index)``."""
+    if not normals.is_cuda:
+        return segment_mesh_host(normals, knn_edges(knn_index), max_weight, min_verts, trim, unsigned=unsigned)
+    lib = L.load()
+    if normals.dtype != torch.float32:
+        raise L.VlsatError("segment_cloud: normals must be float32 [V,3]")
+    if len(knn_index.shape) != 2 or knn_index.shape[0] != normals.shape[0] or not 1 <= knn_index.shape[1] <= CLOUD_MAX_K:
+        raise L.VlsatError("segment_cloud: knn_index must be int32 [V,K] with 1 <= K <= 32")
+    _segment_args(normals, torch.empty((0, 2)), max_weight, min_verts)
+    dev, normals = normals.device, normals.contiguous()
+    index = knn_index.to(device=dev, dtype=torch.int32).contiguous()
+    v, k = index.shape
+    scratch = torch.empty(int(lib.vlsat_segment_mesh_scratch_bytes(v, v * k)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(v, dtype=torch.int32, device=dev)
+    seg_size = torch.empty(v, dtype=torch.int32, device=dev)
+    n_segments = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_segment_cloud(normals.data_ptr(), index.data_ptr(), v, k, float(max_weight), int(min_verts), int(bool(unsigned)),
+                                    scratch.data_ptr(), labels.data_ptr(), n_segments.data_ptr(), seg_size.data_ptr(), L.stream_ptr()))
     out = MeshSegments(labels, n_segments, seg_size)
     return out.trim() if trim else out

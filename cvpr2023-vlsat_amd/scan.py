@@ -688,3 +688,62 @@ def segment_scan(mesh_or_path, max_angle_deg: float = 10.0, min_verts: int = 20,
     mesh["n_segments"] = int(seg.n_segments)
     mesh["seg_size"] = seg.seg_size.cpu().numpy()
     return mesh
+
+
+def segment_cloud(cloud_or_path, radius: float, k: int = 16, max_angle_deg: float = 10.0, min_verts: int = 20, max_curvature: float = 0.02,
+                  min_points: int = 5, viewpoint=None, device="cuda:0", recompute_normals: bool = False) -> Dict[str, Optional[np.ndarray]]:
+    """A point cloud WITHOUT faces over-segmented into segments on the device: -> a copy of the dict with ``normals`` f64 [V,3],
+    ``curvature`` f32 [V], ``instances`` (int64 [V]: 0 = dropped, else 1..S), ``n_segments`` = S and ``seg_size`` int32 [S] filled.
+    ``cloud_or_path``: a PLY path (``read_mesh``) or a dict with ``points``; faces, if any, are ignored.
+
+    ``radius`` has no default because none is free of units: it is the distance, in the cloud's units, within which two points count
+    as neighbours -- about three times the sampling distance is a start.  ``max_sq_dist = np.float32(radius) ** 2`` is computed once
+    here, on the host.  Every point gets its ``k`` nearest neighbours within ``radius`` (``prep.knn_points``), from them a normal and the
+    surface variation ``curvature`` (``prep.cloud_normals``; fewer than ``min_points`` members: no normal), and the rule of
+    ``segment_scan`` runs over the neighbour pairs (``prep.segment_cloud``; include/vlsat_cloud.h states all three).  Normals the cloud
+    already carries are kept, and weighed with their sign, unless ``recompute_normals``; computed ones are turned towards ``viewpoint``
+    (x, y, z) when there is one and weighed with their sign, else weighed by 1 - |dot|.
+
+    The flatness mask: a point whose curvature exceeds ``max_curvature`` is handed to the segmenter with a zero normal.  It then weighs
+    1 against everyone, links to nobody and is absorbed by a neighbouring segment (or by other such points).  Without it the normals
+    of a neighbourhood estimate turn gradually across a crease, and a chain of small steps joins two faces.  The returned ``normals`` are
+    the unmasked ones.
+
+    ``device=None`` (or "cpu") runs the numpy restatements, which give the same result bit for bit.  The output goes straight into
+    ``write_ply`` and ``prepare_scan``, as ``segment_scan``'s does.  ``k``, ``max_curvature`` and the angle are starting values, not
+    tuned operating points: no scan data and no checkpoint is available to this project, so accuracy on real scans is unmeasured."""
+    import math
+
+    import torch
+
+    from . import prep
+
+    cloud = dict(read_mesh(cloud_or_path) if isinstance(cloud_or_path, (str, os.PathLike)) else cloud_or_path)
+    pts = np.ascontiguousarray(np.asarray(cloud["points"])[:, :3], dtype=np.float32)
+    if not 1 <= len(pts) <= prep.SEG_MAX_VERTS:
+        raise ScanError("segment_cloud: 1 .. 2^24 points")
+    if not float(radius) >= 0.0:
+        raise ScanError("segment_cloud: radius must be >= 0")
+    if not 0.0 <= float(max_angle_deg) <= 180.0:
+        raise ScanError("segment_cloud: max_angle_deg must be in [0, 180]")
+    max_sq_dist = float(np.float32(radius) ** 2)
+    max_weight = np.float32(1.0 - math.cos(math.radians(float(max_angle_deg))))
+    on_host = device is None or torch.device(device).type == "cpu"
+    d_pts = torch.from_numpy(pts) if on_host else torch.from_numpy(pts).to(device)
+    table = prep.knn_points(d_pts, k, max_sq_dist)
+    normals, curvature = prep.cloud_normals(d_pts, table.index, table.count, min_points, viewpoint)
+    given = cloud.get("normals")
+    unsigned = viewpoint is None
+    if given is not None and not recompute_normals:
+        normals = torch.from_numpy(np.ascontiguousarray(np.asarray(given)[:, :3], dtype=np.float32)).to(normals.device)
+        if len(normals) != len(pts):
+            raise ScanError("segment_cloud: one normal per point")
+        unsigned = False
+    masked = torch.where((curvature > float(np.float32(max_curvature)))[:, None], torch.zeros_like(normals), normals)
+    seg = prep.segment_cloud(masked, table.index, float(max_weight), min_verts, unsigned=unsigned)     # trim=True: the one host wait
+    cloud["normals"] = normals.cpu().numpy().astype(np.float64)
+    cloud["curvature"] = curvature.cpu().numpy()
+    cloud["instances"] = seg.labels.cpu().numpy().astype(np.int64)
+    cloud["n_segments"] = int(seg.n_segments)
+    cloud["seg_size"] = seg.seg_size.cpu().numpy()
+    return cloud

@@ -234,3 +234,21 @@ def make_box_mesh(n_obj: int, step: float, seed: int, normal_noise: float = 0.0,
         normals /= np.linalg.norm(normals, axis=1, keepdims=True)
     return {"points": points, "colors": None, "normals": normals, "instances": np.concatenate(inst),
             "faces": np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), "plane": np.concatenate(plane)}
+
+
+def make_plates(step: float, jitter: float, seed: int) -> dict:
+    """Two perpendicular unit plates that share an edge -- an L -- as a CLOUD without faces, for the cloud segmenter: plate 0 is z = 0
+    over x, y in [0, 1], plate 1 is x = 0 over y, z in [0, 1], both sampled on a grid of spacing ``step``; the shared line x = z = 0
+    is sampled once and belongs to plate 0.  ``jitter`` > 0 adds that many standard normals to every coordinate.
+    -> {"points": f64 [V,3], "plate": i32 [V]}, plate 0 first, each plate in the order of the coordinate that leaves the crease."""
+    g = np.random.default_rng([int(seed) & 0x7FFFFFFF, 0x91A7E5])
+    n = max(1, int(round(1.0 / float(step))))
+    i, j = (x.ravel() for x in np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij"))
+    zero = np.zeros(i.size)
+    a = np.stack([i / n, j / n, zero], 1)
+    keep = i > 0
+    b = np.stack([zero, j / n, i / n], 1)[keep]
+    points = np.concatenate([a, b])
+    if jitter > 0:
+        points = points + float(jitter) * g.standard_normal(points.shape)
+    return {"points": points, "plate": np.concatenate([np.zeros(len(a), np.int32), np.ones(len(b), np.int32)])}
