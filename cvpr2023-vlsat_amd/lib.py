@@ -20,6 +20,7 @@ SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split
 CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
 SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_segment.h")
 CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud.h")
+VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel.h")
 
 
 class VlsatDims(C.Structure):
@@ -155,6 +156,13 @@ _SIGNATURES_CLOUD = {
     "vlsat_segment_cloud": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_voxel.h: a cloud resampled on a voxel grid -- cells and numbering, then means of positions, normals and colours (csrc/voxel.hip)
+_SIGNATURES_VOXEL = {
+    "vlsat_voxel_scratch_bytes": (_sz, [_i64]),
+    "vlsat_voxel_assign": (C.c_int, [_vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vlsat_voxel_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -168,7 +176,7 @@ def identity(lib_path: str = "") -> dict:
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH,
+    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
                                           os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
@@ -208,6 +216,11 @@ def declared_cloud_symbols() -> list:
     return _declared(CLOUD_HEADER_PATH)
 
 
+def declared_voxel_symbols() -> list:
+    """Every function include/vlsat_voxel.h declares."""
+    return _declared(VOXEL_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -218,7 +231,7 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()):
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

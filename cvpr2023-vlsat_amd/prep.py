@@ -947,3 +947,149 @@ def segment_cloud(normals: torch.Tensor, knn_index: torch.Tensor, max_weight: fl
                                     scratch.data_ptr(), labels.data_ptr(), n_segments.data_ptr(), seg_size.data_ptr(), L.stream_ptr()))
     out = MeshSegments(labels, n_segments, seg_size)
     return out.trim() if trim else out
+
+
+# ---- a cloud resampled on a voxel grid (csrc/voxel.hip; the rule is stated in include/vlsat_voxel.h) --------------------------------------
+VOXEL_CELL_LIMIT = 1 << 20
+VOXEL_COORD_LIMIT = 32768.0
+
+
+class VoxelCloud(NamedTuple):
+    """``voxel_downsample``: ``points`` f32 [M,3], ``normals`` f32 [M,3] | None, ``colors`` u8 [M,3] | None, ``voxel_of_point`` int32 [V]
+    (-1: out of range or in a dropped voxel), ``first_point`` int32 [M] (the lowest input index of each voxel), ``count`` int32 [M]."""
+    points: object
+    normals: object
+    colors: object
+    voxel_of_point: object
+    first_point: object
+    count: object
+
+
+def _voxel_args(shape, voxel, origin, min_count, normals_shape, colors_shape):
+    """-> (inv as np.float32, origin as np.float32 [3]); raises on anything the rule refuses"""
+    import numpy as np
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= SEG_MAX_VERTS:
+        raise L.VlsatError("voxel_downsample: points must be float32 [V,3] with 1 <= V <= 2^24")
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        size = np.float32(voxel)
+        inv = np.float32(1.0) / size
+    if not (size > 0 and inv > 0 and np.isfinite(inv)):
+        raise L.VlsatError("voxel_downsample: voxel must be > 0 and finite, and so must 1 / voxel in fp32")
+    if len(origin) != 3:
+        raise L.VlsatError("voxel_downsample: the origin is three numbers")
+    with np.errstate(over="ignore"):
+        o = np.asarray([float(x) for x in origin], dtype=np.float32)
+    if not np.isfinite(o).all():
+        raise L.VlsatError("voxel_downsample: the origin must be finite")
+    if int(min_count) < 1:
+        raise L.VlsatError("voxel_downsample: min_count must be at least 1")
+    for what, s in (("normals", normals_shape), ("colors", colors_shape)):
+        if s is not None and tuple(s) != tuple(shape):
+            raise L.VlsatError(f"voxel_downsample: {what} must be [V,3], one row per point")
+    return inv, o
+
+
+def voxel_keys_host(points, voxel: float, origin=(0.0, 0.0, 0.0)):
+    """Rule 1 of include/vlsat_voxel.h in numpy: -> (key uint64 [V], in_range bool [V]); the key of a point out of range is all ones."""
+    import numpy as np
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 3)
+    inv, o = _voxel_args(p.shape, voxel, origin, 1, None, None)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.floor((p - o[None, :]) * inv)                          # fp32: the difference and the product each rounded on their own
+        ok = (np.abs(p) < np.float32(VOXEL_COORD_LIMIT)).all(1) & (np.abs(t) < np.float32(VOXEL_CELL_LIMIT)).all(1)
+    c = (np.where(ok[:, None], t, np.float32(0)).astype(np.int64) + VOXEL_CELL_LIMIT).astype(np.uint64)
+    key = (c[:, 2] << np.uint64(42)) | (c[:, 1] << np.uint64(21)) | c[:, 0]
+    return np.where(ok, key, np.uint64(0xFFFFFFFFFFFFFFFF)), ok
+
+
+def _group_sums(np, values, order, starts):
+    """int64 [V,C] summed over the runs of ``order`` that begin at ``starts``: exact, integer, in any order the same"""
+    return np.add.reduceat(values[order], starts, axis=0) if len(starts) else np.zeros((0, values.shape[1]), np.int64)
+
+
+def voxel_downsample_host(points, voxel: float, origin=(0.0, 0.0, 0.0), min_count: int = 1, normals=None, colors=None) -> VoxelCloud:
+    """The rule of include/vlsat_voxel.h in numpy -> ``VoxelCloud`` of numpy arrays, every bit the device's: cells and keys in fp32,
+    voxels by ``np.unique`` over the keys, numbered by their first point, positions and normals as int64 sums of quantised values
+    (``np.rint`` rounds half to even, as llrint does), colours as integer means rounded half up."""
+    import numpy as np
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(np.asarray(normals, dtype=np.float32)).reshape(-1, 3)
+    col = None if colors is None else np.ascontiguousarray(np.asarray(colors, dtype=np.uint8)).reshape(-1, 3)
+    _voxel_args(p.shape, voxel, origin, min_count, None if nrm is None else nrm.shape, None if col is None else col.shape)
+    key, ok = voxel_keys_host(p, voxel, origin)
+    idx = np.nonzero(ok)[0]
+    _, first, inverse, count = np.unique(key[idx], return_index=True, return_inverse=True, return_counts=True)
+    first = idx[first]                                               # np.unique names the first occurrence: the lowest point index
+    kept = np.nonzero(count >= int(min_count))[0]
+    kept = kept[np.argsort(first[kept], kind="stable")]              # numbered by ascending first point
+    number = np.full(len(count), -1, dtype=np.int64)
+    number[kept] = np.arange(len(kept))
+    voxel_of_point = np.full(len(p), -1, dtype=np.int32)
+    voxel_of_point[idx] = number[inverse.reshape(-1)]
+    members = np.nonzero(voxel_of_point >= 0)[0]
+    order = members[np.argsort(voxel_of_point[members], kind="stable")]
+    n = count[kept].astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64) if len(kept) else np.zeros(0, np.int64)
+    q = np.rint(p.astype(np.float64) * 2.0 ** 24)
+    q = np.where(ok[:, None], q, 0.0).astype(np.int64)
+    out_points = (_group_sums(np, q, order, starts).astype(np.float64) / n[:, None].astype(np.float64) * 2.0 ** -24).astype(np.float32)
+    out_normals = out_colors = None
+    if nrm is not None:
+        with np.errstate(invalid="ignore", over="ignore"):
+            counted = np.abs(nrm) < np.float32(VOXEL_COORD_LIMIT)
+            qn = np.rint(np.where(counted, nrm, np.float32(0)).astype(np.float64) * 2.0 ** 20).astype(np.int64)
+        s = _group_sums(np, qn, order, starts).astype(np.float64)
+        length = np.sqrt((s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1]) + s[:, 2] * s[:, 2])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out_normals = np.where(length[:, None] == 0, 0.0, s / length[:, None]).astype(np.float32)
+    if col is not None:
+        s = _group_sums(np, col.astype(np.int64), order, starts)
+        out_colors = ((2 * s + n[:, None]) // (2 * n[:, None])).astype(np.uint8)
+    return VoxelCloud(out_points, out_normals, out_colors, voxel_of_point, first[kept].astype(np.int32), count[kept].astype(np.int32))
+
+
+def voxel_downsample(points, voxel: float, origin=(0.0, 0.0, 0.0), min_count: int = 1, normals=None, colors=None) -> VoxelCloud:
+    """points f32 [V,3] resampled on a grid of cells of edge ``voxel`` anchored at ``origin`` -> ``VoxelCloud``: one representative per
+    occupied cell that holds at least ``min_count`` points -- the mean position, the normalised mean normal and the mean colour, all
+    from integer sums, so exact and the same in every run -- numbered by the cell's first point in the input, and ``voxel_of_point``
+    to carry a result on the resampled cloud back to every input point (include/vlsat_voxel.h states the rule and its limits: |x| <
+    32768 and cell coordinates below 2^20 in magnitude, else a point belongs to no voxel).  The origin anchors the grid to the frame,
+    not to the cloud: two clouds in one frame share cells.  Device tensors run the HIP kernels (one host wait: the number of voxels is
+    read to size the outputs); CPU tensors or arrays run ``voxel_downsample_host`` and get CPU tensors, with equal bits."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x       # noqa: E731
+        out = voxel_downsample_host(as_np(points), voxel, origin, min_count, None if normals is None else as_np(normals),
+                                    None if colors is None else as_np(colors))
+        return VoxelCloud(*(None if x is None else torch.from_numpy(x) for x in out))
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("voxel_downsample: points must be float32 [V,3]")
+    for what, x, dtype in (("normals", normals, torch.float32), ("colors", colors, torch.uint8)):
+        if x is not None and not (isinstance(x, torch.Tensor) and x.device == points.device and x.dtype == dtype):
+            raise L.VlsatError(f"voxel_downsample: {what} must be a {dtype} tensor on the device of the points")
+    _, o = _voxel_args(points.shape, voxel, origin, min_count, None if normals is None else normals.shape,
+                       None if colors is None else colors.shape)
+    dev, points, v = points.device, points.contiguous(), points.shape[0]
+    normals = None if normals is None else normals.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    scratch = torch.empty(int(lib.vlsat_voxel_scratch_bytes(v)), dtype=torch.uint8, device=dev)
+    voxel_of_point = torch.empty(v, dtype=torch.int32, device=dev)
+    first_point = torch.empty(v, dtype=torch.int32, device=dev)
+    count = torch.empty(v, dtype=torch.int32, device=dev)
+    n_voxels = torch.empty(2, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_voxel_assign(points.data_ptr(), v, float(voxel), float(o[0]), float(o[1]), float(o[2]), int(min_count),
+                                   scratch.data_ptr(), voxel_of_point.data_ptr(), first_point.data_ptr(), count.data_ptr(),
+                                   n_voxels.data_ptr(), L.stream_ptr()))
+    m, overflow = (int(x) for x in n_voxels.tolist())                # the one host wait: the outputs are sized from the device's count
+    if overflow:
+        raise L.VlsatError("voxel_downsample: the hash table overflowed (the device raised its error flag)")
+    first_point, count = first_point[:m].clone(), count[:m].clone()
+    out_points = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    out_normals = None if normals is None else torch.empty((m, 3), dtype=torch.float32, device=dev)
+    out_colors = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=dev)
+    if m:                                                            # no voxel: nothing to launch
+        L.check(lib.vlsat_voxel_reduce(points.data_ptr(), 0 if normals is None else normals.data_ptr(),
+                                       0 if colors is None else colors.data_ptr(), voxel_of_point.data_ptr(), count.data_ptr(), v, m,
+                                       scratch.data_ptr(), out_points.data_ptr(), 0 if out_normals is None else out_normals.data_ptr(),
+                                       0 if out_colors is None else out_colors.data_ptr(), L.stream_ptr()))
+    return VoxelCloud(out_points, out_normals, out_colors, voxel_of_point, first_point, count)

@@ -691,7 +691,8 @@ def segment_scan(mesh_or_path, max_angle_deg: float = 10.0, min_verts: int = 20,
 
 
 def segment_cloud(cloud_or_path, radius: float, k: int = 16, max_angle_deg: float = 10.0, min_verts: int = 20, max_curvature: float = 0.02,
-                  min_points: int = 5, viewpoint=None, device="cuda:0", recompute_normals: bool = False) -> Dict[str, Optional[np.ndarray]]:
+                  min_points: int = 5, viewpoint=None, device="cuda:0", recompute_normals: bool = False,
+                  voxel: Optional[float] = None) -> Dict[str, Optional[np.ndarray]]:
     """A point cloud WITHOUT faces over-segmented into segments on the device: -> a copy of the dict with ``normals`` f64 [V,3],
     ``curvature`` f32 [V], ``instances`` (int64 [V]: 0 = dropped, else 1..S), ``n_segments`` = S and ``seg_size`` int32 [S] filled.
     ``cloud_or_path``: a PLY path (``read_mesh``) or a dict with ``points``; faces, if any, are ignored.
@@ -711,7 +712,15 @@ def segment_cloud(cloud_or_path, radius: float, k: int = 16, max_angle_deg: floa
 
     ``device=None`` (or "cpu") runs the numpy restatements, which give the same result bit for bit.  The output goes straight into
     ``write_ply`` and ``prepare_scan``, as ``segment_scan``'s does.  ``k``, ``max_curvature`` and the angle are starting values, not
-    tuned operating points: no scan data and no checkpoint is available to this project, so accuracy on real scans is unmeasured."""
+    tuned operating points: no scan data and no checkpoint is available to this project, so accuracy on real scans is unmeasured.
+
+    ``voxel`` (default None: nothing changes): the cloud is first resampled on a grid of that edge (``downsample_cloud``, origin 0,
+    ``min_count`` 1) and the RESAMPLED cloud is segmented -- for a cloud of uneven density, where the ``k`` nearest neighbours of a
+    densely sampled point lie within the sensor noise.  ``radius``, ``k`` and ``min_verts`` then speak of resampled points (about
+    three times ``voxel`` is a start for the radius).  The result is still the INPUT cloud: ``instances``, ``normals`` and ``curvature``
+    are gathered through ``voxel_of_point`` (a point without a voxel: 0, a zero normal, +inf), ``n_segments`` is the segmenter's,
+    ``seg_size`` is recounted over the input points, and ``resampled`` holds the ``downsample_cloud`` dict with the segmenter's
+    fields filled in.  Normals the input carries are averaged per voxel and kept, as without ``voxel``."""
     import math
 
     import torch
@@ -719,6 +728,18 @@ def segment_cloud(cloud_or_path, radius: float, k: int = 16, max_angle_deg: floa
     from . import prep
 
     cloud = dict(read_mesh(cloud_or_path) if isinstance(cloud_or_path, (str, os.PathLike)) else cloud_or_path)
+    if voxel is not None:
+        small = segment_cloud(downsample_cloud(cloud, voxel, device=device), radius, k, max_angle_deg, min_verts, max_curvature, min_points,
+                              viewpoint, device, recompute_normals)
+        of = small["voxel_of_point"].astype(np.int64)
+        has, at = of >= 0, np.maximum(of, 0)
+        cloud["instances"] = np.where(has, small["instances"][at], 0).astype(np.int64)
+        cloud["normals"] = np.where(has[:, None], small["normals"][at], 0.0)
+        cloud["curvature"] = np.where(has, small["curvature"][at], np.float32(np.inf)).astype(np.float32)
+        cloud["n_segments"] = small["n_segments"]
+        cloud["seg_size"] = np.bincount(cloud["instances"][cloud["instances"] > 0] - 1, minlength=small["n_segments"]).astype(np.int32)
+        cloud["resampled"] = small
+        return cloud
     pts = np.ascontiguousarray(np.asarray(cloud["points"])[:, :3], dtype=np.float32)
     if not 1 <= len(pts) <= prep.SEG_MAX_VERTS:
         raise ScanError("segment_cloud: 1 .. 2^24 points")
@@ -747,3 +768,51 @@ def segment_cloud(cloud_or_path, radius: float, k: int = 16, max_angle_deg: floa
     cloud["n_segments"] = int(seg.n_segments)
     cloud["seg_size"] = seg.seg_size.cpu().numpy()
     return cloud
+
+
+def downsample_cloud(cloud_or_path, voxel: float, origin=(0.0, 0.0, 0.0), min_count: int = 1, device="cuda:0") -> Dict[str, Optional[np.ndarray]]:
+    """A point cloud resampled on a voxel grid on the device (``prep.voxel_downsample``; include/vlsat_voxel.h states the rule): -> the
+    dict ``read_mesh`` returns and ``write_ply`` takes, one point per occupied cell of edge ``voxel`` that holds at least ``min_count``
+    points, in the order in which the cells first occur in the input.  ``points`` f64 [M,3] are the cell means (float32 values),
+    ``normals`` the normalised means and ``colors`` the rounded means where the input has them; ``instances``, and every other
+    one-dimensional integer array of one entry per point, take the value at the cell's first point; ``faces`` are dropped.  Added:
+    ``voxel_of_point`` int32 [V] (the resampled point each input point went into, -1 for none: a non-finite or out-of-range point, or
+    a cell below ``min_count``), ``first_point`` int32 [M] and ``voxel_count`` int32 [M].  ``origin`` anchors the grid to the frame, not
+    to the cloud, so two clouds in one frame share cells.  ``device=None`` (or "cpu") runs the numpy restatement, with equal bits."""
+    import torch
+
+    from . import prep
+
+    cloud = dict(read_mesh(cloud_or_path) if isinstance(cloud_or_path, (str, os.PathLike)) else cloud_or_path)
+    pts = np.ascontiguousarray(np.asarray(cloud["points"])[:, :3], dtype=np.float32)
+    if not 1 <= len(pts) <= prep.SEG_MAX_VERTS:
+        raise ScanError("downsample_cloud: 1 .. 2^24 points")
+    nrm, col = cloud.get("normals"), cloud.get("colors")
+    nrm = None if nrm is None else np.ascontiguousarray(np.asarray(nrm)[:, :3], dtype=np.float32)
+    col = None if col is None else np.ascontiguousarray(np.asarray(col)[:, :3], dtype=np.uint8)
+    if any(x is not None and len(x) != len(pts) for x in (nrm, col)):
+        raise ScanError("downsample_cloud: one normal and one colour per point")
+    on_host = device is None or torch.device(device).type == "cpu"
+    put = lambda x: None if x is None else (torch.from_numpy(x) if on_host else torch.from_numpy(x).to(device))      # noqa: E731
+    try:
+        vc = prep.voxel_downsample(put(pts), voxel, origin, min_count, put(nrm), put(col))
+    except prep.L.VlsatError as e:
+        raise ScanError(f"downsample_cloud: {e}") from e
+    get = lambda x: None if x is None else x.cpu().numpy()      # noqa: E731
+    first = get(vc.first_point)
+    out = {}
+    for name, value in cloud.items():                          # every integer field of one entry per point: the value at the first point
+        if name in ("points", "normals", "colors", "faces") or value is None or isinstance(value, (str, bytes, dict)):
+            continue
+        value = np.asarray(value)
+        if value.dtype.kind in "iu" and value.shape == (len(pts),):
+            out[name] = value[first]
+    out["points"] = get(vc.points).astype(np.float64)
+    out["colors"] = get(vc.colors)
+    out["normals"] = None if vc.normals is None else get(vc.normals).astype(np.float64)
+    out.setdefault("instances", np.zeros(len(first), dtype=np.int64))
+    out["faces"] = np.zeros((0, 3), dtype=np.int32)
+    out["voxel_of_point"] = get(vc.voxel_of_point)
+    out["first_point"] = first
+    out["voxel_count"] = get(vc.count)
+    return out

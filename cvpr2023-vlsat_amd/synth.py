@@ -252,3 +252,22 @@ def make_plates(step: float, jitter: float, seed: int) -> dict:
     if jitter > 0:
         points = points + float(jitter) * g.standard_normal(points.shape)
     return {"points": points, "plate": np.concatenate([np.zeros(len(a), np.int32), np.ones(len(b), np.int32)])}
+
+
+def make_fused_cloud(points, seed: int = 7, jitter: float = 0.002, views: int = 8, view_noise: float = 0.005, x_below: float = 5.0) -> np.ndarray:
+    """A cloud of uneven density, as fusing overlapping frames leaves it: every point of ``points`` with N(0, ``jitter``) added to each
+    coordinate, then the points with x < ``x_below`` ``views`` more times, each time with fresh N(0, ``view_noise``) noise, one view
+    after the other.  -> f64 [V + views * H, 3]; row i < V belongs to input point i, and ``make_fused_index`` names the input point of
+    every row."""
+    g = np.random.default_rng(int(seed))
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    half = p[p[:, 0] < x_below]
+    parts = [p + g.normal(0.0, jitter, p.shape)]
+    parts += [half + g.normal(0.0, view_noise, half.shape) for _ in range(int(views))]
+    return np.concatenate(parts)
+
+
+def make_fused_index(points, views: int = 8, x_below: float = 5.0) -> np.ndarray:
+    """The input point behind every row of ``make_fused_cloud``: int64 [V + views * H]."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    return np.concatenate([np.arange(len(p))] + [np.nonzero(p[:, 0] < x_below)[0]] * int(views))
