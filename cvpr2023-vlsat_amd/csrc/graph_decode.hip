@@ -128,7 +128,7 @@ __global__ __launch_bounds__(GD_SCENE_THREADS) void gd_scene_kernel(const int32_
     constexpr int NW = GD_SCENE_THREADS / 64;
     __shared__ unsigned long long s_row[GD_MAX_REL];
     __shared__ int s_red[NW];
-    __shared__ unsigned long long s_scan[NW];
+    __shared__ long long s_scan[NW];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int e0 = clampi(ptr[s], 0, E), e1 = max(e0, clampi(ptr[s + 1], 0, E));
     int c = 0;

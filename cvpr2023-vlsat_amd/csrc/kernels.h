@@ -309,7 +309,8 @@ int launch_merge_segments(const float* obj_probs, const float* rel_probs, const 
                           int32_t* pair_count, float* pair_probs, hipStream_t s);
 // the three steps merge_segments shares with fuse_splits (scene_split.hip), defined in segment_merge.hip: a contract-off source.
 // Unchecked launches: the caller's launch check covers them.
-//   scan     out[0..n] = exclusive scan of in[0..n-1] by one block of 1024; *total = *total2 = out[n] (either may be null)
+//   scan     out[0..n] = exclusive scan of in[0..n-1] by one block of 1024; *total = *total2 = out[n] (either may be null); out may be
+//            in: a thread reads each element of its own run before writing it
 //   members  one wave per object o < totals[0]: the rows n >= obj_root[o] with root[n] == obj_root[o], ascending, into
 //            members[member_ptr[o] ..]; bid given: the walk ends with the root's scene
 //   pool     one wave per object, members in order: s = fl(s + fl(w p)), W = fl(W + w), out_probs = fl(s / W), out_weight = W

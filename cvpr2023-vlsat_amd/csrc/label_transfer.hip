@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "nn_grid.h"
 #include "select_core.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
@@ -133,32 +134,22 @@ __global__ __launch_bounds__(NN_THREADS) void nn_hist_kernel(const float* __rest
 // tiles of NN_SCAN_THREADS x NN_SCAN_PER with a running total.
 __global__ __launch_bounds__(NN_SCAN_THREADS) void nn_scan_kernel(const NnGrid* __restrict__ gp, int32_t* __restrict__ counts,
                                                                   int32_t* __restrict__ start) {
-    __shared__ int wave_sum[NN_SCAN_THREADS / 64];
-    __shared__ int carry;
+    __shared__ int s_wave[NN_SCAN_THREADS / 64];
     const int n = min(gp->n_cells, NN_MAX_CELLS);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    int carry = 0;                                                    // the total of the tiles before this one, in every thread
     for (int base = 0; base < n; base += NN_SCAN_THREADS * NN_SCAN_PER) {
         const int i0 = base + tid * NN_SCAN_PER;
-        int v[NN_SCAN_PER], sum = 0;
+        int v[NN_SCAN_PER], sum = 0, tile;
 #pragma unroll
         for (int k = 0; k < NN_SCAN_PER; ++k) { v[k] = i0 + k < n ? counts[i0 + k] : 0; sum += v[k]; }
-        int incl = sum;                                               // inclusive scan over the wave
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-        if (lane == 63) wave_sum[wave] = incl;
-        __syncthreads();
-        int off = carry;
-        for (int w = 0; w < wave; ++w) off += wave_sum[w];
-        int acc = off + incl - sum;
+        int acc = carry + block_scan_excl<NN_SCAN_THREADS>(sum, s_wave, tile);
 #pragma unroll
         for (int k = 0; k < NN_SCAN_PER; ++k) {
             if (i0 + k < n) { start[i0 + k] = acc; counts[i0 + k] = acc; }
             acc += v[k];
         }
-        __syncthreads();
-        if (tid == NN_SCAN_THREADS - 1) carry = acc;
-        __syncthreads();
+        carry += tile;
     }
     if (tid == 0) start[n] = carry;
 }

@@ -1,9 +1,8 @@
 // An unlabelled mesh over-segmented into segments (include/vlsat_segment.h states the rule; prep.segment_mesh_host restates it in
 // numpy with the same operations): smoothness-constrained region growing -- connected components of the edges whose normals agree --
 // then R rounds in which every small component joins its best neighbour, then dense numbering.  The weight, the key packing, the round
-// count and the scratch layout are segment_core.h's.  The union-find is segment_merge.hip's pattern: a hook puts the larger root under
-// the smaller (atomicCAS on a root), finds halve paths with atomicMin (a parent only ever decreases, so a tree's root is its lowest
-// vertex), and a launch boundary is the only cross-block ordering.
+// count and the scratch layout are segment_core.h's.  The union-find is union_find.h's (a tree's root is its lowest vertex); a launch
+// boundary is the only cross-block ordering.
 //
 // Launches, V vertices, M edges, R = seg_rounds(min_verts):
 //   ms_init_kernel           parent[v] = v, seg_size[v] = 0, n_segments = 0
@@ -17,13 +16,13 @@
 //        ms_flatten_kernel   (M > 0)
 //   ms_count_kernel          the final sizes
 //   ms_flag_count_kernel     per tile of 1024 vertices the number of kept roots (root[v] == v and size >= min_verts)
-//   sm_scan_kernel           exclusive scan of the tile counts (at most 2^14 of them: one block); the total is S
+//   scan_i32_kernel          exclusive scan of the tile counts (at most 2^14 of them: one block); the total is S
 //   ms_number_kernel         per tile: num[v] = 1 + tile's first + rank inside the tile for a kept root, else 0; seg_size[num - 1] = size
 //   ms_label_kernel          labels[v] = num[root[v]]
 // With M == 0 no round can change anything and only the counts are run: 7 launches; otherwise 8 + 4 R.
 // Nothing depends on the order blocks run in: minima define roots and choices, sums are integer.  The hot root (a floor holds a third of
-// all vertices) is read by many and written by none once it is the lowest vertex of its component; its size takes one add per wave and
-// distinct root, and no thread retries a CAS on it: a CAS is only ever aimed at the LARGER of two roots, which then stops being a root.
+// all vertices) is read by many and written by none once it is the lowest vertex of its component (union_find.h); its size takes one add
+// per wave and distinct root.
 // build.py compiles THIS file with -ffp-contract=off (PER_SOURCE_FLAGS): seg_weight rounds every product and sum on its own.
 //
 // vlsat_segment_cloud (include/vlsat_cloud.h) runs the same launches over a cloud's neighbour table: the edge loader and the weight are
@@ -35,38 +34,14 @@
 #include "common.h"
 #include "kernels.h"
 #include "segment_core.h"
+#include "union_find.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
 constexpr int MS_THREADS = 256;
 constexpr int MS_PER_THREAD = SEG_NUMBER_TILE / MS_THREADS;
 static_assert(MS_PER_THREAD * MS_THREADS == SEG_NUMBER_TILE, "a numbering tile is a whole number of vertices per thread");
-
-__device__ __forceinline__ int ms_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of v as far as this thread can see it (a stale answer is an ancestor: the CAS of the caller then fails and it walks on)
-__device__ __forceinline__ int ms_find(int32_t* __restrict__ parent, int v) {
-    int curr = ms_load(parent + v);
-    if (curr == v) return v;
-    int prev = v, next;
-    while ((next = ms_load(parent + curr)) < curr) {
-        atomicMin(parent + prev, next);                               // path halving
-        prev = curr;
-        curr = next;
-    }
-    return curr;
-}
-
-__device__ __forceinline__ void ms_unite(int32_t* __restrict__ parent, int a, int b) {
-    int ra = ms_find(parent, a), rb = ms_find(parent, b);
-    while (ra != rb) {
-        if (ra < rb) { const int t = ra; ra = rb; rb = t; }           // ra > rb: hook ra under rb
-        const int old = atomicCAS(parent + ra, ra, rb);
-        if (old == ra) break;
-        ra = ms_find(parent, old);                                    // ra had been hooked meanwhile (old < ra): strictly downwards
-        rb = ms_find(parent, rb);
-    }
-}
 
 // Where the edges come from -- a template parameter of the two kernels that read them: an explicit list (a mesh), or the neighbour
 // table of a cloud, whose edge e joins point e / K and nbr[e] (a -1 entry fails seg_edge_ok like any end out of range).
@@ -112,20 +87,14 @@ __global__ __launch_bounds__(MS_THREADS) void ms_link_kernel(const float* __rest
     if (e >= n_edges) return;
     const MsEdge ed = edges.load(n_verts, e);
     if (!ed.ok || !(ms_weight<UNSIGNED>(normals, ed.a, ed.b) <= max_weight)) return;
-    ms_unite(parent, ed.a, ed.b);
+    uf_unite(parent, ed.a, ed.b);
 }
 
 __global__ __launch_bounds__(MS_THREADS) void ms_flatten_kernel(const int32_t* __restrict__ parent, int n_verts, int32_t* __restrict__ root,
                                                                 int32_t* __restrict__ size, unsigned long long* __restrict__ key) {
     const int v = blockIdx.x * MS_THREADS + threadIdx.x;
     if (v >= n_verts) return;
-    int r = v;
-    for (int step = 0; step < n_verts; ++step) {                      // (parent[r] <= r: the walk ends; the bound is a belt)
-        const int p = parent[r];
-        if (p >= r || p < 0) break;
-        r = p;
-    }
-    root[v] = r;
+    root[v] = uf_root(parent, v, n_verts);
     size[v] = 0;
     key[v] = SEG_NO_KEY;
 }
@@ -176,27 +145,12 @@ __global__ __launch_bounds__(MS_THREADS) void ms_hook_kernel(int n_verts, int mi
     if (k == SEG_NO_KEY) return;
     const int target = seg_key_root(k);
     if (target < 0 || target >= n_verts) return;
-    ms_unite(parent, v, target);
+    uf_unite(parent, v, target);
 }
 
 // ---- dense numbering: per-tile counts, a scan of the counts, then apply --------------------------------------------------------------
 __device__ __forceinline__ bool ms_kept(const int32_t* __restrict__ root, const int32_t* __restrict__ size, int n_verts, int min_verts, int v) {
     return v < n_verts && root[v] == v && size[v] >= min_verts;
-}
-
-// the exclusive prefix of `mine` over the block's threads in thread order, and the block's total
-__device__ __forceinline__ int ms_block_prefix(int mine, int* __restrict__ wave_sum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < MS_THREADS / 64; ++k) { const int s = wave_sum[k]; if (k < wave) before += s; total += s; }
-    return before + incl - mine;
 }
 
 __global__ __launch_bounds__(MS_THREADS) void ms_flag_count_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ size, int n_verts,
@@ -206,8 +160,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_flag_count_kernel(const int32_t
     int mine = 0;
 #pragma unroll
     for (int k = 0; k < MS_PER_THREAD; ++k) mine += ms_kept(root, size, n_verts, min_verts, v0 + k);
-    int total;
-    ms_block_prefix(mine, wave_sum, total);
+    const int total = block_sum<MS_THREADS>(mine, wave_sum);
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
@@ -221,7 +174,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_number_kernel(const int32_t* __
 #pragma unroll
     for (int k = 0; k < MS_PER_THREAD; ++k) { kept[k] = ms_kept(root, size, n_verts, min_verts, v0 + k); mine += kept[k]; }
     int total;
-    int at = block_first[blockIdx.x] + ms_block_prefix(mine, wave_sum, total);
+    int at = block_first[blockIdx.x] + block_scan_excl<MS_THREADS>(mine, wave_sum, total);
 #pragma unroll
     for (int k = 0; k < MS_PER_THREAD; ++k) {
         const int v = v0 + k;

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "select_core.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
@@ -282,22 +283,12 @@ __global__ __launch_bounds__(PROX_THREADS) void prox_rows_kernel(const float* __
 // row_off[0..N] = exclusive scan of row_count, edge_ptr[s] = row_off[node_ptr[s]].  One block; a thread owns a contiguous run.
 __global__ __launch_bounds__(256) void prox_scan_kernel(const int32_t* __restrict__ row_count, int n_nodes, const int32_t* __restrict__ node_ptr,
                                                         int n_scenes, int64_t* __restrict__ row_off, int64_t* __restrict__ edge_ptr) {
-    __shared__ int64_t part[256];
+    __shared__ int64_t s_wave[256 / 64];
     const int tid = threadIdx.x;
-    const int per = (n_nodes + 255) / 256;
-    const int b = min(tid * per, n_nodes), e = min(b + per, n_nodes);
-    int64_t sum = 0;
-    for (int i = b; i < e; ++i) sum += row_count[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t acc = 0;
-        for (int t = 0; t < 256; ++t) { const int64_t v = part[t]; part[t] = acc; acc += v; }
-        row_off[n_nodes] = acc;
-    }
-    __syncthreads();
-    int64_t acc = part[tid];
-    for (int i = b; i < e; ++i) { row_off[i] = acc; acc += row_count[i]; }
+    const RunScan<int64_t> r = block_run_scan<256>(row_count, n_nodes, s_wave);
+    int64_t acc = r.before;
+    for (int i = r.b; i < r.e; ++i) { row_off[i] = acc; acc += row_count[i]; }
+    if (tid == 0) row_off[n_nodes] = r.total;
     __syncthreads();                                     // (row_off of this block's writes is read below)
     for (int s = tid; s <= n_scenes; s += 256) edge_ptr[s] = row_off[min(max(node_ptr[s], 0), n_nodes)];
 }

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(SG_SCENE_THREADS) void sg_scene_kernel(const int32_
     constexpr int NW = SG_SCENE_THREADS / 64;
     __shared__ uint32_t s_k[SG_MAX_K], s_e[SG_MAX_K], s_p[SG_MAX_K];
     __shared__ int s_red[NW];
-    __shared__ unsigned long long s_scan[NW];
+    __shared__ long long s_scan[NW];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int e0 = clampi(ptr[s], 0, E), e1 = max(e0, clampi(ptr[s + 1], 0, E));
     const long long total = (long long)(e1 - e0) * L;

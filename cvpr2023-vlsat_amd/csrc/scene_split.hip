@@ -5,8 +5,9 @@
 // Seeds (reference data_processing/gen_data.py:69-85).  One init launch, then per seed two launches:
 //   ss_update_kernel     dmin2[v] = min(dmin2[v], dx*dx + dy*dy) to the newest seed in fp64; per 1024-vertex block the number of selectable
 //                        vertices (dmin2 > distance^2), a plain store
-//   ss_pick_kernel       one block: scans the block counts, takes the rank (the counter-based draw, or ranks[k]), finds the block that
-//                        holds it and the vertex inside that block (ballot prefixes: ascending vertex order), appends the seed
+//   ss_pick_kernel       one block: scans the block counts (wave_core.h: a run of them per thread), takes the rank (the counter-based
+//                        draw, or ranks[k]), finds the block that holds it and the vertex inside that block (a block scan of the
+//                        selectable flags: ascending vertex order), appends the seed
 // The number of seeds is data dependent; the caller passes a cap and that many iterations are enqueued.  Once no vertex is selectable
 // the pick kernel raises a done flag in device memory and every later launch returns at its first instruction: no read-back per seed, no
 // cooperative launch, no barrier or spin-wait between blocks -- the launch boundary is the only cross-block ordering.
@@ -26,6 +27,7 @@
 #include "../../include/vlsat_split.h"
 #include "common.h"
 #include "kernels.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
@@ -109,32 +111,15 @@ __global__ __launch_bounds__(SS_PICK_THREADS) void ss_pick_kernel(const double* 
                                                                   const int32_t* __restrict__ block_cnt, int n_blocks, int draw_index,
                                                                   unsigned long long seed, const int64_t* __restrict__ ranks, int64_t n_ranks,
                                                                   int max_seeds, int32_t* __restrict__ seeds, int32_t* __restrict__ state) {
-    __shared__ long long part[SS_PICK_THREADS];
+    __shared__ long long s_wave[SS_PICK_THREADS / 64];
     __shared__ int wave_cnt[SS_PICK_THREADS / 64];
-    __shared__ long long s_total, s_rank;
+    __shared__ long long s_rank;
     __shared__ int s_block, s_in_block, s_stop;
     if (state[SS_DONE]) return;
     const int tid = threadIdx.x;
-    const int per = (n_blocks + SS_PICK_THREADS - 1) / SS_PICK_THREADS;
-    const int b0 = (int)min((int64_t)tid * per, (int64_t)n_blocks), b1 = (int)min((int64_t)b0 + per, (int64_t)n_blocks);
-    long long sum = 0;
-    for (int b = b0; b < b1; ++b) sum += block_cnt[b];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid < 64) {                                                   // one wave scans the 1024 partial sums, 16 each
-        long long v[SS_PICK_THREADS / 64], s = 0;
-#pragma unroll
-        for (int k = 0; k < SS_PICK_THREADS / 64; ++k) { v[k] = part[tid * (SS_PICK_THREADS / 64) + k]; s += v[k]; }
-        long long incl = s;
-        for (int o = 1; o < 64; o <<= 1) { const long long t = __shfl_up(incl, o); if (tid >= o) incl += t; }
-        long long acc = incl - s;
-#pragma unroll
-        for (int k = 0; k < SS_PICK_THREADS / 64; ++k) { part[tid * (SS_PICK_THREADS / 64) + k] = acc; acc += v[k]; }
-        if (tid == 63) s_total = incl;
-    }
-    __syncthreads();
+    const RunScan<long long> r = block_run_scan<SS_PICK_THREADS>(block_cnt, n_blocks, s_wave);   // a run of blocks per thread
     if (tid == 0) {
-        const long long n = s_total;
+        const long long n = r.total;
         int stop = 0, status = 0;
         long long rank = 0;
         if (n == 0) stop = 1;                                         // no vertex is selectable: the seeds are complete
@@ -156,9 +141,9 @@ __global__ __launch_bounds__(SS_PICK_THREADS) void ss_pick_kernel(const double* 
     __syncthreads();
     if (s_stop) return;
     const long long rank = s_rank;
-    if (rank >= part[tid] && rank < part[tid] + sum) {                // the rank lies in this thread's run of blocks
-        long long acc = part[tid];
-        for (int b = b0; b < b1; ++b) {
+    if (rank >= r.before && rank < r.before + r.sum) {                // the rank lies in this thread's run of blocks
+        long long acc = r.before;
+        for (int b = r.b; b < r.e; ++b) {
             const int c = block_cnt[b];
             if (rank < acc + c) { s_block = b; s_in_block = (int)(rank - acc); break; }
             acc += c;
@@ -169,11 +154,8 @@ __global__ __launch_bounds__(SS_PICK_THREADS) void ss_pick_kernel(const double* 
     if (blk < 0) return;                                              // (cannot happen: 0 <= rank < the total)
     const int64_t v = (int64_t)blk * SS_CHUNK + tid;
     const bool sel = v < n_points && dmin2[v] > d2_max;
-    const unsigned long long m = __ballot(sel);
-    if ((tid & 63) == 0) wave_cnt[tid >> 6] = (int)__popcll(m);
-    __syncthreads();
-    int before = (int)__popcll(m & ((1ull << (tid & 63)) - 1));
-    for (int w = 0; w < (tid >> 6); ++w) before += wave_cnt[w];
+    int n_sel;
+    const int before = block_scan_excl<SS_PICK_THREADS>((int)sel, wave_cnt, n_sel);       // selectable vertices of the block before v
     if (sel && before == s_in_block) {
         const int k = state[SS_COUNT];
         seeds[k] = (int)v;
@@ -229,8 +211,7 @@ __global__ __launch_bounds__(256) void sg_count_kernel(const unsigned* __restric
     if (k >= n_seeds) return;
     int c = 0;
     for (int w = lane; w < words; w += 64) c += __popc(mask[(size_t)k * words + w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum_i(c);
     if (lane == 0) { counts[k] = c; keep[k] = c >= min_seg; }
 }
 
@@ -316,8 +297,7 @@ __global__ __launch_bounds__(FS_THREADS) void fs_row_count_kernel(const unsigned
     if (a >= n) return;
     int c = 0;
     for (int w = lane; w < words; w += 64) c += __popc(bits[(size_t)a * words + w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum_i(c);
     if (lane == 0) row_cnt[a] = c;
 }
 

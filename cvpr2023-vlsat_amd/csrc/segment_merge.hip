@@ -7,23 +7,24 @@
 //   sm_clear_kernel          parent[n] = n, counters and every output to their "past the end" value
 //   sm_table_clear_kernel    the open-addressing table (64-bit keys, capacity = the power of two >= 2 E: at most half full)
 //   sm_link_insert_kernel    mutual only: key (a, b) of every edge that passes the threshold
-//   sm_union_kernel          every link hooks the larger of the two roots under the smaller (atomicCAS on a root), finds with path
-//                            halving (atomicMin: a parent only ever decreases, so a tree's root is its lowest row)
+//   sm_union_kernel          every link unites its two rows (union_find.h: a tree's root is its lowest row)
 //   sm_flatten_kernel        root[n], is_root[n]
-//   sm_scan_kernel           exclusive scan (one block; a thread owns a contiguous run) -> dense object numbers, M
+//   scan_i32_kernel          exclusive scan (one block; a thread owns a contiguous run: wave_core.h) -> dense object numbers, M
 //   sm_object_kernel         object[n], member counts, obj_batch_ids, n_objects
-//   sm_scan_kernel           -> member_ptr
+//   scan_i32_kernel          -> member_ptr
 //   sm_members_kernel        one wave per object: the rows from its root to the end of its scene, compacted in order by ballot prefixes
 //   sm_pool_kernel           one wave per object, lanes over classes, members in order: s = fl(s + fl(w p)), W = fl(W + w), fl(s / W)
 //   sm_pair_insert_kernel    key (object[a], object[b]) of every edge between two objects; atomicMin of the edge row per key
 //   sm_pair_flag_kernel      an edge is the representative of its pair when it is that minimum
-//   sm_scan_kernel           -> pair numbers in the order of the representatives, E'
+//   scan_i32_kernel          -> pair numbers in the order of the representatives, E'
 //   sm_pair_emit_kernel      one thread per (edge, predicate): atomicMax on the float bits (values >= 0), counts, pair_edges
 // Nothing here depends on the order blocks run in: minima define roots and pair order, maxima the pair probabilities, the member order
 // the sums.  build.py compiles THIS file with -ffp-contract=off (PER_SOURCE_FLAGS) so that the pooled sum rounds w * p and the addition
 // separately.
 #include "common.h"
 #include "kernels.h"
+#include "union_find.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
@@ -31,8 +32,6 @@ constexpr int SM_THREADS = 256;
 constexpr int SM_SCAN_THREADS = 1024;
 constexpr unsigned long long SM_EMPTY = ~0ull;          // never a key: both halves of a key are below 2^31
 constexpr int SM_NONE = 0x7fffffff;
-
-__device__ __forceinline__ int sm_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ unsigned sm_hash(unsigned long long k, unsigned mask) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
@@ -112,19 +111,6 @@ __global__ __launch_bounds__(SM_THREADS) void sm_link_insert_kernel(const float*
     sm_table_insert(keys, mask, ((unsigned long long)(unsigned)ed.a << 32) | (unsigned)ed.b);
 }
 
-// the root of v as far as this thread can see it (a stale answer is an ancestor: the CAS of the caller then fails and it walks on)
-__device__ __forceinline__ int sm_find(int32_t* __restrict__ parent, int v) {
-    int curr = sm_load(parent + v);
-    if (curr == v) return v;
-    int prev = v, next;
-    while ((next = sm_load(parent + curr)) < curr) {
-        atomicMin(parent + prev, next);                               // path halving
-        prev = curr;
-        curr = next;
-    }
-    return curr;
-}
-
 template <bool MUTUAL>
 __global__ __launch_bounds__(SM_THREADS) void sm_union_kernel(const float* __restrict__ rel_probs, const int64_t* __restrict__ edges,
                                                               const int64_t* __restrict__ bid, int n_nodes, int n_edges, int R, int same_part,
@@ -135,55 +121,26 @@ __global__ __launch_bounds__(SM_THREADS) void sm_union_kernel(const float* __res
     const SmEdge ed = sm_edge(edges, bid, n_nodes, e);
     if (!ed.ok || !(rel_probs[e * R + same_part] >= threshold)) return;
     if (MUTUAL && !sm_table_has(keys, mask, ((unsigned long long)(unsigned)ed.b << 32) | (unsigned)ed.a)) return;
-    int ra = sm_find(parent, ed.a), rb = sm_find(parent, ed.b);
-    while (ra != rb) {
-        if (ra < rb) { const int t = ra; ra = rb; rb = t; }           // ra > rb: hook ra under rb
-        const int old = atomicCAS(parent + ra, ra, rb);
-        if (old == ra) break;
-        ra = sm_find(parent, old);                                    // ra had been hooked meanwhile (old < ra): strictly downwards
-        rb = sm_find(parent, rb);
-    }
+    uf_unite(parent, ed.a, ed.b);
 }
 
 __global__ __launch_bounds__(SM_THREADS) void sm_flatten_kernel(const int32_t* __restrict__ parent, int n_nodes, int32_t* __restrict__ root,
                                                                 int32_t* __restrict__ flag) {
     const int n = blockIdx.x * SM_THREADS + threadIdx.x;
     if (n >= n_nodes) return;
-    int r = n;
-    for (int step = 0; step < n_nodes; ++step) {                      // (parent[r] <= r: the walk ends; the bound is a belt)
-        const int p = parent[r];
-        if (p >= r || p < 0) break;
-        r = p;
-    }
+    const int r = uf_root(parent, n, n_nodes);
     root[n] = r;
     flag[n] = r == n;
 }
 
-// out[0..n] = exclusive scan of in[0..n-1]; *total = *total2 = out[n] (either may be null).  One block; a thread owns a contiguous run.
-__global__ __launch_bounds__(SM_SCAN_THREADS) void sm_scan_kernel(const int32_t* __restrict__ in, int n, int32_t* __restrict__ out,
-                                                                  int32_t* __restrict__ total, int32_t* __restrict__ total2) {
-    __shared__ int part[SM_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    const int per = (n + SM_SCAN_THREADS - 1) / SM_SCAN_THREADS;
-    const int b = (int)min((int64_t)tid * per, (int64_t)n), e = (int)min((int64_t)b + per, (int64_t)n);
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += in[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid < 64) {                                                   // one wave scans the 1024 partial sums, 16 each
-        int v[SM_SCAN_THREADS / 64], s = 0;
-#pragma unroll
-        for (int k = 0; k < SM_SCAN_THREADS / 64; ++k) { v[k] = part[tid * (SM_SCAN_THREADS / 64) + k]; s += v[k]; }
-        int incl = s;
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (tid >= o) incl += t; }
-        int acc = incl - s;
-#pragma unroll
-        for (int k = 0; k < SM_SCAN_THREADS / 64; ++k) { part[tid * (SM_SCAN_THREADS / 64) + k] = acc; acc += v[k]; }
-        if (tid == 63) { out[n] = incl; if (total) *total = incl; if (total2) *total2 = incl; }
-    }
-    __syncthreads();
-    int acc = part[tid];
-    for (int i = b; i < e; ++i) { const int v = in[i]; out[i] = acc; acc += v; }
+// out[0..n] = exclusive scan of in[0..n-1]; *total = *total2 = out[n] (either may be null).  One block; out may be in.
+__global__ __launch_bounds__(SM_SCAN_THREADS) void scan_i32_kernel(const int32_t* in, int n, int32_t* out, int32_t* __restrict__ total,
+                                                                   int32_t* __restrict__ total2) {
+    __shared__ int s_wave[SM_SCAN_THREADS / 64];
+    const RunScan<int> r = block_run_scan<SM_SCAN_THREADS>(in, n, s_wave);
+    int acc = r.before;
+    for (int i = r.b; i < r.e; ++i) { const int v = in[i]; out[i] = acc; acc += v; }
+    if (threadIdx.x == 0) { out[n] = r.total; if (total) *total = r.total; if (total2) *total2 = r.total; }
 }
 
 __global__ __launch_bounds__(SM_THREADS) void sm_object_kernel(const int32_t* __restrict__ root, const int32_t* __restrict__ num,
@@ -308,7 +265,7 @@ __global__ __launch_bounds__(SM_THREADS) void sm_pair_emit_kernel(const float* _
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 // (the three launchers below leave the launch check to their caller, which names the entry point)
 void launch_scan_i32(const int32_t* in, int n, int32_t* out, int32_t* total, int32_t* total2, hipStream_t s) {
-    hipLaunchKernelGGL(sm_scan_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, in, n, out, total, total2);
+    hipLaunchKernelGGL(scan_i32_kernel, dim3(1), dim3(SM_SCAN_THREADS), 0, s, in, n, out, total, total2);
 }
 static dim3 sm_waves(int n) { return dim3((unsigned)((n + SM_THREADS / 64 - 1) / (SM_THREADS / 64))); }
 void launch_members(const int32_t* root, const int32_t* obj_root, const int32_t* member_ptr, const int64_t* bid, const int32_t* totals, int n,

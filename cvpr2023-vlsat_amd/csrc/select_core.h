@@ -7,13 +7,16 @@
 //              trials, each a count.  T = 0 when there are fewer than K keys.
 //   ties       the keys > T are all kept (fewer than K of them); of the keys == T the first K - #{key > T} in the order the
 //              caller enumerates them (lane order in a wave; (list, slot) order over lists).
-// The integer helpers compile for the host as well (tests/select_host_check.cpp); the wave and block code is device only.
+// The integer helpers compile for the host as well (tests/select_host_check.cpp); the wave and block code is device only (its sums
+// and scans are wave_core.h's).
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+
+#include "wave_core.h"
 #define VLSAT_HD __host__ __device__ __forceinline__
 #else
 #define VLSAT_HD inline
@@ -87,12 +90,6 @@ static_assert(tri_count(100, 32) == 1365, "the table of topk_each = 100 and 32 p
 
 #if defined(__HIPCC__)
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // position of lane's value among the values of lanes 0 .. R-1 in descending order, equal values to the lower lane
 __device__ __forceinline__ int rank_desc_in_wave(float rv, int lane, int R) {
     int rk = 0;
@@ -117,29 +114,6 @@ __device__ __forceinline__ uint32_t wave_kth_largest(const uint32_t (&v)[PER], i
     return T;
 }
 
-// inclusive scan over the wave (int: one count, or two 16-bit counts; long long: two 32-bit counts)
-template <typename T>
-__device__ __forceinline__ T wave_scan_incl(T v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T x = __shfl_up(v, o);
-        if (lane >= o) v += x;
-    }
-    return v;
-}
-
-// sum over the block, in every thread; s_red: THREADS / 64 ints of LDS
-template <int THREADS>
-__device__ __forceinline__ int block_sum(int c, int* s_red) {
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    int tot = 0;
-    for (int i = 0; i < THREADS / 64; ++i) tot += s_red[i];
-    __syncthreads();
-    return tot;
-}
-
 // The Kk largest keys over the descending lists of edges [e0, e1) (list of e: keys + e * stride, len_of(e) entries), by one block
 // of THREADS (thread = edge, chunks of THREADS edges): the threshold T by bisection (bisect = false: every key is kept, T = 0), the
 // count above it, and the gather -- sink(pos, e, j) for slot j of edge e at output position pos < Kk: the keys above T in
@@ -148,9 +122,8 @@ __device__ __forceinline__ int block_sum(int c, int* s_red) {
 // s_red / s_scan: THREADS / 64 entries of LDS each.
 template <int THREADS, typename LenOf, typename Sink>
 __device__ __forceinline__ void select_topk_lists(const uint32_t* __restrict__ keys, int stride, LenOf len_of, int e0, int e1, int Kk, bool bisect,
-                                                  int* s_red, unsigned long long* s_scan, Sink sink) {
-    constexpr int NW = THREADS / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+                                                  int* s_red, long long* s_scan, Sink sink) {
+    const int tid = threadIdx.x;
     uint32_t T = 0;
     if (bisect)
         for (int bit = 31; bit >= 0; --bit) {
@@ -174,16 +147,8 @@ __device__ __forceinline__ void select_topk_lists(const uint32_t* __restrict__ k
             q = count_ge(p, len, T) - g;
         }
         const long long mine = (long long)g | ((long long)q << 32);
-        long long off = wave_scan_incl(mine, lane);                            // over the wave, then over the block's waves
-        if (lane == 63) s_scan[wv] = (unsigned long long)off;
-        __syncthreads();
-        long long pre = base, all = 0;
-        for (int i = 0; i < NW; ++i) {
-            if (i < wv) pre += (long long)s_scan[i];
-            all += (long long)s_scan[i];
-        }
-        __syncthreads();
-        off += pre - mine;
+        long long all;
+        const long long off = base + block_scan_excl<THREADS>(mine, s_scan, all);
         const int oa = (int)(off & 0xffffffffll);
         const long long oq = off >> 32;
         for (int j = 0; j < g; ++j)

@@ -9,7 +9,9 @@
 //                         loop never spins); first by atomicMin, count by atomicAdd; the slot is remembered per point.  Which slot a
 //                         key lands in varies from run to run; first and count are a minimum and a sum over a set, which do not.
 //   voxel_heads_kernel    point i is a head when first[slot] == i and count >= min_count; heads per block of 256 points
-//   voxel_scan_kernel     ONE block: the exclusive scan of the per-block counts, a chunk of them per thread; the total is M
+//   scan_i32_kernel       (launch_scan_i32, segment_merge.hip) ONE block: the exclusive scan of the per-block counts in place, a run
+//                         of them per thread; the total is M.  Every count is a sum of 0 / 1 flags over the points i < V of a block, so
+//                         the total is at most V
 //   voxel_number_kernel   the block's own exclusive scan on top of its offset: a head gets its number m and writes first_point[m],
 //                         voxel_count[m] and head_number[i]
 //   voxel_map_kernel      every point: the number of its slot's head, or -1
@@ -24,11 +26,11 @@
 #include "common.h"
 #include "kernels.h"
 #include "voxel_core.h"
+#include "wave_core.h"
 
 namespace vlsat {
 
 constexpr int VX_THREADS = VOXEL_THREADS;
-constexpr int VX_SCAN_THREADS = 1024;
 constexpr int VX_WAVE = 64;
 
 struct __attribute__((aligned(16))) VoxelSlot {
@@ -93,69 +95,23 @@ __device__ __forceinline__ int voxel_is_head(const VoxelSlot* __restrict__ table
 __global__ __launch_bounds__(VX_THREADS) void voxel_heads_kernel(const VoxelSlot* __restrict__ table, uint32_t slots,
                                                                  const int32_t* __restrict__ slot_of_point, int n_points, int min_count,
                                                                  int32_t* __restrict__ block_heads) {
+    __shared__ int s_red[VX_THREADS / 64];
     int32_t count;
     const int head = voxel_is_head(table, slots, slot_of_point, blockIdx.x * VX_THREADS + threadIdx.x, n_points, min_count, count);
-    const int total = __syncthreads_count(head);
+    const int total = block_sum<VX_THREADS>(head, s_red);
     if (threadIdx.x == 0) block_heads[blockIdx.x] = total;
-}
-
-// inclusive scan over the lanes of a wave
-__device__ __forceinline__ int voxel_wave_scan(int v) {
-    const int lane = threadIdx.x & (VX_WAVE - 1);
-#pragma unroll
-    for (int d = 1; d < VX_WAVE; d <<= 1) {
-        const int o = __shfl_up(v, d, VX_WAVE);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-// exclusive scan of one value per thread over a block of THREADS (a multiple of 64); `total` is the block's sum
-template <int THREADS>
-__device__ __forceinline__ int voxel_block_scan(int v, int& total) {
-    __shared__ int wave_sum[THREADS / VX_WAVE];
-    const int inc = voxel_wave_scan(v);
-    if ((threadIdx.x & (VX_WAVE - 1)) == VX_WAVE - 1) wave_sum[threadIdx.x / VX_WAVE] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / VX_WAVE; ++w) {
-        const int s = wave_sum[w];
-        before += w < (int)(threadIdx.x / VX_WAVE) ? s : 0;
-        total += s;
-    }
-    return before + inc - v;
-}
-
-// one block: block_heads[0 .. n_blocks) becomes its exclusive scan, block_heads[n_blocks] and n_voxels[0] the total
-__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(int32_t* __restrict__ block_heads, int n_blocks, int n_points,
-                                                                     int32_t* __restrict__ n_voxels) {
-    const int chunk = (n_blocks + VX_SCAN_THREADS - 1) / VX_SCAN_THREADS;
-    const int b0 = min((int)threadIdx.x * chunk, n_blocks), b1 = min(b0 + chunk, n_blocks);
-    int sum = 0;
-    for (int b = b0; b < b1; ++b) sum += min(max(block_heads[b], 0), VX_THREADS);
-    int total;
-    int run = voxel_block_scan<VX_SCAN_THREADS>(sum, total);
-    for (int b = b0; b < b1; ++b) {
-        const int c = min(max(block_heads[b], 0), VX_THREADS);
-        block_heads[b] = run;
-        run += c;
-    }
-    if (threadIdx.x == 0) {
-        block_heads[n_blocks] = total;
-        n_voxels[0] = min(total, n_points);
-    }
 }
 
 __global__ __launch_bounds__(VX_THREADS) void voxel_number_kernel(const VoxelSlot* __restrict__ table, uint32_t slots,
                                                                   const int32_t* __restrict__ slot_of_point, int n_points, int min_count,
                                                                   const int32_t* __restrict__ block_heads, int32_t* __restrict__ head_number,
                                                                   int32_t* __restrict__ first_point, int32_t* __restrict__ voxel_count) {
+    __shared__ int s_wave[VX_THREADS / 64];
     const int i = blockIdx.x * VX_THREADS + threadIdx.x;
     int32_t count;
     const int head = voxel_is_head(table, slots, slot_of_point, i, n_points, min_count, count);
     int total;
-    const int m = block_heads[blockIdx.x] + voxel_block_scan<VX_THREADS>(head, total);
+    const int m = block_heads[blockIdx.x] + block_scan_excl<VX_THREADS>(head, s_wave, total);
     if (i >= n_points) return;
     const bool ok = head && m >= 0 && m < n_points;
     head_number[i] = ok ? m : -1;
@@ -314,7 +270,7 @@ int vlsat_voxel_assign(const float* points, int64_t n_points, float voxel, float
     hipLaunchKernelGGL(voxel_insert_kernel, dim3(blocks), dim3(VX_THREADS), 0, s, points, V, ox, oy, oz, inv, table, log2_slots, slot_of_point,
                        n_voxels);
     hipLaunchKernelGGL(voxel_heads_kernel, dim3(blocks), dim3(VX_THREADS), 0, s, table, slots, slot_of_point, V, (int)min_count, block_heads);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, s, block_heads, (int)blocks, V, n_voxels);
+    launch_scan_i32(block_heads, (int)blocks, block_heads, n_voxels, nullptr, s);   // in place; n_voxels[0] = the total <= V
     hipLaunchKernelGGL(voxel_number_kernel, dim3(blocks), dim3(VX_THREADS), 0, s, table, slots, slot_of_point, V, (int)min_count, block_heads,
                        head_number, first_point, voxel_count);
     hipLaunchKernelGGL(voxel_map_kernel, dim3(blocks), dim3(VX_THREADS), 0, s, table, slots, slot_of_point, head_number, V, voxel_of_point);

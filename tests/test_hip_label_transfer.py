@@ -81,12 +81,24 @@ def test_sizes_that_are_no_multiple_of_the_wave():
     assert (check_nearest(q, r, 0.01, "")[0] < 0).sum() > 2
 
 
+def _grid_cells(ref, max_sq_dist):
+    """The cell count of the grid rule in include/vlsat.h (nearest_points), when the first cell edge fits: edge = fl(sqrt(max_sq_dist)
+    (1 + 2^-6)), floor(extent / edge) + 1 cells per axis, in fp32."""
+    f = np.float32
+    inv = f(1) / f(np.sqrt(f(max_sq_dist)) * f(1.015625))
+    n = [int(f(f(hi - lo) * inv)) + 1 for lo, hi in zip(ref.min(0), ref.max(0))]
+    assert max(n) <= 1024 and n[0] * n[1] * n[2] <= 1 << 21, n
+    return n[0] * n[1] * n[2]
+
+
 def test_a_room_of_many_blocks():
     _need_gpu()
     rng = np.random.default_rng(11)
     ext = np.array([6.0, 6.0, 3.0])
     r = (rng.uniform(0, 1, size=(30000, 3)) * ext).astype(np.float32)
     q = (rng.uniform(-0.05, 1.05, size=(20000, 3)) * ext).astype(np.float32)
+    # the scan of the cell counts walks tiles of 4096: less than one tile at 0.1, 101 tiles and a ragged one at 0.004
+    assert _grid_cells(r, 0.1) == 19 * 19 * 10 and _grid_cells(r, 0.004) == 94 * 94 * 47 == 101 * 4096 + 1596
     gi, _ = check_nearest(q, r, 0.1, "20000x30000")
     assert (gi >= 0).mean() > 0.9
     gi, _ = check_nearest(q[:4000], r, 0.004, "4000x30000, small radius")

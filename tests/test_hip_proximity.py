@@ -85,10 +85,12 @@ def _crowded(n, seed):
     return room_boxes(n, seed, extent=(side, side, 2.0))
 
 
-@pytest.mark.parametrize("n_obj", [1, 2, 63, 64, 65, 300])
+@pytest.mark.parametrize("n_obj", [1, 2, 63, 64, 65, 257, 300, 600, 601])
 def test_edges_equal_the_host_rule_on_one_scene(n_obj):
     """Wave boundary (63 / 64 / 65 targets), 300 objects (38 blocks of 8 rows, five lane passes per row); no cap, a cap that bites
-    (3, 8), a cap of N and one above N; padding 0 and 0.2."""
+    (3, 8), a cap of N and one above N; padding 0 and 0.2.  The 256 threads of the row-count scan own runs of two at 257 and 300 rows
+    (thread 128 owns the odd row of 257; the threads after it, and from 150 on, own nothing) and runs of three at 600 and 601 (200
+    threads, then one ragged run of a single row)."""
     _need_gpu()
     boxes = _crowded(n_obj, 400 + n_obj)
     sizes = {}

@@ -8,7 +8,7 @@ import torch
 import vlsat_amd  # noqa: F401
 from vlsat_amd import evaluate as EV, lib as L, metrics as M
 
-from segment_merge_checks import assert_tables, path, random_groups
+from segment_merge_checks import assert_tables, brute, path, random_groups
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -39,14 +39,22 @@ CASES = {
     "three_scenes_empty_middle": lambda: random_groups(150, 12, 1200, 13, scenes=[70, 0, 80], weights="mixed"),
     "one_class_one_predicate": lambda: random_groups(130, 10, 900, 14, c=1, r=1, same_part=0, weights="mixed"),
     "1024_classes_32_predicates": lambda: random_groups(90, 7, 700, 15, c=1024, r=32, same_part=31, mutual=True),
+    # the one-block scans (1024 threads) past one element per thread: 1025 nodes are runs of 2 and threads 513.. own nothing; 2500
+    # nodes are runs of 3 with a ragged last one (thread 833 owns one node), 6000 edges runs of 6
+    "path1025_descending": lambda: path(1025, descending=True),
+    "random_6000_over_2500": lambda: random_groups(2500, 200, 6000, 16),
 }
+LONG_RUNS = ("path1025_descending", "random_6000_over_2500")                                 # also against the rule as loops
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_hip_equals_host(name):
     _need_gpu()
-    got, want = _both(CASES[name]())
+    c = CASES[name]()
+    got, want = _both(c)
     assert_tables(got, want, name)
+    if name in LONG_RUNS:
+        assert_tables(got, brute(c), name)
 
 
 def test_what_the_cases_exercise():

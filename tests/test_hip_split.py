@@ -66,6 +66,27 @@ def test_one_vertex_one_seed_and_non_finite():
     assert _split(bad, seg, np.unique(seg), ranks=[10])[0] == [10]
 
 
+def test_seeds_with_two_blocks_per_thread_of_the_pick():
+    """1024 * 1024 + 1025 vertices are 1026 blocks of 1024: the 1024 threads of the pick own runs of two blocks (thread 512 the last
+    full block and the one-vertex block after it, the threads after it nothing).  Three clusters far apart give three seeds; the ranks
+    put the second seed into block 1, the second block of thread 0's run, and the third into the last, partial block."""
+    _need_gpu()
+    v = 1024 * 1024 + 1025
+    g = np.random.default_rng(21)
+    cluster = g.integers(0, 3, v)
+    cluster[0], cluster[-1] = 0, 2
+    pts = (np.asarray([[0, 0, 0], [10, 0, 0], [0, 10, 0]], dtype=np.float32)[cluster] + g.random((v, 3)) * 0.1).astype(np.float32)
+    other = np.nonzero(cluster != 0)[0]
+    r1 = int((other < 1024).sum()) + 5                                            # the sixth selectable vertex of block 1
+    second = int(other[r1])
+    assert 1024 <= second < 2048 and cluster[second] == 1                         # (seed 21 draws it so; then cluster 2 is what is left)
+    ranks = [0, r1, int((cluster == 2).sum()) - 1]
+    want = P.split_seeds_host(pts, 1.0, 0, ranks)
+    assert want.tolist() == [0, second, v - 1]
+    got = P.split_seeds(torch.from_numpy(pts).to(DEV), 1.0, 0, ranks, max_seeds=5)
+    assert got.cpu().numpy().tolist() == want.tolist()
+
+
 def test_golden_reference_runs_replay_on_the_device():
     _need_gpu()
     z = np.load(GOLDEN)

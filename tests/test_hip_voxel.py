@@ -2,7 +2,7 @@
 cell edges each (one voxel for all: every atomic hits one destination; a voxel per point; in between, about a thousand voxels on
 many_cells and so probe collisions), min_count 1, 2 and above every count (M = 0: empty outputs, nothing launched), with and without
 normals and colours, a non-zero origin, points on cell faces, both signs, points and cells out of range, normals that cancel or are not
-finite, 65 and 257 points for the wave and block edges of the scan, 300 000 points for the scan of the per-block counts, two runs
+finite, 65 and 257 points for the wave and block edges of the scan, 300 000, 262 144 and 262 145 points for the scan of the per-block counts, two runs
 bit-equal; scan.downsample_cloud and scan.segment_cloud(voxel=...) on the device equal to the host; and the route from a faceless PLY
 through resampling and segmentation to a written graph."""
 import numpy as np
@@ -65,7 +65,8 @@ def test_normals_alone_and_colours_alone():
 
 
 def test_the_scan_of_the_block_counts():
-    """300 000 points are 1172 blocks of 256: the one-block scan of the per-block head counts takes two counts per thread"""
+    """300 000 points are 1172 blocks of 256: the one-block scan of the per-block head counts takes two counts per thread; then the
+    thread count itself, 1024 blocks, and one block more"""
     _need_gpu()
     g = np.random.default_rng(8)
     p = (g.uniform(0, 1, (300000, 3)) * np.array([8.0, 8.0, 0.5])).astype(np.float32)
@@ -73,6 +74,16 @@ def test_the_scan_of_the_block_counts():
         want = VC.host(p, voxel, (0, 0, 0), min_count)
         assert len(want.points) > 20000
         VC.assert_same_cloud(_device(p, voxel, (0, 0, 0), min_count), want, (voxel, min_count))
+    # 1024 blocks give every thread of the scan one count; 1025 give runs of two and leave half the block idle.  The scan is in place
+    # and sees zeros: the second half of these clouds repeats the first, so no voxel opens there.
+    for n_points in (262144, 262145):
+        half = p[:(n_points + 1) // 2]
+        twice = np.concatenate([half, half[:n_points - len(half)]])
+        for min_count in (1, 3):
+            want = VC.host(twice, 0.05, (0, 0, 0), min_count)
+            heads = np.bincount(want.first_point // 256, minlength=(n_points + 255) // 256)
+            assert len(heads) == (n_points + 255) // 256 and (heads[:400] > 0).all() and (heads[520:] == 0).all() and len(want.points) > 20000
+            VC.assert_same_cloud(_device(twice, 0.05, (0, 0, 0), min_count), want, (n_points, min_count))
 
 
 def test_two_runs_are_bit_equal():
