@@ -21,6 +21,7 @@ CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib
 SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_segment.h")
 CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud.h")
 VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel.h")
+OBJECTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_objects.h")
 
 
 class VlsatDims(C.Structure):
@@ -163,6 +164,14 @@ _SIGNATURES_VOXEL = {
     "vlsat_voxel_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_objects.h: a cloud segmented into objects -- structural planes found and removed, the rest clustered (csrc/objects.hip)
+_SIGNATURES_OBJECTS = {
+    "vlsat_cloud_planes_scratch_bytes": (_sz, [_i64, _i32]),
+    "vlsat_cloud_planes": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vlsat_cloud_clusters_scratch_bytes": (_sz, [_i64]),
+    "vlsat_cloud_clusters": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -177,7 +186,7 @@ def identity(lib_path: str = "") -> dict:
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
-                                          os.path.join(_HERE, "build.py")]:
+                                          OBJECTS_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -221,6 +230,11 @@ def declared_voxel_symbols() -> list:
     return _declared(VOXEL_HEADER_PATH)
 
 
+def declared_objects_symbols() -> list:
+    """Every function include/vlsat_objects.h declares."""
+    return _declared(OBJECTS_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -231,7 +245,7 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()):
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1093,3 +1093,228 @@ def voxel_downsample(points, voxel: float, origin=(0.0, 0.0, 0.0), min_count: in
                                        scratch.data_ptr(), out_points.data_ptr(), 0 if out_normals is None else out_normals.data_ptr(),
                                        0 if out_colors is None else out_colors.data_ptr(), L.stream_ptr()))
     return VoxelCloud(out_points, out_normals, out_colors, voxel_of_point, first_point, count)
+
+
+# ---- a cloud segmented into objects: structural planes, then clusters (csrc/objects.hip; the rules are stated in include/vlsat_objects.h) ----
+PLANE_MAX_HYP = 4096
+PLANE_MAX_PLANES = 32
+PLANE_MAX_PPM = 500000
+
+
+class CloudPlanes(NamedTuple):
+    """``cloud_planes``: ``plane_id`` int32 [V] (0 = no plane, else 1..n), ``planes`` f32 [P,4] = (nx, ny, nz, d) and ``counts`` int32
+    [P,3] = (inliers, above, below) per found plane (unused rows zero), ``n_planes`` int32 [1]."""
+    plane_id: object
+    planes: object
+    counts: object
+    n_planes: object
+
+
+class CloudClusters(NamedTuple):
+    """``cloud_clusters``: ``labels`` int32 [V] (0 = none, else 1..S by lowest point), ``n_clusters`` int32 [1], ``cluster_size`` int32
+    [V] (entry s - 1 is the size of cluster s, zeros past S)."""
+    labels: object
+    n_clusters: object
+    cluster_size: object
+
+
+def _planes_args(shape, n_hyp, max_planes, dist, min_inliers, outside_ppm):
+    """-> dist as np.float32; raises on anything the rule refuses"""
+    import numpy as np
+    if len(shape) != 2 or shape[1] != 3 or not 3 <= shape[0] <= SEG_MAX_VERTS:
+        raise L.VlsatError("cloud_planes: points must be float32 [V,3] with 3 <= V <= 2^24")
+    if not 1 <= int(n_hyp) <= PLANE_MAX_HYP:
+        raise L.VlsatError("cloud_planes: 1 <= n_hyp <= 4096")
+    if not 1 <= int(max_planes) <= PLANE_MAX_PLANES:
+        raise L.VlsatError("cloud_planes: 1 <= max_planes <= 32")
+    with np.errstate(over="ignore"):
+        d = np.float32(dist)
+    if not (d > 0 and np.isfinite(d)):
+        raise L.VlsatError("cloud_planes: dist must be > 0 and finite in fp32")
+    if not 3 <= int(min_inliers) < 1 << 31:
+        raise L.VlsatError("cloud_planes: min_inliers must be at least 3")
+    if not 0 <= int(outside_ppm) <= PLANE_MAX_PPM:
+        raise L.VlsatError("cloud_planes: outside_ppm must be in 0 .. 500000")
+    return d
+
+
+def plane_draws(seed: int, k, n: int):
+    """``split_draw(seed, k, n)`` for an array of counters k (uint64 arithmetic that wraps, as the device's does) -> int64 ranks"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * (np.asarray(k, dtype=np.uint64) + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+        return (((z >> np.uint64(32)) * np.uint64(int(n))) >> np.uint64(32)).astype(np.int64)
+
+
+def plane_from_points_host(a, b, c):
+    """Rule 3 of include/vlsat_objects.h on arrays of points f32 [H,3] (plane_from_points of csrc/plane_core.h: fp64, the same operations
+    in the same order) -> (planes f32 [H,4], ok bool [H]); a void hypothesis has a zero row."""
+    import numpy as np
+    a, b, c = (np.asarray(x, dtype=np.float32).astype(np.float64) for x in (a, b, c))
+    with np.errstate(all="ignore"):
+        u, v = b - a, c - a
+        mx = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+        my = u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2]
+        mz = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+        l2 = (mx * mx + my * my) + mz * mz
+        ok = (l2 > 0.0) & (l2 < np.inf)
+        length = np.sqrt(np.where(ok, l2, 1.0))
+        nx, ny, nz = mx / length, my / length, mz / length
+        big = nx
+        big = np.where(np.abs(ny) > np.abs(big), ny, big)
+        big = np.where(np.abs(nz) > np.abs(big), nz, big)
+        flip = big < 0.0
+        nx, ny, nz = (np.where(flip, -x, x) for x in (nx, ny, nz))
+        d = -((nx * a[:, 0] + ny * a[:, 1]) + nz * a[:, 2])
+        planes = np.stack([nx, ny, nz, d], 1).astype(np.float32)
+    return np.where(ok[:, None], planes, np.float32(0.0)).astype(np.float32), ok
+
+
+def plane_scores_host(planes, points):
+    """Rule 4: s = fl(fl(fl(fl(nx x) + fl(ny y)) + fl(nz z)) + d) in fp32 for planes f32 [H,4] x points f32 [n,3] -> f32 [H,n]"""
+    import numpy as np
+    pl, p = np.asarray(planes, dtype=np.float32), np.asarray(points, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        return ((pl[:, 0, None] * p[None, :, 0] + pl[:, 1, None] * p[None, :, 1]) + pl[:, 2, None] * p[None, :, 2]) + pl[:, 3, None]
+
+
+def cloud_planes_host(points, n_hyp: int, max_planes: int, dist: float, min_inliers: int, outside_ppm: int, seed: int = 0) -> CloudPlanes:
+    """The plane rule of include/vlsat_objects.h in numpy, the same operations in the same order -> ``CloudPlanes`` of numpy arrays,
+    every bit the device's: per round the alive list, the draws of ``split_draw``, the planes in fp64 rounded to fp32, the scores in
+    fp32, integer counts, the eligibility test and the key."""
+    import numpy as np
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, 3)
+    dist = _planes_args(p.shape, n_hyp, max_planes, dist, min_inliers, outside_ppm)
+    n_hyp, max_planes, min_inliers, outside_ppm = int(n_hyp), int(max_planes), int(min_inliers), int(outside_ppm)
+    alive = np.isfinite(p).all(1)
+    plane_id = np.zeros(len(p), dtype=np.int32)
+    planes = np.zeros((max_planes, 4), dtype=np.float32)
+    counts = np.zeros((max_planes, 3), dtype=np.int32)
+    found = 0
+    for r in range(max_planes):
+        idx = np.nonzero(alive)[0]
+        n = len(idx)
+        if n < 3:
+            break
+        k = (np.arange(n_hyp, dtype=np.uint64) + np.uint64(r * n_hyp)) * np.uint64(3)
+        a, b, c = (p[idx[plane_draws(seed, k + np.uint64(j), n)]] for j in range(3))
+        hyp, ok = plane_from_points_host(a, b, c)
+        q = p[idx]
+        inliers, above = np.zeros(n_hyp, dtype=np.int64), np.zeros(n_hyp, dtype=np.int64)
+        step = max(1, (1 << 22) // n)
+        with np.errstate(invalid="ignore"):
+            for h0 in range(0, n_hyp, step):
+                s = plane_scores_host(hyp[h0:h0 + step], q)
+                inliers[h0:h0 + step] = (np.abs(s) <= dist).sum(1)
+                above[h0:h0 + step] = (s > dist).sum(1)
+        below = n - inliers - above
+        eligible = ok & (inliers >= min_inliers) & (np.minimum(above, below) <= (n * outside_ppm) // 1000000)
+        if not eligible.any():
+            break
+        key = (inliers.astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.arange(n_hyp, dtype=np.uint64))
+        h = int(np.argmax(np.where(eligible, key, np.uint64(0))))
+        with np.errstate(invalid="ignore"):
+            hit = np.abs(plane_scores_host(hyp[h:h + 1], q)[0]) <= dist
+        plane_id[idx[hit]] = r + 1
+        alive[idx[hit]] = False
+        planes[r] = hyp[h]
+        counts[r] = (inliers[h], above[h], below[h])
+        found = r + 1
+    return CloudPlanes(plane_id, planes, counts, np.asarray([found], dtype=np.int32))
+
+
+def cloud_planes(points, n_hyp: int, max_planes: int, dist: float, min_inliers: int, outside_ppm: int, seed: int = 0) -> CloudPlanes:
+    """points f32 [V,3] -> ``CloudPlanes``: the structural planes of a room (include/vlsat_objects.h, vlsat_cloud_planes).  In each of up
+    to ``max_planes`` rounds ``n_hyp`` planes through three drawn points (``split_draw`` under ``seed``) are scored against every
+    point that is still alive; a plane is eligible when it has at least ``min_inliers`` points within ``dist`` AND at most
+    ``outside_ppm`` millionths of the alive points on one of its sides -- a floor or a wall, not a table top; the eligible plane with
+    most inliers wins and its inliers leave.  There is no refit: ``planes`` are the planes that were scored.  Device tensors run the HIP
+    kernels: all rounds are enqueued, the rounds after a stop return at once, and nothing is read back (``n_planes`` stays on the
+    device).  CPU tensors or arrays run ``cloud_planes_host`` and get CPU tensors, with equal bits."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        out = cloud_planes_host(points.numpy() if isinstance(points, torch.Tensor) else points, n_hyp, max_planes, dist, min_inliers,
+                                outside_ppm, seed)
+        return CloudPlanes(*(torch.from_numpy(x) for x in out))
+    lib = L.load()
+    if points.dtype != torch.float32:
+        raise L.VlsatError("cloud_planes: points must be float32 [V,3]")
+    dist = _planes_args(points.shape, n_hyp, max_planes, dist, min_inliers, outside_ppm)
+    dev, points, v = points.device, points.contiguous(), points.shape[0]
+    scratch = torch.empty(int(lib.vlsat_cloud_planes_scratch_bytes(v, int(n_hyp))), dtype=torch.uint8, device=dev)
+    plane_id = torch.empty(v, dtype=torch.int32, device=dev)
+    planes = torch.empty((int(max_planes), 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((int(max_planes), 3), dtype=torch.int32, device=dev)
+    n_planes = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_cloud_planes(points.data_ptr(), v, int(n_hyp), int(max_planes), float(dist), int(min_inliers), int(outside_ppm),
+                                   int(seed) & _M64, scratch.data_ptr(), plane_id.data_ptr(), planes.data_ptr(), counts.data_ptr(),
+                                   n_planes.data_ptr(), L.stream_ptr()))
+    return CloudPlanes(plane_id, planes, counts, n_planes)
+
+
+def _clusters_args(index_shape, sqdist_shape, mask_shape, max_sq_dist, min_points):
+    import math
+    if len(index_shape) != 2 or not 1 <= index_shape[0] <= SEG_MAX_VERTS or not 1 <= index_shape[1] <= CLOUD_MAX_K:
+        raise L.VlsatError("cloud_clusters: knn_index must be int32 [V,K] with 1 <= V <= 2^24 and 1 <= K <= 32")
+    if tuple(sqdist_shape) != tuple(index_shape):
+        raise L.VlsatError("cloud_clusters: knn_sqdist must be float32 [V,K], the shape of knn_index")
+    if tuple(mask_shape) != (index_shape[0],):
+        raise L.VlsatError("cloud_clusters: mask must be int32 [V]")
+    if math.isnan(float(max_sq_dist)):
+        raise L.VlsatError("cloud_clusters: max_sq_dist is NaN")
+    if not 1 <= int(min_points) < 1 << 31:
+        raise L.VlsatError("cloud_clusters: min_points must be at least 1")
+
+
+def cloud_clusters_host(knn_index, knn_sqdist, mask, max_sq_dist: float, min_points: int = 1) -> CloudClusters:
+    """The cluster rule of include/vlsat_objects.h in numpy -> ``CloudClusters`` of numpy arrays, equal to the device's: the table
+    entries that join two eligible points within ``max_sq_dist`` are united (``_seg_unite``: the lowest member is the root), components
+    below ``min_points`` get 0 and the rest are numbered by lowest point."""
+    import numpy as np
+    nbr = np.asarray(knn_index).astype(np.int64)
+    d2 = np.asarray(knn_sqdist, dtype=np.float32)
+    m = np.asarray(mask).reshape(-1) != 0
+    _clusters_args(nbr.shape, d2.shape, m.shape, max_sq_dist, min_points)
+    v, k = nbr.shape
+    i = np.repeat(np.arange(v, dtype=np.int64), k)
+    j = nbr.reshape(-1)
+    with np.errstate(invalid="ignore"):
+        ok = (j >= 0) & (j < v) & (j != i) & (d2.reshape(-1) <= np.float32(max_sq_dist))
+    ok &= m[i] & m[np.where(ok, j, 0)]
+    parent = _seg_unite(np.arange(v, dtype=np.int64), i[ok], j[ok])
+    size = np.bincount(parent[m], minlength=v)
+    kept = m & (parent == np.arange(v)) & (size >= int(min_points))
+    num = np.where(kept, np.cumsum(kept), 0)
+    labels = np.where(m, num[parent], 0).astype(np.int32)
+    s = int(kept.sum())
+    cluster_size = np.zeros(v, dtype=np.int32)
+    cluster_size[:s] = size[kept]
+    return CloudClusters(labels, np.asarray([s], dtype=np.int32), cluster_size)
+
+
+def cloud_clusters(knn_index, knn_sqdist, mask, max_sq_dist: float, min_points: int = 1) -> CloudClusters:
+    """The table of ``knn_points`` and a mask int32 [V] (non-zero: the point takes part) -> ``CloudClusters``: Euclidean clusters, the
+    connected components of the table entries that join two eligible points at a squared distance of at most ``max_sq_dist``
+    (include/vlsat_objects.h, vlsat_cloud_clusters).  A component of fewer than ``min_points`` points gets 0; the rest are numbered 1..S
+    by lowest point.  Points that touch through the table are one cluster: two objects closer than the radius merge.  Device tensors run
+    the HIP kernels (7 launches, nothing read back); CPU tensors or arrays run ``cloud_clusters_host`` and get CPU tensors."""
+    if not (isinstance(knn_index, torch.Tensor) and knn_index.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x   # noqa: E731
+        out = cloud_clusters_host(as_np(knn_index), as_np(knn_sqdist), as_np(mask), max_sq_dist, min_points)
+        return CloudClusters(*(torch.from_numpy(x) for x in out))
+    lib = L.load()
+    _clusters_args(knn_index.shape, knn_sqdist.shape, mask.shape, max_sq_dist, min_points)
+    dev = knn_index.device
+    index = knn_index.to(dtype=torch.int32).contiguous()
+    sqdist = knn_sqdist.to(device=dev, dtype=torch.float32).contiguous()
+    mask = (mask.to(device=dev) != 0).to(torch.int32).contiguous()
+    v, k = index.shape
+    scratch = torch.empty(int(lib.vlsat_cloud_clusters_scratch_bytes(v)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(v, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
+    cluster_size = torch.empty(v, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_cloud_clusters(index.data_ptr(), sqdist.data_ptr(), mask.data_ptr(), v, k, float(max_sq_dist), int(min_points),
+                                     scratch.data_ptr(), labels.data_ptr(), n_clusters.data_ptr(), cluster_size.data_ptr(), L.stream_ptr()))
+    return CloudClusters(labels, n_clusters, cluster_size)

@@ -11,7 +11,8 @@ class does on the host before ``Mmgnet.forward`` sees a scene, without trimesh -
 * ``prepare_scan``             all of it + the per-object point selection, zero-mean, descriptor on the DEVICE (``prep.py``; reference
                                ``:279-294``) -> one batch dict in the layout ``evaluate.validation`` and ``VLSATModel.forward`` take;
 * ``read_mesh`` / ``write_ply`` / ``vertex_normals`` / ``segment_scan``   a bare mesh with its faces, and the over-segmentation (on the
-                               DEVICE, ``prep.segment_mesh``) that stands in for the instance ids when nobody has made any.
+                               DEVICE, ``prep.segment_mesh``) that stands in for the instance ids when nobody has made any;
+* ``segment_objects``          a bare cloud to OBJECT-level instances on the device: structural planes removed, the rest clustered.
 
 The union point sets (``rel_points``, ``:337-359``) are not produced: ``Mmgnet.forward`` never reads them.  The host-side
 functions are plain numpy; ``prepare_scan`` needs the GPU library.  Parity: PINNED to the reference's own dataset code --
@@ -816,3 +817,85 @@ def downsample_cloud(cloud_or_path, voxel: float, origin=(0.0, 0.0, 0.0), min_co
     out["first_point"] = first
     out["voxel_count"] = get(vc.count)
     return out
+
+
+def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 16, n_hyp: int = 1024, max_planes: int = 8,
+                    min_plane_share: float = 0.02, outside_frac: float = 0.01, min_points: int = 50, voxel: Optional[float] = None,
+                    seed: int = 0, device="cuda:0") -> Dict[str, Optional[np.ndarray]]:
+    """A point cloud segmented into OBJECT-level instances on the device, without a trained model: -> a copy of the dict with
+    ``instances`` (int64 [V]: the structural planes are 1..P, the clusters P+1..P+S, 0 = dropped), ``n_planes`` = P, ``planes`` f32
+    [P,4] = (nx, ny, nz, d), ``n_segments`` = P + S and ``seg_size`` int32 [P + S] filled.  ``cloud_or_path``: a PLY path
+    (``read_mesh``) or a dict with ``points``; faces, if any, are ignored.
+
+    First the room's structural planes -- floor, walls, ceiling -- are found and removed (``prep.cloud_planes``): a plane drawn through
+    three points is structural when at least ``min_plane_share`` of the valid points lie within ``dist`` of it AND at most
+    ``outside_frac`` of the remaining points lie on one of its sides, which is true of a floor and not of a table top;
+    ``min_inliers = ceil(min_plane_share x valid points)``, ``outside_ppm = round(outside_frac x 10^6)``, ``n_hyp`` planes are tried
+    per round.  Then the points no plane took are clustered by proximity (``prep.knn_points`` over THOSE points, ``k`` neighbours
+    within ``cluster_radius``, then ``prep.cloud_clusters``); a cluster of fewer than ``min_points`` points is dropped.
+    include/vlsat_objects.h states both rules.  ``dist`` and ``cluster_radius`` have no defaults because none is free of units: the
+    sensor noise, and about one and a half times the sampling distance, are a start.
+
+    ``voxel``: as in ``segment_cloud`` -- the cloud is resampled first (``downsample_cloud``, origin 0, ``min_count`` 1), the RESAMPLED
+    cloud is segmented (all parameters then speak of resampled points) and ``instances`` are gathered back through
+    ``voxel_of_point`` (a point without a voxel: 0); ``seg_size`` is recounted over the input points and ``resampled`` holds the small
+    cloud's result.  ``device=None`` (or "cpu") runs the numpy restatements, which give the same result bit for bit.  The output goes
+    straight into ``write_ply`` and ``prepare_scan``, as ``segment_scan``'s does.
+
+    Objects that touch -- closer than ``cluster_radius`` -- come out as ONE cluster, and an object standing against a wall loses the
+    points within ``dist`` of it to the wall.  Every default is a starting value, not a tuned operating point: no scan data and no
+    checkpoint is available to this project, so accuracy on real scans is unmeasured."""
+    import math
+
+    import torch
+
+    from . import prep
+
+    cloud = dict(read_mesh(cloud_or_path) if isinstance(cloud_or_path, (str, os.PathLike)) else cloud_or_path)
+    if voxel is not None:
+        small = segment_objects(downsample_cloud(cloud, voxel, device=device), dist, cluster_radius, k, n_hyp, max_planes, min_plane_share,
+                                outside_frac, min_points, None, seed, device)
+        of = small["voxel_of_point"].astype(np.int64)
+        cloud["instances"] = np.where(of >= 0, small["instances"][np.maximum(of, 0)], 0).astype(np.int64)
+        cloud["n_planes"], cloud["planes"], cloud["n_segments"] = small["n_planes"], small["planes"], small["n_segments"]
+        cloud["seg_size"] = np.bincount(cloud["instances"][cloud["instances"] > 0] - 1, minlength=small["n_segments"]).astype(np.int32)
+        cloud["resampled"] = small
+        return cloud
+    pts = np.ascontiguousarray(np.asarray(cloud["points"])[:, :3], dtype=np.float32)
+    if not 3 <= len(pts) <= prep.SEG_MAX_VERTS:
+        raise ScanError("segment_objects: 3 .. 2^24 points")
+    if not float(cluster_radius) >= 0.0:
+        raise ScanError("segment_objects: cluster_radius must be >= 0")
+    if not (0.0 < float(min_plane_share) <= 1.0 and 0.0 <= float(outside_frac) <= 0.5):
+        raise ScanError("segment_objects: min_plane_share must be in (0, 1] and outside_frac in [0, 0.5]")
+    n_valid = int(np.isfinite(pts).all(1).sum())
+    min_inliers = max(3, int(math.ceil(float(min_plane_share) * n_valid)))
+    outside_ppm = int(round(float(outside_frac) * 1e6))
+    max_sq_dist = float(np.float32(cluster_radius) ** 2)
+    on_host = device is None or torch.device(device).type == "cpu"
+    d_pts = torch.from_numpy(pts) if on_host else torch.from_numpy(pts).to(device)
+    try:
+        found = prep.cloud_planes(d_pts, n_hyp, max_planes, dist, min_inliers, outside_ppm, seed)
+    except prep.L.VlsatError as e:
+        raise ScanError(f"segment_objects: {e}") from e
+    n_planes = int(found.n_planes.reshape(-1)[0])                                    # the first host wait
+    plane_id = found.plane_id.cpu().numpy().astype(np.int64)
+    instances = plane_id.copy()
+    rest = np.nonzero((plane_id == 0) & np.isfinite(pts).all(1))[0]
+    sizes = [found.counts[:n_planes, 0].cpu().numpy().astype(np.int32)]
+    n_clusters = 0
+    if len(rest):
+        d_rest = d_pts[torch.from_numpy(rest).to(d_pts.device)]
+        table = prep.knn_points(d_rest, k, max_sq_dist)
+        mask = torch.ones(len(rest), dtype=torch.int32, device=d_pts.device)
+        grown = prep.cloud_clusters(table.index, table.sqdist, mask, max_sq_dist, min_points)
+        n_clusters = int(grown.n_clusters.reshape(-1)[0])
+        labels = grown.labels.cpu().numpy().astype(np.int64)
+        instances[rest] = np.where(labels > 0, labels + n_planes, 0)
+        sizes.append(grown.cluster_size[:n_clusters].cpu().numpy().astype(np.int32))
+    cloud["instances"] = instances
+    cloud["n_planes"] = n_planes
+    cloud["planes"] = found.planes[:n_planes].cpu().numpy()
+    cloud["n_segments"] = n_planes + n_clusters
+    cloud["seg_size"] = np.concatenate(sizes)
+    return cloud

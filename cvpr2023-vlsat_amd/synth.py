@@ -271,3 +271,31 @@ def make_fused_index(points, views: int = 8, x_below: float = 5.0) -> np.ndarray
     """The input point behind every row of ``make_fused_cloud``: int64 [V + views * H]."""
     p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     return np.concatenate([np.arange(len(p))] + [np.nonzero(p[:, 0] < x_below)[0]] * int(views))
+
+
+def make_walled_room(n_obj: int, step: float, seed: int, height: float = 2.0, extent=(10.0, 10.0)) -> dict:
+    """A room with WALLS as a cloud without faces, for the object segmenter: the points and ``instances`` of ``make_box_mesh(n_obj,
+    step, seed, extent=extent)`` plus four walls of ``height`` metres on the floor's border -- x = 0, x = extent[0], y = 0, y =
+    extent[1] -- sampled on the same grid of spacing ``step`` from z = step upwards (the row z = 0 is the floor's; a corner column
+    belongs to the x wall).  -> {"points": f64 [V,3], "instances": i64 [V] (1 = floor, 2 + k = box k, n_obj + 2 + w = wall w in the
+    order above), "plane": i32 [V] (``make_box_mesh``'s numbering, then 1 + 6 n_obj + w for wall w), "structural": bool [V] (floor and
+    walls), "n_obj", "step", "height", "extent"}."""
+    room = make_box_mesh(n_obj, step, seed, extent=extent)
+    step = float(step)
+    nx, ny = (max(2, int(round(e / step))) for e in extent)
+    nz = max(1, int(round(float(height) / step)))
+    pts, inst, plane = [room["points"]], [room["instances"]], [room["plane"]]
+    for w in range(4):
+        along = np.arange((ny if w < 2 else nx) + 1)
+        if w >= 2:
+            along = along[1:-1]
+        a, z = (x.ravel() for x in np.meshgrid(along, np.arange(1, nz + 1), indexing="ij"))
+        fixed = np.full(a.size, (0, nx, 0, ny)[w] * step)
+        p = np.stack([fixed, a * step, z * step], 1) if w < 2 else np.stack([a * step, fixed, z * step], 1)
+        pts.append(p)
+        inst.append(np.full(len(p), n_obj + 2 + w, np.int64))
+        plane.append(np.full(len(p), 1 + 6 * n_obj + w, np.int32))
+    instances = np.concatenate(inst)
+    return {"points": np.concatenate(pts), "instances": instances, "plane": np.concatenate(plane),
+            "structural": (instances == 1) | (instances >= n_obj + 2), "n_obj": int(n_obj), "step": step, "height": nz * step,
+            "extent": (nx * step, ny * step)}
