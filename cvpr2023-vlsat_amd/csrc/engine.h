@@ -154,6 +154,7 @@ struct vlsat_ctx {
     int gate_fuse_agg = 1;                   // gate at the default head geometry, GCN_AGGR = max: aggregation fused into the gate kernel: 0 never, 1 the bf16 modes, 2 fp32 as well ("gate_fuse_agg")
     int flash_ablate = 0;                    // timing experiments on the bf16 edge attention (FlashSplit::ablate; results are garbage)
     int flash_pv_terms = 3;                  // split-bf16 edge attention: MFMAs per P.V product (3, or 2 = probabilities single-rounded)
+    int flash_exact = -1;                    // fp32 mode, head dim 64: -1 / 0 the split-fp16 edge attention (three f16 MFMAs per product), 1 the exact fp32-MFMA kernel (debug option "flash_exact")
     int ln_resid = 1;                        // split-pair mode: post-attention residual added in the LayerNorm kernel
     int half_fmt = 1;                        // single-rounding modes: those tensors as plain bf16 (half rows) instead of split pairs
     int split_fmt = 1;                       // bf16 modes: edge tensors between matrix kernels in the split-pair format

@@ -53,6 +53,8 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //                       kernels as bf16 hi/lo pairs or half rows, attention / object encoder / gate on the bf16 matrix cores, V operand by
 //                       LDS transpose read, attention residual added by the LayerNorm kernel (0: the fp32 forms; parity-tested both ways)
 //   "flash_pv_terms" 3|2   split-bf16 edge attention: MFMAs per P.V product
+//   "flash_exact" -1|0|1   fp32 mode, head dim 64: the edge attention's products as three fp16 MFMAs each (-1 default, 0) or the exact
+//                       fp32-MFMA kernel (1: the forward of the releases before the split-fp16 kernel, bit for bit)
 //   "flash_bq_big" 0|1   half-row edge attention on plans whose scenes all have >= 4096 edges: 256 queries per block (1, default) or 128
 //   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes (default) / fp32 too
 //   "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2   gate kernel variants the tests compare bit for bit
@@ -83,6 +85,7 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "ln_resid") h->ln_resid = value != 0;
     else if (k == "gate_fuse_agg") h->gate_fuse_agg = value < 0 ? 0 : value > 2 ? 2 : value;
     else if (k == "flash_pv_terms") h->flash_pv_terms = value == 2 ? 2 : 3;
+    else if (k == "flash_exact") h->flash_exact = value < 0 ? -1 : value != 0;
     else if (k == "flash_bf16") h->flash_bf16 = value != 0;
     else if (k == "pointnet_bf16") h->pointnet_bf16 = value != 0;
     else if (k == "gate_bf16") h->gate_bf16 = value != 0;
@@ -257,6 +260,43 @@ int vlsat_k_flash_attn_bf16(const float* Q, const float* K, const float* V, floa
     int r = launch_flash_attn_bf16(Q, ld, K, V, ld, O, ld, static_cast<const int4*>(d.d), n, scale * 1.4426950408889634f, terms, use_tr != 0,
                                    use_tr == 2 ? 1 : use_tr == 3 ? 2 : 0, st, &sp);
     hipStreamSynchronize(st);     // test entry point only: the tile table is freed right away
+    return r;
+}
+
+// key_parts > 1: the split-key path on a table made here -- every tile key_parts times, part p of a scene of kt 32-key tiles covers
+// tiles [kt p / key_parts, kt (p + 1) / key_parts), empty parts included (more parts than tiles: a part without keys, and, where it
+// starts at an odd tile, one whose only 64-key tile is masked throughout)
+int vlsat_k_flash_attn_f16x3(const float* Q, const float* K, const float* V, float* O, int32_t ld, const int64_t* tok_ptr,
+                             int32_t n_scenes, int32_t n_heads, float scale, int32_t key_parts, int32_t use_tr, void* stream) {
+    if (key_parts < 1 || key_parts > 64) return fail(VLSAT_EINVAL, "flash_attn_f16x3: key_parts must be 1..64");
+    if (!tok_ptr || n_scenes <= 0) return fail(VLSAT_EINVAL, "flash_attn: bad scene table");
+    std::vector<PlanTile> tiles, split, krange;
+    for (int s = 0; s < n_scenes; ++s) append_tile_rows(tiles, tok_ptr[s], tok_ptr[s + 1] - tok_ptr[s], n_heads, FLASH_BQ);
+    if (tiles.empty()) return 0;
+    const int rows = (int)tok_ptr[n_scenes];
+    FlashSplit sp;
+    sp.rows = rows;
+    DevTable d, dk, dw;
+    if (key_parts > 1) {
+        for (const PlanTile& t : tiles) {
+            const int kt = (t.y + 31) / 32;
+            for (int p = 0; p < key_parts; ++p) {
+                split.push_back(t);
+                krange.push_back({(int)((int64_t)kt * p / key_parts), (int)((int64_t)kt * (p + 1) / key_parts), p, 0});
+            }
+        }
+        tiles.swap(split);
+        RUN(dk.put(krange.data(), krange.size() * sizeof(PlanTile)));
+        const size_t o_floats = (size_t)key_parts * rows * ld, ml_floats = (size_t)key_parts * rows * n_heads;
+        std::vector<float> zeros(o_floats + 2 * ml_floats, 0.f);
+        RUN(dw.put(zeros.data(), zeros.size() * sizeof(float)));
+        sp.parts = key_parts; sp.krange = static_cast<const int4*>(dk.d); sp.heads = n_heads; sp.part_stride = (size_t)rows * ld;
+        sp.o_part = static_cast<float*>(dw.d); sp.m_part = sp.o_part + o_floats; sp.l_part = sp.m_part + ml_floats;
+    }
+    RUN(d.put(tiles.data(), tiles.size() * sizeof(PlanTile)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int r = launch_flash_attn_f16x3(Q, ld, K, V, ld, O, ld, static_cast<const int4*>(d.d), (int)tiles.size(), scale * 1.4426950408889634f, use_tr, st, &sp);
+    hipStreamSynchronize(st);     // test entry point only: the tables are freed right away
     return r;
 }
 

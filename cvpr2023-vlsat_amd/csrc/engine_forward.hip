@@ -379,6 +379,7 @@ struct EdgeAttnFmt {
                      // never see this block, keep the split-bf16 accuracy; profiles/r05_probes/precision_mix_study.txt)
     int dh;          // head dim
     bool fa16;       // the bf16 attention kernel is built for this head dim and mode
+    bool x3;         // fp32 mode: the split-fp16 attention kernel (fp32 tensors, three f16 MFMAs per product) instead of the exact fp32 one
     int SA;          // format of Q / K|V / O: that of the chain with the bf16 attention kernel, else fp32
     bool ln_resid;   // the residual is added by the LayerNorm kernel, not by the out-projection
     bool o16;        // the out-projection writes fp16 half rows for the LayerNorm
@@ -391,6 +392,8 @@ EdgeAttnFmt edge_attn_fmt(const vlsat_ctx* h) {
     // (mode 4: the chain tensors are split pairs, but Q / K|V / O feed a single-rounded attention only -- they travel as half rows,
     //  which puts the attention on its LDS-direct kernel and the out-projection on the 8-phase one)
     f.SA = f.fa16 ? ((PA == 1 && S == 1 && h->half_fmt && dh == 64) ? 2 : S) : 0;
+    // fp32 mode: the split-fp16 attention kernel where its list has one (head dim 64); every other case keeps the exact fp32 kernel
+    f.x3 = h->prec == 0 && PA == 0 && h->flash_exact != 1 && flash_f16x3_supports(dh, h->flash_tr ? 1 : 0);
     // Split-pair mode: the residual is added by the LayerNorm kernel (as an accumulator init it made the out-projection 60 % slower
     // there -- 397 vs 243 us at the bench size -- against +1 KB per row in the LayerNorm).  Half rows: the same (the 8-phase GEMM has no
     // fast accumulator-init path).
@@ -424,6 +427,9 @@ int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAtt
     if (dh != 32 && dh != 64 && dh != 128)   // any other head dim: VALU attention over the scenes' edge ranges (no bias)
         return launch_node_attn(p->Qe, D, kve, 2 * D, kve + D, 2 * D, p->Oe, D, nullptr, p->d_edge_ptr32, nullptr, h->edge_scope == 1 ? 1 : p->S,
                                 h->edge_scope == 1 ? E : p->max_e, h->H, dh, 1.f / std::sqrt((float)dh), s, h->node_attn_split);
+    // fp32 mode at the shipped head dim: the products as three fp16 MFMAs each (split-fp16, 2^-22 per operand: fp32-grade results at the
+    // bf16 matrix rate), Q / K|V / O plain fp32 as for the exact kernel; "flash_exact" 1 keeps the exact fp32-MFMA kernel
+    if (f.x3) return launch_flash_attn_f16x3(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, h->flash_tr ? 1 : 0, s, &sp, dh);
     if (!f.fa16) return launch_flash_attn(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, s, &sp, dh);   // (head dims 32 / 128: NUM_HEADS 16 / 4)
     const bool big = SA == 2 && dh == 64 && p->n_tiles_big && h->flash_tr && h->flash_dma == 1 && h->flash_bq_big;
     if (big) sp.bq = FLASH_BQ_BIG;

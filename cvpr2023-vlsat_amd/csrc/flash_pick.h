@@ -2,6 +2,7 @@
 // the one function that picks among them.  No HIP header: tests/flash_pick_check.cpp compiles this with g++.  flash_bf16_pick works out
 // the ten template arguments a call asks for and looks them up, so what is not in the list is an error, never another kernel; the
 // kernel's static_asserts state the same rules on the device side, and a row that breaks them does not compile.
+// The split-fp16 form of the three-term kernel (flash_attn_f16x3_kernel) has a list and a pick function of its own at the end.
 #pragma once
 
 namespace vlsat {
@@ -103,5 +104,35 @@ inline FlashPick flash_bf16_pick(int d, int terms, int use_tr, int io, int pv_te
 inline bool flash_attn_bf16_supports(int head_dim, int terms, int use_tr, int io_split) {
     return flash_bf16_pick(head_dim, terms, use_tr, io_split).index >= 0;
 }
+
+// ---- the split-fp16 form of the three-term kernel (flash_attn_f16x3_kernel, flash_attn_bf16.hip): the edge attention of the fp32
+// precision mode.  fp32 tensors in and out, every operand carried as fp16 hi + fp16 lo (2^-22), three f16 MFMAs per product,
+// register-staged K / V, split keys supported.  A list and a pick function of its own: the bf16 list above and flash_bf16_pick stay
+// what tests/flash_pick_check.cpp pins them to.  Y(TR, FB_D), one row per instantiation: the transpose read, and the gather form
+// the tests hold it against.
+#define VLSAT_FLASH_F16X3_VARIANTS(Y) Y(true, 64) Y(false, 64)
+
+struct FlashF16x3Variant {
+    bool tr; int d;
+    constexpr bool operator==(const FlashF16x3Variant& o) const { return tr == o.tr && d == o.d; }
+};
+#define VLSAT_FLASH_F16X3_ROW(R, D) {R, D},
+constexpr FlashF16x3Variant kFlashF16x3Variants[] = {VLSAT_FLASH_F16X3_VARIANTS(VLSAT_FLASH_F16X3_ROW)};
+#undef VLSAT_FLASH_F16X3_ROW
+constexpr int kFlashF16x3VariantCount = (int)(sizeof kFlashF16x3Variants / sizeof kFlashF16x3Variants[0]);
+
+// The split-fp16 kernel for head dim d; use_tr 0 gather | 1 transpose read; io 0 (fp32 tensors: the only format); bq, qg, ablate as in
+// FlashSplit (128-query tiles, 32 queries per wave, no timing ablation: the only forms).  Split keys need no row of their own.  What
+// is not in the list is an error, never another kernel.
+inline FlashPick flash_f16x3_pick(int d, int use_tr, int io = 0, int bq = FLASH_BQ, int qg = 0, int ablate = 0) {
+    if (io != 0) return {-1, "flash_attn_f16x3: built for fp32 tensors only"};
+    if (use_tr != 0 && use_tr != 1) return {-1, "flash_attn_f16x3: use_tr must be 0 (gather) or 1 (transpose read)"};
+    if (bq != FLASH_BQ || qg != 0) return {-1, "flash_attn_f16x3: built for 128-query tiles with 32 queries per wave only"};
+    if (ablate != 0) return {-1, "flash_attn_f16x3: no timing ablations are built"};
+    for (int i = 0; i < kFlashF16x3VariantCount; ++i)
+        if (kFlashF16x3Variants[i] == FlashF16x3Variant{use_tr == 1, d}) return {i, nullptr};
+    return {-1, "flash_attn_f16x3: head dim not built"};
+}
+inline bool flash_f16x3_supports(int head_dim, int use_tr) { return flash_f16x3_pick(head_dim, use_tr).index >= 0; }
 
 }  // namespace vlsat

@@ -61,6 +61,13 @@ int launch_flash_merge(float* O, int ldo, const FlashSplit& sp, hipStream_t s, i
 int launch_flash_attn_bf16(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
                            const int4* tiles, int n_tiles, float scale_log2e, int terms, int use_tr, int io_split,
                            hipStream_t s, const FlashSplit* split = nullptr, int pv_terms = 3, int head_dim = 64);
+// the split-fp16 form of the three-term kernel (flash_attn_bf16.hip; the edge attention of the fp32 precision mode): plain fp32 Q, K,
+// V, O, every operand as fp16 hi + fp16 lo (2^-22), three f16 MFMAs per product, fp32 accumulate and softmax.  Domain: |Q * scale_log2e|,
+// |K| < 65504, |V| < 65504 / 2^3 (V is pre-scaled by 2^3; clamped there).  use_tr 0 | 1 as above; split keys as above.  Its kernels and
+// what a call gets: flash_f16x3_pick of flash_pick.h; what is not in that list is an error.
+int launch_flash_attn_f16x3(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
+                            const int4* tiles, int n_tiles, float scale_log2e, int use_tr, hipStream_t s,
+                            const FlashSplit* split = nullptr, int head_dim = 64);
 
 // ---- node attention with distance bias (per scene, per head) ----
 // scene_ptr: device [n_scenes+1] node offsets; bias_ptr: device [n_scenes] offsets into bias

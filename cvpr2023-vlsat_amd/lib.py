@@ -15,6 +15,7 @@ import torch  # noqa: F401  (maps libamdhip64 before our library is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlsat_hip.so")
+_IN_TREE_LIB_PATH = LIB_PATH
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
 SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
 CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
@@ -22,6 +23,7 @@ SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_seg
 CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud.h")
 VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel.h")
 OBJECTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_objects.h")
+FLASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_flash.h")
 
 
 class VlsatDims(C.Structure):
@@ -164,6 +166,11 @@ _SIGNATURES_VOXEL = {
     "vlsat_voxel_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_flash.h: the split-fp16 edge attention of the fp32 precision mode on its own (csrc/flash_attn_bf16.hip)
+_SIGNATURES_FLASH = {
+    "vlsat_k_flash_attn_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _i32, _vp]),
+}
+
 # include/vlsat_objects.h: a cloud segmented into objects -- structural planes found and removed, the rest clustered (csrc/objects.hip)
 _SIGNATURES_OBJECTS = {
     "vlsat_cloud_planes_scratch_bytes": (_sz, [_i64, _i32]),
@@ -186,7 +193,7 @@ def identity(lib_path: str = "") -> dict:
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
-                                          OBJECTS_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -235,6 +242,11 @@ def declared_objects_symbols() -> list:
     return _declared(OBJECTS_HEADER_PATH)
 
 
+def declared_flash_symbols() -> list:
+    """Every function include/vlsat_flash.h declares."""
+    return _declared(FLASH_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -245,7 +257,9 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()):
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()):
+        if name in _SIGNATURES_FLASH and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
+            continue          # another build, loaded for a same-box A/B (bench.py --lib), may predate this test entry point: calling it is then an AttributeError
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

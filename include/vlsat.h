@@ -139,7 +139,11 @@ int vlsat_forward_train(vlsat_handle h, vlsat_plan p,
 
 
 /* Operand precision of the matrix kernels inside vlsat_forward (BASELINE configs[2], "bf16 MFMA for the
- * QKV/FFN GEMMs"): 0 = exact fp32 MFMA (default; BASELINE configs[1]); 3 = split-bf16 (a_hi.w_hi + a_lo.w_hi +
+ * QKV/FFN GEMMs"): 0 = fp32 (default; BASELINE configs[1]): fp32 MFMA on every GEMM, the gate and the encoders; the edge
+ * cross-attention's products (head dim 64) as three fp16 MFMAs each (operands split into fp16 hi + lo, 2^-22), fp32 accumulate and
+ * softmax -- 1.1 to 2 times the exact kernel's error, far inside 1e-4 on the outputs; domain |Q / sqrt(d_k) * log2 e|, |K| < 65504 and, V
+ * being multiplied by 2^3 before the split, |V| < 65504 / 8 = 8188 (values beyond are clamped there);
+ * vlsat_debug_option "flash_exact" 1 restores the exact fp32-MFMA attention kernel; 3 = split-bf16 (a_hi.w_hi + a_lo.w_hi +
  * a_hi.w_lo on v_mfma_f32_32x32x16_bf16, fp32 accumulate, ~1e-5 error); 1 = single-rounded bf16 operands
  * everywhere (~2e-2 on the x14.29 object logits: outside the config's 1e-2); 2 = mixed: single-rounded bf16 on the
  * edge-row GEMMs / attention / gate and split-bf16 on the node-row GEMMs (meets 1e-2 at Xavier-scale weights);
@@ -759,6 +763,9 @@ int vlsat_debug_gemm_clock_probe(int64_t* buf);
  *                         LayerNorm as fp16 half rows instead of fp32 (-1 = default: on);
  *   "split_fmt", "flash_bf16", "flash_tr", "pointnet_bf16", "gate_bf16", "ln_resid" 0|1   bf16 modes: tensor formats and kernels (0: the
  *                         fp32 forms) -- every one parity-tested both ways (tests/test_hip_forward.py);
+ *   "flash_exact" -1|0|1  fp32 mode at head dim 64: the edge cross-attention's products as three fp16 MFMAs each (-1 = default, 0), or the
+ *                         exact fp32-MFMA kernel (1): the forward of the releases before the split-fp16 kernel, bit for bit, without its
+ *                         operand domain (|Q / sqrt(d_k) * log2 e|, |K| < 65504, |V| < 8188);
  *   "flash_bq_big" 0|1    half-row edge attention, plans whose scenes all have >= 4096 edges: 256 queries per block (default) or 128;
  *   "flash_bq_big_min" n  ... that bound (plans created afterwards).  At the bench batch (1560 edges per scene) 256-query tiles are 1 %
  *                         slower per step than 128-query ones (profiles/r06_probes/ab_flash_bq_big_min.txt): the default stays 4096;
