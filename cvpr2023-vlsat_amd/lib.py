@@ -24,6 +24,7 @@ CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud
 VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel.h")
 OBJECTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_objects.h")
 FLASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_flash.h")
+CONVEX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_convex.h")
 
 
 class VlsatDims(C.Structure):
@@ -179,6 +180,12 @@ _SIGNATURES_OBJECTS = {
     "vlsat_cloud_clusters": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_convex.h: clusters cut at concave junctions, for bodies that touch (csrc/convex.hip)
+_SIGNATURES_CONVEX = {
+    "vlsat_convex_clusters_scratch_bytes": (_sz, [_i64]),
+    "vlsat_convex_clusters": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -193,7 +200,7 @@ def identity(lib_path: str = "") -> dict:
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
-                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, CONVEX_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -247,6 +254,11 @@ def declared_flash_symbols() -> list:
     return _declared(FLASH_HEADER_PATH)
 
 
+def declared_convex_symbols() -> list:
+    """Every function include/vlsat_convex.h declares."""
+    return _declared(CONVEX_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -257,9 +269,9 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()):
-        if name in _SIGNATURES_FLASH and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
-            continue          # another build, loaded for a same-box A/B (bench.py --lib), may predate this test entry point: calling it is then an AttributeError
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()) + list(_SIGNATURES_CONVEX.items()):
+        if (name in _SIGNATURES_FLASH or name in _SIGNATURES_CONVEX) and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
+            continue          # another build, loaded for a same-box A/B (bench.py --lib), may predate these entry points: calling one is then an AttributeError
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

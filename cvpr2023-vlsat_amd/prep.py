@@ -1318,3 +1318,152 @@ def cloud_clusters(knn_index, knn_sqdist, mask, max_sq_dist: float, min_points: 
     L.check(lib.vlsat_cloud_clusters(index.data_ptr(), sqdist.data_ptr(), mask.data_ptr(), v, k, float(max_sq_dist), int(min_points),
                                      scratch.data_ptr(), labels.data_ptr(), n_clusters.data_ptr(), cluster_size.data_ptr(), L.stream_ptr()))
     return CloudClusters(labels, n_clusters, cluster_size)
+
+
+# ---- convexity-aware clusters: bodies that touch are cut at their concave junctions (csrc/convex.hip; include/vlsat_convex.h states the rule) ----
+CONVEX_MAX_ROUNDS = 64
+
+
+class ConvexClusters(NamedTuple):
+    """``convex_clusters``: ``labels`` int32 [V] (0 = none, else 1..S by lowest core point), ``n_clusters`` int32 [1], ``cluster_size``
+    int32 [V] (entry s - 1 counts ALL final members of cluster s, zeros past S), ``state`` int32 [V]: 0 not eligible, 1 core of a kept
+    component, 2 boundary (concave evidence), 3 eligible without a usable normal, 4 core of a dissolved component."""
+    labels: object
+    n_clusters: object
+    cluster_size: object
+    state: object
+
+
+def _convex_args(points_shape, normals_shape, index_shape, sqdist_shape, mask_shape, link_sq_dist, concavity, min_points, absorb_rounds):
+    """-> concavity as np.float32; raises on anything the rule refuses"""
+    import math
+
+    import numpy as np
+    if len(index_shape) != 2 or not 1 <= index_shape[0] <= SEG_MAX_VERTS or not 1 <= index_shape[1] <= CLOUD_MAX_K:
+        raise L.VlsatError("convex_clusters: knn_index must be int32 [V,K] with 1 <= V <= 2^24 and 1 <= K <= 32")
+    if tuple(points_shape) != (index_shape[0], 3) or tuple(normals_shape) != (index_shape[0], 3):
+        raise L.VlsatError("convex_clusters: points and normals must be float32 [V,3]")
+    if tuple(sqdist_shape) != tuple(index_shape):
+        raise L.VlsatError("convex_clusters: knn_sqdist must be float32 [V,K], the shape of knn_index")
+    if tuple(mask_shape) != (index_shape[0],):
+        raise L.VlsatError("convex_clusters: mask must be int32 [V]")
+    if math.isnan(float(link_sq_dist)):
+        raise L.VlsatError("convex_clusters: link_sq_dist is NaN")
+    tau = np.float32(concavity)
+    if not (tau >= 0 and tau <= 1):
+        raise L.VlsatError("convex_clusters: concavity must be in [0, 1] (the sine of the tolerated concave angle)")
+    if not 1 <= int(min_points) < 1 << 31:
+        raise L.VlsatError("convex_clusters: min_points must be at least 1")
+    if not 0 <= int(absorb_rounds) <= CONVEX_MAX_ROUNDS:
+        raise L.VlsatError("convex_clusters: absorb_rounds must be in 0 .. 64")
+    return tau
+
+
+def convex_evidence_host(xi, ni, xj, nj, sqdist, concavity):
+    """Rule 2 of include/vlsat_convex.h on arrays of float32 rows [n,3] (convex_c and convex_concave of csrc/convex_core.h, the same
+    operations in the same order, each rounded to fp32) -> (c f32 [n], concave bool [n]).  Whether an entry COUNTS is the caller's."""
+    import numpy as np
+    xi, ni, xj, nj = (np.asarray(x, dtype=np.float32) for x in (xi, ni, xj, nj))
+    q, tau = np.asarray(sqdist, dtype=np.float32), np.float32(concavity)
+    with np.errstate(all="ignore"):
+        d = xj - xi
+        a = (ni[:, 0] * d[:, 0] + ni[:, 1] * d[:, 1]) + ni[:, 2] * d[:, 2]
+        b = (nj[:, 0] * d[:, 0] + nj[:, 1] * d[:, 1]) + nj[:, 2] * d[:, 2]
+        c = a - b
+        concave = (c > 0) & (c * c > (tau * tau) * q)
+    return c, concave
+
+
+def convex_clusters_host(points, normals, knn_index, knn_sqdist, mask, link_sq_dist: float, concavity: float, min_points: int = 1,
+                         absorb_rounds: int = 8) -> ConvexClusters:
+    """The rule of include/vlsat_convex.h in numpy, the same operations in the same order (float32 throughout the predicate) ->
+    ``ConvexClusters`` of numpy arrays, equal to the device's bit for bit: the concave table entries mark both their ends as boundary,
+    the remaining oriented points are united along the entries within ``link_sq_dist`` (``_seg_unite``), components below
+    ``min_points`` are dissolved, and in ``absorb_rounds`` synchronous rounds every unlabelled eligible point takes the label of the
+    first labelled entry of its row."""
+    import numpy as np
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+    n = np.ascontiguousarray(np.asarray(normals, dtype=np.float32))
+    nbr = np.asarray(knn_index).astype(np.int64)
+    q = np.asarray(knn_sqdist, dtype=np.float32)
+    m = np.asarray(mask) != 0
+    tau = _convex_args(p.shape, n.shape, nbr.shape, q.shape, m.shape, link_sq_dist, concavity, min_points, absorb_rounds)
+    v, k = nbr.shape
+    rows = np.arange(v, dtype=np.int64)
+    eligible = m & np.isfinite(p).all(1)
+    oriented = eligible & np.isfinite(n).all(1) & (n != 0).any(1)
+    i, j = np.repeat(rows, k), nbr.reshape(-1)
+    valid = (j >= 0) & (j < v) & (j != i)                                              # an entry that names another point
+    js = np.where(valid, j, 0)
+    qf = q.reshape(-1)
+    with np.errstate(invalid="ignore"):
+        counts = valid & oriented[i] & oriented[js] & np.isfinite(qf) & (qf >= 0)
+    _, concave = convex_evidence_host(p[i], n[i], p[js], n[js], qf, tau)
+    concave &= counts
+    boundary = np.zeros(v, dtype=bool)
+    boundary[i[concave]] = True
+    boundary[js[concave]] = True
+    core = oriented & ~boundary
+    with np.errstate(invalid="ignore"):
+        link = valid & core[i] & core[js] & (qf <= np.float32(link_sq_dist))
+    parent = _seg_unite(rows.copy(), i[link], js[link])
+    size = np.bincount(parent[core], minlength=v)
+    kept = core & (parent == rows) & (size >= int(min_points))
+    label = np.where(core & (size[parent] >= int(min_points)), parent, -1)             # the root, until the numbering
+    state = np.select([~eligible, boundary, ~oriented, label < 0], [0, 2, 3, 4], 1).astype(np.int32)
+    valid2, js2 = valid.reshape(v, k), js.reshape(v, k)
+    for _ in range(int(absorb_rounds)):
+        wait = np.nonzero(eligible & (label < 0))[0]
+        if not len(wait):
+            break
+        seen = np.where(valid2[wait], label[js2[wait]], -1)                           # the labels at the end of the round before
+        has = seen >= 0
+        first = np.argmax(has, axis=1)
+        take = has.any(1)
+        if not take.any():
+            break                                                                      # nothing can change in a later round either
+        new = label.copy()
+        new[wait[take]] = seen[take, first[take]]
+        label = new
+    num = np.where(kept, np.cumsum(kept), 0)
+    labels = np.where(label >= 0, num[np.maximum(label, 0)], 0).astype(np.int32)
+    s = int(kept.sum())
+    cluster_size = np.zeros(v, dtype=np.int32)
+    cluster_size[:s] = np.bincount(labels[labels > 0] - 1, minlength=s)[:s]
+    return ConvexClusters(labels, np.asarray([s], dtype=np.int32), cluster_size, state)
+
+
+def convex_clusters(points, normals, knn_index, knn_sqdist, mask, link_sq_dist: float, concavity: float, min_points: int = 1,
+                    absorb_rounds: int = 8) -> ConvexClusters:
+    """points and ORIENTED normals f32 [V,3], the table of ``knn_points`` and a mask int32 [V] -> ``ConvexClusters``: clusters that are
+    cut where two bodies meet in a CONCAVE junction (include/vlsat_convex.h, vlsat_convex_clusters; the local-convexity criterion of
+    Stein et al., CVPR 2014).  A table entry is concave when c = n_i . d - n_j . d > 0 for d = x_j - x_i and c^2 > ``concavity``^2 x
+    its squared distance -- ``concavity`` is the sine of the tolerated concave angle.  Both ends of a concave entry are eroded; the
+    remaining oriented points are clustered along the entries within ``link_sq_dist`` (a SQUARED distance), components of fewer than
+    ``min_points`` are dissolved, and in ``absorb_rounds`` (0 .. 64) rounds every unlabelled point takes the label of the first labelled
+    entry of its row, all points at once.  Device tensors run the HIP kernels (8 + ``absorb_rounds`` launches, nothing read back); CPU
+    tensors or arrays run ``convex_clusters_host`` and get CPU tensors, with equal bits."""
+    if not (isinstance(knn_index, torch.Tensor) and knn_index.is_cuda):
+        as_np = lambda x: x.numpy() if isinstance(x, torch.Tensor) else x   # noqa: E731
+        out = convex_clusters_host(as_np(points), as_np(normals), as_np(knn_index), as_np(knn_sqdist), as_np(mask), link_sq_dist, concavity,
+                                   min_points, absorb_rounds)
+        return ConvexClusters(*(torch.from_numpy(x) for x in out))
+    lib = L.load()
+    tau = _convex_args(points.shape, normals.shape, knn_index.shape, knn_sqdist.shape, mask.shape, link_sq_dist, concavity, min_points,
+                       absorb_rounds)
+    dev = knn_index.device
+    points = points.to(device=dev, dtype=torch.float32).contiguous()
+    normals = normals.to(device=dev, dtype=torch.float32).contiguous()
+    index = knn_index.to(dtype=torch.int32).contiguous()
+    sqdist = knn_sqdist.to(device=dev, dtype=torch.float32).contiguous()
+    mask = (mask.to(device=dev) != 0).to(torch.int32).contiguous()
+    v, k = index.shape
+    scratch = torch.empty(int(lib.vlsat_convex_clusters_scratch_bytes(v)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(v, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
+    cluster_size = torch.empty(v, dtype=torch.int32, device=dev)
+    state = torch.empty(v, dtype=torch.int32, device=dev)
+    L.check(lib.vlsat_convex_clusters(points.data_ptr(), normals.data_ptr(), index.data_ptr(), sqdist.data_ptr(), mask.data_ptr(), v, k,
+                                      float(link_sq_dist), float(tau), int(min_points), int(absorb_rounds), scratch.data_ptr(),
+                                      labels.data_ptr(), n_clusters.data_ptr(), cluster_size.data_ptr(), state.data_ptr(), L.stream_ptr()))
+    return ConvexClusters(labels, n_clusters, cluster_size, state)

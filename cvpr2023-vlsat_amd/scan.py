@@ -821,7 +821,9 @@ def downsample_cloud(cloud_or_path, voxel: float, origin=(0.0, 0.0, 0.0), min_co
 
 def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 16, n_hyp: int = 1024, max_planes: int = 8,
                     min_plane_share: float = 0.02, outside_frac: float = 0.01, min_points: int = 50, voxel: Optional[float] = None,
-                    seed: int = 0, device="cuda:0") -> Dict[str, Optional[np.ndarray]]:
+                    seed: int = 0, device="cuda:0", concavity_deg: Optional[float] = None, viewpoint=None,
+                    normal_radius: Optional[float] = None, absorb_rounds: int = 8,
+                    recompute_normals: bool = False) -> Dict[str, Optional[np.ndarray]]:
     """A point cloud segmented into OBJECT-level instances on the device, without a trained model: -> a copy of the dict with
     ``instances`` (int64 [V]: the structural planes are 1..P, the clusters P+1..P+S, 0 = dropped), ``n_planes`` = P, ``planes`` f32
     [P,4] = (nx, ny, nz, d), ``n_segments`` = P + S and ``seg_size`` int32 [P + S] filled.  ``cloud_or_path``: a PLY path
@@ -844,7 +846,19 @@ def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 
 
     Objects that touch -- closer than ``cluster_radius`` -- come out as ONE cluster, and an object standing against a wall loses the
     points within ``dist`` of it to the wall.  Every default is a starting value, not a tuned operating point: no scan data and no
-    checkpoint is available to this project, so accuracy on real scans is unmeasured."""
+    checkpoint is available to this project, so accuracy on real scans is unmeasured.
+
+    ``concavity_deg`` (default None: nothing changes, the same calls and the same outputs): the points no plane took are clustered by
+    LOCAL CONVEXITY instead (``prep.convex_clusters``; include/vlsat_convex.h states the rule), which cuts bodies that touch where their
+    surfaces meet in a concave junction -- a box on a table, a cupboard against a desk.  One table ``prep.knn_points(rest, k,
+    normal_radius^2)`` serves the normals and the clusters, ``normal_radius`` defaulting to 2 x ``cluster_radius``; the link distance
+    stays ``cluster_radius`` and the tolerance is sin(``concavity_deg``): 10 is a start.  Convexity needs ORIENTED normals: the ones the
+    cloud carries are taken (normalised in fp32) unless there are none or ``recompute_normals``; then they are estimated over that
+    table and turned towards ``viewpoint`` (x, y, z) (``prep.cloud_normals``).  With neither, ``ScanError``.  A point that lost its
+    place at a concave junction is handed to the nearest cluster within ``absorb_rounds`` rings.  The result also carries ``concave``
+    bool [V]: the points that showed concave evidence.  What this does NOT do: one viewpoint orients only the surfaces seen from it;
+    bodies whose faces are coplanar and closer than ``cluster_radius`` can still merge; a patch of surface enclosed by concave
+    junctions becomes a cluster of its own."""
     import math
 
     import torch
@@ -854,16 +868,32 @@ def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 
     cloud = dict(read_mesh(cloud_or_path) if isinstance(cloud_or_path, (str, os.PathLike)) else cloud_or_path)
     if voxel is not None:
         small = segment_objects(downsample_cloud(cloud, voxel, device=device), dist, cluster_radius, k, n_hyp, max_planes, min_plane_share,
-                                outside_frac, min_points, None, seed, device)
+                                outside_frac, min_points, None, seed, device, concavity_deg, viewpoint, normal_radius, absorb_rounds,
+                                recompute_normals)
         of = small["voxel_of_point"].astype(np.int64)
         cloud["instances"] = np.where(of >= 0, small["instances"][np.maximum(of, 0)], 0).astype(np.int64)
         cloud["n_planes"], cloud["planes"], cloud["n_segments"] = small["n_planes"], small["planes"], small["n_segments"]
         cloud["seg_size"] = np.bincount(cloud["instances"][cloud["instances"] > 0] - 1, minlength=small["n_segments"]).astype(np.int32)
         cloud["resampled"] = small
+        if concavity_deg is not None:
+            cloud["concave"] = (of >= 0) & small["concave"][np.maximum(of, 0)]
         return cloud
     pts = np.ascontiguousarray(np.asarray(cloud["points"])[:, :3], dtype=np.float32)
     if not 3 <= len(pts) <= prep.SEG_MAX_VERTS:
         raise ScanError("segment_objects: 3 .. 2^24 points")
+    given = None
+    if concavity_deg is not None:
+        if not 0.0 <= float(concavity_deg) <= 90.0:
+            raise ScanError("segment_objects: concavity_deg must be in [0, 90]")
+        if normal_radius is not None and not float(normal_radius) >= 0.0:
+            raise ScanError("segment_objects: normal_radius must be >= 0")
+        given = None if recompute_normals else cloud.get("normals")
+        if given is None and viewpoint is None:
+            raise ScanError("segment_objects: convexity needs a side -- normals the cloud carries, or a viewpoint to turn estimated ones to")
+        if given is not None:
+            given = np.ascontiguousarray(np.asarray(given)[:, :3], dtype=np.float32)
+            if len(given) != len(pts):
+                raise ScanError("segment_objects: one normal per point")
     if not float(cluster_radius) >= 0.0:
         raise ScanError("segment_objects: cluster_radius must be >= 0")
     if not (0.0 < float(min_plane_share) <= 1.0 and 0.0 <= float(outside_frac) <= 0.5):
@@ -884,7 +914,29 @@ def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 
     rest = np.nonzero((plane_id == 0) & np.isfinite(pts).all(1))[0]
     sizes = [found.counts[:n_planes, 0].cpu().numpy().astype(np.int32)]
     n_clusters = 0
-    if len(rest):
+    if len(rest) and concavity_deg is not None:
+        d_rest = d_pts[torch.from_numpy(rest).to(d_pts.device)]
+        reach = 2.0 * float(cluster_radius) if normal_radius is None else float(normal_radius)
+        table = prep.knn_points(d_rest, k, float(np.float32(reach) ** 2))
+        if given is None:
+            normals = prep.cloud_normals(d_rest, table.index, table.count, viewpoint=viewpoint)[0]
+        else:
+            with np.errstate(all="ignore"):
+                g = given[rest]
+                normals = torch.from_numpy(g / np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])[:, None]).to(d_pts.device)
+        mask = torch.ones(len(rest), dtype=torch.int32, device=d_pts.device)
+        try:
+            grown = prep.convex_clusters(d_rest, normals, table.index, table.sqdist, mask, max_sq_dist,
+                                         float(np.float32(math.sin(math.radians(float(concavity_deg))))), min_points, absorb_rounds)
+        except prep.L.VlsatError as e:
+            raise ScanError(f"segment_objects: {e}") from e
+        n_clusters = int(grown.n_clusters.reshape(-1)[0])
+        labels = grown.labels.cpu().numpy().astype(np.int64)
+        instances[rest] = np.where(labels > 0, labels + n_planes, 0)
+        sizes.append(grown.cluster_size[:n_clusters].cpu().numpy().astype(np.int32))
+        cloud["concave"] = np.zeros(len(pts), dtype=bool)
+        cloud["concave"][rest] = grown.state.cpu().numpy() == 2
+    elif len(rest):
         d_rest = d_pts[torch.from_numpy(rest).to(d_pts.device)]
         table = prep.knn_points(d_rest, k, max_sq_dist)
         mask = torch.ones(len(rest), dtype=torch.int32, device=d_pts.device)
@@ -893,6 +945,8 @@ def segment_objects(cloud_or_path, dist: float, cluster_radius: float, k: int = 
         labels = grown.labels.cpu().numpy().astype(np.int64)
         instances[rest] = np.where(labels > 0, labels + n_planes, 0)
         sizes.append(grown.cluster_size[:n_clusters].cpu().numpy().astype(np.int32))
+    if concavity_deg is not None and not len(rest):
+        cloud["concave"] = np.zeros(len(pts), dtype=bool)
     cloud["instances"] = instances
     cloud["n_planes"] = n_planes
     cloud["planes"] = found.planes[:n_planes].cpu().numpy()

@@ -299,3 +299,48 @@ def make_walled_room(n_obj: int, step: float, seed: int, height: float = 2.0, ex
     return {"points": np.concatenate(pts), "instances": instances, "plane": np.concatenate(plane),
             "structural": (instances == 1) | (instances >= n_obj + 2), "n_obj": int(n_obj), "step": step, "height": nz * step,
             "extent": (nx * step, ny * step)}
+
+
+STACKED_BOXES = (((0.0, 0.0, 0.0), (1.0, 1.0, 0.5)), ((0.3, 0.3, 0.5), (0.6, 0.6, 0.8)), ((1.0, 0.2, 0.0), (1.4, 0.6, 0.3)),
+                 ((0.05, 0.62, 0.5), (0.35, 0.92, 0.7)), ((0.35, 0.62, 0.5), (0.55, 0.9, 0.95)))
+
+
+def make_stacked_boxes(step: float = 0.02, jitter: float = 0.0008, seed: int = 0, viewpoint=(3.0, -2.5, 2.5)) -> dict:
+    """Bodies that TOUCH, as one scan sees them, for the convexity clusters: a table (box 0), three boxes standing on it -- boxes 3 and 4
+    touch each other and their fronts y = 0.62 are coplanar -- and a lower box against the table's side (``STACKED_BOXES``, (lo, hi) in
+    metres at ``step`` = 0.02; another ``step`` scales the boxes by step / 0.02, so the number of points does not change; ``jitter``
+    and ``viewpoint`` are taken as given).  Of every box only the faces whose outward normal faces ``viewpoint`` (from the face's
+    centre) are sampled, on a grid of ``step`` that starts at the box's lower corner -- an extent that is no whole number of steps
+    (box 4 is 22.5 high) leaves the last half step empty -- so an edge between two visible faces is sampled once by each, with that
+    face's normal.  Every point inside or on ANOTHER box (closed, widened by 1e-6) is removed: a scan has no hidden surfaces.
+    ``jitter`` > 0 then adds that many standard normals to every coordinate.
+    -> {"points": f64 [V,3], "normals": f64 [V,3] (the exact face normals), "instances": i64 [V] (1 + box), "viewpoint": (x, y, z)};
+    box by box, face by face in the order -x, +x, -y, +y, -z, +z."""
+    g = np.random.default_rng([int(seed) & 0x7FFFFFFF, 0x57AC4ED])
+    step = float(step)
+    view = np.asarray([float(x) for x in viewpoint], dtype=np.float64)
+    boxes = [(np.asarray(lo) * (step / 0.02), np.asarray(hi) * (step / 0.02)) for lo, hi in STACKED_BOXES]
+    pts, nrm, inst = [], [], []
+    for b, (lo, hi) in enumerate(boxes):
+        grid = [lo[a] + step * np.arange(int(np.floor((hi[a] - lo[a]) / step + 1e-6)) + 1) for a in range(3)]
+        for axis in range(3):
+            for sign, end in ((-1.0, lo[axis]), (1.0, hi[axis])):
+                if sign * (view[axis] - end) <= 0.0:
+                    continue
+                u, v = (a for a in range(3) if a != axis)
+                uu, vv = (x.ravel() for x in np.meshgrid(grid[u], grid[v], indexing="ij"))
+                p = np.zeros((uu.size, 3))
+                p[:, axis], p[:, u], p[:, v] = end, uu, vv
+                n = np.zeros((uu.size, 3))
+                n[:, axis] = sign
+                pts.append(p)
+                nrm.append(n)
+                inst.append(np.full(uu.size, 1 + b, np.int64))
+    points, normals, instances = np.concatenate(pts), np.concatenate(nrm), np.concatenate(inst)
+    keep = np.ones(len(points), dtype=bool)
+    for b, (lo, hi) in enumerate(boxes):
+        keep &= ~(((points >= lo - 1e-6) & (points <= hi + 1e-6)).all(1) & (instances != 1 + b))
+    points = points[keep]
+    if jitter > 0:
+        points = points + float(jitter) * g.standard_normal(points.shape)
+    return {"points": points, "normals": normals[keep], "instances": instances[keep], "viewpoint": tuple(float(x) for x in view)}
