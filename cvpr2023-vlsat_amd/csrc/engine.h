@@ -155,6 +155,7 @@ struct vlsat_ctx {
     int flash_ablate = 0;                    // timing experiments on the bf16 edge attention (FlashSplit::ablate; results are garbage)
     int flash_pv_terms = 3;                  // split-bf16 edge attention: MFMAs per P.V product (3, or 2 = probabilities single-rounded)
     int flash_exact = -1;                    // fp32 mode, head dim 64: -1 / 0 the split-fp16 edge attention (three f16 MFMAs per product), 1 the exact fp32-MFMA kernel (debug option "flash_exact")
+    int gemm_exact = -1;                     // fp32 mode: -1 / 0 the large edge-row launches on the split-fp16 8-phase kernel (GemmArgs::f16s), 1 the exact fp32-MFMA kernels (debug option "gemm_exact")
     int ln_resid = 1;                        // split-pair mode: post-attention residual added in the LayerNorm kernel
     int half_fmt = 1;                        // single-rounding modes: those tensors as plain bf16 (half rows) instead of split pairs
     int split_fmt = 1;                       // bf16 modes: edge tensors between matrix kernels in the split-pair format
@@ -170,6 +171,8 @@ struct vlsat_ctx {
                              // mode 4 = split-bf16 with a single-rounded edge attention (1)
     std::map<const float*, std::pair<uint16_t*, uint16_t*>> split;
     std::map<const float*, uint16_t*> f16w;        // fp16 planes of the same matrices (made when mode 5 is set)
+    struct F16sPlanes { uint16_t *hi, *lo; int k; };
+    std::map<const float*, F16sPlanes> f16s;       // split-fp16 planes and exponent of the same matrices (gemm_f16s_planes.h; made when the mode is 0)
     // workspace arenas of destroyed plans, re-used by the next plan that fits (an eval loop may build one plan per
     // scene; hipMalloc/hipFree per scene would dominate small scenes), pinned upload buffers, spare events
     std::vector<vlsat::Arena> arena_pool;

@@ -55,6 +55,8 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //   "flash_pv_terms" 3|2   split-bf16 edge attention: MFMAs per P.V product
 //   "flash_exact" -1|0|1   fp32 mode, head dim 64: the edge attention's products as three fp16 MFMAs each (-1 default, 0) or the exact
 //                       fp32-MFMA kernel (1: the forward of the releases before the split-fp16 kernel, bit for bit)
+//   "gemm_exact" -1|0|1    fp32 mode: the full rounds of the large edge-row GEMM launches as three fp16 MFMAs per product (-1 default, 0;
+//                       gemm_p8s_kernel) or on the exact fp32-MFMA kernel (1; with "flash_exact" 1: the forward of the releases before, bit for bit)
 //   "flash_bq_big" 0|1   half-row edge attention on plans whose scenes all have >= 4096 edges: 256 queries per block (1, default) or 128
 //   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes (default) / fp32 too
 //   "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2   gate kernel variants the tests compare bit for bit
@@ -86,6 +88,7 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "gate_fuse_agg") h->gate_fuse_agg = value < 0 ? 0 : value > 2 ? 2 : value;
     else if (k == "flash_pv_terms") h->flash_pv_terms = value == 2 ? 2 : 3;
     else if (k == "flash_exact") h->flash_exact = value < 0 ? -1 : value != 0;
+    else if (k == "gemm_exact") h->gemm_exact = value < 0 ? -1 : value != 0;
     else if (k == "flash_bf16") h->flash_bf16 = value != 0;
     else if (k == "pointnet_bf16") h->pointnet_bf16 = value != 0;
     else if (k == "gate_bf16") h->gate_bf16 = value != 0;
@@ -199,6 +202,52 @@ int vlsat_k_gemm_bf16(const float* A, int32_t lda, const float* W, int32_t ldw, 
     int r = launch_split_bf16(W, n, hi, lo, st);
     if (!r) r = vlsat_k_gemm_planes(A, lda, W, hi, lo, ldw, C, ldc, M, N, K, bias, resid, ldr, resid_scale, g0, gi0, ldg0, g1, gi1,
                                     ldg1, relu_a, act, prec, no_dma, -1, 0, 1.f, stream);
+    hipStreamSynchronize(st);
+    hipFree(hi);
+    hipFree(lo);
+    return r;
+}
+
+// include/vlsat_gemm.h -- w[i] 2^k -> fp16 hi[i] + fp16 lo[i] with the tensor's exponent k (gemm_f16s_planes.h): the planes the split-fp16
+// 8-phase GEMM reads.  Allocates two words of scratch and synchronises the stream (k comes back to the host): a test entry point.
+int vlsat_k_split_f16s(const float* w, size_t n, uint16_t* hi, uint16_t* lo, int32_t* k, void* stream) {
+    if (!w || !hi || !lo || !k) return fail(VLSAT_EINVAL, "split_f16s: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned* scratch = nullptr;
+    *k = 0;
+    if (!n) return 0;
+    VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), 256));
+    int r = launch_split_f16s(w, n, hi, lo, scratch, st);
+    if (!r && hipMemcpyAsync(k, scratch + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess) r = fail(VLSAT_EHIP, "split_f16s: copy failed");
+    hipStreamSynchronize(st);
+    hipFree(scratch);
+    return r;
+}
+
+// vlsat_k_gemm as the fp32 precision mode runs an edge-row launch: the planes of a dense W [N,K] are made on the spot (allocates,
+// synchronises), the full rounds of a launch the planner sends to the 8-phase kernel run on its split-fp16 sibling, everything else on the
+// exact kernels.  p8_part_min: GemmArgs::p8_part_min (tests reach the 8-phase kernel with a few tiles).  relu_a: bit 0 only.
+int vlsat_k_gemm_f16s(const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc, int32_t M, int32_t N,
+                      int32_t K, const float* bias, const float* rowscale, const float* resid, int32_t ldr, float resid_scale,
+                      const float* g0, const int32_t* gi0, int32_t ldg0, const float* g1, const int32_t* gi1, int32_t ldg1,
+                      int32_t relu_a, int32_t act, int32_t p8_part_min, void* stream) {
+    if (!W || ldw != K || N <= 0 || K <= 0) return fail(VLSAT_EINVAL, "gemm_f16s: W must be dense [N,K] (the planes are made from it)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)N * K;
+    GemmArgs a;
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
+    a.bias = bias; a.rowscale = rowscale; a.resid = resid; a.ldr = ldr; a.resid_scale = resid_scale;
+    a.g0 = g0; a.gi0 = gi0; a.ldg0 = ldg0; a.g1 = g1; a.gi1 = gi1; a.ldg1 = ldg1; a.relu_a = relu_a & 1; a.act = act;
+    a.p8_part_min = p8_part_min < 0 ? 0 : p8_part_min;
+    uint16_t *hi = nullptr, *lo = nullptr;
+    VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hi), n * 2 + 256));
+    VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&lo), n * 2 + 256));
+    int32_t k = 0;
+    int r = vlsat_k_split_f16s(W, n, hi, lo, &k, stream);
+    if (!r) {
+        a.f16s = 1; a.Wh16 = hi; a.Wl16 = lo; a.w_exp = k;
+        r = launch_gemm(a, st);
+    }
     hipStreamSynchronize(st);
     hipFree(hi);
     hipFree(lo);

@@ -118,6 +118,13 @@ static int gemm_resolve(vlsat_ctx* h, int ws_lane, GemmArgs& a, int prec_overrid
         a.Whi = it->second.first;
         a.Wlo = it->second.second;
     }
+    // fp32 mode: every launch that is not a node-row launch may run its full rounds on the split-fp16 sibling of the 8-phase kernel
+    // (launch_gemm_p8; tails and small launches stay exact) -- unless "gemm_exact" asks for the exact kernels
+    if (prec == 0 && h->prec_edge == 0 && h->gemm_exact != 1 && !(a.M == h->cur_N && !edge_fmt)) {
+        auto f = h->f16s.find(a.W);
+        if (f == h->f16s.end()) return fail(VLSAT_ESTATE, "gemm: weight has no split-fp16 planes");
+        a.f16s = 1; a.Wh16 = f->second.hi; a.Wl16 = f->second.lo; a.w_exp = f->second.k;
+    }
     if (h->half_f16) {                      // mode 5: the half-row format is fp16 (engine.h)
         if (a.r_split == 2) return fail(VLSAT_ESTATE, "gemm: a half-row residual is not built on fp16 (the LayerNorm adds it)");
         if (a.a_split == 2) {               // fp16 operands: fp16 weight plane, f16 MFMA

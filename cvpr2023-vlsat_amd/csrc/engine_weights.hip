@@ -208,11 +208,12 @@ int prepare_stn(vlsat_ctx* h, Prep& P, const std::string& enc, StnW& w) {
 }  // namespace
 
 namespace vlsat {
-// bf16 hi/lo planes of every registered GEMM weight (idempotent); runs on the null stream and completes before returning
+// the 16-bit planes of every registered GEMM weight that the handle's precision mode reads (idempotent): bf16 hi/lo in the bf16 modes, the
+// split-fp16 planes in fp32 mode; runs on the null stream and completes before returning
 int split_all_weights(vlsat_ctx* h) {
     bool any = false;
     for (auto& gw : h->gemm_w) {
-        if (h->split.count(gw.first)) continue;
+        if (!h->prec || h->split.count(gw.first)) continue;
         uint16_t *hi = nullptr, *lo = nullptr;
         VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hi), gw.second * 2 + 256));
         VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&lo), gw.second * 2 + 256));
@@ -229,6 +230,22 @@ int split_all_weights(vlsat_ctx* h) {
             h->f16w.emplace(gw.first, f);
             any = true;
         }
+    // fp32 mode: the split-fp16 planes of the 8-phase GEMM's sibling (the edge-row launches of the forward; gemm_exact = 1 ignores them)
+    if (h->prec == 0) {
+        unsigned* scratch = nullptr;
+        for (auto& gw : h->gemm_w) {
+            if (h->f16s.count(gw.first)) continue;
+            if (!scratch) VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), 256));
+            vlsat_ctx::F16sPlanes pl{nullptr, nullptr, 0};
+            VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pl.hi), gw.second * 2 + 256));
+            VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pl.lo), gw.second * 2 + 256));
+            RUN(launch_split_f16s(gw.first, gw.second, pl.hi, pl.lo, scratch, nullptr));
+            VLSAT_HIP_CHECK(hipMemcpy(&pl.k, scratch + 1, sizeof(int), hipMemcpyDeviceToHost));      // (waits for the null stream)
+            h->f16s.emplace(gw.first, pl);
+            any = true;
+        }
+        if (scratch) VLSAT_HIP_CHECK(hipFree(scratch));
+    }
     if (any) VLSAT_HIP_CHECK(hipDeviceSynchronize());
     return 0;
 }
@@ -272,6 +289,8 @@ static void free_device_weights(vlsat_ctx* h) {
     h->split.clear();
     for (auto& kv : h->f16w) hipFree(kv.second);
     h->f16w.clear();
+    for (auto& kv : h->f16s) { hipFree(kv.second.hi); hipFree(kv.second.lo); }
+    h->f16s.clear();
     h->trip = TripletW{};
 }
 
@@ -441,7 +460,7 @@ int vlsat_finalize_weights(vlsat_handle h) {
     h->host.clear();
     h->finalized = true;
     ++h->config_epoch;
-    if (h->prec) RUN(split_all_weights(h));
+    RUN(split_all_weights(h));
     for (int i = 0; i < 3 && !h->sk_ws[i]; ++i) {     // split-K workspaces of the small GEMM launches (gemm_splitk.hip), once per handle
         VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->sk_ws[i]), SPLITK_WS_FLOATS * sizeof(float)));
         VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->sk_cnt[i]), SPLITK_COUNTERS * sizeof(unsigned)));
@@ -468,7 +487,7 @@ int vlsat_set_gemm_precision(vlsat_handle h, int32_t mode) {
     h->prec_edge = mode == 2 ? 1 : mode == 4 ? 3 : mode;
     h->prec_node = mode == 2 || mode == 4 ? 3 : mode;
     h->prec_attn = mode == 4 ? 1 : h->prec_edge;
-    if (mode && h->finalized) RUN(split_all_weights(h));
+    if (h->finalized) RUN(split_all_weights(h));
     return 0;
 }
 

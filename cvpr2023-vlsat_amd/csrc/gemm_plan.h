@@ -57,6 +57,13 @@ struct GemmArgs {
     // launches), owned by the caller and private to the stream the launch goes to; null = never split
     float* sk_ws = nullptr; size_t sk_ws_floats = 0;
     unsigned* sk_counters = nullptr; size_t sk_n_counters = 0;
+    // split-fp16 form of the exact-fp32 8-phase launch (prec 0 only; gemm_p8s_pick): fp16 planes Wh16 = f16(W 2^w_exp), Wl16 = f16(W 2^w_exp - Wh16)
+    // of the weight tensor ([N,K], pitch ldw; gemm_f16s_planes.h), fp32 tensors in and out, three f16 MFMAs per product.  Every other kernel
+    // a launch may get (tails, small launches) ignores these fields and stays exact.
+    int f16s = 0;
+    const uint16_t* Wh16 = nullptr;
+    const uint16_t* Wl16 = nullptr;
+    int w_exp = 0;
 };
 // The first launch of a GEMM as plan_gemm chooses it: kernel family, the row of the family's list, geometry, and the rows [0, rows) it
 // covers -- the rows after them are planned again as a problem of their own (the tail).
@@ -170,6 +177,26 @@ inline GemmPick gemm_p8_pick(const GemmArgs& a) {
     const int i = gemm_p8_find(mode, add, a.relu_a != 0, cf, abl);
     return i < 0 ? GemmPick{-1, "gemm_p8: operand combination not built"} : GemmPick{i, nullptr};
 }
+// Split-fp16 siblings of the exact-fp32 rows (MODE 1): X(ADD, RELU) = gemm_p8s_kernel<2, ADD, RELU, 0> -- the (additive operands,
+// ReLU-on-A) combinations the fp32 forward launches.  A sibling takes the launch of its MODE 1 row as planned: same tiles, grid and rows.
+#define VLSAT_GEMM_P8S_VARIANTS(X) X(0, false) X(0, true) X(1, false) X(6, false) X(6, true)
+struct GemmP8sVariant { int add; bool relu; };
+#define VLSAT_ROW(A, R) {A, R},
+constexpr GemmP8sVariant kGemmP8sVariants[] = {VLSAT_GEMM_P8S_VARIANTS(VLSAT_ROW)};
+#undef VLSAT_ROW
+constexpr int kGemmP8sCount = (int)(sizeof kGemmP8sVariants / sizeof kGemmP8sVariants[0]);
+constexpr int gemm_p8s_find(int add, bool relu) {
+    for (int i = 0; i < kGemmP8sCount; ++i)
+        if (kGemmP8sVariants[i].add == add && kGemmP8sVariants[i].relu == relu) return i;
+    return -1;
+}
+// The sibling that runs row `variant` of the 8-phase list for a launch with GemmArgs::f16s set, or -1: the row itself runs.  The one
+// place that decides it (launch_gemm_p8 asks; a pair of problems never is an 8-phase launch, gemm_pair_plan).
+inline int gemm_p8s_pick(const GemmArgs& a, int variant) {
+    if (!a.f16s || variant < 0 || variant >= kGemmP8Count) return -1;
+    const GemmP8Variant& v = kGemmP8Variants[variant];
+    return v.mode == 1 && v.abl == 0 ? gemm_p8s_find(v.add, v.relu) : -1;
+}
 // n_tiles tiles of the problem on a grid of `grid` blocks: the kernel keeps one column tile per block (bias registers)
 inline bool gemm_p8_geometry_ok(int M, int N, long n_tiles, long grid) {
     return n_tiles <= (long)((M + 255) / 256) * (N / 256) && grid % 8 == 0 && (grid / 8) % (N / 256) == 0;
@@ -259,6 +286,9 @@ inline const char* gemm_invalid(const GemmArgs& a) {
     if (a.half_f16 && (a.prec != 1 || a.a_split != 2 || a.c_split || a.r_split)) return "gemm: fp16 operands are half-row A launches of the single-rounding precision; their half-row output is c_f16_cols == N";
     if ((a.c_f16_cols || a.g_f16) && a.prec == 0) return "gemm: fp16 half-row columns / tables belong to the bf16 modes (the exact-fp32 kernels read and write fp32)";
     if (a.c_f16_cols && ((a.c_f16_cols != a.N && a.c_f16_cols % 256) || a.c_f16_cols > a.N || a.c_split)) return "gemm: c_f16_cols must be N or a multiple of 256 within N, of an fp32 output";
+    if (a.f16s && (a.prec != 0 || !a.Wh16 || !a.Wl16 || (a.ldw & 7) || ((reinterpret_cast<uintptr_t>(a.Wh16) | reinterpret_cast<uintptr_t>(a.Wl16)) & 15) ||
+                   a.w_exp < -100 || a.w_exp > 100))
+        return "gemm: f16s is the exact-fp32 precision with two 16-byte aligned fp16 weight planes, ldw % 8 == 0 and |w_exp| <= 100";
     if (a.g_f16 && (a.resid || !(a.g0 || a.g1) || a.N % 256 || ((a.ldg0 | a.ldg1) & 1) || ((reinterpret_cast<uintptr_t>(a.g0) | reinterpret_cast<uintptr_t>(a.g1)) & 7)))
         return "gemm: g_f16 needs gathered rows, no residual, N % 256 == 0 and 8-byte aligned tables";
     return nullptr;

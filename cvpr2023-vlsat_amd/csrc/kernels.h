@@ -194,6 +194,9 @@ int launch_aggregate(const float* gated, int n_ch, const int32_t* rowptr, const 
 // w[i] -> bf16 hi[i] + bf16 lo[i] (split-bf16 GEMM weights, one-time)
 int launch_split_bf16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, hipStream_t s);
 int launch_to_f16(const float* w, size_t n, uint16_t* out, hipStream_t s);        // fp16 plane (precision mode fp16_mixed)
+// w[i] 2^k -> fp16 hi[i] + fp16 lo[i], k = 13 - ceil(log2(max |w|)) (gemm_f16s_planes.h; GemmArgs::f16s): scratch2[0] receives the bits of
+// max |w|, scratch2[1] the integer k (device, two words, read back by the caller once the stream has run)
+int launch_split_f16s(const float* w, size_t n, uint16_t* hi, uint16_t* lo, unsigned* scratch2, hipStream_t s);
 
 // ---- eval ranking step: softmax + top-k ranks by counting ----
 int launch_softmax_rows(const float* x, int ld, int rows, int cols, float* out, int log_out, hipStream_t s);

@@ -1,5 +1,6 @@
 // Small fused VALU kernels of the path (all HBM/latency-bound glue around the MFMA kernels).
 #include "common.h"
+#include "gemm_f16s_planes.h"
 #include "kernels.h"
 
 namespace vlsat {
@@ -595,6 +596,38 @@ int launch_split_bf16(const float* w, size_t n, uint16_t* hi, uint16_t* lo, hipS
     if (!n) return 0;
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, hi, lo);
     VLSAT_LAUNCH_CHECK("split_bf16");
+    return 0;
+}
+
+// One-time weight preparation of the split-fp16 8-phase GEMM of the fp32 mode (gemm_f16s_planes.h has the arithmetic): the largest |w|
+// of the tensor by an integer-ordered atomic max over its bit patterns (exact and order-independent), then k and the two planes.
+__global__ void f16s_absmax_kernel(const float* __restrict__ w, size_t n, unsigned* __restrict__ max_bits) {
+    unsigned m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned a = f16s_bits(w[i]) & 0x7fffffffu;
+        m = a > m ? a : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned v = __shfl_xor(m, o); m = v > m ? v : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(max_bits, m);
+}
+__global__ void f16s_split_kernel(const float* __restrict__ w, size_t n, const unsigned* __restrict__ max_bits, uint16_t* __restrict__ hi,
+                                  uint16_t* __restrict__ lo, int* __restrict__ k_out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = f16s_exponent(*max_bits);
+    if (i == 0) *k_out = k;
+    if (i >= n) return;
+    uint16_t h, l;
+    f16s_split(w[i], k, h, l);
+    hi[i] = h;
+    lo[i] = l;
+}
+int launch_split_f16s(const float* w, size_t n, uint16_t* hi, uint16_t* lo, unsigned* scratch2, hipStream_t s) {
+    if (!n) return 0;
+    launch_zero_f32(reinterpret_cast<float*>(scratch2), 2, s);
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(f16s_absmax_kernel, dim3(blocks), dim3(256), 0, s, w, n, scratch2);
+    hipLaunchKernelGGL(f16s_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, n, scratch2, hi, lo, reinterpret_cast<int*>(scratch2 + 1));
+    VLSAT_LAUNCH_CHECK("split_f16s");
     return 0;
 }
 }  // namespace vlsat

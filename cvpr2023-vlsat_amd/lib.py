@@ -25,6 +25,7 @@ VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel
 OBJECTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_objects.h")
 FLASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_flash.h")
 CONVEX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_convex.h")
+GEMM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_gemm.h")
 
 
 class VlsatDims(C.Structure):
@@ -186,6 +187,13 @@ _SIGNATURES_CONVEX = {
     "vlsat_convex_clusters": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/vlsat_gemm.h: the split-fp16 8-phase GEMM of the fp32 precision mode on its own, and its weight planes (csrc/gemm_bf16_p8.hip)
+_SIGNATURES_GEMM = {
+    "vlsat_k_split_f16s": (C.c_int, [_vp, _sz, _vp, _vp, C.POINTER(_i32), _vp]),
+    "vlsat_k_gemm_f16s": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32,
+                                    _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+}
+
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
@@ -200,7 +208,7 @@ def identity(lib_path: str = "") -> dict:
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
-                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, CONVEX_HEADER_PATH, os.path.join(_HERE, "build.py")]:
+                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, CONVEX_HEADER_PATH, GEMM_HEADER_PATH, os.path.join(_HERE, "build.py")]:
         fp = f if os.path.isabs(f) else os.path.join(csrc, f)
         if fp.endswith((".hip", ".h", ".py")):
             h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
@@ -259,6 +267,11 @@ def declared_convex_symbols() -> list:
     return _declared(CONVEX_HEADER_PATH)
 
 
+def declared_gemm_symbols() -> list:
+    """Every function include/vlsat_gemm.h declares."""
+    return _declared(GEMM_HEADER_PATH)
+
+
 def load():
     """Load the shared library; raises VlsatError when it has not been built."""
     global _lib
@@ -269,8 +282,8 @@ def load():
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()) + list(_SIGNATURES_CONVEX.items()):
-        if (name in _SIGNATURES_FLASH or name in _SIGNATURES_CONVEX) and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
+            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()) + list(_SIGNATURES_CONVEX.items()) + list(_SIGNATURES_GEMM.items()):
+        if (name in _SIGNATURES_FLASH or name in _SIGNATURES_CONVEX or name in _SIGNATURES_GEMM) and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
             continue          # another build, loaded for a same-box A/B (bench.py --lib), may predate these entry points: calling one is then an AttributeError
         fn = getattr(lib, name)
         fn.restype = res

@@ -139,7 +139,12 @@ int vlsat_forward_train(vlsat_handle h, vlsat_plan p,
 
 
 /* Operand precision of the matrix kernels inside vlsat_forward (BASELINE configs[2], "bf16 MFMA for the
- * QKV/FFN GEMMs"): 0 = fp32 (default; BASELINE configs[1]): fp32 MFMA on every GEMM, the gate and the encoders; the edge
+ * QKV/FFN GEMMs"): 0 = fp32 (default; BASELINE configs[1]): fp32 MFMA on the node-row, tail and small GEMM launches, the gate and the
+ * encoders; the full rounds of the large edge-row GEMM launches (256 x 256 8-phase kernel) as three fp16 MFMAs per product into an fp32
+ * accumulator -- fp32 tensors in and out, A split in registers into fp16 hi + (lo 2^11), the weights as fp16 planes of W 2^k (k per
+ * tensor, made when the weights are finalised; vlsat_gemm.h), 0.3 to 1.3 times the exact kernel's error against fp64; domain
+ * |A| <= 65504 (beyond, the operand saturates and results stay finite), weights below 2^-16 of their tensor's largest lose low bits;
+ * vlsat_debug_option "gemm_exact" 1 restores the exact fp32-MFMA kernels; the edge
  * cross-attention's products (head dim 64) as three fp16 MFMAs each (operands split into fp16 hi + lo, 2^-22), fp32 accumulate and
  * softmax -- 1.1 to 2 times the exact kernel's error, far inside 1e-4 on the outputs; domain |Q / sqrt(d_k) * log2 e|, |K| < 65504 and, V
  * being multiplied by 2^3 before the split, |V| < 65504 / 8 = 8188 (values beyond are clamped there);
@@ -766,6 +771,9 @@ int vlsat_debug_gemm_clock_probe(int64_t* buf);
  *   "flash_exact" -1|0|1  fp32 mode at head dim 64: the edge cross-attention's products as three fp16 MFMAs each (-1 = default, 0), or the
  *                         exact fp32-MFMA kernel (1): the forward of the releases before the split-fp16 kernel, bit for bit, without its
  *                         operand domain (|Q / sqrt(d_k) * log2 e|, |K| < 65504, |V| < 8188);
+ *   "gemm_exact" -1|0|1   fp32 mode: the full rounds of the large edge-row GEMM launches as three fp16 MFMAs per product (-1 = default, 0), or
+ *                         on the exact fp32-MFMA kernel (1), without the operand domain |A| <= 65504; with "flash_exact" 1: the forward of
+ *                         the releases before either split-fp16 kernel, bit for bit;
  *   "flash_bq_big" 0|1    half-row edge attention, plans whose scenes all have >= 4096 edges: 256 queries per block (default) or 128;
  *   "flash_bq_big_min" n  ... that bound (plans created afterwards).  At the bench batch (1560 edges per scene) 256-query tiles are 1 %
  *                         slower per step than 128-query ones (profiles/r06_probes/ab_flash_bq_big_min.txt): the default stays 4096;
