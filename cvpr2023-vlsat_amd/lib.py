@@ -1,4 +1,4 @@
-"""ctypes binding of libvlsat_hip.so (C ABI in include/vlsat.h).
+"""ctypes binding of libvlsat_hip.so (C ABI in include/vlsat.h and the include/vlsat_*.h beside it: the registry HEADERS).
 
 The library is loaded from this directory (built in-tree by ``build.py``).  There is no
 fallback: if it is missing, ``load()`` raises -- the product path never computes on the CPU.
@@ -7,6 +7,7 @@ torch must be imported first so that the HIP runtime already mapped by torch
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import re
@@ -16,16 +17,7 @@ import torch  # noqa: F401  (maps libamdhip64 before our library is loaded)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvlsat_hip.so")
 _IN_TREE_LIB_PATH = LIB_PATH
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat.h")
-SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_split.h")
-CALIB_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_calib.h")
-SEGMENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_segment.h")
-CLOUD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_cloud.h")
-VOXEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_voxel.h")
-OBJECTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_objects.h")
-FLASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_flash.h")
-CONVEX_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_convex.h")
-GEMM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vlsat_gemm.h")
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 
 class VlsatDims(C.Structure):
@@ -42,7 +34,13 @@ class VlsatError(RuntimeError):
 _lib = None
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
-_SIGNATURES = {
+# The public C ABI, stated once: one row per header of include/ -- its file name and {function: (restype, argtypes)}.  Paths, declared
+# names, the source digest, what load() binds and what build() checks all follow from it; a new header is a new row.
+Header = collections.namedtuple("Header", "file signatures")
+HEADERS = {}
+
+# include/vlsat.h: the forward, its plans and weights, the kernels' test entries, evaluation, graphs and preparation (csrc/engine_api.hip and others)
+HEADERS["vlsat"] = Header("vlsat.h", {
     "vlsat_last_error": (C.c_char_p, []),
     "vlsat_version": (C.c_char_p, []),
     "vlsat_create": (C.c_int, [C.POINTER(VlsatDims), C.POINTER(_vp)]),
@@ -130,74 +128,104 @@ _SIGNATURES = {
     "vlsat_debug_read": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
     "vlsat_debug_buffer": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i32),
                                      C.POINTER(_i32)]),
-}
+})
 
 # include/vlsat_split.h: splitting a scan into sub-scenes and fusing the per-split graphs (csrc/scene_split.hip)
-_SIGNATURES_SPLIT = {
+HEADERS["split"] = Header("vlsat_split.h", {
     "vlsat_split_seeds_scratch_bytes": (_sz, [_i64]),
     "vlsat_split_seeds": (C.c_int, [_vp, _i64, C.c_double, C.c_uint64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "vlsat_split_groups": (C.c_int, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "vlsat_fuse_splits_scratch_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "vlsat_fuse_splits": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_vp] * 15 + [_vp]),
-}
+})
 
 # include/vlsat_calib.h: score histograms against ground truth, for thresholds and calibration (csrc/calibration.hip)
-_SIGNATURES_CALIB = {
+HEADERS["calib"] = Header("vlsat_calib.h", {
     "vlsat_score_hist": (C.c_int, [_vp] * 4 + [_i32] * 6 + [_vp] * 3 + [_vp]),
     "vlsat_score_hist_geometry": (None, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
-}
+})
 
 # include/vlsat_segment.h: an unlabelled mesh over-segmented into segments (csrc/mesh_segment.hip)
-_SIGNATURES_SEGMENT = {
+HEADERS["segment"] = Header("vlsat_segment.h", {
     "vlsat_segment_mesh_scratch_bytes": (_sz, [_i64, _i64]),
     "vlsat_segment_mesh": (C.c_int, [_vp, _vp, _i64, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
-}
+})
 
 # include/vlsat_cloud.h: a cloud without faces -- kNN table, normals and flatness (csrc/cloud.hip), segments over the table (csrc/mesh_segment.hip)
-_SIGNATURES_CLOUD = {
+HEADERS["cloud"] = Header("vlsat_cloud.h", {
     "vlsat_cloud_knn_scratch_bytes": (_sz, [_i64, _i32]),
     "vlsat_cloud_knn": (C.c_int, [_vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "vlsat_cloud_normals": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
     "vlsat_segment_cloud": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-}
+})
 
 # include/vlsat_voxel.h: a cloud resampled on a voxel grid -- cells and numbering, then means of positions, normals and colours (csrc/voxel.hip)
-_SIGNATURES_VOXEL = {
+HEADERS["voxel"] = Header("vlsat_voxel.h", {
     "vlsat_voxel_scratch_bytes": (_sz, [_i64]),
     "vlsat_voxel_assign": (C.c_int, [_vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vlsat_voxel_reduce": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-}
-
-# include/vlsat_flash.h: the split-fp16 edge attention of the fp32 precision mode on its own (csrc/flash_attn_bf16.hip)
-_SIGNATURES_FLASH = {
-    "vlsat_k_flash_attn_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _i32, _vp]),
-}
+})
 
 # include/vlsat_objects.h: a cloud segmented into objects -- structural planes found and removed, the rest clustered (csrc/objects.hip)
-_SIGNATURES_OBJECTS = {
+HEADERS["objects"] = Header("vlsat_objects.h", {
     "vlsat_cloud_planes_scratch_bytes": (_sz, [_i64, _i32]),
     "vlsat_cloud_planes": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vlsat_cloud_clusters_scratch_bytes": (_sz, [_i64]),
     "vlsat_cloud_clusters": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
-}
+})
+
+# include/vlsat_flash.h: the split-fp16 edge attention of the fp32 precision mode on its own (csrc/flash_attn_bf16.hip)
+HEADERS["flash"] = Header("vlsat_flash.h", {
+    "vlsat_k_flash_attn_f16x3": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _f32, _i32, _i32, _vp]),
+})
 
 # include/vlsat_convex.h: clusters cut at concave junctions, for bodies that touch (csrc/convex.hip)
-_SIGNATURES_CONVEX = {
+HEADERS["convex"] = Header("vlsat_convex.h", {
     "vlsat_convex_clusters_scratch_bytes": (_sz, [_i64]),
     "vlsat_convex_clusters": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-}
+})
 
 # include/vlsat_gemm.h: the split-fp16 8-phase GEMM of the fp32 precision mode on its own, and its weight planes (csrc/gemm_bf16_p8.hip)
-_SIGNATURES_GEMM = {
+HEADERS["gemm"] = Header("vlsat_gemm.h", {
     "vlsat_k_split_f16s": (C.c_int, [_vp, _sz, _vp, _vp, C.POINTER(_i32), _vp]),
     "vlsat_k_gemm_f16s": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32,
                                     _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-}
+})
+
+
+def header_path(name: str = "vlsat") -> str:
+    return os.path.join(_INCLUDE, HEADERS[name].file)
+
+
+def signatures(name=None) -> dict:
+    """{function: (restype, argtypes)} of one header, or of all of them merged (no function is bound twice)."""
+    if name is not None:
+        return HEADERS[name].signatures
+    merged = {}
+    for h in HEADERS.values():
+        assert not merged.keys() & h.signatures.keys(), (h.file, sorted(merged.keys() & h.signatures.keys()))
+        merged.update(h.signatures)
+    return merged
+
+
+def declared_symbols(name: str = "vlsat") -> list:
+    """Every function the header declares (parsed from its text)."""
+    txt = open(header_path(name)).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(vlsat_[a-z0-9_]+)\s*\(", txt)))
+
+
+def source_files() -> list:
+    """What the library is built from, in the order the source digest takes it: csrc/*.hip and *.h sorted, the headers in registry order,
+    build.py (its flags and source list)."""
+    csrc = os.path.join(_HERE, "csrc")
+    return ([os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+            + [header_path(name) for name in HEADERS] + [os.path.join(_HERE, "build.py")])
 
 
 def identity(lib_path: str = "") -> dict:
     """What a measurement was taken on: SHA-256 of the shared library that is (or would be) loaded and of the sources it is
-    built from (csrc/*.hip, csrc/*.h, include/*.h, build flags) -- the GPU box has no .git, so the source digest is what a
+    built from (source_files()) -- the GPU box has no .git, so the source digest is what a
     profile summary and a later bench run can compare; the commit is added when the summary is published (tools/)."""
     import hashlib
     path = lib_path or LIB_PATH
@@ -206,74 +234,16 @@ def identity(lib_path: str = "") -> dict:
         out["lib_sha256"] = hashlib.sha256(open(path, "rb").read()).hexdigest()
         out["lib_bytes"] = os.path.getsize(path)
     h = hashlib.sha256()
-    csrc = os.path.join(_HERE, "csrc")
-    for f in sorted(os.listdir(csrc)) + [HEADER_PATH, SPLIT_HEADER_PATH, CALIB_HEADER_PATH, SEGMENT_HEADER_PATH, CLOUD_HEADER_PATH, VOXEL_HEADER_PATH,
-                                          OBJECTS_HEADER_PATH, FLASH_HEADER_PATH, CONVEX_HEADER_PATH, GEMM_HEADER_PATH, os.path.join(_HERE, "build.py")]:
-        fp = f if os.path.isabs(f) else os.path.join(csrc, f)
-        if fp.endswith((".hip", ".h", ".py")):
-            h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
+    for fp in source_files():
+        h.update(os.path.basename(fp).encode() + b"\0" + open(fp, "rb").read())
     out["source_sha256"] = h.hexdigest()
     return out
 
 
-def _declared(path: str) -> list:
-    txt = open(path).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(vlsat_[a-z0-9_]+)\s*\(", txt)))
-
-
-def declared_symbols() -> list:
-    """Every function include/vlsat.h declares (parsed from the header text)."""
-    return _declared(HEADER_PATH)
-
-
-def declared_split_symbols() -> list:
-    """Every function include/vlsat_split.h declares."""
-    return _declared(SPLIT_HEADER_PATH)
-
-
-def declared_calib_symbols() -> list:
-    """Every function include/vlsat_calib.h declares."""
-    return _declared(CALIB_HEADER_PATH)
-
-
-def declared_segment_symbols() -> list:
-    """Every function include/vlsat_segment.h declares."""
-    return _declared(SEGMENT_HEADER_PATH)
-
-
-def declared_cloud_symbols() -> list:
-    """Every function include/vlsat_cloud.h declares."""
-    return _declared(CLOUD_HEADER_PATH)
-
-
-def declared_voxel_symbols() -> list:
-    """Every function include/vlsat_voxel.h declares."""
-    return _declared(VOXEL_HEADER_PATH)
-
-
-def declared_objects_symbols() -> list:
-    """Every function include/vlsat_objects.h declares."""
-    return _declared(OBJECTS_HEADER_PATH)
-
-
-def declared_flash_symbols() -> list:
-    """Every function include/vlsat_flash.h declares."""
-    return _declared(FLASH_HEADER_PATH)
-
-
-def declared_convex_symbols() -> list:
-    """Every function include/vlsat_convex.h declares."""
-    return _declared(CONVEX_HEADER_PATH)
-
-
-def declared_gemm_symbols() -> list:
-    """Every function include/vlsat_gemm.h declares."""
-    return _declared(GEMM_HEADER_PATH)
-
-
 def load():
-    """Load the shared library; raises VlsatError when it has not been built."""
+    """Load the shared library; raises VlsatError when it has not been built.  The in-tree library must export every bound name.  A
+    library from another path (LIB_PATH reassigned: bench.py --lib, tools/pointnet_probe.py) is another build, loaded for a same-box A/B,
+    and may predate any entry point: that one stays unbound, and calling it is an AttributeError."""
     global _lib
     if _lib is not None:
         return _lib
@@ -281,10 +251,9 @@ def load():
         raise VlsatError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc, gfx950).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SIGNATURES_SPLIT.items()) + list(_SIGNATURES_CALIB.items()) + list(
-            _SIGNATURES_SEGMENT.items()) + list(_SIGNATURES_CLOUD.items()) + list(_SIGNATURES_VOXEL.items()) + list(_SIGNATURES_OBJECTS.items()) + list(_SIGNATURES_FLASH.items()) + list(_SIGNATURES_CONVEX.items()) + list(_SIGNATURES_GEMM.items()):
-        if (name in _SIGNATURES_FLASH or name in _SIGNATURES_CONVEX or name in _SIGNATURES_GEMM) and LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
-            continue          # another build, loaded for a same-box A/B (bench.py --lib), may predate these entry points: calling one is then an AttributeError
+    for name, (res, args) in signatures().items():
+        if LIB_PATH != _IN_TREE_LIB_PATH and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

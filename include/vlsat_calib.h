@@ -1,8 +1,8 @@
 /*
  * vlsat_calib.h -- the part of libvlsat_hip.so's C ABI that histograms a batch's scores against ground truth, for choosing the decode's
  * per-predicate thresholds and for judging the calibration of the object head (csrc/calibration.hip).  Conventions, error codes and
- * vlsat_last_error() are those of vlsat.h; the symbols are exported from the same library and bound by lib.py from its third table
- * (_SIGNATURES_CALIB).
+ * vlsat_last_error() are those of vlsat.h; the symbols are exported from the same library and bound by lib.py from its registry row
+ * HEADERS["calib"].
  *
  * Why.  vlsat_graph_decode_counts gives the tp / fp / fn of the decode at ONE threshold vector, so a sweep over thresholds costs one
  * pass over the validation set per candidate.  A histogram of the predicate scores, split by ground truth, over a power-of-two number

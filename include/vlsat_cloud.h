@@ -2,8 +2,8 @@
  * vlsat_cloud.h -- the part of libvlsat_hip.so's C ABI that takes a point cloud WITHOUT faces to the segmenter (csrc/cloud.hip, and
  * vlsat_segment_cloud in csrc/mesh_segment.hip): the K nearest neighbours of every point, a normal and a flatness measure per point
  * from that neighbourhood, and the rules of vlsat_segment.h run over the neighbour table.  Conventions, error codes and
- * vlsat_last_error() are those of vlsat.h; the symbols are exported from the same library and bound by lib.py from its fifth table
- * (_SIGNATURES_CLOUD).
+ * vlsat_last_error() are those of vlsat.h; the symbols are exported from the same library and bound by lib.py from its registry row
+ * HEADERS["cloud"].
  *
  * Why.  vlsat_segment_mesh reads mesh edges and vertex normals, both of which come from triangles.  A fused RGB-D or LiDAR cloud, or a
  * reconstruction saved without its face element, has neither.  prep.knn_points_host and prep.cloud_normals_host restate the rules below

@@ -1,7 +1,7 @@
 /*
  * vlsat_convex.h -- the part of libvlsat_hip.so's C ABI that clusters a point cloud by LOCAL CONVEXITY (csrc/convex.hip): bodies that
  * touch are cut where their surfaces meet in a concave junction.  Conventions, error codes and vlsat_last_error() are those of vlsat.h;
- * the symbols are exported from the same library and bound by lib.py from its ninth table (_SIGNATURES_CONVEX).
+ * the symbols are exported from the same library and bound by lib.py from its registry row HEADERS["convex"].
  *
  * Why.  vlsat_cloud_clusters (vlsat_objects.h) joins whatever touches: with floor and walls removed, a desk and all it carries are one
  * cluster.  The surfaces of one body meet in convex creases, and two bodies resting on each other meet in a concave one (Stein et al.,

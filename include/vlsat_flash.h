@@ -2,7 +2,7 @@
  * vlsat_flash.h -- the part of libvlsat_hip.so's C ABI that runs the split-fp16 edge attention on its own (csrc/flash_attn_bf16.hip,
  * flash_attn_f16x3_kernel): the kernel the fp32 precision mode uses for the edge cross-attention at head dim 64, next to
  * vlsat_k_flash_attn (the exact fp32-MFMA kernel) and vlsat_k_flash_attn_bf16 of vlsat.h.  Conventions, error codes and
- * vlsat_last_error() are those of vlsat.h; the symbol is exported from the same library and bound by lib.py from _SIGNATURES_FLASH.
+ * vlsat_last_error() are those of vlsat.h; the symbol is exported from the same library and bound by lib.py from its registry row HEADERS["flash"].
  */
 #ifndef VLSAT_FLASH_H
 #define VLSAT_FLASH_H

@@ -2,7 +2,7 @@
  * vlsat_gemm.h -- the part of libvlsat_hip.so's C ABI that runs the split-fp16 8-phase GEMM on its own (csrc/gemm_bf16_p8.hip,
  * gemm_p8s_kernel): the kernel the fp32 precision mode uses for the full rounds of its large edge-row launches, next to vlsat_k_gemm
  * (always the exact fp32-MFMA kernels) of vlsat.h.  Conventions, error codes and vlsat_last_error() are those of vlsat.h; the symbols
- * are exported from the same library and bound by lib.py from _SIGNATURES_GEMM.
+ * are exported from the same library and bound by lib.py from its registry row HEADERS["gemm"].
  */
 #ifndef VLSAT_GEMM_H
 #define VLSAT_GEMM_H

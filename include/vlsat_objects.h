@@ -2,7 +2,7 @@
  * vlsat_objects.h -- the part of libvlsat_hip.so's C ABI that takes a point cloud to OBJECT-level instances without a trained model
  * (csrc/objects.hip): the room's structural planes (floor, walls, ceiling) are found and removed, and what is left is clustered by
  * Euclidean proximity over the neighbour table of vlsat_cloud_knn.  Conventions, error codes and vlsat_last_error() are those of
- * vlsat.h; the symbols are exported from the same library and bound by lib.py from its seventh table (_SIGNATURES_OBJECTS).
+ * vlsat.h; the symbols are exported from the same library and bound by lib.py from its registry row HEADERS["objects"].
  *
  * Why.  vlsat_segment_mesh and vlsat_segment_cloud over-segment: a table top and each of its sides are separate segments, and the only
  * way back to objects is merging along "same part" edges, a relation the 26-name list of the published checkpoints does not have.

@@ -1,7 +1,7 @@
 /*
  * vlsat_segment.h -- the part of libvlsat_hip.so's C ABI that over-segments an unlabelled mesh into segments (csrc/mesh_segment.hip):
  * the per-vertex instance id every other entry point takes as given.  Conventions, error codes and vlsat_last_error() are those of
- * vlsat.h; the symbols are exported from the same library and bound by lib.py from its fourth table (_SIGNATURES_SEGMENT).
+ * vlsat.h; the symbols are exported from the same library and bound by lib.py from its registry row HEADERS["segment"].
  *
  * Why.  prepare_scan, split_scan, transfer_labels and merge_graph all start from a segmentation someone else made: the annotators'
  * objectId, or the output of an outside tool (the reference's data_processing/gen_data.py:188 reads an inseg.ply that ships with

@@ -1,7 +1,7 @@
 /*
  * vlsat_split.h -- the part of libvlsat_hip.so's C ABI that splits a scan into sub-scenes and fuses the per-split predictions back
  * into one graph per scan (csrc/scene_split.hip).  Conventions, error codes and vlsat_last_error() are those of vlsat.h; the symbols
- * are exported from the same library and bound by lib.py from its second table (_SIGNATURES_SPLIT).
+ * are exported from the same library and bound by lib.py from its registry row HEADERS["split"].
  *
  * Why.  The reference trains and evaluates on SUB-SCENES: every entry of relationships_*.json is scan + "_" + split
  * (src/dataset/dataset_3dssg.py:238-240), and a split is the group of segments its generate_groups collects around a seed point

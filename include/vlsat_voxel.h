@@ -2,7 +2,7 @@
  * vlsat_voxel.h -- the part of libvlsat_hip.so's C ABI that resamples a point cloud on a voxel grid before it is segmented
  * (csrc/voxel.hip): one representative point per occupied cell, and a map from every input point to its cell's representative.
  * Conventions, error codes and vlsat_last_error() are those of vlsat.h; the symbols are exported from the same library and bound by
- * lib.py from its sixth table (_SIGNATURES_VOXEL).
+ * lib.py from its registry row HEADERS["voxel"].
  *
  * Why.  vlsat_cloud_knn takes K neighbours within one radius and the segmenter counts points, which presumes ONE sampling distance.  A
  * fused RGB-D or LiDAR cloud is dense where many frames overlapped: there the K nearest neighbours lie within the sensor noise, the

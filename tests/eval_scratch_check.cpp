@@ -1,5 +1,5 @@
 // Host-only check of the evaluation-scratch layout of csrc/engine.h (EvalScratch, eval_scratch_carve, eval_scratch_floats / _ints; built
-// with g++ by tests/select_host.py; opens no device).  Prints one "N E C R -> ok" line per case and exits 1 at the first failure.
+// with g++ by tests/host_check.py; opens no device).  Prints one "N E C R -> ok" line per case and exits 1 at the first failure.
 #include <stdio.h>
 #include <stdlib.h>
 

@@ -1,4 +1,4 @@
-// Host-only check of the split-fp16 part of csrc/flash_pick.h (built with g++ by tests/flash_f16x3_core_host.py; opens no device):
+// Host-only check of the split-fp16 part of csrc/flash_pick.h (built with g++ by tests/host_check.py; opens no device):
 // flash_f16x3_pick over its whole input space.  The form exists for fp32 tensors at head dim 64 with 128-query tiles, 32 queries per
 // wave and no timing ablation, with the transpose read on or off; every such call must name the row of kFlashF16x3Variants with that
 // (tr, d), every other call must be an error with a text and never another kernel, and every row must be reached.

@@ -1,4 +1,4 @@
-// Host-only check of csrc/flash_pick.h (built with g++ by tests/select_host.py; opens no device): flash_bf16_pick against the
+// Host-only check of csrc/flash_pick.h (built with g++ by tests/host_check.py; opens no device): flash_bf16_pick against the
 // if-cascade launch_flash_attn_bf16 had before the selector existed, over the whole input space.
 // Prints one "name -> ok ..." line per check and exits 1 at the first failure.
 // With -DVLSAT_EXPERIMENTS the list has the lab rows as well, and the ablation values are enumerated too.

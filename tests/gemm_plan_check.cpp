@@ -1,4 +1,4 @@
-// Host-only check of csrc/gemm_plan.h (built with g++ by tests/select_host.py; opens no device): the planner and the four variant
+// Host-only check of csrc/gemm_plan.h (built with g++ by tests/host_check.py; opens no device): the planner and the four variant
 // lists against the planner and the four launcher dispatches the library had before the lists existed, over whole launch sequences.
 // Prints one "name -> ok ..." line per check and exits 1 at the first failure; "bench" prints the launch sequences of the bench
 // batch's shapes as "table | ..." lines.  With -DVLSAT_EXPERIMENTS the lists have the lab rows and the lab switches are enumerated too.

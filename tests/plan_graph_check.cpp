@@ -1,4 +1,4 @@
-// Host-only check of csrc/plan_graph.h (built with g++ by tests/select_host.py; opens no device): the graph analysis, the workspace list and
+// Host-only check of csrc/plan_graph.h (built with g++ by tests/host_check.py; opens no device): the graph analysis, the workspace list and
 // the arena arithmetic against the body vlsat_plan_create had before them, kept here word for word from the scene loop down to the offset
 // loop (legacy_plan_create; `int4` is the header's four-int tile, `fail` records code and text, the arena pick is a function of its own
 // because the old one sat between HIP calls, and the list of items is handed out at the end).  Old and new must agree with NO difference in

@@ -1,4 +1,4 @@
-// Host-only check of the integer helpers of csrc/select_core.h (built with g++ by tests/select_host.py; opens no device).
+// Host-only check of the integer helpers of csrc/select_core.h (built with g++ by tests/host_check.py; opens no device).
 // Prints one "name -> ok" line per check and exits 1 at the first failure.
 #include <float.h>
 #include <math.h>

@@ -1,6 +1,6 @@
 """Score histograms without a GPU: the host restatement against the existing decode counts at every checked threshold,
-evaluate.operating_points against a brute-force loop over thresholds and a direct numpy statement of the object figures, the C ABI's
-third header, and the bin function of csrc/calib_core.h under ASan + UBSan against the PyTorch restatement."""
+evaluate.operating_points against a brute-force loop over thresholds and a direct numpy statement of the object figures, and
+the bin function of csrc/calib_core.h under ASan + UBSan against the PyTorch restatement."""
 import numpy as np
 import pytest
 import torch
@@ -8,7 +8,7 @@ import torch
 import vlsat_amd  # noqa: F401
 from vlsat_amd import evaluate as EV, lib as L, metrics as M
 
-import calib_host
+import host_check
 from calibration_checks import assert_counts_match, brute_object_numbers, host_tables, make_case, special_scores
 
 CASES = [(1, True), (26, True), (32, True), (27, False)]
@@ -127,20 +127,17 @@ def test_operating_points_of_empty_tables_are_nan_not_errors():
         EV.operating_points(M.ScoreTables(3, 4, 16), default=0.3)
 
 
-def test_calib_header_symbols_are_bound_and_disjoint():
-    names = {"vlsat_score_hist", "vlsat_score_hist_geometry"}
-    assert names == set(L.declared_calib_symbols()) == set(L._SIGNATURES_CALIB)
-    assert not names & set(L.declared_symbols()) and not names & set(L._SIGNATURES)
-    assert not names & set(L.declared_split_symbols()) and not names & set(L._SIGNATURES_SPLIT)
-    assert len(L.declared_symbols()) == 81 and len(L.declared_split_symbols()) == 5
-    assert len(L._SIGNATURES_CALIB["vlsat_score_hist"][1]) == 14
-    lib = L.load()
-    assert all(hasattr(lib, n) for n in names)
-    assert L.CALIB_HEADER_PATH.endswith("vlsat_calib.h") and len(L.identity()["source_sha256"]) == 64
+def _bin_rows(sanitize):
+    """rows (bins, fp32 bit pattern, eligible, column) that tests/calib_host_check.cpp printed"""
+    rows = []
+    for left, col in host_check.lines("calib_host_check", sanitize=sanitize):
+        bins, bits, eligible = left.split(":")
+        rows.append((int(bins), int(bits, 16), int(eligible), int(col)))
+    return rows
 
 
 def test_bin_function_under_host_sanitizers_equals_the_restatement():
-    rows = calib_host.run(sanitize=True)
+    rows = _bin_rows(sanitize=True)
     assert len(rows) == sum((3 * b + 10) * 2 for b in (16, 1024, 4096))
     for bins in (16, 1024, 4096):
         sel = [x for x in rows if x[0] == bins]
@@ -149,4 +146,4 @@ def test_bin_function_under_host_sanitizers_equals_the_restatement():
         want = M._score_columns(p, elig, bins)
         assert want.tolist() == [x[3] for x in sel], bins
         assert {x[3] for x in sel if not x[2]} == {bins}
-    assert rows == calib_host.run(sanitize=False)
+    assert rows == _bin_rows(sanitize=False)

@@ -1,7 +1,7 @@
 """The point-cloud front end on the host (the rules are stated in include/vlsat_cloud.h): the numpy restatement of the neighbour search
 against a brute force, csrc/cloud_core.h through g++ (with ASan + UBSan in the stand-alone program) against the restatements bit for
-bit, the restated normals against np.linalg.eigh, the segmenter on the plate cases, scan.segment_cloud on the host, and the fifth
-header's symbols."""
+bit, the restated normals against np.linalg.eigh, the segmenter on the plate cases, scan.segment_cloud on the host, and what the
+entry points refuse without a device (the header's symbols: test_c_abi_cpu.py)."""
 import numpy as np
 import pytest
 import torch
@@ -218,21 +218,9 @@ def test_scan_segment_cloud_on_the_host_feeds_write_ply(tmp_path):
         scan.segment_scan({"points": room["points"]}, device=None)                 # the mesh entry still wants faces
 
 
-# ---- the header and the symbols --------------------------------------------------------------------------------------------------------
-def test_cloud_header_symbols_are_bound_and_disjoint():
-    names = {"vlsat_cloud_knn_scratch_bytes", "vlsat_cloud_knn", "vlsat_cloud_normals", "vlsat_segment_cloud"}
-    assert names == set(L.declared_cloud_symbols()) == set(L._SIGNATURES_CLOUD)
-    for other in (L.declared_symbols(), L._SIGNATURES, L.declared_split_symbols(), L._SIGNATURES_SPLIT, L.declared_calib_symbols(),
-                  L._SIGNATURES_CALIB, L.declared_segment_symbols(), L._SIGNATURES_SEGMENT):
-        assert not names & set(other)
-    assert len(L.declared_symbols()) == 81 and len(L._SIGNATURES_SEGMENT["vlsat_segment_mesh"][1]) == 11
-    total = sum(len(x) for x in (L._SIGNATURES, L._SIGNATURES_SPLIT, L._SIGNATURES_CALIB, L._SIGNATURES_SEGMENT, L._SIGNATURES_CLOUD))
-    assert total == 94
-    assert {n: len(L._SIGNATURES_CLOUD[n][1]) for n in names} == {"vlsat_cloud_knn_scratch_bytes": 2, "vlsat_cloud_knn": 9,
-                                                                  "vlsat_cloud_normals": 13, "vlsat_segment_cloud": 12}
+# ---- the entry points without a device ---------------------------------------------------------------------------------------------------
+def test_cloud_entry_points_refuse_what_is_out_of_range_without_a_device():
     lib = L.load()
-    assert all(hasattr(lib, n) and getattr(lib, n).argtypes is not None for n in names)
-    assert L.CLOUD_HEADER_PATH.endswith("vlsat_cloud.h") and len(L.identity()["source_sha256"]) == 64
     size = lib.vlsat_cloud_knn_scratch_bytes
     assert size(0, 8) == 0 and size((1 << 24) + 1, 8) == 0 and size(10, 0) == 0 and size(10, 33) == 0
     assert size(1, 1) > 0 and size(1000, 32) - size(1, 32) == 999 * 16 + 4000 - 16 and size(1 << 24, 32) > 20 << 24

@@ -1,8 +1,8 @@
 """csrc/flash_pick.h, the split-fp16 list and its pick function, compiled by g++ (tests/flash_f16x3_pick_check.cpp through
-tests/flash_f16x3_core_host.py): no HIP header, no library, no device."""
+tests/host_check.py): no HIP header, no library, no device."""
 import pytest
 
-import flash_f16x3_core_host
+import host_check
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
@@ -12,7 +12,7 @@ def test_flash_f16x3_pick_lists_two_kernels_and_refuses_everything_else(sanitize
     row of kFlashF16x3Variants, every other call gets -1 and an error text that names the kernel family, both rows are reached, no row
     is listed twice, and flash_f16x3_supports is the pick with the defaults.  "asan_ubsan": the same stand-alone binary under ASan +
     UBSan."""
-    rows = flash_f16x3_core_host.run(sanitize)
+    rows = dict(host_check.lines("flash_f16x3_pick_check", sanitize=sanitize))
     assert set(rows) == {"listed", "unlisted", "reachable", "supports", "rows"}, rows
     assert all(v.split()[0] == "ok" for v in rows.values()), rows
     assert rows["listed"] == "ok 4320 cases, 2 launches"

@@ -1,6 +1,6 @@
 """The mesh segmenter on the host (the rule is stated in include/vlsat_segment.h): the numpy restatement against answers typed in by
-hand, its invariances, synth.make_box_mesh and what the rule makes of it, the mesh reader and writer, the fourth header's symbols, and
-csrc/segment_core.h under ASan + UBSan in a stand-alone program against the restatement and the library."""
+hand, its invariances, synth.make_box_mesh and what the rule makes of it, the mesh reader and writer, what the entry points
+refuse without a device, and csrc/segment_core.h under ASan + UBSan in a stand-alone program against the restatement and the library."""
 import math
 
 import numpy as np
@@ -194,16 +194,9 @@ def test_refused_arguments():
             bad()
 
 
-# ---- the header, the symbols, the core under sanitizers ----------------------------------------------------------------------------
-def test_segment_header_symbols_are_bound_and_disjoint():
-    names = {"vlsat_segment_mesh", "vlsat_segment_mesh_scratch_bytes"}
-    assert names == set(L.declared_segment_symbols()) == set(L._SIGNATURES_SEGMENT)
-    for other in (L.declared_symbols(), L._SIGNATURES, L.declared_split_symbols(), L._SIGNATURES_SPLIT, L.declared_calib_symbols(), L._SIGNATURES_CALIB):
-        assert not names & set(other)
-    assert len(L._SIGNATURES_SEGMENT["vlsat_segment_mesh"][1]) == 11
+# ---- the entry points without a device, the core under sanitizers --------------------------------------------------------------------
+def test_segment_entry_points_refuse_what_is_out_of_range_without_a_device():
     lib = L.load()
-    assert all(hasattr(lib, n) and getattr(lib, n).argtypes is not None for n in names)
-    assert L.SEGMENT_HEADER_PATH.endswith("vlsat_segment.h") and len(L.identity()["source_sha256"]) == 64
     assert lib.vlsat_segment_mesh_scratch_bytes(0, 0) == 0 and lib.vlsat_segment_mesh_scratch_bytes((1 << 24) + 1, 0) == 0
     assert lib.vlsat_segment_mesh_scratch_bytes(10, -1) == 0 and lib.vlsat_segment_mesh_scratch_bytes(10, 1 << 31) == 0
     assert lib.vlsat_segment_mesh(0, 0, 0, 0, 0.1, 20, 0, 0, 0, 0, 0) != 0 and b"segment_mesh" in lib.vlsat_last_error()

@@ -1,7 +1,7 @@
 """The object segmenter without a GPU (include/vlsat_objects.h): csrc/plane_core.h on the host against the numpy restatement, bit for
 bit, plain and under ASan + UBSan; the restatement against an independent scalar brute force, against answers derived by hand on
 dyadic coordinates, and end to end on the box rooms and the walled room; the cluster rule; scan.segment_objects on the host route; the
-arguments that are refused; synth.make_walled_room; the header, the seventh signature table and the build list."""
+arguments that are refused; synth.make_walled_room; the build list and the scratch sizes (the header and its table: test_c_abi_cpu.py)."""
 import numpy as np
 import pytest
 import torch
@@ -328,21 +328,9 @@ def test_make_walled_room():
     assert room["structural"].sum() == (base["instances"] == 1).sum() + len(walls) and room["height"] == 2.0
 
 
-# ---- the header, the binding and the build list -------------------------------------------------------------------------------------------
-def test_objects_header_symbols_are_bound_and_disjoint():
-    names = {"vlsat_cloud_planes_scratch_bytes", "vlsat_cloud_planes", "vlsat_cloud_clusters_scratch_bytes", "vlsat_cloud_clusters"}
-    assert names == set(L.declared_objects_symbols()) == set(L._SIGNATURES_OBJECTS)
-    others = (L.declared_symbols(), L._SIGNATURES, L.declared_split_symbols(), L._SIGNATURES_SPLIT, L.declared_calib_symbols(),
-              L._SIGNATURES_CALIB, L.declared_segment_symbols(), L._SIGNATURES_SEGMENT, L.declared_cloud_symbols(), L._SIGNATURES_CLOUD,
-              L.declared_voxel_symbols(), L._SIGNATURES_VOXEL)
-    for other in others:
-        assert not names & set(other)
-    assert {n: len(L._SIGNATURES_OBJECTS[n][1]) for n in names} == {"vlsat_cloud_planes_scratch_bytes": 2, "vlsat_cloud_planes": 14,
-                                                                     "vlsat_cloud_clusters_scratch_bytes": 1, "vlsat_cloud_clusters": 12}
+# ---- the build list and the scratch sizes -----------------------------------------------------------------------------------------------
+def test_objects_source_is_built_with_fp_contract_off_and_scratch_sizes_need_no_device():
     lib = L.load()
-    assert all(hasattr(lib, n) and getattr(lib, n).argtypes is not None for n in names)
-    assert sum(len(x) for x in others[1::2]) + len(L._SIGNATURES_OBJECTS) == 101
-    assert open(L.OBJECTS_HEADER_PATH).read().count("vlsat_cloud_planes(") == 1
     assert "objects.hip" in B.SOURCES and B.PER_SOURCE_FLAGS["objects.hip"] == ["-ffp-contract=off"]
     # the scratch sizes need no device: 0 for what is out of range, the layout's bytes otherwise
     assert lib.vlsat_cloud_planes_scratch_bytes(2, 8) == 0 and lib.vlsat_cloud_planes_scratch_bytes(3, 4097) == 0

@@ -1,7 +1,7 @@
 """The proximity edge rule on the host (vlsat_amd/prep.py::proximity_edges_host, the numpy restatement of csrc/proximity.hip):
 against a brute force written here independently, its stated properties, the reference's own padded boxes
-(tests/golden/proximity_cases.npz, made by make_golden_proximity.py from data_preparation's ``instances_box``), the annotation
-coverage, and the bindings.  No comparison uses a tolerance.  No GPU."""
+(tests/golden/proximity_cases.npz, made by make_golden_proximity.py from data_preparation's ``instances_box``), and the annotation
+coverage (the bindings: test_c_abi_cpu.py).  No comparison uses a tolerance.  No GPU."""
 import os
 import struct
 
@@ -229,9 +229,3 @@ def test_make_room_is_deterministic_and_has_spatial_structure():
     assert sorted(set(ia.tolist())) == list(range(1, 41))
     e = prep.proximity_edges_host(boxes_of(a, ia, range(1, 41)), [40], 0.2, 0)[0]
     assert 0 < e.shape[1] < 40 * 39 // 4                            # far from fully connected
-
-
-def test_the_new_symbols_are_declared_and_bound():
-    names = {"vlsat_instance_boxes", "vlsat_proximity_count", "vlsat_proximity_fill", "vlsat_proximity_scratch_bytes",
-             "vlsat_proximity_lds_boxes"}
-    assert names <= set(L.declared_symbols()) and names <= set(L._SIGNATURES)

@@ -1,7 +1,8 @@
 """The voxel-grid filter on the host (the rule is stated in include/vlsat_voxel.h): the numpy restatement against an independent brute
 force, csrc/voxel_core.h through g++ (with ASan + UBSan in the stand-alone program) against the restatement bit for bit, the refused
 arguments of the C entry points, the permutation property, scan.downsample_cloud through write_ply / read_mesh, scan.segment_cloud
-with and without `voxel`, the density case, and the sixth header's symbols.  Every comparison is of bits: nothing here has a tolerance."""
+with and without `voxel`, and the density case (the header's symbols: test_c_abi_cpu.py).  Every comparison is of bits:
+nothing here has a tolerance."""
 import ctypes
 
 import numpy as np
@@ -283,19 +284,3 @@ def test_resampling_a_fused_cloud_restores_the_uniform_segmentation(step):
           "dropped", int((out["instances"] == 0).sum()))
     assert (out["instances"] > 0).all() and (out["resampled"]["instances"] > 0).all()
     assert out["n_segments"] <= 1.25 * base["n_segments"]
-
-
-# ---- the header and the symbols ---------------------------------------------------------------------------------------------------------
-def test_voxel_header_symbols_are_bound_and_disjoint():
-    names = {"vlsat_voxel_scratch_bytes", "vlsat_voxel_assign", "vlsat_voxel_reduce"}
-    assert names == set(L.declared_voxel_symbols()) == set(L._SIGNATURES_VOXEL)
-    for other in (L.declared_symbols(), L._SIGNATURES, L.declared_split_symbols(), L._SIGNATURES_SPLIT, L.declared_calib_symbols(),
-                  L._SIGNATURES_CALIB, L.declared_segment_symbols(), L._SIGNATURES_SEGMENT, L.declared_cloud_symbols(), L._SIGNATURES_CLOUD):
-        assert not names & set(other)
-    assert {n: len(L._SIGNATURES_VOXEL[n][1]) for n in names} == {"vlsat_voxel_scratch_bytes": 1, "vlsat_voxel_assign": 13,
-                                                                  "vlsat_voxel_reduce": 12}
-    lib = L.load()
-    assert all(hasattr(lib, n) and getattr(lib, n).argtypes is not None for n in names)
-    total = sum(len(x) for x in (L._SIGNATURES, L._SIGNATURES_SPLIT, L._SIGNATURES_CALIB, L._SIGNATURES_SEGMENT, L._SIGNATURES_CLOUD,
-                                 L._SIGNATURES_VOXEL))
-    assert total == 97 and open(L.VOXEL_HEADER_PATH).read().count("vlsat_voxel_assign(") == 1
