@@ -56,7 +56,13 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //   "flash_exact" -1|0|1   fp32 mode, head dim 64: the edge attention's products as three fp16 MFMAs each (-1 default, 0) or the exact
 //                       fp32-MFMA kernel (1: the forward of the releases before the split-fp16 kernel, bit for bit)
 //   "gemm_exact" -1|0|1    fp32 mode: the full rounds of the large edge-row GEMM launches as three fp16 MFMAs per product (-1 default, 0;
-//                       gemm_p8s_kernel) or on the exact fp32-MFMA kernel (1; with "flash_exact" 1: the forward of the releases before, bit for bit)
+//                       gemm_p8s_kernel) or on the exact fp32-MFMA kernel (1); governs the 8-phase launches only
+//   "gemm_small_exact" -1|0|1  fp32 mode: the launches of the persistent GEMM kernel (tails, small launches, node rows) as three fp16 MFMAs
+//                       per product (-1 default, 0; gemm_f16s_kernel) or exact, and node rows exact on every kernel (1); independent of "gemm_exact"
+//   "pointnet_exact" -1|0|1  fp32 mode: conv2 / conv3 of the object encoder as three fp16 MFMAs per product (-1 default, 0;
+//                       pointnet_bf16_kernel<CIN, 5>) or the exact fp32-MFMA kernel (1)
+//                       ("flash_exact", "gemm_exact", "gemm_small_exact" and "pointnet_exact" all 1: the forward of the releases before the
+//                       split-fp16 kernels, bit for bit)
 //   "flash_bq_big" 0|1   half-row edge attention on plans whose scenes all have >= 4096 edges: 256 queries per block (1, default) or 128
 //   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes (default) / fp32 too
 //   "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2   gate kernel variants the tests compare bit for bit
@@ -89,6 +95,8 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "flash_pv_terms") h->flash_pv_terms = value == 2 ? 2 : 3;
     else if (k == "flash_exact") h->flash_exact = value < 0 ? -1 : value != 0;
     else if (k == "gemm_exact") h->gemm_exact = value < 0 ? -1 : value != 0;
+    else if (k == "pointnet_exact") h->pointnet_exact = value < 0 ? -1 : value != 0;
+    else if (k == "gemm_small_exact") h->gemm_small_exact = value < 0 ? -1 : value != 0;
     else if (k == "flash_bf16") h->flash_bf16 = value != 0;
     else if (k == "pointnet_bf16") h->pointnet_bf16 = value != 0;
     else if (k == "gate_bf16") h->gate_bf16 = value != 0;
@@ -226,7 +234,8 @@ int vlsat_k_split_f16s(const float* w, size_t n, uint16_t* hi, uint16_t* lo, int
 
 // vlsat_k_gemm as the fp32 precision mode runs an edge-row launch: the planes of a dense W [N,K] are made on the spot (allocates,
 // synchronises), the full rounds of a launch the planner sends to the 8-phase kernel run on its split-fp16 sibling, everything else on the
-// exact kernels.  p8_part_min: GemmArgs::p8_part_min (tests reach the 8-phase kernel with a few tiles).  relu_a: bit 0 only.
+// exact kernels.  p8_part_min >= 0: GemmArgs::p8_part_min (tests reach the 8-phase kernel with a few tiles); v < 0: GemmArgs::f16s = 2 -- the
+// launches of the persistent kernel run on their split-fp16 siblings as well -- with p8_part_min = -1 - v.  relu_a: bit 0 only.
 int vlsat_k_gemm_f16s(const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc, int32_t M, int32_t N,
                       int32_t K, const float* bias, const float* rowscale, const float* resid, int32_t ldr, float resid_scale,
                       const float* g0, const int32_t* gi0, int32_t ldg0, const float* g1, const int32_t* gi1, int32_t ldg1,
@@ -238,14 +247,15 @@ int vlsat_k_gemm_f16s(const float* A, int32_t lda, const float* W, int32_t ldw, 
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
     a.bias = bias; a.rowscale = rowscale; a.resid = resid; a.ldr = ldr; a.resid_scale = resid_scale;
     a.g0 = g0; a.gi0 = gi0; a.ldg0 = ldg0; a.g1 = g1; a.gi1 = gi1; a.ldg1 = ldg1; a.relu_a = relu_a & 1; a.act = act;
-    a.p8_part_min = p8_part_min < 0 ? 0 : p8_part_min;
+    const int f16s = p8_part_min < 0 ? 2 : 1;        // v < 0: the persistent kernel's launches on their siblings too, p8_part_min = -1 - v
+    a.p8_part_min = p8_part_min < 0 ? -1 - p8_part_min : p8_part_min;
     uint16_t *hi = nullptr, *lo = nullptr;
     VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&hi), n * 2 + 256));
     VLSAT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&lo), n * 2 + 256));
     int32_t k = 0;
     int r = vlsat_k_split_f16s(W, n, hi, lo, &k, stream);
     if (!r) {
-        a.f16s = 1; a.Wh16 = hi; a.Wl16 = lo; a.w_exp = k;
+        a.f16s = f16s; a.Wh16 = hi; a.Wl16 = lo; a.w_exp = k;
         r = launch_gemm(a, st);
     }
     hipStreamSynchronize(st);
@@ -835,7 +845,7 @@ int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32
                         const float* w2, const float* b2, const float* w3, const float* b3, int32_t n_out, int32_t terms,
                         float* out, void* stream) {
     if (!pts || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return fail(VLSAT_EINVAL, "pointnet_ex: null argument");
-    if (terms < 0 || terms > 3) return fail(VLSAT_EINVAL, "pointnet_ex: terms 0 (fp32) | 1 (bf16) | 2 (fp16) | 3 (split-bf16)");
+    if ((terms < 0 || terms > 3) && terms != 5) return fail(VLSAT_EINVAL, "pointnet_ex: terms 0 (fp32) | 1 (bf16) | 2 (fp16) | 3 (split-bf16) | 5 (split-fp16)");
     if (n_out <= 0) return fail(VLSAT_EINVAL, "pointnet_ex: n_out must be > 0");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (terms == 0) return launch_pointnet(pts, n_obj, n_points, cin, w1, b1, w2, b2, w3, b3, n_out, out, st);
@@ -845,14 +855,18 @@ int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32
     uint16_t* w2h = static_cast<uint16_t*>(planes.d);
     uint16_t *w2l = w2h + n2, *w3h = w2l + n2, *w3l = w3h + n3;
     int r;
-    if (terms == 2) {
+    int32_t k2 = 0, k3 = 0;
+    if (terms == 5) {                           // the fp32 mode's planes (gemm_f16s_planes.h) and their exponents
+        r = vlsat_k_split_f16s(w2, n2, w2h, w2l, &k2, stream);
+        if (!r) r = vlsat_k_split_f16s(w3, n3, w3h, w3l, &k3, stream);
+    } else if (terms == 2) {
         r = launch_to_f16(w2, n2, w2h, st);
         if (!r) r = launch_to_f16(w3, n3, w3h, st);
     } else {
         r = launch_split_bf16(w2, n2, w2h, w2l, st);
         if (!r) r = launch_split_bf16(w3, n3, w3h, w3l, st);
     }
-    if (!r) r = launch_pointnet_bf16(pts, n_obj, n_points, cin, w1, b1, w2h, w2l, b2, w3h, w3l, b3, n_out, terms, out, st);
+    if (!r) r = launch_pointnet_bf16(pts, n_obj, n_points, cin, w1, b1, w2h, w2l, b2, w3h, w3l, b3, n_out, terms, out, st, k2, k3);
     hipStreamSynchronize(st);     // test entry point only: the planes are freed right away
     return r;
 }

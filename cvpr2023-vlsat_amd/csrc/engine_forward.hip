@@ -118,12 +118,19 @@ static int gemm_resolve(vlsat_ctx* h, int ws_lane, GemmArgs& a, int prec_overrid
         a.Whi = it->second.first;
         a.Wlo = it->second.second;
     }
-    // fp32 mode: every launch that is not a node-row launch may run its full rounds on the split-fp16 sibling of the 8-phase kernel
-    // (launch_gemm_p8; tails and small launches stay exact) -- unless "gemm_exact" asks for the exact kernels
-    if (prec == 0 && h->prec_edge == 0 && h->gemm_exact != 1 && !(a.M == h->cur_N && !edge_fmt)) {
-        auto f = h->f16s.find(a.W);
-        if (f == h->f16s.end()) return fail(VLSAT_ESTATE, "gemm: weight has no split-fp16 planes");
-        a.f16s = 1; a.Wh16 = f->second.hi; a.Wl16 = f->second.lo; a.w_exp = f->second.k;
+    // fp32 mode: every launch may run on the split-fp16 siblings of the exact kernels (GemmArgs::f16s) -- the full rounds of an 8-phase launch
+    // (launch_gemm_p8) unless "gemm_exact" asks for the exact kernel, the persistent kernel's launches (tails, small launches, node rows;
+    // gemm_f16s_tiled_pick) unless "gemm_small_exact" does.  With "gemm_small_exact" 1 node-row launches are exact whatever they run on
+    // (the releases before the persistent kernel's siblings).  Split-K launches are always exact.
+    if (prec == 0 && h->prec_edge == 0) {
+        const bool node = a.M == h->cur_N && !edge_fmt;
+        const bool small = h->gemm_small_exact != 1, big = h->gemm_exact != 1 && !(node && !small);
+        const int f16s = small ? (big ? 2 : 3) : (big ? 1 : 0);
+        if (f16s) {
+            auto f = h->f16s.find(a.W);
+            if (f == h->f16s.end()) return fail(VLSAT_ESTATE, "gemm: weight has no split-fp16 planes");
+            a.f16s = f16s; a.Wh16 = f->second.hi; a.Wl16 = f->second.lo; a.w_exp = f->second.k;
+        }
     }
     if (h->half_f16) {                      // mode 5: the half-row format is fp16 (engine.h)
         if (a.r_split == 2) return fail(VLSAT_ESTATE, "gemm: a half-row residual is not built on fp16 (the LayerNorm adds it)");
@@ -641,6 +648,11 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
             }
             RUN(launch_pointnet_bf16(pts, N, p->P, h->d.dim_point, h->pn_w1, h->pn_b1, w2h, w2->second.second, h->pn_b2,
                                      w3h, w3->second.second, h->pn_b3, h->C_pt, terms, p->F, s));
+        } else if (h->prec == 0 && h->pointnet_exact != 1) {     // fp32 mode: conv2 / conv3 as three fp16 MFMAs per product, on the planes
+            auto w2 = h->f16s.find(h->pn_w2), w3 = h->f16s.find(h->pn_w3);      // split_all_weights made ("pointnet_exact" 1: the exact kernel)
+            if (w2 == h->f16s.end() || w3 == h->f16s.end()) return fail(VLSAT_ESTATE, "pointnet: weights have no split-fp16 planes");
+            RUN(launch_pointnet_bf16(pts, N, p->P, h->d.dim_point, h->pn_w1, h->pn_b1, w2->second.hi, w2->second.lo, h->pn_b2,
+                                     w3->second.hi, w3->second.lo, h->pn_b3, h->C_pt, 5, p->F, s, w2->second.k, w3->second.k));
         } else {
             RUN(launch_pointnet(pts, N, p->P, h->d.dim_point, h->pn_w1, h->pn_b1, h->pn_w2, h->pn_b2, h->pn_w3, h->pn_b3, h->C_pt, p->F, s));
         }

@@ -16,6 +16,7 @@
 #pragma once
 #include <type_traits>
 #include "common.h"
+#include "gemm_f16s_planes.h"
 #include "kernels.h"
 
 namespace vlsat {
@@ -376,6 +377,16 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 }
 
+template <int TM, int TN>
+__device__ __forceinline__ void scale_acc(f32x16 (&acc)[TM][TN], float f) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] *= f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Operand pipelines of the persistent GEMM (gemm_f32.hip): how a [BM|BN][32] k-slice travels
 // HBM -> registers -> LDS -> MFMA fragments.  PipeF32 is the exact-fp32 path above.
@@ -512,6 +523,38 @@ __device__ __forceinline__ f32x16 mfma_h(const bf16x8& a, const bf16x8& b, const
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// Split-fp16 operand of the fp32 mode (gemm_f16s_planes.h; the scheme of gemm_p8_kernel.h, FS): eight fp32 words -> Ah = f16(x) and
+// Al = f16((x - Ah) 2^11), x = the word clamped to [lower, 65504] (one v_med3: lower = 0 is the ReLU, -65504 none).  (x - Ah) 2^11 =
+// fma(Ah, -2^11, x 2^11) as ONE mixed-precision fma per word (v_fma_mixlo / mixhi_f16 on the halves of a register; hipcc does not select
+// them from C++): both products and their sum are exact in fp32, the only rounding is the one to fp16.
+// (one word: h = the fp16 bits of Ah = f16(x) in the low half, x already clamped -> Al in the low half of the result)
+__device__ __forceinline__ unsigned f16s_lo1(unsigned h, float x) {
+    unsigned r;
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "s"(-2048.f), "v"(x * 2048.f));      // 2^F16S_A_SHIFT
+    return r;
+}
+__device__ __forceinline__ void f16s_split8(const f32x4& x0, const f32x4& x1, float lower, bf16x8& hi, bf16x8& lo) {
+    typedef float f32x8_s __attribute__((ext_vector_type(8)));
+    typedef unsigned u32x4_s __attribute__((ext_vector_type(4)));
+    f32x8_s x;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { x[c] = __builtin_amdgcn_fmed3f(x0[c], lower, 65504.f); x[4 + c] = __builtin_amdgcn_fmed3f(x1[c], lower, 65504.f); }
+    const u32x4_s h = __builtin_bit_cast(u32x4_s, __builtin_convertvector(x, f16x8));
+    u32x4_s l;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        unsigned r = f16s_lo1(h[c], x[2 * c]);
+        asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(h[c]), "s"(-2048.f), "v"(x[2 * c + 1] * 2048.f));
+        l[c] = r;
+    }
+    hi = __builtin_bit_cast(bf16x8, h);
+    lo = __builtin_bit_cast(bf16x8, l);
+}
+// ... and the third operand of a product, Wh 2^-11, from a Wh fragment (exact for |Wh| >= 2^-3 or zero)
+__device__ __forceinline__ bf16x8 f16s_w_small(const bf16x8& wh) {
+    return __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8, wh) * (_Float16)0.00048828125f);
+}
+
 template <int BM, int BN, int TERMS>
 struct PipeBF16 {
     static constexpr bool PREFETCH = false;
@@ -614,9 +657,15 @@ struct PipeBF16 {
 template <int BM, int BN, int TERMS, int AFMT = 0>
 struct PipeSplitDma {
     static constexpr bool AS = AFMT == 1;
-    static constexpr bool AH = AFMT >= 2;             // (3: the half rows and the weight plane hold fp16, products on the f16 MFMA)
-    static constexpr bool F16 = AFMT == 3;
+    static constexpr bool AH = AFMT == 2 || AFMT == 3;             // (3: the half rows and the weight plane hold fp16, products on the f16 MFMA)
+    // 4 (FS, TERMS 3): the split-fp16 form of AFMT 0 for the fp32 mode -- fp32 A staged as for AFMT 0 and split on the fragment-read side into
+    // Ah | Al 2^11 (f16s_split8: its clamp does the ReLU, one body for both settings), the weight planes Wh16 / Wl16 of gemm_f16s_planes.h
+    // staged exactly like the bf16 ones (the stage bytes equal the fp32 pipe's), per 16-wide k-step the terms (Wh 2^-11).Al, Wl.Ah, Wh.Ah
+    // -- the order and the k sets of gemm_p8s_kernel.  The accumulator holds the product times 2^w_exp (the kernel scales inits and results).
+    static constexpr bool FS = AFMT == 4;
+    static constexpr bool F16 = AFMT == 3 || FS;
     static_assert(!AH || TERMS == 1, "half-row operands carry no low part");
+    static_assert(!FS || TERMS == 3, "the split-fp16 form has three terms");
     // With bf16 MFMAs a k-slice is 256 (bf16) to 768 (bf16x3) matrix-pipe cycles per wave, far less than the latency of
     // an A line that comes from HBM / the Infinity Cache, and LDS cannot hold enough slices in flight to cover it: the
     // kernel touches the A lines of the slice `prefetch` steps ahead (one dword per line into a dead register) so
@@ -662,7 +711,7 @@ struct PipeSplitDma {
         }
 #pragma unroll
         for (int pl = 0; pl < PL; ++pl) {
-            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(pl ? p.Wlo : p.Whi), 0, c.nw, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(FS ? (pl ? p.Wl16 : p.Wh16) : (pl ? p.Wlo : p.Whi)), 0, c.nw, 0x00020000);
             char* sw = stage + A_BYTES + pl * W_PLANE + wave * 16 * BK * 2;
 #pragma unroll
             for (int i = 0; i < BN / 64; ++i)
@@ -717,8 +766,47 @@ struct PipeSplitDma {
         }
     }
     static __device__ __forceinline__ void mma(const char* stage, int wm, int wn, f32x16 (&acc)[TM][TN], int lane, int relu_a = 0) {
+        if constexpr (FS) { mma_fs(stage, wm, wn, acc, lane, relu_a ? 0.f : -65504.f); return; }
         if (relu_a) mma_t<true>(stage, wm, wn, acc, lane);          // wave-uniform: two straight-line bodies, no per-element select
         else mma_t<false>(stage, wm, wn, acc, lane);
+    }
+    // FS: lower = the clamp's lower bound (0: ReLU-on-A)
+    static __device__ __forceinline__ void mma_fs(const char* stage, int wm, int wn, f32x16 (&acc)[TM][TN], int lane, float lower) {
+        const int li = lane & 31, hi = lane >> 5;
+        const float* sA = reinterpret_cast<const float*>(stage) + (wm * TM * 32 + li) * BK;
+        const char* sW = stage + A_BYTES + (wn * TN * 32 + li) * BK * 2;
+        const int swa = (li >> 1) & 7, sww = (li >> 2) & 3;
+#pragma unroll
+        for (int ks = 0; ks < BK / 16; ++ks) {
+            bf16x8 a[2][TM], w[2][TN], ws[TN];
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm) {
+                const int c0 = (4 * ks + 2 * hi) ^ swa;                   // as mma_t: the first four k, the next four at c0 ^ 1
+                const f32x4 x0 = *reinterpret_cast<const f32x4*>(sA + tm * 32 * BK + 4 * c0);
+                const f32x4 x1 = *reinterpret_cast<const f32x4*>(sA + tm * 32 * BK + 4 * (c0 ^ 1));
+                f16s_split8(x0, x1, lower, a[0][tm], a[1][tm]);
+            }
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn)
+                    w[pl][tn] = *reinterpret_cast<const bf16x8*>(sW + pl * W_PLANE + tn * 32 * BK * 2 + 16 * ((2 * ks + hi) ^ sww));
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) ws[tn] = f16s_w_small(w[0][tn]);
+            // term-major order, small terms first (the transposed product: weights are the first operand, see mma_slice)
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_h<true>(ws[tn], a[1][tm], acc[tm][tn]);
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_h<true>(w[1][tn], a[0][tm], acc[tm][tn]);
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_h<true>(w[0][tn], a[0][tm], acc[tm][tn]);
+        }
     }
     template <bool RELU>
     static __device__ __forceinline__ void mma_t(const char* stage, int wm, int wn, f32x16 (&acc)[TM][TN], int lane) {
@@ -777,5 +865,6 @@ template <int BM, int BN> struct PipeSel<BM, BN, 9> { using type = PipeSplitDma<
 template <int BM, int BN> struct PipeSel<BM, BN, 11> { using type = PipeSplitDma<BM, BN, 3, 1>; };
 template <int BM, int BN> struct PipeSel<BM, BN, 13> { using type = PipeSplitDma<BM, BN, 1, 2>; };  // ... A as half rows (bf16)
 template <int BM, int BN> struct PipeSel<BM, BN, 15> { using type = PipeSplitDma<BM, BN, 1, 3>; };  // ... A as half rows of fp16, fp16 weight plane
+template <int BM, int BN> struct PipeSel<BM, BN, 17> { using type = PipeSplitDma<BM, BN, 3, 4>; };  // internal: split-fp16 on fp32 A (the fp32 mode's sibling kernel, gemm_f16s_kernel)
 
 }  // namespace vlsat

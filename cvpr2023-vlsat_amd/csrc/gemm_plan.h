@@ -58,8 +58,9 @@ struct GemmArgs {
     float* sk_ws = nullptr; size_t sk_ws_floats = 0;
     unsigned* sk_counters = nullptr; size_t sk_n_counters = 0;
     // split-fp16 form of the exact-fp32 8-phase launch (prec 0 only; gemm_p8s_pick): fp16 planes Wh16 = f16(W 2^w_exp), Wl16 = f16(W 2^w_exp - Wh16)
-    // of the weight tensor ([N,K], pitch ldw; gemm_f16s_planes.h), fp32 tensors in and out, three f16 MFMAs per product.  Every other kernel
-    // a launch may get (tails, small launches) ignores these fields and stays exact.
+    // of the weight tensor ([N,K], pitch ldw; gemm_f16s_planes.h), fp32 tensors in and out, three f16 MFMAs per product.  f16s = 1: the 8-phase
+    // launches only, every other kernel a launch may get (tails, small launches) stays exact; 2: the persistent kernel's launches too, on
+    // gemm_f16s_kernel (gemm_f16s_tiled_pick); 3: those only.  Split-K launches always stay exact.
     int f16s = 0;
     const uint16_t* Wh16 = nullptr;
     const uint16_t* Wl16 = nullptr;
@@ -190,10 +191,14 @@ constexpr int gemm_p8s_find(int add, bool relu) {
         if (kGemmP8sVariants[i].add == add && kGemmP8sVariants[i].relu == relu) return i;
     return -1;
 }
-// The sibling that runs row `variant` of the 8-phase list for a launch with GemmArgs::f16s set, or -1: the row itself runs.  The one
+// GemmArgs::f16s: which exact-fp32 launches of a problem run on their split-fp16 sibling -- 1 the 8-phase launches, 2 those and the
+// persistent kernel's, 3 the persistent kernel's only (the split-K launches always stay exact)
+inline bool gemm_f16s_p8(const GemmArgs& a) { return a.f16s == 1 || a.f16s == 2; }
+inline bool gemm_f16s_tiled(const GemmArgs& a) { return a.f16s == 2 || a.f16s == 3; }
+// The sibling that runs row `variant` of the 8-phase list for a launch with GemmArgs::f16s 1 or 2, or -1: the row itself runs.  The one
 // place that decides it (launch_gemm_p8 asks; a pair of problems never is an 8-phase launch, gemm_pair_plan).
 inline int gemm_p8s_pick(const GemmArgs& a, int variant) {
-    if (!a.f16s || variant < 0 || variant >= kGemmP8Count) return -1;
+    if (!gemm_f16s_p8(a) || variant < 0 || variant >= kGemmP8Count) return -1;
     const GemmP8Variant& v = kGemmP8Variants[variant];
     return v.mode == 1 && v.abl == 0 ? gemm_p8s_find(v.add, v.relu) : -1;
 }
@@ -256,6 +261,31 @@ inline GemmPick gemm_tiled_pick(const GemmArgs& a, bool relu_a, bool twin = fals
     const int i = gemm_tiled_find(gemm_add_mode(a), pipe.index);
     if (i < 0) return {-1, "gemm: this precision / additive-operand combination is not built"};
     return twin && !kGemmTiledVariants[i].twin ? GemmPick{-1, "gemm: no twin form"} : GemmPick{i, nullptr};
+}
+// Split-fp16 siblings of the persistent kernel's exact-fp32 rows (PREC 0 / 4): X(ADD) = gemm_f16s_kernel<.., ADD, 17, ..> on every tile of
+// kGemmTiles and as a twin.  One pipe for both ReLU-on-A settings (its clamp does the ReLU).  A sibling takes the launch as planned: same
+// tile, grid and rows.
+#define VLSAT_GEMM_F16S_TILED_VARIANTS(X) X(0) X(1) X(6)
+#define VLSAT_ROW(A) A,
+constexpr int kGemmF16sTiledAdds[] = {VLSAT_GEMM_F16S_TILED_VARIANTS(VLSAT_ROW)};
+#undef VLSAT_ROW
+constexpr int kGemmF16sTiledCount = (int)(sizeof kGemmF16sTiledAdds / sizeof kGemmF16sTiledAdds[0]);
+// The sibling that runs row `variant` of the persistent kernel's list for a launch, or -1 and the reason: the row itself (the exact
+// kernel) runs.  ReLU-on-A does not enter: one sibling serves both settings, of one problem or of a pair.  Not built for: the VGPR-staged pipe where it was picked for anything but ReLU-on-A (operands
+// beyond 32-bit offsets, additive modes 2-5 and 7, GemmArgs::no_dma), operand formats, fewer than 64 output columns (less than one column
+// tile: such a launch is bound by its latency, not by the matrix pipe).  K: a multiple of 32 like every launch; the planes need ldw % 8 == 0
+// (gemm_invalid).  The one place that decides it (launch_tiled asks, for single and paired launches).
+inline GemmPick gemm_f16s_tiled_pick(const GemmArgs& a, int variant) {
+    if (!gemm_f16s_tiled(a)) return {-1, "gemm_f16s: not asked for"};
+    if (variant < 0 || variant >= kGemmTiledCount) return {-1, "gemm_f16s: no planned row"};
+    const GemmTiledVariant& v = kGemmTiledVariants[variant];
+    if (v.prec != 0 && v.prec != 4) return {-1, "gemm_f16s: the siblings are those of the exact-fp32 rows"};
+    if (a.prec != 0 || a.a_split || a.r_split || a.c_split || a.c_scale != 1.f || a.c_f16_cols || a.g_f16) return {-1, "gemm_f16s: fp32 tensors in and out"};
+    if (gemm_pipe_prec(a, false, true).index != 4) return {-1, "gemm_f16s: needs the LDS-direct pipe (32-bit offsets, additive operands none | residual | both gathered rows)"};
+    if (a.N < 64) return {-1, "gemm_f16s: fewer than 64 output columns"};
+    for (int i = 0; i < kGemmF16sTiledCount; ++i)
+        if (kGemmF16sTiledAdds[i] == v.add) return {i, nullptr};
+    return {-1, "gemm_f16s: additive-operand combination not built"};
 }
 
 // ---- split-K kernel: X(PREC), the PipeSel code; every row single and as a twin, every additive mode ----

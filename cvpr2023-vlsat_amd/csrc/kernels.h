@@ -29,10 +29,11 @@ int launch_pointnet(const float* pts, int n_obj, int n_points, int cin, const fl
                     float* out, hipStream_t s);
 
 // the same on the bf16 matrix cores (pointnet_bf16.hip): conv2 / conv3 weights as bf16 hi / lo planes ([128,64], [n_out,128]);
-// terms = 3 split-bf16 | 1 single-rounded (the lo planes are then not read)
+// terms = 3 split-bf16 | 1 single-rounded (the lo planes are then not read) | 2 single-rounded fp16 | 5 split-fp16 (the fp32 mode: the
+// planes are the fp16 ones of gemm_f16s_planes.h, k2 / k3 their tensors' exponents; fp32-grade results)
 int launch_pointnet_bf16(const float* pts, int n_obj, int n_points, int cin, const float* w1, const float* b1,
                          const uint16_t* w2h, const uint16_t* w2l, const float* b2, const uint16_t* w3h, const uint16_t* w3l,
-                         const float* b3, int n_out, int terms, float* out, hipStream_t s);
+                         const float* b3, int n_out, int terms, float* out, hipStream_t s, int k2 = 0, int k3 = 0);
 
 // ---- edge cross-attention (flash style, fp32 MFMA) ----
 // tiles: device array of int4 {row_base, n_tokens, q0, head}; one block per entry.

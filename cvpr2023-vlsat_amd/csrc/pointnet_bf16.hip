@@ -13,7 +13,19 @@
 //                     registers; epilogue relu + running column max in registers
 // The H / W2 pitches are 16 B off a multiple of 128 B: conflict-free ds_read_b128 fragment reads.
 // The bf16 planes of W2 / W3 are the ones vlsat_set_gemm_precision makes for every GEMM weight.
+//
+// TERMS = 5 (FS): the split-fp16 form of TERMS = 3 for the fp32 precision mode, the number scheme of gemm_p8s_kernel (gemm_p8_kernel.h, FS;
+// gemm_f16s_planes.h) -- fp32-grade results on the 16-bit matrix pipe.  The LDS image, staging, chunk walk and merge are TERMS = 3's; the
+// differences:
+//   * the H1 / H2 planes hold  Ah = f16(x)  and  Al = f16((x - Ah) 2^11),  x = the activation clamped to [0, 65504] (one v_med3: its
+//     lower bound is the ReLU)
+//   * the weight planes are the fp16 ones of the tensor:  Wh = f16(W 2^k),  Wl = f16(W 2^k - Wh);  the third operand Wh 2^-11 is made from
+//     the Wh fragment by packed fp16 multiplies
+//   * three v_mfma_f32_32x32x16_f16 per product into one fp32 accumulator, small terms first: (Wh 2^-11).Al, Wl.Ah, Wh.Ah
+//   * the accumulator is the layer's result times 2^k: the epilogues multiply by 2^-k of the layer's tensor (inv2 / inv3, exact) before
+//     bias and ReLU
 #include "gemm_core.h"
+#include "gemm_f16s_planes.h"
 #include "kernels.h"
 
 namespace vlsat {
@@ -48,13 +60,29 @@ __device__ __forceinline__ void store8(char* plane0, int plane_stride, int off, 
     }
 }
 
+// FS: one 16-wide k-step of a product, the terms in the order (Wh 2^-11).Al, Wl.Ah, Wh.Ah (the split and Wh 2^-11: gemm_core.h)
+__device__ __forceinline__ f32x16 mma_f16s(const bf16x8& ah, const bf16x8& al, const bf16x8& wh, const bf16x8& wl, f32x16 acc) {
+    acc = mfma_h<true>(al, f16s_w_small(wh), acc);
+    acc = mfma_h<true>(ah, wl, acc);
+    return mfma_h<true>(ah, wh, acc);
+}
+
+// FS: eight activations -> the Ah and Al plane pieces (the clamp's lower bound 0 is the ReLU)
+__device__ __forceinline__ void store8_f16s(char* plane0, int plane_stride, int off, const f32x4& a, const f32x4& b) {
+    bf16x8 h, l;
+    f16s_split8(a, b, 0.f, h, l);
+    *reinterpret_cast<bf16x8*>(plane0 + off) = h;
+    *reinterpret_cast<bf16x8*>(plane0 + plane_stride + off) = l;
+}
+
 template <int CIN, int TERMS>
 __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
     const float* __restrict__ pts, int P, const float* __restrict__ w1, const float* __restrict__ b1,
     const uint16_t* __restrict__ w2h, const uint16_t* __restrict__ w2l, const float* __restrict__ b2,
     const uint16_t* __restrict__ w3h, const uint16_t* __restrict__ w3l, const float* __restrict__ b3, int n_out,
-    float* __restrict__ out, int nsplit) {
-    constexpr int PL = TERMS == 3 ? 2 : 1;
+    float* __restrict__ out, int nsplit, float inv2, float inv3) {
+    constexpr bool FS = TERMS == 5;              // split-fp16 (w2h / w2l / w3h / w3l are the fp16 planes of W 2^k; inv2 / inv3 = 2^-k)
+    constexpr int PL = TERMS == 3 || FS ? 2 : 1;
     constexpr bool F16 = TERMS == 2;             // fp16 operands (w2h / w3h are then fp16 planes)
     constexpr int S1 = (CIN + 4) & ~3;
     constexpr int WREG = 2 * PL * PB_W3 > PL * PB_W ? 2 * PL * PB_W3 : PL * PB_W;      // conv2: [PL][128][144]; conv3: 2 stages of [PL][128][80]
@@ -121,8 +149,13 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
                     for (int k = CIN - 1; k >= 0; --k) a = fmaf(w[k], xin[k], a);
                     hq[c4][c] = fmaxf(a, 0.f);
                 }
-            store8<PL, F16>(sH, PB_H, pp * PB_P1 + cg * 2, hq[0], hq[1]);
-            store8<PL, F16>(sH, PB_H, pp * PB_P1 + cg * 2 + 16, hq[2], hq[3]);
+            if constexpr (FS) {
+                store8_f16s(sH, PB_H, pp * PB_P1 + cg * 2, hq[0], hq[1]);
+                store8_f16s(sH, PB_H, pp * PB_P1 + cg * 2 + 16, hq[2], hq[3]);
+            } else {
+                store8<PL, F16>(sH, PB_H, pp * PB_P1 + cg * 2, hq[0], hq[1]);
+                store8<PL, F16>(sH, PB_H, pp * PB_P1 + cg * 2 + 16, hq[2], hq[3]);
+            }
         }
         // ---- W2 planes [128][64] -> LDS (pitch 144): 128 rows x 8 pieces = 1024 pieces per plane ----
 #pragma unroll
@@ -147,6 +180,11 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
 #pragma unroll
                 for (int tn = 0; tn < 2; ++tn) {
                     const bf16x8 bh = *reinterpret_cast<const bf16x8*>(bp + tn * 32 * PB_PW2 + 32 * ks);
+                    if constexpr (FS) {
+                        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(bp + PB_W + tn * 32 * PB_PW2 + 32 * ks);
+                        acc[tn] = mma_f16s(ah, al, bh, bl, acc[tn]);
+                        continue;
+                    }
                     if (PL == 2) {
                         const bf16x8 bl = *reinterpret_cast<const bf16x8*>(bp + PB_W + tn * 32 * PB_PW2 + 32 * ks);
                         acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[tn], 0, 0, 0);
@@ -165,6 +203,15 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
             const float bb = b2[col];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                if constexpr (FS) {
+                    char* dst = sH + (wm * 32 + crow32(r, hi)) * PB_P2 + col * 2;
+                    const float x = __builtin_amdgcn_fmed3f(acc[tn][r] * inv2 + bb, 0.f, 65504.f);
+                    const _Float16 xh = (_Float16)x;
+                    const unsigned hb = __builtin_bit_cast(unsigned short, xh);
+                    *reinterpret_cast<_Float16*>(dst) = xh;
+                    *reinterpret_cast<unsigned short*>(dst + PB_H) = (unsigned short)f16s_lo1(hb, x);
+                    continue;
+                }
                 const float v = fmaxf(acc[tn][r] + bb, 0.f);
                 char* dst = sH + (wm * 32 + crow32(r, hi)) * PB_P2 + col * 2;
                 if constexpr (F16) { *reinterpret_cast<_Float16*>(dst) = (_Float16)fminf(v, 65504.f); continue; }
@@ -195,6 +242,11 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
 #pragma unroll
                 for (int tn = 0; tn < 2; ++tn) {
                     const bf16x8 bh = *reinterpret_cast<const bf16x8*>(bp + tn * 32 * PB_PW3 + po);
+                    if constexpr (FS) {
+                        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(bp + 128 * PB_PW3 + tn * 32 * PB_PW3 + po);
+                        acc[tn] = mma_f16s(ah, al, bh, bl, acc[tn]);
+                        continue;
+                    }
                     if (PL == 2) {
                         const bf16x8 bl = *reinterpret_cast<const bf16x8*>(bp + 128 * PB_PW3 + tn * 32 * PB_PW3 + po);
                         acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[tn], 0, 0, 0);
@@ -209,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
                     const float bb = b3[nc * 128 + wn * 64 + tn * 32 + li];
                     float m = 0.f;                                   // relu folded into the max with 0
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) m = fmaxf(m, acc[tn][r] + bb);
+                    for (int r = 0; r < 16; ++r) m = fmaxf(m, FS ? acc[tn][r] * inv3 + bb : acc[tn][r] + bb);
                     m = half_max(m);
 #pragma unroll
                     for (int q = 0; q < PB_MAXNC; ++q)
@@ -244,19 +296,21 @@ __global__ __launch_bounds__(512, 2) void pointnet_bf16_kernel(
 
 int launch_pointnet_bf16(const float* pts, int n_obj, int n_points, int cin, const float* w1, const float* b1,
                          const uint16_t* w2h, const uint16_t* w2l, const float* b2, const uint16_t* w3h, const uint16_t* w3l,
-                         const float* b3, int n_out, int terms, float* out, hipStream_t s) {
+                         const float* b3, int n_out, int terms, float* out, hipStream_t s, int k2, int k3) {
     if (n_obj <= 0) return 0;
     if (n_points <= 0) return fail(-1, "pointnet: n_points must be > 0");
     if (n_out % 128 || n_out > 128 * PB_MAXNC) return fail(-1, "pointnet: n_out must be a multiple of 128, <= 768");
-    if (terms != 1 && terms != 2 && terms != 3) return fail(-1, "pointnet_bf16: terms must be 1, 3 or 2 (single-rounded fp16)");
+    if (terms != 1 && terms != 2 && terms != 3 && terms != 5) return fail(-1, "pointnet_bf16: terms must be 1, 3, 2 (single-rounded fp16) or 5 (split-fp16)");
+    if (terms == 5 && (k2 < -F16S_K_MAX || k2 > F16S_K_MAX || k3 < -F16S_K_MAX || k3 > F16S_K_MAX)) return fail(-1, "pointnet_bf16: plane exponent out of range");
+    const float inv2 = terms == 5 ? f16s_pow2(-k2) : 1.f, inv3 = terms == 5 ? f16s_pow2(-k3) : 1.f;
     const int n_chunks = (n_points + PB_M - 1) / PB_M;
     int nsplit = (256 + n_obj - 1) / n_obj;
     if (nsplit > n_chunks) nsplit = n_chunks;
     if (nsplit < 1) nsplit = 1;
     if (nsplit > 1 && launch_zero_f32(out, (size_t)n_obj * n_out, s)) return -1;
 #define VLSAT_PB(CIN, T) hipLaunchKernelGGL((pointnet_bf16_kernel<CIN, T>), dim3(n_obj * nsplit), dim3(512), 0, s, pts, n_points, w1, b1, \
-                                            w2h, w2l, b2, w3h, w3l, b3, n_out, out, nsplit)
-#define VLSAT_PB_CASE(CIN) case CIN: if (terms == 3) VLSAT_PB(CIN, 3); else if (terms == 2) VLSAT_PB(CIN, 2); else VLSAT_PB(CIN, 1); break;
+                                            w2h, w2l, b2, w3h, w3l, b3, n_out, out, nsplit, inv2, inv3)
+#define VLSAT_PB_CASE(CIN) case CIN: if (terms == 5) VLSAT_PB(CIN, 5); else if (terms == 3) VLSAT_PB(CIN, 3); else if (terms == 2) VLSAT_PB(CIN, 2); else VLSAT_PB(CIN, 1); break;
     switch (cin) {
         VLSAT_PB_CASE(3) VLSAT_PB_CASE(6) VLSAT_PB_CASE(9)
         default: return fail(-1, "pointnet: point channels must be 3, 6 or 9");

@@ -296,7 +296,9 @@ int vlsat_k_dist_bias(const float* desc, int32_t ld_desc, const int64_t* node_pt
 /* vlsat_k_pointnet for every encoder kernel and operand form: pts [N,cin,P] with cin in {3, 6, 9} (W1 [64,cin]), n_out a
  * multiple of 128 up to 768.  terms: 0 = the fp32 kernel; 1 / 2 / 3 = the matrix-core kernel of the 16-bit modes with conv2 /
  * conv3 operands as single-rounded bf16 / single-rounded fp16 (clamped to +-65504) / split bf16 (hi + lo, three MFMAs per
- * product); conv1, the biases, the ReLUs and the max stay fp32.  The planes of W2 / W3 are made on the spot from the fp32
+ * product); 5 = the same kernel as the fp32 precision mode runs it: split fp16 -- activations as fp16 hi + (lo 2^11), clamped to 65504,
+ * the weights as the planes of vlsat_k_split_f16s, three f16 MFMAs per product, the exact kernel's error against fp64 (4 is refused);
+ * conv1, the biases, the ReLUs and the max stay fp32.  The planes of W2 / W3 are made on the spot from the fp32
  * weights (terms != 0: allocates, synchronises). */
 int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32_t cin,
                         const float* w1, const float* b1, const float* w2, const float* b2,

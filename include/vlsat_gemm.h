@@ -25,6 +25,10 @@ int vlsat_k_split_f16s(const float* w, size_t n, uint16_t* hi, uint16_t* lo, int
  * fp32 accumulator -- A as fp16 hi + (lo 2^11), the weights as the planes above -- 0.5 to 1 times the exact kernel's error against fp64.
  * Every other row (tail launches, small launches) is the exact kernel's, bit for bit.  W must be dense [N,K] (ldw == K): its planes
  * are made on the spot (allocates, synchronises).
+ * p8_part_min = v < 0: the bound is -1 - v (so -1 keeps the built-in one), and the launches of the persistent kernel -- tails, small launches,
+ * node rows -- run on ITS split-fp16 siblings as well (gemm_f16s_kernel: same tiles and grids, same arithmetic), as the fp32 mode's forward
+ * runs them: N >= 64, additive operands none | residual | both gathered rows, operands within 32-bit byte offsets; anything else, and every
+ * split-K launch, stays the exact kernel's, bit for bit.
  * Domain: |A| <= 65504 -- beyond, the operand saturates at +-65504 and results stay finite (no Inf or NaN from finite input);
  * weights below 2^-16 of their tensor's largest lose low bits. */
 int vlsat_k_gemm_f16s(const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc, int32_t M, int32_t N,
