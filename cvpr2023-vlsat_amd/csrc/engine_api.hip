@@ -498,8 +498,12 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
                       const int64_t* gt_rel, const int64_t* edges, int32_t n_nodes, int32_t n_edges, int32_t n_rel_class,
                       int32_t n_scenes, uint64_t* counts, void* stream) {
     if (!counts || n_nodes < 0 || n_edges < 0) return fail(VLSAT_EINVAL, "eval_counts: bad argument");
-    if (n_nodes > 0 && (!obj_rank_3d || !obj_rank_2d || !gt_class)) return fail(VLSAT_EINVAL, "eval_counts: null node argument");
-    if (n_edges > 0 && (!rel_rank_3d || !rel_rank_2d || !tri_rank_3d || !tri_rank_2d || !cnt || !gt_rel || !edges || !gt_class || !obj_rank_3d))
+    // the three 2D tables go together: all NULL counts the 3D branch alone (a table without rows -- n_nodes / n_edges = 0 -- is not looked at)
+    const bool two = obj_rank_2d || rel_rank_2d || tri_rank_2d;
+    if (two && ((n_nodes > 0 && !obj_rank_2d) || (n_edges > 0 && (!rel_rank_2d || !tri_rank_2d))))
+        return fail(VLSAT_EINVAL, "eval_counts: the 2D rank tables go together (obj, rel and tri: all, or none for the 3D branch alone)");
+    if (n_nodes > 0 && (!obj_rank_3d || !gt_class)) return fail(VLSAT_EINVAL, "eval_counts: null node argument");
+    if (n_edges > 0 && (!rel_rank_3d || !tri_rank_3d || !cnt || !gt_rel || !edges || !gt_class || !obj_rank_3d))
         return fail(VLSAT_EINVAL, "eval_counts: null edge argument");
     return launch_eval_counts(obj_rank_3d, obj_rank_2d, rel_rank_3d, rel_rank_2d, tri_rank_3d, tri_rank_2d, cnt, gt_class, gt_rel, edges,
                               n_nodes, n_edges, n_rel_class, n_scenes, reinterpret_cast<unsigned long long*>(counts),
@@ -510,7 +514,8 @@ int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank
                              const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int32_t n_edges, int32_t n_obj_class,
                              int32_t n_rel_class, uint64_t* counts, void* stream) {
     if (!counts || n_edges < 0) return fail(VLSAT_EINVAL, "eval_triplet_split: bad argument");
-    if (n_edges > 0 && (!tri_rank_3d || !tri_rank_2d || !cnt || !gt_class || !gt_rel || !edges || !table))
+    // (tri_rank_2d NULL: the 3D half of counts alone)
+    if (n_edges > 0 && (!tri_rank_3d || !cnt || !gt_class || !gt_rel || !edges || !table))
         return fail(VLSAT_EINVAL, "eval_triplet_split: null edge argument");
     return launch_eval_triplet_split(tri_rank_3d, tri_rank_2d, cnt, gt_class, gt_rel, edges, table, n_edges, n_obj_class, n_rel_class,
                                      reinterpret_cast<unsigned long long*>(counts), static_cast<hipStream_t>(stream));
@@ -525,6 +530,8 @@ int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank
 // Top-k bounds and threshold are process_val's constants (topk 11 / 6 / 101, 0.5: reference :463-472).
 // MODEL.multi_rel_outputs only (the single-label variant ranks exp(log-softmax) in a second pass: use the separate entry points).
 // split_table / split_counts (vlsat_process_val_counts_split): the zero-shot split of the triplet ranks is counted as well.
+// obj_2d_feats NULL: the 3D-only step -- vlsat_forward without its 2D outputs, one softmax, one ranking pass, the one-branch counts and
+// split; the 2D blocks of counts / split_counts are not touched and the plan's scratch is the same (its 2D halves stay unused).
 static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
                               const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2, int32_t n_scenes,
                               uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts, void* stream) {
@@ -535,18 +542,21 @@ static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_poi
     if (E > 0 && (!gt_rel || !edges_e2)) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: null edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const EvalScratch v = eval_scratch_carve(p->ev_f, p->ev_i, N, E, C, R);        // (sorted: [N, min(C, 101)] of it)
-    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, v.obj2, v.rel3, v.rel2, stream));
-    for (int br = 0; br < 2; ++br) {
+    // obj_2d_feats NULL: the 3D-only step -- the 3D-only forward, one softmax, one ranking pass, the one-branch counts (and split); the 2D
+    // halves of the scratch are not touched, the 2D blocks of counts / split_counts neither
+    const bool do2d = obj_2d_feats != nullptr;
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, do2d ? v.obj2 : nullptr, v.rel3, do2d ? v.rel2 : nullptr, stream));
+    for (int br = 0; br < (do2d ? 2 : 1); ++br) {
         const float* lg = br ? v.obj2 : v.obj3;
         float* pr = br ? v.prob2 : v.prob3;
         RUN(launch_softmax_rows(lg, C, N, C, pr, 0, s));
         RUN(launch_eval_ranks(lg, pr, br ? v.rel2 : v.rel3, gt_class, gt_rel, edges_e2, N, E, C, R, 11, 6, 101, 0.5f, br ? v.or2 : v.or3,
                               br ? v.rr2 : v.rr3, br ? v.tr2 : v.tr3, br ? v.cn2 : v.cn3, v.sorted, s));
     }
-    RUN(launch_eval_counts(v.or3, v.or2, v.rr3, v.rr2, v.tr3, v.tr2, v.cn3, gt_class, gt_rel, edges_e2, N, E, R, n_scenes,
-                           reinterpret_cast<unsigned long long*>(counts), s));
+    RUN(launch_eval_counts(v.or3, do2d ? v.or2 : nullptr, v.rr3, do2d ? v.rr2 : nullptr, v.tr3, do2d ? v.tr2 : nullptr, v.cn3, gt_class, gt_rel,
+                           edges_e2, N, E, R, n_scenes, reinterpret_cast<unsigned long long*>(counts), s));
     if (split_counts)
-        RUN(launch_eval_triplet_split(v.tr3, v.tr2, v.cn3, gt_class, gt_rel, edges_e2, split_table, E, C, R,
+        RUN(launch_eval_triplet_split(v.tr3, do2d ? v.tr2 : nullptr, v.cn3, gt_class, gt_rel, edges_e2, split_table, E, C, R,
                                       reinterpret_cast<unsigned long long*>(split_counts), s));
     VLSAT_HIP_CHECK(hipEventRecord(p->last_use, s));       // (the scratch is the plan's: its next owner orders behind the counting)
     return 0;
@@ -603,6 +613,7 @@ int vlsat_scene_graph_topk(const float* obj_probs, const float* rel_probs, const
 // scratch, and the candidate slots (8 bytes x topk_each per edge) in Hbig, the 4 KB-per-edge hidden buffer that is dead once the
 // forward has finished -- the arena does not grow.  With MODEL.multi_rel_outputs = false the log-probabilities are exponentiated
 // in place first.
+// obj_2d_feats and the three 2D outputs go together: all NULL runs the 3D-only forward and one selection; a mixture is refused.
 int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan p, const float* obj_points, const float* obj_2d_feats, const float* descriptor,
                               const int64_t* edges_e2, int32_t n_scenes, int32_t mode, int32_t top_k, int32_t topk_each,
                               int32_t* triplets_3d, float* scores_3d, int32_t* n_valid_3d, int32_t* triplets_2d, float* scores_2d,
@@ -612,13 +623,17 @@ int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan p, const float* obj_poi
     const int N = (int)p->N, E = (int)p->E, C = h->d.n_obj_class, R = h->d.n_rel_class;
     RUN(scene_graph_check_args(C, R, mode, top_k, topk_each));
     if (n_scenes != p->S) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: n_scenes is not the plan's scene count");
-    if (!triplets_3d || !scores_3d || !n_valid_3d || !triplets_2d || !scores_2d || !n_valid_2d)
-        return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null output");
+    if (!triplets_3d || !scores_3d || !n_valid_3d) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null 3D output");
+    const bool any2 = triplets_2d || scores_2d || n_valid_2d;
+    const bool all2 = triplets_2d && scores_2d && n_valid_2d;
+    const bool do2d = obj_2d_feats != nullptr;
+    if (do2d ? !all2 : any2)
+        return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: obj_2d_feats and the three 2D outputs go together (all, or none for 3D-only)");
     if (E > 0 && !edges_e2) return fail(VLSAT_EINVAL, "vlsat_forward_scene_graph: null edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const EvalScratch v = eval_scratch_carve(p->ev_f, p->ev_i, N, E, C, R);
-    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, v.obj2, v.rel3, v.rel2, stream));
-    for (int br = 0; br < 2; ++br) {
+    RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, do2d ? v.obj2 : nullptr, v.rel3, do2d ? v.rel2 : nullptr, stream));
+    for (int br = 0; br < (do2d ? 2 : 1); ++br) {
         float* lg = br ? v.obj2 : v.obj3;
         float* pr = br ? v.prob2 : v.prob3;
         float* rl = br ? v.rel2 : v.rel3;

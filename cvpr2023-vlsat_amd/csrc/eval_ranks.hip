@@ -320,7 +320,10 @@ int launch_scene_checksums(const float* obj3d, const float* obj2d, long N, int C
 // 64-bit integer atomics: the result does not depend on timing, so scenes may be accumulated from concurrent streams.
 // The host path (evaluate.accumulate, numpy) stays as the reference-compatible one; this kernel keeps a one-scene-per-call
 // evaluation loop free of host round trips.  Integer / latency work.
+// NBR = 2: both branches; NBR = 1: the 3D branch alone (the 2D rank tables are not read, the 2D block of the block histogram stays zero
+// and the flush, which skips zero counters, leaves the 2D block of `out` untouched) -- compiled, not tested per slot.
 constexpr int CNT_MAX_R = 32;
+template <int NBR>
 __global__ __launch_bounds__(256) void eval_counts_kernel(const int32_t* __restrict__ obj_rank3, const int32_t* __restrict__ obj_rank2,
                                                           const int32_t* __restrict__ rel_rank3, const int32_t* __restrict__ rel_rank2,
                                                           const int32_t* __restrict__ tri_rank3, const int32_t* __restrict__ tri_rank2,
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(256) void eval_counts_kernel(const int32_t* __restr
     if (t < N) {
         const int32_t* ranks[2] = {obj_rank3, obj_rank2};
 #pragma unroll
-        for (int br = 0; br < 2; ++br) {
+        for (int br = 0; br < NBR; ++br) {
             unsigned* b = s_h + 1 + R + br * per_br;
             const int r = ranks[br][t];
             atomicAdd(b + 0, 1u);
@@ -365,7 +368,7 @@ __global__ __launch_bounds__(256) void eval_counts_kernel(const int32_t* __restr
             const int32_t* rr[2] = {rel_rank3, rel_rank2};
             const int32_t* tt[2] = {tri_rank3, tri_rank2};
 #pragma unroll
-            for (int br = 0; br < 2; ++br) {
+            for (int br = 0; br < NBR; ++br) {
                 unsigned* b = s_h + 1 + R + br * per_br;
                 const int r = rr[br][(size_t)t * R + j], tr = tt[br][(size_t)t * R + j];
                 atomicAdd(b + 4, 1u);
@@ -409,8 +412,10 @@ int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const
     if (n <= 0 && n_scenes <= 0) return 0;
     const int n_out = 1 + R + 2 * (11 + 6 * R);
     const int grid = n > 0 ? (n + 255) / 256 : 1;
-    hipLaunchKernelGGL(eval_counts_kernel, dim3(grid), dim3(256), (n_out + R + 1) * sizeof(unsigned), s, obj_rank3, obj_rank2, rel_rank3,
-                       rel_rank2, tri_rank3, tri_rank2, cnt, gt_cls, gt_rel, edges, N, E, R, n_scenes, out);
+    const bool two = obj_rank2 || rel_rank2 || tri_rank2;      // (all NULL: the 3D branch alone; the entry point refuses a mixture)
+    if (two && ((N > 0 && !obj_rank2) || (E > 0 && (!rel_rank2 || !tri_rank2)))) return fail(-1, "eval_counts: the 2D rank tables go together");
+    hipLaunchKernelGGL(two ? eval_counts_kernel<2> : eval_counts_kernel<1>, dim3(grid), dim3(256), (n_out + R + 1) * sizeof(unsigned), s, obj_rank3,
+                       obj_rank2, rel_rank3, rel_rank2, tri_rank3, tri_rank2, cnt, gt_cls, gt_rel, edges, N, E, R, n_scenes, out);
     VLSAT_LAUNCH_CHECK("eval_counts");
     return 0;
 }
@@ -425,7 +430,9 @@ int launch_eval_counts(const int32_t* obj_rank3, const int32_t* obj_rank2, const
 // a per-edge predicate bit mask in LDS (a thread walking its own 208-byte row stalls on every load: 21 us per 1 560-edge scene);
 // every later read of a thread (node classes, table bytes, rank slots) then has a known address.  Per-thread counts are packed two
 // to a word (16 bits each: <= 64 lanes x 32 slots), summed across the wave with shuffles, one LDS atomic per counter and wave, one
-// 64-bit global atomic per counter and block: exact and order-independent.
+// 64-bit global atomic per counter and block: exact and order-independent.  NBR = 1: the 3D ranks alone (tri_rank2 is not read, the 2D half of
+// `out` is not touched).
+template <int NBR>
 __global__ __launch_bounds__(256) void eval_triplet_split_kernel(const int32_t* __restrict__ tri_rank3, const int32_t* __restrict__ tri_rank2,
                                                                  const int32_t* __restrict__ cnt, const int64_t* __restrict__ gt_cls,
                                                                  const int64_t* __restrict__ gt_rel, const int64_t* __restrict__ edges,
@@ -456,9 +463,12 @@ __global__ __launch_bounds__(256) void eval_triplet_split_kernel(const int32_t* 
         for (int j = 0; m && j < n; ++j, m &= m - 1) {   // slot j: the j-th set column, ascending
             const int q = __ffs(m) - 1;
             const bool zs = in && row[q] != 0;
-            const int r3 = tri_rank3[(size_t)t * R + j], r2 = tri_rank2[(size_t)t * R + j];
+            const int r3 = tri_rank3[(size_t)t * R + j];
             add(0, true); add(1, r3 <= 50); add(2, r3 <= 100); add(3, zs); add(4, zs && r3 <= 50); add(5, zs && r3 <= 100);
-            add(6, true); add(7, r2 <= 50); add(8, r2 <= 100); add(9, zs); add(10, zs && r2 <= 50); add(11, zs && r2 <= 100);
+            if (NBR == 2) {
+                const int r2 = tri_rank2[(size_t)t * R + j];
+                add(6, true); add(7, r2 <= 50); add(8, r2 <= 100); add(9, zs); add(10, zs && r2 <= 50); add(11, zs && r2 <= 100);
+            }
         }
     }
 #pragma unroll
@@ -481,8 +491,8 @@ int launch_eval_triplet_split(const int32_t* tri_rank3, const int32_t* tri_rank2
     if (R <= 0 || R > CNT_MAX_R) return fail(-1, "eval_triplet_split: at most 32 relation classes");
     if (C <= 0) return fail(-1, "eval_triplet_split: the object class count must be positive");
     if (E <= 0) return 0;
-    hipLaunchKernelGGL(eval_triplet_split_kernel, dim3((E + 255) / 256), dim3(256), 0, s, tri_rank3, tri_rank2, cnt, gt_cls, gt_rel, edges,
-                       table, E, C, R, out);
+    hipLaunchKernelGGL(tri_rank2 ? eval_triplet_split_kernel<2> : eval_triplet_split_kernel<1>, dim3((E + 255) / 256), dim3(256), 0, s, tri_rank3,
+                       tri_rank2, cnt, gt_cls, gt_rel, edges, table, E, C, R, out);
     VLSAT_LAUNCH_CHECK("eval_triplet_split");
     return 0;
 }

@@ -50,7 +50,8 @@ def _index(n_rel: int) -> Dict[str, int]:
 
 def accumulate(vec: np.ndarray, ranks: Dict[str, np.ndarray], cls_matrix: np.ndarray, n_scenes: int, n_rel: int = N_REL):
     """Add one batch's rank arrays (process_val outputs) into the counts vector (in place).  Histogram form
-    (bincount per predicate class) of the per-class loops of get_mean_recall / compute_mean_predicate."""
+    (bincount per predicate class) of the per-class loops of get_mean_recall / compute_mean_predicate.  A branch whose
+    ``top_k_obj*`` entry is missing or None (the 2D one of a 3D-only run) is skipped: its fields stay as they are."""
     idx = _index(n_rel)
     vec[idx["scenes"]] += n_scenes
     cm = np.asarray(cls_matrix, dtype=np.int64).reshape(-1, 5) if len(cls_matrix) else np.zeros((0, 5), np.int64)
@@ -62,9 +63,10 @@ def accumulate(vec: np.ndarray, ranks: Dict[str, np.ndarray], cls_matrix: np.nda
             vec[idx[f"cm_ge{k}"]] += int(ge[k])
     has = pred >= 0
     pc = pred[has]
-    for br, o, r, t in (("3d", ranks["top_k_obj"], ranks["top_k_rel"], ranks["top_k_triplet"]),
-                        ("2d", ranks["top_k_obj_2d"], ranks["top_k_rel_2d"], ranks["top_k_triplet_2d"])):
-        o, r, t = np.asarray(o), np.asarray(r), np.asarray(t)
+    for br, sfx in (("3d", ""), ("2d", "_2d")):
+        if ranks.get("top_k_obj" + sfx) is None:
+            continue
+        o, r, t = (np.asarray(ranks[name + sfx]) for name in ("top_k_obj", "top_k_rel", "top_k_triplet"))
         vec[idx[f"obj_n_{br}"]] += len(o)
         vec[idx[f"rel_n_{br}"]] += len(r)
         vec[idx[f"tri_n_{br}"]] += len(t)
@@ -89,11 +91,15 @@ def accumulate(vec: np.ndarray, ranks: Dict[str, np.ndarray], cls_matrix: np.nda
     return vec
 
 
-def summarize(vec: np.ndarray, n_rel: int = N_REL) -> Dict[str, float]:
-    """Percentages validation() prints, from the (all-reduced) counts."""
+def _branches(use_2d: bool):
+    return ("3d", "2d") if use_2d else ("3d",)
+
+
+def summarize(vec: np.ndarray, n_rel: int = N_REL, use_2d: bool = True) -> Dict[str, float]:
+    """Percentages validation() prints, from the (all-reduced) counts.  ``use_2d=False``: ``scenes`` and the 3D branch's keys only."""
     idx = _index(n_rel)
     out = {"scenes": float(vec[idx["scenes"]])}
-    for br in ("3d", "2d"):
+    for br in _branches(use_2d):
         for name, ks in (("obj", _OBJ_K), ("rel", _REL_K), ("tri", _TRI_K)):
             n = max(vec[idx[f"{name}_n_{br}"]], 1)
             for k in ks:
@@ -123,9 +129,9 @@ def recall_fields(n_rel: int = N_REL):
     return f
 
 
-def recall_vector(c3: torch.Tensor, c2: torch.Tensor, n_rel: int = N_REL) -> torch.Tensor:
+def recall_vector(c3: torch.Tensor, c2: torch.Tensor | None, n_rel: int = N_REL) -> torch.Tensor:
     """The recall_fields() vector (fp64, on the counts' device, no synchronisation) of one batch from the per-scene counts
-    ``metrics.recallk_counts`` returned for its 3D (``c3``) and 2D (``c2``) outputs."""
+    ``metrics.recallk_counts`` returned for its 3D (``c3``) and 2D (``c2``) outputs.  ``c2=None``: the 2D entries are zero."""
     r = n_rel
     gt = c3[:, 0].double()
     gtc = c3[:, 1:1 + r].double()
@@ -134,6 +140,9 @@ def recall_vector(c3: torch.Tensor, c2: torch.Tensor, n_rel: int = N_REL) -> tor
     n_cls = cls_on.sum(1).clamp(min=1).double()
     parts = [valid.sum().double().view(1), gt.sum().view(1), gtc.sum(0)]
     for c in (c3, c2):
+        if c is None:                                   # (same layout and length: the branch's block adds nothing)
+            parts.append(torch.zeros(len(_RK_VARIANTS) * 3 * (3 + r), dtype=torch.float64, device=c3.device))
+            continue
         for v in _RK_VARIANTS:
             base = recallk_offset(v, r)
             hits = c[:, base:base + 3].double()                                        # [S, 3]
@@ -145,16 +154,17 @@ def recall_vector(c3: torch.Tensor, c2: torch.Tensor, n_rel: int = N_REL) -> tor
     return torch.cat(parts)
 
 
-def recall_summarize(vec: np.ndarray, n_rel: int = N_REL) -> Dict[str, float]:
+def recall_summarize(vec: np.ndarray, n_rel: int = N_REL, use_2d: bool = True) -> Dict[str, float]:
     """Percentages from the (all-reduced) recall_fields() vector.  ``{v}_R@{K}_{br}`` / ``{v}_mR@{K}_{br}``: the per-scene
     Recall@K / mR@K (what evaluate_triplet_recallk / _mrecallk return for one scene; mR = mean over the scene's predicate
     classes) averaged over the scenes with at least one gt edge.  ``..._pooled``: hits over gt edges of all scenes, and the
-    mean over predicate classes of the pooled per-class recall.  The reference never aggregates across scenes; both are given."""
+    mean over predicate classes of the pooled per-class recall.  The reference never aggregates across scenes; both are given.
+    ``use_2d=False``: the 3D branch's keys only."""
     idx = {k: i for i, k in enumerate(recall_fields(n_rel))}
     n_sc, n_gt = vec[idx["rk_scenes"]], vec[idx["rk_gt_edges"]]
     gtc = np.array([vec[idx[f"rk_gt_cls{c}"]] for c in range(n_rel)])
     out = {}
-    for br in ("3d", "2d"):
+    for br in _branches(use_2d):
         for v in _RK_VARIANTS:
             for k in _RK_K:
                 ch = np.array([vec[idx[f"{v}_cls{c}_hit@{k}_{br}"]] for c in range(n_rel)])
@@ -179,20 +189,23 @@ def split_fields():
 
 def accumulate_split(vec: np.ndarray, top_k_triplet, top_k_triplet_2d, cls_matrix, table, n_rel: int = N_REL):
     """Add one batch's zero-shot split counts (the split_fields() vector) from process_val's triplet ranks of both branches
-    (``out[4]``, ``out[5]``) and its ``cls_matrix`` (``out[6]``), in place; ``table`` from zeroshot.zero_shot_table."""
+    (``out[4]``, ``out[5]``) and its ``cls_matrix`` (``out[6]``), in place; ``table`` from zeroshot.zero_shot_table.
+    ``top_k_triplet_2d=None``: the 2D half stays as it is."""
     from .zeroshot import split_counts_host
     vec[0:6] += split_counts_host(top_k_triplet, cls_matrix, table, n_rel)
-    vec[6:12] += split_counts_host(top_k_triplet_2d, cls_matrix, table, n_rel)
+    if top_k_triplet_2d is not None:
+        vec[6:12] += split_counts_host(top_k_triplet_2d, cls_matrix, table, n_rel)
     return vec
 
 
-def split_summarize(vec: np.ndarray) -> Dict[str, float]:
+def split_summarize(vec: np.ndarray, use_2d: bool = True) -> Dict[str, float]:
     """``zero_shot_recall@K_{br}``, ``non_zero_shot_recall@K_{br}`` and ``all_zero_shot_recall@K_{br}`` (K = 50, 100) from the
     (all-reduced) split_fields() vector: what get_zero_shot_recall returns (reference eva_utils_acc.py:267-333; NaN for an empty
-    group).  The reference reports the 3D branch; the 2D values, the same definition on the 2D triplet ranks, are an extension."""
+    group).  The reference reports the 3D branch; the 2D values, the same definition on the 2D triplet ranks, are an extension
+    (``use_2d=False``: left out)."""
     from .zeroshot import recall_from_counts
     out = {}
-    for b, br in enumerate(("3d", "2d")):
+    for b, br in enumerate(_branches(use_2d)):
         an, a50, a100, zn, z50, z100 = (int(x) for x in vec[6 * b:6 * b + 6])
         for k, ah, zh in ((50, a50, z50), (100, a100, z100)):
             out[f"zero_shot_recall@{k}_{br}"] = recall_from_counts(zn, zh)
@@ -226,11 +239,12 @@ def _n_scenes(b) -> int:
     return int(b["batch_ids"].max().item()) + 1
 
 
-def merge_batches(bs) -> dict:
+def merge_batches(bs, use_2d: bool = True) -> dict:
     """Consecutive batches (the reference loader's item names) collated into ONE on the device: node offsets applied to
     ``edge_indices``, scene offsets to ``batch_ids``, ``fc_sizes`` hints concatenated when every batch carries one (what
     collate_fn_mmg does for a bigger batch_size, reference DataLoader.py:160-172).  Counts are additive over scenes, so a loop
-    may hand the library several of its one-scene batches at a time."""
+    may hand the library several of its one-scene batches at a time.  ``use_2d=False``: ``obj_2d_feats`` is neither read nor
+    part of the result."""
     if len(bs) == 1:
         return bs[0]
     ei, bid, n_off, s_off = [], [], 0, 0
@@ -242,7 +256,8 @@ def merge_batches(bs) -> dict:
         bid.append(ids + s_off)
         n_off += n
         s_off += _n_scenes(b)
-    out = {k: torch.cat([b[k] for b in bs]) for k in ("obj_points", "obj_2d_feats", "descriptor", "gt_class", "gt_rel_cls")}
+    keys = ("obj_points", "obj_2d_feats", "descriptor", "gt_class", "gt_rel_cls") if use_2d else ("obj_points", "descriptor", "gt_class", "gt_rel_cls")
+    out = {k: torch.cat([b[k] for b in bs]) for k in keys}
     out["edge_indices"], out["batch_ids"], out["n_scenes"] = torch.cat(ei), torch.cat(bid), s_off
     if all("fc_sizes" in b for b in bs):
         out["fc_sizes"] = [int(x) for b in bs for x in b["fc_sizes"]]
@@ -333,7 +348,7 @@ def _split_scene_graphs(pair, b):
         return
     _, start = _scene_starts(b, n_sc, nodes=False)
     for s in range(n_sc):
-        yield g3.scene(s, start[s]), g2.scene(s, start[s])
+        yield g3.scene(s, start[s]), (None if g2 is None else g2.scene(s, start[s]))
 
 
 def _split_decoded(pair, b):
@@ -370,7 +385,7 @@ def _split_merged(pairs, b):
 
 @torch.no_grad()
 def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False,
-                          zero_shot=None):
+                          zero_shot=None, use_2d: bool = True):
     """The counts vector of this rank's batches with NO host round trip per batch and ``workers`` batches in flight
     (``_run_pool``); forward, ranking and counting of a batch are enqueued back to back
     (``metrics.process_val_counts``) and the counts accumulate on the device with integer atomics.  One scene per batch --
@@ -380,6 +395,7 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     ``merge`` > 1: every worker takes that many consecutive batches at a time and collates them on the device into one call
     (``merge_batches``): the forward then runs at its batched rate.  Counts are additive, so the summary is the same up to
     near-ties (a batched forward differs from a one-scene forward in the last bits: a rank may move by one).
+    ``use_2d=False``: every batch takes the 3D-only step (``obj_2d_feats`` is not read); the 2D entries of the vectors stay zero.
     Returns the counts vector; with ``recall_k`` or ``zero_shot`` (the device uint8 table) the tuple (counts, recall vector or
     None, split vector or None)."""
     from . import metrics as M
@@ -393,8 +409,8 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
             yield group
 
     def one(k, m, group):
-        b = merge_batches(group)
-        M.process_val_counts(m, counts[k], b["obj_points"], b["obj_2d_feats"], b["gt_class"], b["descriptor"],
+        b = merge_batches(group, use_2d)
+        M.process_val_counts(m, counts[k], b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["gt_class"], b["descriptor"],
                              b["gt_rel_cls"], b["edge_indices"], b.get("batch_ids"), _n_scenes(b), b.get("fc_sizes"),
                              recall=recall[k], split_table=zero_shot, split_counts=split[k])
 
@@ -407,10 +423,11 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
 
 
 @torch.no_grad()
-def predict(model, batches: Iterable[dict], device=None, workers: int = 0, **graph_args):
+def predict(model, batches: Iterable[dict], device=None, workers: int = 0, use_2d: bool = True, **graph_args):
     """The predicted scene graph of every scene of ``batches`` (the loader's dicts; no labels are read), in input order: yields
     one ``(graph_3d, graph_2d)`` pair of one-scene ``metrics.SceneGraph`` per scene, edge rows counted within the scene's own
-    edge list.  ``graph_args``: ``top_k``, ``topk_each``, ``evaluate`` of ``VLSATModel.predict_graph``.  workers = 0: one batch
+    edge list.  ``use_2d=False`` takes the 3D-only forward (``obj_2d_feats`` is not read; ``graph_2d`` is None).
+    ``graph_args``: ``top_k``, ``topk_each``, ``evaluate`` of ``VLSATModel.predict_graph``.  workers = 0: one batch
     after the other on the current stream.  workers >= 1: as the pipelined validation loop -- every worker thread owns a replica
     of the model and a stream and takes the next batch; nothing is read back per batch."""
     workers = int(workers)
@@ -418,7 +435,7 @@ def predict(model, batches: Iterable[dict], device=None, workers: int = 0, **gra
         raise ValueError("predict(workers > 0) needs the device")
 
     def one(m, b):
-        return m.predict_graph(b["obj_points"], b["obj_2d_feats"], b["edge_indices"].t(), b["descriptor"], b.get("batch_ids"),
+        return m.predict_graph(b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["edge_indices"].t(), b["descriptor"], b.get("batch_ids"),
                                fc_sizes=b.get("fc_sizes"), **graph_args)
 
     yield from _in_order(model, batches, device, workers, one, _split_scene_graphs)
@@ -630,7 +647,7 @@ def calibrate(model, batches: Iterable[dict], device=None, workers: int = 0, use
 
 @torch.no_grad()
 def validation(model, batches: Iterable[dict], device=None, workers: int = 0, merge: int = 1,
-               recall_k: bool = False, zero_shot=None) -> Dict[str, float]:
+               recall_k: bool = False, zero_shot=None, use_2d: bool = True) -> Dict[str, float]:
     """``batches`` yields this rank's dicts with the reference loader's item names
     (obj_points [N,3,P], obj_2d_feats, gt_class, gt_rel_cls, edge_indices [E,2], descriptor, batch_ids; optionally
     ``fc_sizes``: objects per scene when edge_indices is the canonical fully-connected list, which spares the graph plan a
@@ -646,7 +663,10 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
     annotations): the result also holds the zero-shot split of the triplet recall (split_summarize: zero_shot_recall@K,
     non_zero_shot_recall@K, all_zero_shot_recall@K, K = 50, 100) of both branches -- get_zero_shot_recall, reference
     src/model/model.py:253; the reference reports the 3D branch, the ``_2d`` values are an extension -- from a split_fields()
-    vector concatenated onto the others, still one all-reduce.  None: the result and the work are unchanged."""
+    vector concatenated onto the others, still one all-reduce.  None: the result and the work are unchanged.
+    use_2d = False: the model as deployed -- every batch takes the 3D-only forward and one ranking pass, ``obj_2d_feats`` is not
+    read (a batch may lack the key).  The vectors keep their layout and length (the 2D entries stay zero: the same one all-reduce)
+    and the result holds ``scenes`` and the 3D branch's keys only, with the values of the two-branch run."""
     from . import metrics as M
     if zero_shot is not None:
         if workers > 0:
@@ -657,18 +677,20 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
     if workers > 0:
         if device is None:
             raise ValueError("validation(workers > 0) needs the device")
-        vec = _validation_pipelined(model, batches, device, int(workers), int(merge), bool(recall_k), zero_shot)
+        vec = _validation_pipelined(model, batches, device, int(workers), int(merge), bool(recall_k), zero_shot, bool(use_2d))
         if recall_k or zero_shot is not None:
             vec = np.concatenate([v for v in vec if v is not None])
-            return _summaries(vdist.allreduce_metrics(torch.from_numpy(vec).to(device)).cpu().numpy(), recall_k, zero_shot is not None)
+            return _summaries(vdist.allreduce_metrics(torch.from_numpy(vec).to(device)).cpu().numpy(), recall_k, zero_shot is not None,
+                              use_2d)
         t = vdist.allreduce_metrics(torch.from_numpy(vec).to(device))
-        return summarize(t.cpu().numpy())
+        return summarize(t.cpu().numpy(), use_2d=use_2d)
     vec = np.zeros(len(fields()), dtype=np.float64)
     rvec = np.zeros(len(recall_fields()), dtype=np.float64) if recall_k else None
     svec = np.zeros(len(split_fields()), dtype=np.float64) if zero_shot is not None else None
     for b in batches:
         # process_val, with the forward's outputs kept for the recall counts
-        outs = M._forward_eval(model, b["obj_points"], b["obj_2d_feats"], b["descriptor"], b["edge_indices"], b["batch_ids"])
+        outs = M._forward_eval(model, b["obj_points"], b["obj_2d_feats"] if use_2d else None, b["descriptor"], b["edge_indices"],
+                               b["batch_ids"], use_2d=use_2d)
         out = M._process_val_from(model, outs, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], True)
         ranks = dict(top_k_obj=out[0], top_k_obj_2d=out[1], top_k_rel=out[2], top_k_rel_2d=out[3],
                      top_k_triplet=out[4], top_k_triplet_2d=out[5])
@@ -677,7 +699,7 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
         if recall_k:
             multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
             bid = b["batch_ids"].view(-1)
-            c3, c2 = (M.recallk_counts(o, rl, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], bid, n_scenes, multi)
+            c3, c2 = (None if o is None else M.recallk_counts(o, rl, b["gt_class"], b["gt_rel_cls"], b["edge_indices"], bid, n_scenes, multi)
                       for o, rl in ((outs[0], outs[2]), (outs[1], outs[3])))
             rvec += recall_vector(c3, c2, outs[2].shape[1]).cpu().numpy()
         if svec is not None:
@@ -687,17 +709,17 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
         t = t.to(device)
     t = vdist.allreduce_metrics(t)
     if recall_k or svec is not None:
-        return _summaries(t.cpu().numpy(), recall_k, svec is not None)
-    return summarize(t.cpu().numpy())
+        return _summaries(t.cpu().numpy(), recall_k, svec is not None, use_2d)
+    return summarize(t.cpu().numpy(), use_2d=use_2d)
 
 
-def _summaries(v: np.ndarray, recall_k: bool = True, split: bool = False) -> Dict[str, float]:
+def _summaries(v: np.ndarray, recall_k: bool = True, split: bool = False, use_2d: bool = True) -> Dict[str, float]:
     n = len(fields())
-    out = summarize(v[:n])
+    out = summarize(v[:n], use_2d=use_2d)
     if recall_k:
         m = n + len(recall_fields())
-        out.update(recall_summarize(v[n:m]))
+        out.update(recall_summarize(v[n:m], use_2d=use_2d))
         n = m
     if split:
-        out.update(split_summarize(v[n:n + len(split_fields())]))
+        out.update(split_summarize(v[n:n + len(split_fields())], use_2d))
     return out

@@ -107,27 +107,31 @@ def rank_tables(obj_logits: torch.Tensor, rel_probs: torch.Tensor, gt_class: tor
     return {"obj_rank": obj_rank, "rel_rank": rel_rank, "tri_rank": tri_rank, "cnt": cnt}
 
 
-def eval_counts(counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str, torch.Tensor], gt_class: torch.Tensor,
+def eval_counts(counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str, torch.Tensor] | None, gt_class: torch.Tensor,
                 gt_rel: torch.Tensor, edges: torch.Tensor, n_scenes: int) -> torch.Tensor:
     """counts (device int64 [len(evaluate.fields())], zeroed once by the caller) += the additive counts of one batch, from the
     rank tables of its 3D (``t3``) and 2D (``t2``) outputs: ``vlsat_eval_counts`` -- the device twin of
-    ``evaluate.accumulate`` (integer atomics: exact, order-independent, safe from several streams).  No synchronisation."""
+    ``evaluate.accumulate`` (integer atomics: exact, order-independent, safe from several streams).  No synchronisation.
+    ``t2=None``: the 3D branch alone -- ``scenes``, ``cm_ge*`` and the ``_3d`` fields get what the two-branch call adds, the
+    ``_2d`` fields are not touched."""
     lib = L.load()
     e, r = t3["rel_rank"].shape
     n = t3["obj_rank"].numel()
     if counts.dtype != torch.int64 or counts.numel() != 1 + r + 2 * (11 + 6 * r) or not counts.is_contiguous():
         raise L.VlsatError("eval_counts: counts must be a contiguous int64 vector of 1 + R + 2 (11 + 6 R) entries")
-    L.check(lib.vlsat_eval_counts(t3["obj_rank"].data_ptr(), t2["obj_rank"].data_ptr(), t3["rel_rank"].data_ptr(), t2["rel_rank"].data_ptr(),
-                                  t3["tri_rank"].data_ptr(), t2["tri_rank"].data_ptr(), t3["cnt"].data_ptr(), gt_class.data_ptr(),
+    o2, r2, tr2 = (None, None, None) if t2 is None else (t2["obj_rank"], t2["rel_rank"], t2["tri_rank"])
+    L.check(lib.vlsat_eval_counts(t3["obj_rank"].data_ptr(), L.ptr(o2), t3["rel_rank"].data_ptr(), L.ptr(r2),
+                                  t3["tri_rank"].data_ptr(), L.ptr(tr2), t3["cnt"].data_ptr(), gt_class.data_ptr(),
                                   gt_rel.data_ptr(), edges.data_ptr(), n, e, r, int(n_scenes), counts.data_ptr(), L.stream_ptr()))
     return counts
 
 
-def eval_triplet_split(split_counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str, torch.Tensor], gt_class: torch.Tensor,
+def eval_triplet_split(split_counts: torch.Tensor, t3: Dict[str, torch.Tensor], t2: Dict[str, torch.Tensor] | None, gt_class: torch.Tensor,
                        gt_rel: torch.Tensor, edges: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
     """split_counts (device int64 [12], zeroed once by the caller) += the zero-shot split of one batch's triplet ranks, from the
     rank tables of its 3D (``t3``) and 2D (``t2``) outputs (``rank_tables``) and the uint8 [C*C*R] table of
-    ``zeroshot.zero_shot_table``: ``vlsat_eval_triplet_split`` (layout: ``evaluate.split_fields``).  No synchronisation."""
+    ``zeroshot.zero_shot_table``: ``vlsat_eval_triplet_split`` (layout: ``evaluate.split_fields``).  No synchronisation.
+    ``t2=None``: the 3D half alone; the ``_2d`` half is not touched."""
     lib = L.load()
     e, r = t3["tri_rank"].shape
     c = table_shape(table, r)
@@ -136,7 +140,7 @@ def eval_triplet_split(split_counts: torch.Tensor, t3: Dict[str, torch.Tensor], 
     if (table.dtype != torch.uint8 or not table.is_contiguous() or not split_counts.is_cuda or table.device != split_counts.device
             or t3["tri_rank"].device != split_counts.device):
         raise L.VlsatError("eval_triplet_split: the table must be a contiguous uint8 tensor on the device of the counts and ranks")
-    L.check(lib.vlsat_eval_triplet_split(t3["tri_rank"].data_ptr(), t2["tri_rank"].data_ptr(), t3["cnt"].data_ptr(), gt_class.data_ptr(),
+    L.check(lib.vlsat_eval_triplet_split(t3["tri_rank"].data_ptr(), L.ptr(None if t2 is None else t2["tri_rank"]), t3["cnt"].data_ptr(), gt_class.data_ptr(),
                                          gt_rel.data_ptr(), edges.data_ptr(), table.data_ptr(), e, c, r, split_counts.data_ptr(),
                                          L.stream_ptr()))
     return split_counts
@@ -152,7 +156,9 @@ def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt
     ``edge_indices`` is [E,2] as the data loader yields it, on the device.  ``recall``: a device fp64 vector of
     ``evaluate.recall_fields()`` that additionally accumulates the Recall@K / mR@K of both branches (``recallk_counts``).
     ``split_table`` / ``split_counts``: the device uint8 zero-shot table (``zeroshot.zero_shot_table``) and the device int64 [12]
-    vector of ``evaluate.split_fields()`` that additionally accumulates the zero-shot split of the triplet ranks."""
+    vector of ``evaluate.split_fields()`` that additionally accumulates the zero-shot split of the triplet ranks.
+    ``obj_2d_feats=None``: the 3D branch alone, on both routes -- the one call runs its 3D-only step, the separate calls are
+    ``forward_3d`` + one ``rank_tables`` + one ``recallk_counts``; the ``_2d`` entries of every vector are not touched."""
     if (split_table is None) != (split_counts is None):
         raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
@@ -166,16 +172,20 @@ def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt
             return counts
     # with the fully-connected hint the plan never reads the edge list: the [2,E] view is enough (no transpose kernel)
     ei_t = edges.t() if fc_sizes is not None else edges.t().contiguous()
-    obj3, obj2, rel3, rel2 = model(obj_points, obj_2d_feats, ei_t, descriptor, batch_ids, istrain=False, fc_sizes=fc_sizes)
+    use_2d = obj_2d_feats is not None
+    if use_2d:
+        obj3, obj2, rel3, rel2 = model(obj_points, obj_2d_feats, ei_t, descriptor, batch_ids, istrain=False, fc_sizes=fc_sizes)
+    else:
+        obj3, rel3 = model.forward_3d(obj_points, ei_t, descriptor, batch_ids, fc_sizes=fc_sizes)
     gt_rel = multihot_targets(gt_rel_cls, rel3.shape[1]).to(torch.int64).contiguous()
     gt_cls = gt_cls.to(torch.int64).contiguous().view(-1)
     t3 = rank_tables(obj3, rel3, gt_cls, gt_rel, edges, multi)
-    t2 = rank_tables(obj2, rel2, gt_cls, gt_rel, edges, multi)
+    t2 = rank_tables(obj2, rel2, gt_cls, gt_rel, edges, multi) if use_2d else None
     if recall is not None:
         from . import evaluate as EV
         bid = None if batch_ids is None else batch_ids.view(-1)
         c3 = recallk_counts(obj3, rel3, gt_cls, gt_rel, edges, bid, n_scenes, multi)
-        c2 = recallk_counts(obj2, rel2, gt_cls, gt_rel, edges, bid, n_scenes, multi)
+        c2 = recallk_counts(obj2, rel2, gt_cls, gt_rel, edges, bid, n_scenes, multi) if use_2d else None
         recall += EV.recall_vector(c3, c2, rel3.shape[1])
     if split_table is not None:
         eval_triplet_split(split_counts, t3, t2, gt_cls, gt_rel, edges, split_table)
@@ -198,8 +208,12 @@ def cls_matrix(gt_class: torch.Tensor, gt_rel: torch.Tensor, edges: torch.Tensor
     return torch.stack([gt_class[a], obj_topk[a].long(), gt_class[b], obj_topk[b].long(), ki - 1], 1)
 
 
-def _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids):
+def _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids, use_2d=True):
+    """(obj3, obj2, rel3, rel2) of the forward; ``use_2d=False``: ``forward_3d``, ``obj_2d_feats`` not read, the 2D outputs None."""
     ei_t = edge_indices.t().contiguous()
+    if not use_2d:
+        obj3, rel3 = model.forward_3d(obj_points, ei_t, descriptor, batch_ids)
+        return obj3, None, rel3, None
     return model(obj_points, obj_2d_feats, ei_t, descriptor, batch_ids, istrain=False)
 
 
@@ -208,8 +222,9 @@ def process_val(model, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_cls,
                 use_triplet=True):
     """Same call and 10-tuple as ``Mmgnet.process_val`` (reference SGFN_MMG/model.py:458-480);
     ``edge_indices`` is [E,2] as the data loader yields it.  Rank arrays are numpy int64 like the
-    reference's; the score lists come back stacked as tensors."""
-    outs = _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids)
+    reference's; the score lists come back stacked as tensors.  ``obj_2d_feats=None``: the 3D-only forward; the three 2D rank
+    slots of the tuple (``top_k_obj_2d``, ``top_k_rel_2d``, ``top_k_triplet_2d``) are None."""
+    outs = _forward_eval(model, obj_points, obj_2d_feats, descriptor, edge_indices, batch_ids, use_2d=obj_2d_feats is not None)
     return _process_val_from(model, outs, gt_cls, gt_rel_cls, edge_indices, use_triplet)
 
 
@@ -218,9 +233,12 @@ def _process_val_from(model, outs, gt_cls, gt_rel_cls, edge_indices, use_triplet
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))     # self.mconfig.multi_rel_outputs
     gt_rel_cls = multihot_targets(gt_rel_cls, rel3.shape[1])
     r3 = eval_ranks(obj3, rel3, gt_cls, gt_rel_cls, edge_indices, multi_rel_outputs=multi)
-    r2 = eval_ranks(obj2, rel2, gt_cls, gt_rel_cls, edge_indices, multi_rel_outputs=multi)
+    np64 = lambda t: None if t is None else t.cpu().numpy().astype(np.int64)
+    if obj2 is None:                                                       # 3D-only: the 2D rank slots stay None
+        r2 = {"top_k_obj": None, "top_k_rel": None, "top_k_triplet": None}
+    else:
+        r2 = eval_ranks(obj2, rel2, gt_cls, gt_rel_cls, edge_indices, multi_rel_outputs=multi)
     cm = cls_matrix(gt_cls, gt_rel_cls, edge_indices, r3["top_k_obj"])     # obj_topk = 3D ranks for both (:469-470)
-    np64 = lambda t: t.cpu().numpy().astype(np.int64)
     if not use_triplet:
         return np64(r3["top_k_obj"]), np64(r2["top_k_obj"]), np64(r3["top_k_rel"]), np64(r2["top_k_rel"]), [101], None, None, None, None, None
     has = (gt_rel_cls == 1)

@@ -489,6 +489,8 @@ class VLSATModel:
         loader's int64 [E,2] list, ``gt_rel_multihot`` int64 [E,R], ``gt_cls`` int64 [N], ``counts`` the device int64 vector.
         ``split_table`` (device uint8 [C*C*R], zeroshot.zero_shot_table) with ``split_counts`` (device int64 [12]): the same call
         also counts the zero-shot split of the triplet ranks (``vlsat_process_val_counts_split``; layout: evaluate.split_fields).
+        ``obj_2d_feats=None``: the library's 3D-only step (3D-only forward, one ranking pass, one-branch counts and split) -- the
+        ``_2d`` entries of ``counts`` / ``split_counts`` are not touched, the plan and its workspace are the same.
         Returns False (nothing enqueued) when the plan had to permute the edges -- the caller then takes the separate calls."""
         if (split_table is None) != (split_counts is None):
             raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
@@ -500,17 +502,17 @@ class VLSATModel:
                 raise L.VlsatError(f"process_val_counts: split_table must be contiguous uint8 [{c}*{c}*{r}], split_counts int64 [12], "
                                    "both on the counts' device")
         ei = edges_e2.t() if fc_sizes is not None else edges_e2.t().contiguous()
-        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, ei, descriptor)
+        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, ei, descriptor, need_2d=obj_2d_feats is not None)
         with torch.cuda.device(self.device):
             plan = self._plan(ei, batch_ids, n, p, fc_sizes)
             if plan.perm is not None:
                 return False
             if split_table is None:
-                L.check(self._lib.vlsat_process_val_counts(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+                L.check(self._lib.vlsat_process_val_counts(self._h, plan.handle, pts.data_ptr(), L.ptr(f2d), desc.data_ptr(),
                                                            gt_cls.data_ptr(), gt_rel_multihot.data_ptr(), edges_e2.data_ptr(),
                                                            int(n_scenes), counts.data_ptr(), L.stream_ptr()))
             else:
-                L.check(self._lib.vlsat_process_val_counts_split(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+                L.check(self._lib.vlsat_process_val_counts_split(self._h, plan.handle, pts.data_ptr(), L.ptr(f2d), desc.data_ptr(),
                                                                  gt_cls.data_ptr(), gt_rel_multihot.data_ptr(), edges_e2.data_ptr(),
                                                                  int(n_scenes), counts.data_ptr(), split_table.data_ptr(),
                                                                  split_counts.data_ptr(), L.stream_ptr()))
@@ -533,26 +535,29 @@ class VLSATModel:
         """The predicted scene graph of every scene, for both branches: ``(graph_3d, graph_2d)``, two ``metrics.SceneGraph`` with
         the ``top_k`` triplets per scene out of each edge's ``topk_each`` best (``metrics.scene_graph_topk``).  No labels.
         ``vlsat_forward_scene_graph``: forward + softmax of both object heads + the selection of both branches in ONE library
-        call, intermediates in the plan's memory.  Inputs as for ``forward`` (``edge_indices`` int64 [2,E]); the edges must be
+        call, intermediates in the plan's memory.  ``obj_2d_feats=None`` takes the 3D-only forward and one selection and returns
+        ``(graph_3d, None)``, as ``decode_graph`` does.  Inputs as for ``forward`` (``edge_indices`` int64 [2,E]); the edges must be
         grouped by scene in ascending order, as the loader and ``scan.prepare_scan`` yield them."""
         from . import metrics as M
         if evaluate not in M._SG_MODES:
             raise NotImplementedError("evaluate type", evaluate)
-        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, edge_indices, descriptor)
+        use_2d = obj_2d_feats is not None
+        nb = 2 if use_2d else 1
+        pts, f2d, desc, n, p, e = self._inputs(obj_points, obj_2d_feats, edge_indices, descriptor, need_2d=use_2d)
         with torch.cuda.device(self.device):
             plan, n_scenes, edges_e2 = self._scene_plan(edge_indices, batch_ids, n, p, fc_sizes, grouped_for="predict_graph")
             top_k, topk_each = int(top_k), int(topk_each)
             if not 1 <= top_k <= M.SG_MAX_TOP_K or not 1 <= topk_each <= M.SG_MAX_EACH:
                 raise L.VlsatError(f"predict_graph: top_k must be in 1..{M.SG_MAX_TOP_K} and topk_each in 1..{M.SG_MAX_EACH}")
-            trip = torch.empty(2, n_scenes, top_k, 4, dtype=torch.int32, device=self.device)
-            score = torch.empty(2, n_scenes, top_k, dtype=torch.float32, device=self.device)
-            n_valid = torch.empty(2, n_scenes, dtype=torch.int32, device=self.device)
-            L.check(self._lib.vlsat_forward_scene_graph(self._h, plan.handle, pts.data_ptr(), f2d.data_ptr(), desc.data_ptr(),
+            trip = torch.empty(nb, n_scenes, top_k, 4, dtype=torch.int32, device=self.device)
+            score = torch.empty(nb, n_scenes, top_k, dtype=torch.float32, device=self.device)
+            n_valid = torch.empty(nb, n_scenes, dtype=torch.int32, device=self.device)
+            outs = [[t[b].data_ptr() for t in (trip, score, n_valid)] if b < nb else [None] * 3 for b in range(2)]
+            L.check(self._lib.vlsat_forward_scene_graph(self._h, plan.handle, pts.data_ptr(), L.ptr(f2d), desc.data_ptr(),
                                                         edges_e2.data_ptr(), n_scenes, M._SG_MODES[evaluate], top_k, topk_each,
-                                                        trip[0].data_ptr(), score[0].data_ptr(), n_valid[0].data_ptr(),
-                                                        trip[1].data_ptr(), score[1].data_ptr(), n_valid[1].data_ptr(),
-                                                        L.stream_ptr()))
-        return M.SceneGraph(trip[0], score[0], n_valid[0]), M.SceneGraph(trip[1], score[1], n_valid[1])
+                                                        *outs[0], *outs[1], L.stream_ptr()))
+        graphs = [M.SceneGraph(trip[b], score[b], n_valid[b]) for b in range(nb)]
+        return graphs[0], (graphs[1] if use_2d else None)
 
     @torch.no_grad()
     def decode_graph(self, obj_points, obj_2d_feats, edge_indices, descriptor, batch_ids=None, threshold=0.5, score: str = "rel",

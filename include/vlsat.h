@@ -534,7 +534,11 @@ int64_t vlsat_eval_ranks_scratch_floats(int32_t n_nodes, int32_t n_obj_class, in
  * 3D object rank for both branches (SGFN_MMG/model.py:469-470).  counts: device uint64, zeroed by the caller before the first
  * scene; integer atomics only, so scenes may be accumulated from several streams at once and the sums are exact.  This is
  * what lets a one-scene-per-call evaluation loop (validation()'s batch_size = 1, src/model/model.py:185) run without a host
- * round trip per scene.  All device pointers; asynchronous. */
+ * round trip per scene.  All device pointers; asynchronous.
+ * 3D-only: obj_rank_2d, rel_rank_2d and tri_rank_2d all NULL counts the 3D branch alone -- scenes, cm_ge* and the 3D block get exactly
+ * what the two-branch call adds, the 2D block of counts is NOT TOUCHED (the vector is additive: a caller may mix both kinds of
+ * batch).  The three go together: some NULL and some not is VLSAT_EINVAL before any launch (a table without rows -- n_nodes = 0
+ * for obj_rank_2d, n_edges = 0 for the other two -- is not looked at, as before). */
 int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, const int32_t* rel_rank_3d, const int32_t* rel_rank_2d,
                       const int32_t* tri_rank_3d, const int32_t* tri_rank_2d, const int32_t* cnt, const int64_t* gt_class,
                       const int64_t* gt_rel, const int64_t* edges, int32_t n_nodes, int32_t n_edges, int32_t n_rel_class,
@@ -553,7 +557,8 @@ int vlsat_eval_counts(const int32_t* obj_rank_3d, const int32_t* obj_rank_2d, co
  *   counts   uint64 [12], counts[i] += ...: for the 3D and then the 2D ranks, all_n, all_hit@50, all_hit@100, zs_n, zs_hit@50,
  *            zs_hit@100 (hit@K: rank <= K).  Non-zero-shot = all - zs.  Recall = hit / n * 100; an empty group is NaN.
  * n_rel_class <= 32 (as vlsat_eval_counts).  Zeroed by the caller before the first scene; integer atomics only, so scenes may be
- * accumulated from several streams.  All device pointers; asynchronous: no host synchronisation, no runtime fill. */
+ * accumulated from several streams.  All device pointers; asynchronous: no host synchronisation, no runtime fill.
+ * 3D-only: tri_rank_2d NULL counts the 3D half (counts[0..5]) alone; counts[6..11] are not touched. */
 int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank_2d, const int32_t* cnt, const int64_t* gt_class,
                              const int64_t* gt_rel, const int64_t* edges, const uint8_t* table, int32_t n_edges, int32_t n_obj_class,
                              int32_t n_rel_class, uint64_t* counts, void* stream);
@@ -592,7 +597,10 @@ int64_t vlsat_eval_recallk_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32
  * Mmgnet.process_val (reference src/model/SGFN_MMG/model.py:458-480) computes per scene, reduced to what MMGNet.validation keeps of
  * it (src/model/model.py:201-242).  Top-k bounds 11 / 6 / 101 and threshold 0.5 are process_val's.  gt_rel is the multi-hot
  * [E, R] int64 target, edges_e2 the [E, 2] int64 (from, to) list in the plan's edge order, counts as for vlsat_eval_counts.
- * MODEL.multi_rel_outputs only.  All device pointers; asynchronous; one library call per scene on the host side. */
+ * MODEL.multi_rel_outputs only.  All device pointers; asynchronous; one library call per scene on the host side.
+ * 3D-only: obj_2d_feats NULL runs vlsat_forward without its 2D outputs, ONE softmax, ONE ranking pass and the one-branch counts,
+ * all on `stream`, intermediates in the same scratch (the plan's workspace_bytes does not change); the 2D block of counts is not
+ * touched.  Single-label models stay refused here either way. */
 int vlsat_process_val_counts(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                              const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
                              int32_t n_scenes, uint64_t* counts, void* stream);
@@ -600,7 +608,8 @@ int vlsat_process_val_counts(vlsat_handle h, vlsat_plan plan, const float* obj_p
 /* vlsat_process_val_counts, then vlsat_eval_triplet_split on the triplet ranks it left in the plan's scratch: split_table is the
  * uint8 [C * C * R] zero-shot table of the model's n_obj_class C and n_rel_class R (layout: vlsat_eval_triplet_split),
  * split_counts the device uint64 [12] it accumulates into.  A one-scene-per-call loop with the zero-shot split on stays one
- * library call per scene.  counts and every other argument as for vlsat_process_val_counts. */
+ * library call per scene.  counts and every other argument as for vlsat_process_val_counts; with obj_2d_feats NULL the split is
+ * the one-branch one as well (split_counts[6..11] are not touched). */
 int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                                    const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
                                    int32_t n_scenes, uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts,
@@ -650,7 +659,10 @@ int vlsat_k_exp(const float* x, int64_t n, float* out, void* stream);
  * per scene from an unlabelled scan to its predicted graph.  edges_e2 is the [E, 2] int64 (from, to) list in the plan's edge
  * order; n_scenes must be the plan's scene count (the scenes are the plan's).  With MODEL.multi_rel_outputs = false the
  * log-probabilities are exponentiated on the device.  Outputs per branch as for vlsat_scene_graph_topk.  All device pointers;
- * asynchronous. */
+ * asynchronous.
+ * 3D-only: obj_2d_feats and the three 2D outputs go together -- all given, or all NULL: the 3D-only forward and one selection
+ * (a single-label model's log-probabilities are still exponentiated in place).  Any mixture is VLSAT_EINVAL before anything is
+ * launched; the outputs are then untouched. */
 int vlsat_forward_scene_graph(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                               const float* descriptor, const int64_t* edges_e2, int32_t n_scenes, int32_t mode,
                               int32_t top_k, int32_t topk_each, int32_t* triplets_3d, float* scores_3d, int32_t* n_valid_3d,
