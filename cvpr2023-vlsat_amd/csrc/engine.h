@@ -49,6 +49,7 @@ inline EvalScratch eval_scratch_carve(float* f, int32_t* i, size_t N, size_t E, 
 #include "../../include/vlsat.h"
 #include "common.h"
 #include "kernels.h"
+#include "edge_pairs.h"
 
 namespace vlsat {
 
@@ -157,6 +158,8 @@ struct vlsat_ctx {
     int flash_exact = -1;                    // fp32 mode, head dim 64: -1 / 0 the split-fp16 edge attention (three f16 MFMAs per product), 1 the exact fp32-MFMA kernel (debug option "flash_exact")
     int gemm_small_exact = -1;               // fp32 mode: -1 / 0 the persistent GEMM kernel's launches (tails, small launches, node rows) on its split-fp16 siblings (GemmArgs::f16s 2 | 3), 1 exact, node rows exact on every kernel (debug option "gemm_small_exact")
     int pointnet_exact = -1;                // fp32 mode: -1 / 0 the object encoder's conv2 / conv3 on the split-fp16 kernel (pointnet_bf16_kernel<CIN, 5>), 1 the exact fp32-MFMA kernel (debug option "pointnet_exact")
+    int edge_pairs = 1;                      // fp32 mode: edge tensors between split-fp16 GEMMs as pair words where every launch that touches them has the form (edge_pairs.h; debug option "edge_pairs", 0: all fp32)
+    vlsat::EdgePairs pairs{};                // ... the answer for the forward being enqueued (forward_body sets it before the first launch)
     int gemm_exact = -1;                    // fp32 mode: -1 / 0 the large edge-row launches on the split-fp16 8-phase kernel (GemmArgs::f16s), 1 the exact fp32-MFMA kernels (debug option "gemm_exact")
     int ln_resid = 1;                        // split-pair mode: post-attention residual added in the LayerNorm kernel
     int half_fmt = 1;                        // single-rounding modes: those tensors as plain bf16 (half rows) instead of split pairs

@@ -63,6 +63,9 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //                       pointnet_bf16_kernel<CIN, 5>) or the exact fp32-MFMA kernel (1)
 //                       ("flash_exact", "gemm_exact", "gemm_small_exact" and "pointnet_exact" all 1: the forward of the releases before the
 //                       split-fp16 kernels, bit for bit)
+//   "edge_pairs" 0|1     fp32 mode: Hbig, R1 and the 3D chain tensor E3 travel between the split-fp16 GEMMs as pair words (the halves of the
+//                       split operand, made once by the writer) wherever every launch that touches them has the form (1, default;
+//                       edge_pairs.h), or stay fp32 (0: the forward of the releases before the pair words); same outputs bit for bit
 //   "flash_bq_big" 0|1   half-row edge attention on plans whose scenes all have >= 4096 edges: 256 queries per block (1, default) or 128
 //   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes (default) / fp32 too
 //   "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2   gate kernel variants the tests compare bit for bit
@@ -94,6 +97,7 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "gate_fuse_agg") h->gate_fuse_agg = value < 0 ? 0 : value > 2 ? 2 : value;
     else if (k == "flash_pv_terms") h->flash_pv_terms = value == 2 ? 2 : 3;
     else if (k == "flash_exact") h->flash_exact = value < 0 ? -1 : value != 0;
+    else if (k == "edge_pairs") h->edge_pairs = value != 0;
     else if (k == "gemm_exact") h->gemm_exact = value < 0 ? -1 : value != 0;
     else if (k == "pointnet_exact") h->pointnet_exact = value < 0 ? -1 : value != 0;
     else if (k == "gemm_small_exact") h->gemm_small_exact = value < 0 ? -1 : value != 0;

@@ -24,6 +24,10 @@ namespace {
 // that understand the format.
 // Returns the format code: 0 fp32, 1 split-pair words (split-bf16 mode), 2 half rows = plain bf16 at half the HBM
 // traffic (single-rounding modes, whose kernels never read a low part).
+// The fp32 mode (code 0 here) has a producer-side format of its own, the GEMM pair words of its split-fp16 kernels
+// (gemm_f16s_planes.h): which tensors carry them is vlsat_ctx::pairs, the answer of edge_pairs_plan (edge_pairs.h) for the forward
+// being enqueued -- Hbig, R1 and E3 where every launch that touches them has the form, GemmArgs::a_pair / c_pair on those launches.
+// Everything else the fp32 kernels read and write is plain fp32.
 static int split_fmt(const vlsat_ctx* h) {
     // (head geometries other than 8 x 64: the chain tensors keep the format; Q / K|V / O of the edge attention and the gate's
     //  kproj stay fp32 there, because those kernels are the fp32 ones -- see SA in the edge attention below)
@@ -39,7 +43,7 @@ static GateChoice gate_of(const vlsat_ctx* h) {
                        h->gate_heads_bf16 != 0);
 }
 static int gate_launch(vlsat_ctx* h, const GateChoice& gc, const GateArgs& g, hipStream_t s, const GateArgs* twin = nullptr) {
-    const int S = gc.bits16() ? split_fmt(h) : 0;        // (the fp32 gate kernels read plain fp32)
+    const int S = gc.bits16() ? split_fmt(h) : 0;        // (the fp32 gate kernels read plain fp32: KP is never a pair-word tensor)
     return launch_gate(gc.kernel, g, h->H, h->D / h->H, h->A / h->H, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s, twin);
 }
 // whether the max aggregation runs inside the gate kernel: GCN_AGGR = max on a kernel that implements it, no debug tap
@@ -230,8 +234,9 @@ int kv_project(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, con
 int gemm_n(vlsat_ctx* h, hipStream_t s, const GemmArgs* a, int nb) { return nb == 2 ? gemm2(h, s, a[0], a[1]) : gemm(h, s, a[0]); }
 
 // one branch's operands of a GraphEdgeAttenNetwork block / a relation head / an object head
-struct GcnSide { const GcnW* w; float* x; float* e; int e_relu_pending; const Scratch* sc; };
-struct RelSide { const RelHeadW* w; const float* e; int relu_a; float* out; const Scratch* sc; };
+// br: 0 = the 3D branch (its edge tensor is E3), 1 = the 2D one -- which answers of vlsat_ctx::pairs apply
+struct GcnSide { const GcnW* w; float* x; float* e; int e_relu_pending; const Scratch* sc; int br = 0; };
+struct RelSide { const RelHeadW* w; const float* e; int relu_a; float* out; const Scratch* sc; int br = 0; };
 struct ObjSide { const float *x, *w, *b; float* out; const Scratch* sc; };
 // conv2 / conv3 of a relation encoder (+BN folded): rel_encoder_3d (br 0) or rel_encoder_2d (br 1)
 struct RelEncW { const float *w2, *b2, *w3, *b3; };
@@ -251,11 +256,14 @@ int gcn_node_project(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w
 }
 // nn_edge.0 on the edge part `we` of its weight: Hbig = relu(e . we^T + P_i[src] + P_j[dst]); the node columns (with the bias) were made
 // on N rows by the node-side projection.  g_f16: they are fp16 half rows (never for triplet_projector_2d's first Linear, the other caller)
-GemmArgs nn_edge0_args(const vlsat_ctx* h, const vlsat_plan_s* p, const float* we, const float* e, int relu_a, const Scratch& sc, bool g_f16) {
+// e_pair / hbig_pair (fp32 mode): e is read / Hbig is written as GEMM pair words (vlsat_ctx::pairs)
+GemmArgs nn_edge0_args(const vlsat_ctx* h, const vlsat_plan_s* p, const float* we, const float* e, int relu_a, const Scratch& sc, bool g_f16,
+                       bool e_pair, bool hbig_pair) {
     const int D = h->D, NPC = npc_of(h), S = split_fmt(h);
     GemmArgs e1 = G(e, D, we, D, sc.Hbig, 2 * D, (int)p->E, 2 * D, nullptr, ACT_RELU);
     e1.relu_a = relu_a;
     e1.a_split = S; e1.c_split = S;
+    e1.a_pair = e_pair; e1.c_pair = hbig_pair;
     e1.g0 = sc.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
     e1.g_f16 = g_f16;
     e1.g1 = sc.NP + (g_f16 ? D : 2 * D); e1.gi1 = p->d_dst; e1.ldg1 = NPC;       // (fp16 half rows: P_j starts at byte 2 * 2D of the row)
@@ -267,13 +275,15 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
     const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
     const int S = split_fmt(h);
     const GateChoice gc = gate_of(h);
+    const EdgePairs& P = h->pairs;
     GemmArgs a[2];
     GateArgs g[2] = {};
     if (!node_done) {
         for (int i = 0; i < nb; ++i) a[i] = node_project_args(h, p, *side[i].w, side[i].x, *side[i].sc);
         RUN(gemm_n(h, s, a, nb));
     }
-    for (int i = 0; i < nb; ++i) a[i] = nn_edge0_args(h, p, side[i].w->we1, side[i].e, side[i].e_relu_pending, *side[i].sc, gather_f16_on(h));
+    for (int i = 0; i < nb; ++i) a[i] = nn_edge0_args(h, p, side[i].w->we1, side[i].e, side[i].e_relu_pending, *side[i].sc, gather_f16_on(h),
+                                                   side[i].br == 0 && P.e3, P.hbig[side[i].br]);
     RUN(gemm_n(h, s, a, nb));
     if (h->d.use_gcn_edge) {              // proj_edge feeds only the gate MLP (reference network_MMG.py:98-102)
         for (int i = 0; i < nb; ++i) {
@@ -282,6 +292,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
             a[i].relu_a = b.e_relu_pending;
             a[i].a_split = S;
             a[i].c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
+            a[i].a_pair = b.br == 0 && P.e3;
         }
         RUN(gemm_n(h, s, a, nb));
     }
@@ -289,6 +300,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
         const GcnSide& b = side[i];
         a[i] = G(b.sc->Hbig, 2 * D, b.w->we2, 2 * D, b.e, D, E, D, b.w->be2);       // e <- nn_edge output (pre-activation)
         a[i].a_split = S; a[i].c_split = S;
+        a[i].a_pair = P.hbig[b.br]; a[i].c_pair = b.br == 0 && P.e3;
     }
     RUN(gemm_n(h, s, a, nb));
     for (int i = 0; i < nb; ++i) {
@@ -330,12 +342,14 @@ int rel_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const RelSide* side, 
         a[i] = G(b.e, D, b.w->w1, D, b.sc->R1, 512, E, 512, b.w->b1, ACT_RELU);
         a[i].relu_a = b.relu_a;
         a[i].a_split = S; a[i].c_split = S;
+        a[i].a_pair = b.br == 0 && h->pairs.e3; a[i].c_pair = h->pairs.r1[b.br];
     }
     RUN(gemm_n(h, s, a, nb));
     for (int i = 0; i < nb; ++i) {
         const RelSide& b = side[i];
         a[i] = G(b.sc->R1, 512, b.w->w2, 512, b.sc->R2, 256, E, 256, b.w->b2, ACT_RELU);
         a[i].a_split = S; a[i].c_split = S;
+        a[i].a_pair = h->pairs.r1[b.br];
     }
     RUN(gemm_n(h, s, a, nb));
     // multi_rel_outputs: sigmoid (PointNetRelClsMulti) or log_softmax over the R classes (PointNetRelCls)
@@ -379,6 +393,7 @@ int rel_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, int br0, int nb, c
     for (int i = 0, br = br0; i < nb; ++i, ++br) {
         a[i] = G(sc[br]->H2, 128, rel_enc_w(h, br).w3, 128, br ? p->E2 : p->E3, D, E, D, rel_enc_w(h, br).b3, ACT_RELU);
         a[i].a_split = S; a[i].c_split = S;
+        a[i].c_pair = br == 0 && h->pairs.e3;
     }
     return gemm_n(h, s, a, nb);
 }
@@ -429,6 +444,7 @@ int edge_attn_kv(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, c
     const int E = (int)p->E, D = h->D;
     GemmArgs gkv = G(p->E3, D, w.wkv, D, kve, 2 * D, E, 2 * D, w.bkv);
     gkv.a_split = f.S; gkv.c_split = f.SA;
+    gkv.a_pair = h->pairs.e3; gkv.c_pair = h->pairs.kv ? 2 : 0;      // (fp32 mode: K | V as attention pair words for the split-fp16 kernel)
     return gemm(h, s, gkv, f.PA);
 }
 int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAttnFmt& f, const float* kve) {
@@ -443,7 +459,10 @@ int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAtt
                                 h->edge_scope == 1 ? E : p->max_e, h->H, dh, 1.f / std::sqrt((float)dh), s, h->node_attn_split);
     // fp32 mode at the shipped head dim: the products as three fp16 MFMAs each (split-fp16, 2^-22 per operand: fp32-grade results at the
     // bf16 matrix rate), Q / K|V / O plain fp32 as for the exact kernel; "flash_exact" 1 keeps the exact fp32-MFMA kernel
-    if (f.x3) return launch_flash_attn_f16x3(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, h->flash_tr ? 1 : 0, s, &sp, dh);
+    // (h->pairs: K | V arrive as attention pair words, O leaves as GEMM pair words -- edge_pairs.h)
+    if (f.x3) return launch_flash_attn_f16x3(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, h->flash_tr ? 1 : 0, s, &sp, dh,
+                                             h->pairs.flash_io());
+    if (h->pairs.kv) return fail(VLSAT_ESTATE, "edge attention: K | V are pair words and the split-fp16 kernel does not run");
     if (!f.fa16) return launch_flash_attn(p->Qe, D, kve, kve + D, 2 * D, p->Oe, D, p->d_tiles, p->n_tiles, f.qscale, s, &sp, dh);   // (head dims 32 / 128: NUM_HEADS 16 / 4)
     const bool big = SA == 2 && dh == 64 && p->n_tiles_big && h->flash_tr && h->flash_dma == 1 && h->flash_bq_big;
     if (big) sp.bq = FLASH_BQ_BIG;
@@ -460,6 +479,7 @@ int edge_attn_out(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, 
     GemmArgs o = G(p->Oe, D, w.wo, D, pre_ln, D, E, D, w.bo);
     if (!f.ln_resid) { o.resid = p->E2; o.ldr = D; o.r_split = S; }
     o.a_split = f.SA;
+    o.a_pair = h->pairs.oe;
     if (f.o16) o.c_f16_cols = D;
     RUN(gemm(h, s, o, f.PA));
     Scope sc(h, s, PC_LAYERNORM, 0);
@@ -586,6 +606,20 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     //  in flight on K host threads the third stream of every replica competes for the few hardware queues -- 551 vs 926-953 scenes/s at
     //  four in flight in bf16_mixed, profiles/r05_probes/val_loop_bf16_mixed_three_lanes.txt)
     const bool exact = dual && !pair && (h->sched < 0 ? (h->prec_edge != 0 && p->E > 16384) : h->sched != 0);
+    {   // fp32 mode: which edge tensors travel as GEMM pair words in this forward -- one answer, read by every stage below
+        EdgePairsIn in;
+        in.E = p->E; in.D = D; in.G = gemm_slots(); in.option = h->edge_pairs;
+        in.fp32_mode = h->prec == 0 && h->prec_edge == 0 && h->prec_node == 0;
+        in.gemm_exact = h->gemm_exact == 1; in.gemm_small_exact = h->gemm_small_exact == 1;
+        in.no_dma = h->gemm_no_dma != 0; in.no_p8 = h->gemm_no_p8 != 0; in.splitk = h->gemm_splitk != 0;
+        in.p8_part_min = h->gemm_p8_part_min; in.sk_max_tiles = h->gemm_splitk_max_tiles;
+        in.paired = pair; in.do2d = do2d; in.use_gcn_edge = h->d.use_gcn_edge != 0;
+        in.feature_transform = h->d.feature_transform != 0; in.train = tr != nullptr; in.prob_tap = p->prob != nullptr; in.debug_stop = stop;
+        const EdgeAttnFmt af = edge_attn_fmt(h);
+        in.flash_x3 = af.x3 && (af.dh == 32 || af.dh == 64 || af.dh == 128); in.head_dim = af.dh; in.flash_tr = h->flash_tr ? 1 : 0;
+        in.fa_parts = p->fa_parts > 1 ? p->fa_parts : 1;
+        h->pairs = edge_pairs_plan(in);
+    }
     hipStream_t t = s, u = s;
     size_t ev_i = 0;
     if (dual) {
@@ -750,8 +784,8 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
             }
         }
         STAGE(base + 1);
-        GcnSide gs[2] = {{&h->gcn3[l], p->X3, p->E3, e3_pending_relu, &sc3}, {}};      // :224 gcn_3ds[l], :225 gcn_2ds[l]
-        if (do2d) gs[1] = {&h->gcn2[l], p->X2, p->E2, 0, &sc2};
+        GcnSide gs[2] = {{&h->gcn3[l], p->X3, p->E3, e3_pending_relu, &sc3, 0}, {}};      // :224 gcn_3ds[l], :225 gcn_2ds[l]
+        if (do2d) gs[1] = {&h->gcn2[l], p->X2, p->E2, 0, &sc2, 1};
         if (pair) {                                           // as launches of two problems each, behind the previous layer's edge attention
             RUN(wait(s, edge_done));
             RUN(gcn_block(h, p, s, gs, 2, inter));
@@ -798,13 +832,14 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
         // its first Linear on N rows, gathered into the edge GEMM's accumulators like nn_edge.0 (fp32 tables, no ReLU pending)
         if (!h->trip.wnode) return fail(VLSAT_ESTATE, "forward(istrain=True): triplet_projector_2d weights were not loaded");
         RUN(gemm(h, s, G(p->X2, LDX, h->trip.wnode, D, sc2.NP, npc_of(h), N, 4 * D, h->trip.bnode)));
-        RUN(gemm(h, s, nn_edge0_args(h, p, h->trip.we, p->E2, 0, sc2, false)));
+        RUN(gemm(h, s, nn_edge0_args(h, p, h->trip.we, p->E2, 0, sc2, false, false, h->pairs.hbig[1])));
         GemmArgs e2 = G(sc2.Hbig, 2 * D, h->trip.w2, 2 * D, tr->edge_dis, D, E, D, h->trip.b2);
         e2.a_split = split_fmt(h);
+        e2.a_pair = h->pairs.hbig[1];
         RUN(gemm(h, s, e2));
     }
     // a-15 relation heads, a-16 object heads
-    const RelSide rs[2] = {{&h->rel3, p->E3, e3_pending_relu, rel3d, &sc3}, {&h->rel2, p->E2, 0, rel2d, &sc2}};
+    const RelSide rs[2] = {{&h->rel3, p->E3, e3_pending_relu, rel3d, &sc3, 0}, {&h->rel2, p->E2, 0, rel2d, &sc2, 1}};
     const ObjSide os[2] = {{p->X3, h->obj3_w, h->obj3_b, obj3d, &sc3}, {p->X2, h->obj2_w, h->obj2_b, obj2d, &sc2}};
     if (pair) {                                               // both head pairs as launches of two problems each, behind the last edge attention
         RUN(wait(s, edge_done));

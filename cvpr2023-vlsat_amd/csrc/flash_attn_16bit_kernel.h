@@ -12,7 +12,13 @@ __global__ __launch_bounds__(64 * BQW, 2) void VLSAT_FLASH_KERNEL_NAME(
     float* __restrict__ O, int ldq, int ldkv, int ldo, const int4* __restrict__ tiles, int n_tiles,
     float scale_log2e, FlashSplit sp) {
     constexpr bool X3 = VLSAT_FLASH_KERNEL_X3;
-    static_assert(!X3 || (TERMS == 3 && IO == 0 && PVT == 3 && RING == 0 && BQW == 4 && ABL == 0 && QG == 1), "split-fp16: the three-term kernel on fp32 tensors, register-staged");
+    static_assert(!X3 || (TERMS == 3 && (IO == 0 || IO == 4 || IO == 5) && PVT == 3 && RING == 0 && BQW == 4 && ABL == 0 && QG == 1), "split-fp16: the three-term kernel on fp32 tensors or pair words, register-staged");
+    // X3, IO 4 / 5 (fp32 mode, "edge_pairs"): K and V arrive as ATTENTION pair words (gemm_f16s_planes.h f16s_attn_pack: hi << 16 | lo of
+    // split4h<true>, V already times 2^3 -- written by the key | value projection's epilogue), so staging separates the halves with two byte
+    // permutes per plane instead of clamping, converting and subtracting every word once per block of 128 queries; Q stays fp32 (split once
+    // per block anyway).  IO 5: O leaves as GEMM pair words for the out-projection (one key part only: split-key partials stay fp32).
+    constexpr bool KVP = X3 && IO >= 4, OP = X3 && IO == 5;
+    constexpr int IOQ = X3 ? 0 : IO, IOKV = X3 ? (KVP ? 1 : 0) : IO;      // formats load4 / planes_of see (pair words separate like split pairs)
     constexpr int PL = TERMS == 1 ? 1 : 2;
     constexpr int NKS = FB_D / 16, NO = FB_D / 32, NSUB = FB_D / 16;
     constexpr int FB_KPITCH = 2 * FB_D + 16;       // bytes per key row of a K plane (conflict-free ds_read_b128)
@@ -63,14 +69,14 @@ __global__ __launch_bounds__(64 * BQW, 2) void VLSAT_FLASH_KERNEL_NAME(
         const float* qrowp = Q + (size_t)(row_base + qrow) * ldq;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
-            f32x4 x0 = load4<IO>(qrowp, col0 + 8 * hi + 16 * ks), x1 = load4<IO>(qrowp, col0 + 8 * hi + 16 * ks + 4);
-            if (IO == 0) {
+            f32x4 x0 = load4<IOQ>(qrowp, col0 + 8 * hi + 16 * ks), x1 = load4<IOQ>(qrowp, col0 + 8 * hi + 16 * ks + 4);
+            if (IOQ == 0) {
                 x0 *= scale_log2e;
                 x1 *= scale_log2e;
             }
             bf16x4 h0, l0, h1, l1;
-            planes_of<IO, X3>(x0, h0, l0);
-            planes_of<IO, X3>(x1, h1, l1);
+            planes_of<IOQ, X3>(x0, h0, l0);
+            planes_of<IOQ, X3>(x1, h1, l1);
             qh[ks] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
             ql[ks] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
@@ -109,21 +115,21 @@ __global__ __launch_bounds__(64 * BQW, 2) void VLSAT_FLASH_KERNEL_NAME(
         for (int i = 0; i < NKS; ++i) {
             int r = kv0 + krow + RP * i;
             r = r < n_tok ? r : n_tok - 1;
-            rk[i] = load4<IO>(K + (size_t)(row_base + r) * ldkv, col0 + kc4);
+            rk[i] = load4<IOKV>(K + (size_t)(row_base + r) * ldkv, col0 + kc4);
             int rv_ = kv0 + vkey_of(i);
             rv_ = rv_ < n_tok ? rv_ : n_tok - 1;
-            rv[i] = load4<IO>(V + (size_t)(row_base + rv_) * ldkv, col0 + vsub_of(i) * 16 + (lane & 3) * 4);
+            rv[i] = load4<IOKV>(V + (size_t)(row_base + rv_) * ldkv, col0 + vsub_of(i) * 16 + (lane & 3) * 4);
         }
     };
     auto store_tile = [&](char* buf) {
 #pragma unroll
         for (int i = 0; i < NKS; ++i) {
             bf16x4 h, l;
-            planes_of<IO, X3>(rk[i], h, l);
+            planes_of<IOKV, X3 && !KVP>(rk[i], h, l);
             char* kp = buf + (krow + RP * i) * FB_KPITCH + kc4 * 2;
             *reinterpret_cast<bf16x4*>(kp) = h;
             if (PL == 2) *reinterpret_cast<bf16x4*>(kp + FB_KPLANE) = l;
-            planes_of<IO, X3>(X3 ? rv[i] * VS : rv[i], h, l);
+            planes_of<IOKV, X3 && !KVP>((X3 && !KVP) ? rv[i] * VS : rv[i], h, l);
             char* vp = buf + PL * FB_KPLANE + vsub_of(i) * FB_VSUB + vkey_of(i) * 32 + (lane & 3) * 8;
             *reinterpret_cast<bf16x4*>(vp) = h;
             if (PL == 2) *reinterpret_cast<bf16x4*>(vp + FB_VPLANE) = l;
@@ -447,7 +453,18 @@ __global__ __launch_bounds__(64 * BQW, 2) void VLSAT_FLASH_KERNEL_NAME(
                 *reinterpret_cast<f16x4_o*>(reinterpret_cast<char*>(orow) + (col0 + c4) * 2) = __builtin_convertvector(vc, f16x4_o);
             } else if (IO == 2 && !split)
                 *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(orow) + (col0 + c4) * 2) = __builtin_convertvector(v, bf16x4);
-            else
+            else if (OP && !split) {        // GEMM pair words: the out-projection's A operand, split here once (f16s_pack2)
+                typedef unsigned u32x4_o __attribute__((ext_vector_type(4)));
+                u32x4_o w;
+#pragma unroll
+                for (int c = 0; c < 4; c += 2) {
+                    unsigned w0, w1;
+                    f16s_pack2(v[c], v[c + 1], w0, w1);
+                    w[c] = w0;
+                    w[c + 1] = w1;
+                }
+                *reinterpret_cast<u32x4_o*>(orow + col0 + c4) = w;
+            } else
                 *reinterpret_cast<f32x4*>(orow + col0 + c4) = v;
         }
     }

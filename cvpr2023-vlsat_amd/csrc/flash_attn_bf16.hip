@@ -182,6 +182,10 @@ static_assert(sizeof kFlashKernels / sizeof kFlashKernels[0] == kFlashVariantCou
 constexpr FlashKernel kFlashF16x3Kernels[] = {VLSAT_FLASH_F16X3_VARIANTS(VLSAT_FLASH_F16X3_KERNEL)};
 #undef VLSAT_FLASH_F16X3_KERNEL
 static_assert(sizeof kFlashF16x3Kernels / sizeof kFlashF16x3Kernels[0] == kFlashF16x3VariantCount, "one kernel per row of the split-fp16 list");
+#define VLSAT_FLASH_F16X3_PAIR_KERNEL(R, D, I) flash_attn_f16x3_kernel<3, R, I, 3, D>,
+constexpr FlashKernel kFlashF16x3PairKernels[] = {VLSAT_FLASH_F16X3_PAIR_VARIANTS(VLSAT_FLASH_F16X3_PAIR_KERNEL)};
+#undef VLSAT_FLASH_F16X3_PAIR_KERNEL
+static_assert(sizeof kFlashF16x3PairKernels / sizeof kFlashF16x3PairKernels[0] == kFlashF16x3PairVariantCount, "one kernel per row of the pair-word list");
 
 }  // namespace
 
@@ -208,7 +212,7 @@ int launch_flash_attn_bf16(const float* Q, int ldq, const float* K, const float*
 }
 
 int launch_flash_attn_f16x3(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
-                            const int4* tiles, int n_tiles, float scale_log2e, int use_tr, hipStream_t s, const FlashSplit* split, int head_dim) {
+                            const int4* tiles, int n_tiles, float scale_log2e, int use_tr, hipStream_t s, const FlashSplit* split, int head_dim, int io) {
     if (n_tiles <= 0) return 0;
     if ((ldq | ldkv | ldo) & 3) return fail(-1, "flash_attn: leading dims must be multiples of 4");
     FlashSplit sp{};
@@ -218,9 +222,11 @@ int launch_flash_attn_f16x3(const float* Q, int ldq, const float* K, const float
             return fail(-1, "flash_attn: incomplete split-key workspace");
     }
     if (split) { sp.ablate = split->ablate; sp.bq = split->bq; sp.rows = split->rows; sp.qg = split->qg; }
-    const FlashPick pick = flash_f16x3_pick(head_dim, use_tr, 0, sp.bq, sp.qg, sp.ablate);
+    // io 0: fp32 tensors; 4 | 5: K and V as attention pair words (5: O as GEMM pair words) -- what is not in the lists is an error
+    const FlashPick pick = io ? flash_f16x3_pair_pick(head_dim, use_tr, io, sp.parts > 1 ? sp.parts : 1, sp.bq, sp.qg, sp.ablate)
+                              : flash_f16x3_pick(head_dim, use_tr, 0, sp.bq, sp.qg, sp.ablate);
     if (pick.index < 0) return fail(-1, pick.error);
-    hipLaunchKernelGGL(kFlashF16x3Kernels[pick.index], dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
+    hipLaunchKernelGGL(io ? kFlashF16x3PairKernels[pick.index] : kFlashF16x3Kernels[pick.index], dim3(n_tiles), dim3(256), 0, s, Q, K, V, O, ldq, ldkv, ldo, tiles, n_tiles, scale_log2e, sp);
     VLSAT_LAUNCH_CHECK("flash_attn_f16x3");
     if (sp.parts > 1) return launch_flash_merge(O, ldo, sp, s, 0, head_dim);
     return 0;

@@ -134,5 +134,22 @@ inline FlashPick flash_f16x3_pick(int d, int use_tr, int io = 0, int bq = FLASH_
     return {-1, "flash_attn_f16x3: head dim not built"};
 }
 inline bool flash_f16x3_supports(int head_dim, int use_tr) { return flash_f16x3_pick(head_dim, use_tr).index >= 0; }
+// ... on pair words (fp32 mode, "edge_pairs"): Z(TR, FB_D, IO) = flash_attn_f16x3_kernel<3, TR, IO, 3, FB_D>, IO 4: K and V arrive as attention
+// pair words (gemm_f16s_planes.h), 5: and O leaves as GEMM pair words.  A list and a pick of their own: flash_f16x3_pick stays what
+// tests/flash_f16x3_pick_check.cpp pins it to.
+#define VLSAT_FLASH_F16X3_PAIR_VARIANTS(Z) Z(true, 64, 4) Z(true, 64, 5) Z(false, 64, 4) Z(false, 64, 5)
+struct FlashF16x3PairVariant { bool tr; int d, io; };
+#define VLSAT_FLASH_F16X3_ROW(R, D, I) {R, D, I},
+constexpr FlashF16x3PairVariant kFlashF16x3PairVariants[] = {VLSAT_FLASH_F16X3_PAIR_VARIANTS(VLSAT_FLASH_F16X3_ROW)};
+#undef VLSAT_FLASH_F16X3_ROW
+constexpr int kFlashF16x3PairVariantCount = (int)(sizeof kFlashF16x3PairVariants / sizeof kFlashF16x3PairVariants[0]);
+// io 4 | 5; parts: key parts of the launch (O as pair words needs one: the merge kernel writes fp32)
+inline FlashPick flash_f16x3_pair_pick(int d, int use_tr, int io, int parts = 1, int bq = FLASH_BQ, int qg = 0, int ablate = 0) {
+    if (flash_f16x3_pick(d, use_tr, 0, bq, qg, ablate).index < 0) return flash_f16x3_pick(d, use_tr, 0, bq, qg, ablate);
+    if (io == 5 && parts > 1) return {-1, "flash_attn_f16x3: O as pair words needs one key part"};
+    for (int i = 0; i < kFlashF16x3PairVariantCount; ++i)
+        if (const FlashF16x3PairVariant& v = kFlashF16x3PairVariants[i]; v.tr == (use_tr == 1) && v.d == d && v.io == io) return {i, nullptr};
+    return {-1, "flash_attn_f16x3: pair-word form not built"};
+}
 
 }  // namespace vlsat

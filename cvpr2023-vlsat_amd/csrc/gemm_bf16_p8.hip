@@ -79,6 +79,10 @@ static_assert(sizeof kP8Kernels / sizeof kP8Kernels[0] == kGemmP8Count, "one ker
 constexpr P8Kernel kP8sKernels[] = {VLSAT_GEMM_P8S_VARIANTS(VLSAT_P8S_KERNEL)};
 #undef VLSAT_P8S_KERNEL
 static_assert(sizeof kP8sKernels / sizeof kP8sKernels[0] == kGemmP8sCount, "one kernel per row of the sibling list");
+#define VLSAT_P8S_PAIR_KERNEL(...) gemm_p8s_kernel<2, __VA_ARGS__>,
+constexpr P8Kernel kP8sPairKernels[] = {VLSAT_GEMM_P8S_PAIR_VARIANTS(VLSAT_P8S_PAIR_KERNEL)};
+#undef VLSAT_P8S_PAIR_KERNEL
+static_assert(sizeof kP8sPairKernels / sizeof kP8sPairKernels[0] == kGemmP8sPairCount, "one kernel per row of the pair-word list");
 
 // full rounds of a large-M launch on 256 x 256 tiles: half-row bf16 / fp16 operands (prec 1), exact fp32 (prec 0) or split-bf16
 // on split-pair operands (prec 3).  Which launches come here, and as which row, is plan_gemm with gemm_p8_pick.
@@ -89,7 +93,13 @@ static_assert(sizeof kP8sKernels / sizeof kP8sKernels[0] == kGemmP8sCount, "one 
 int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
     // (GemmArgs::f16s: the split-fp16 sibling of an exact-fp32 row takes the launch as planned -- gemm_p8s_pick)
     const int sib = gemm_p8s_pick(a, p.variant);
-    hipLaunchKernelGGL(sib >= 0 ? kP8sKernels[sib] : kP8Kernels[p.variant], dim3(p.grid), dim3(512), 0, s, a, p.n_tiles, a.N / P8_BN);
+    P8Kernel k = sib >= 0 ? kP8sKernels[sib] : kP8Kernels[p.variant];
+    if (a.a_pair || a.c_pair) {                  // GEMM pair words: only the sibling's pair forms read and write them
+        const int pr = gemm_p8s_pair_pick(a, p.variant);
+        if (pr < 0) return fail(-1, "gemm_p8: pair words (a_pair / c_pair) on a launch without a split-fp16 pair form");
+        k = kP8sPairKernels[pr];
+    }
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(512), 0, s, a, p.n_tiles, a.N / P8_BN);
     if (a.launches) ++*a.launches;
     VLSAT_LAUNCH_CHECK("gemm_p8");
     return 0;

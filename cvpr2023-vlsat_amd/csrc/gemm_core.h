@@ -146,7 +146,14 @@ __device__ __forceinline__ void tile_init(const GemmArgs& p, int m0, int n0, int
 // Epilogue of a finished tile: row scale, bias, activation, final scale, store in the output format (c_split).  Everything
 // is straight-line code under WAVE-UNIFORM branches (per-element branches on the runtime flags cost ~30 % of the tile
 // time in the first version of the kernel).  BM / BN: the block tile (for the interior test).
-template <int TM, int TN, bool PLAIN = false>
+// CP (PLAIN only): C is written as GEMM pair words (f16s_pack2, defined below with the split-fp16 operand code)
+__device__ __forceinline__ void f16s_pack2(float x0, float x1, unsigned& w0, unsigned& w1);
+__device__ __forceinline__ float f16s_pack1(float x);
+__device__ __forceinline__ void f16s_attn_pack2(float x0, float x1, float scale, unsigned& w0, unsigned& w1);
+__device__ __forceinline__ float f16s_attn_pack1(float x, float scale);
+// (CP 2: ATTENTION pair words -- the K | V projection: the columns below N / 2 as K words, the others as V words, times 2^3; a block tile
+//  never holds both)
+template <int TM, int TN, bool PLAIN = false, int CP = 0>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, int m0, int n0, int BM, int BN, int wm, int wn, int lane,
                                               f32x16 (&acc)[TM][TN]) {
     const bool c_f16 = !PLAIN && p.c_f16_cols > 0 && (n0 + BN <= p.c_f16_cols || p.c_f16_cols >= p.N);      // (c_f16_cols == N: the whole output, whatever N is)      // this block tile's columns are fp16 half rows (GemmArgs::c_f16_cols)
@@ -264,6 +271,16 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, int m0, int n0,
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) v[c] = pack_split(v[c]);
                             }
+                            if (CP) {
+#pragma unroll
+                                for (int c = 0; c < 4; c += 2) {
+                                    unsigned w0, w1;
+                                    if (CP == 2) f16s_attn_pack2(v[c], v[c + 1], 2 * n0 >= p.N ? 8.f : 1.f, w0, w1);
+                                    else f16s_pack2(v[c], v[c + 1], w0, w1);
+                                    v[c] = __builtin_bit_cast(float, w0);
+                                    v[c + 1] = __builtin_bit_cast(float, w1);
+                                }
+                            }
                             *reinterpret_cast<f32x4*>(crow + col) = v;
                         }
                     }
@@ -283,7 +300,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, int m0, int n0,
                 if (m < p.M && n < p.N) {
                     const float v = acc[tm][tn][r];
                     if (c_split == 2) reinterpret_cast<unsigned short*>(crow)[n] = __builtin_bit_cast(unsigned short, (__bf16)v);
-                    else crow[n] = c_split ? pack_split(v) : v;
+                    else crow[n] = CP == 2 ? f16s_attn_pack1(v, 2 * n0 >= p.N ? 8.f : 1.f) : CP ? f16s_pack1(v) : c_split ? pack_split(v) : v;
                 }
             }
     }
@@ -550,6 +567,61 @@ __device__ __forceinline__ void f16s_split8(const f32x4& x0, const f32x4& x1, fl
     hi = __builtin_bit_cast(bf16x8, h);
     lo = __builtin_bit_cast(bf16x8, l);
 }
+// GEMM pair words (gemm_f16s_planes.h f16s_pair_pack: Ah << 16 | Al, one word per element) -- what a producer stores for a tensor whose
+// readers would all run f16s_split8 on it, with the operations of f16s_split8 (clamp, convert, one mixed fma), so that the halves a
+// reader separates are bit for bit the ones it would have computed.  Two elements at a time: the converts and fmas work on register halves.
+__device__ __forceinline__ void f16s_pack2(float x0, float x1, unsigned& w0, unsigned& w1) {
+    typedef float f32x2_s __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2_s __attribute__((ext_vector_type(2)));
+    x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f);
+    x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f);
+    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_s{x0, x1}), f16x2_s));
+    unsigned l = f16s_lo1(h, x0);
+    asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "s"(-2048.f), "v"(x1 * 2048.f));
+    w0 = __builtin_amdgcn_perm(h, l, 0x05040100u);
+    w1 = __builtin_amdgcn_perm(h, l, 0x07060302u);
+}
+__device__ __forceinline__ float f16s_pack1(float x) {
+    x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+    const unsigned h = (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x);
+    return __builtin_bit_cast(float, (h << 16) | (f16s_lo1(h, x) & 0xffffu));
+}
+// ATTENTION pair words (gemm_f16s_planes.h f16s_attn_pack: hi << 16 | lo of split4h<true>(x scale), flash_attn_bf16.hip), with that
+// function's operations: multiply, clamp, convert, subtract, convert
+__device__ __forceinline__ void f16s_attn_pack2(float x0, float x1, float scale, unsigned& w0, unsigned& w1) {
+    typedef float f32x2_s __attribute__((ext_vector_type(2)));
+    typedef _Float16 f16x2_s __attribute__((ext_vector_type(2)));
+    const f32x2_s x = {__builtin_amdgcn_fmed3f(x0 * scale, -65504.f, 65504.f), __builtin_amdgcn_fmed3f(x1 * scale, -65504.f, 65504.f)};
+    const f16x2_s h2 = __builtin_convertvector(x, f16x2_s);
+    const unsigned h = __builtin_bit_cast(unsigned, h2);
+    const unsigned l = __builtin_bit_cast(unsigned, __builtin_convertvector(x - __builtin_convertvector(h2, f32x2_s), f16x2_s));
+    w0 = __builtin_amdgcn_perm(h, l, 0x05040100u);
+    w1 = __builtin_amdgcn_perm(h, l, 0x07060302u);
+}
+__device__ __forceinline__ float f16s_attn_pack1(float x, float scale) {
+    x = __builtin_amdgcn_fmed3f(x * scale, -65504.f, 65504.f);
+    const _Float16 h = (_Float16)x;
+    const _Float16 l = (_Float16)(x - (float)h);
+    return __builtin_bit_cast(float, ((unsigned)__builtin_bit_cast(unsigned short, h) << 16) | __builtin_bit_cast(unsigned short, l));
+}
+// the reader's side: eight pair words (two 16-byte chunks, eight consecutive k) -> the Ah and Al operand registers; a pending ReLU is a
+// signed max on the word (x < 0 <=> Ah < 0; the halves of zero are both +0)
+template <bool RELU>
+__device__ __forceinline__ void f16s_unpack8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
+    typedef unsigned u32x4_s __attribute__((ext_vector_type(4)));
+    u32x4_s a = __builtin_bit_cast(u32x4_s, x0), b = __builtin_bit_cast(u32x4_s, x1);
+    if (RELU) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { a[c] = (unsigned)max((int)a[c], 0); b[c] = (unsigned)max((int)b[c], 0); }
+    }
+    u32x4_s h, l;
+    h[0] = __builtin_amdgcn_perm(a[1], a[0], 0x07060302u); h[1] = __builtin_amdgcn_perm(a[3], a[2], 0x07060302u);
+    h[2] = __builtin_amdgcn_perm(b[1], b[0], 0x07060302u); h[3] = __builtin_amdgcn_perm(b[3], b[2], 0x07060302u);
+    l[0] = __builtin_amdgcn_perm(a[1], a[0], 0x05040100u); l[1] = __builtin_amdgcn_perm(a[3], a[2], 0x05040100u);
+    l[2] = __builtin_amdgcn_perm(b[1], b[0], 0x05040100u); l[3] = __builtin_amdgcn_perm(b[3], b[2], 0x05040100u);
+    hi = __builtin_bit_cast(bf16x8, h);
+    lo = __builtin_bit_cast(bf16x8, l);
+}
 // ... and the third operand of a product, Wh 2^-11, from a Wh fragment (exact for |Wh| >= 2^-3 or zero)
 __device__ __forceinline__ bf16x8 f16s_w_small(const bf16x8& wh) {
     return __builtin_bit_cast(bf16x8, __builtin_bit_cast(f16x8, wh) * (_Float16)0.00048828125f);
@@ -662,7 +734,10 @@ struct PipeSplitDma {
     // Ah | Al 2^11 (f16s_split8: its clamp does the ReLU, one body for both settings), the weight planes Wh16 / Wl16 of gemm_f16s_planes.h
     // staged exactly like the bf16 ones (the stage bytes equal the fp32 pipe's), per 16-wide k-step the terms (Wh 2^-11).Al, Wl.Ah, Wh.Ah
     // -- the order and the k sets of gemm_p8s_kernel.  The accumulator holds the product times 2^w_exp (the kernel scales inits and results).
-    static constexpr bool FS = AFMT == 4;
+    // 5: AFMT 4 on GEMM PAIR WORDS (gemm_f16s_planes.h; GemmArgs::a_pair): the producer stored Ah | Al, the fragment side separates them with
+    // byte permutes (f16s_unpack8) instead of splitting -- the same operands, the same MFMAs
+    static constexpr bool FS = AFMT == 4 || AFMT == 5;
+    static constexpr bool AP = AFMT == 5;
     static constexpr bool F16 = AFMT == 3 || FS;
     static_assert(!AH || TERMS == 1, "half-row operands carry no low part");
     static_assert(!FS || TERMS == 3, "the split-fp16 form has three terms");
@@ -766,11 +841,17 @@ struct PipeSplitDma {
         }
     }
     static __device__ __forceinline__ void mma(const char* stage, int wm, int wn, f32x16 (&acc)[TM][TN], int lane, int relu_a = 0) {
-        if constexpr (FS) { mma_fs(stage, wm, wn, acc, lane, relu_a ? 0.f : -65504.f); return; }
+        if constexpr (AP) {
+            if (relu_a) mma_fs<1>(stage, wm, wn, acc, lane, 0.f);      // wave-uniform: two straight-line bodies
+            else mma_fs<2>(stage, wm, wn, acc, lane, 0.f);
+            return;
+        }
+        if constexpr (FS) { mma_fs<0>(stage, wm, wn, acc, lane, relu_a ? 0.f : -65504.f); return; }
         if (relu_a) mma_t<true>(stage, wm, wn, acc, lane);          // wave-uniform: two straight-line bodies, no per-element select
         else mma_t<false>(stage, wm, wn, acc, lane);
     }
-    // FS: lower = the clamp's lower bound (0: ReLU-on-A)
+    // FS: lower = the clamp's lower bound (0: ReLU-on-A).  UNP (pair words): 1 = unpack with a pending ReLU, 2 = unpack, 0 = split fp32 words
+    template <int UNP>
     static __device__ __forceinline__ void mma_fs(const char* stage, int wm, int wn, f32x16 (&acc)[TM][TN], int lane, float lower) {
         const int li = lane & 31, hi = lane >> 5;
         const float* sA = reinterpret_cast<const float*>(stage) + (wm * TM * 32 + li) * BK;
@@ -784,7 +865,8 @@ struct PipeSplitDma {
                 const int c0 = (4 * ks + 2 * hi) ^ swa;                   // as mma_t: the first four k, the next four at c0 ^ 1
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(sA + tm * 32 * BK + 4 * c0);
                 const f32x4 x1 = *reinterpret_cast<const f32x4*>(sA + tm * 32 * BK + 4 * (c0 ^ 1));
-                f16s_split8(x0, x1, lower, a[0][tm], a[1][tm]);
+                if constexpr (UNP == 0) f16s_split8(x0, x1, lower, a[0][tm], a[1][tm]);
+                else f16s_unpack8<UNP == 1>(x0, x1, a[0][tm], a[1][tm]);
             }
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl)
@@ -866,5 +948,10 @@ template <int BM, int BN> struct PipeSel<BM, BN, 11> { using type = PipeSplitDma
 template <int BM, int BN> struct PipeSel<BM, BN, 13> { using type = PipeSplitDma<BM, BN, 1, 2>; };  // ... A as half rows (bf16)
 template <int BM, int BN> struct PipeSel<BM, BN, 15> { using type = PipeSplitDma<BM, BN, 1, 3>; };  // ... A as half rows of fp16, fp16 weight plane
 template <int BM, int BN> struct PipeSel<BM, BN, 17> { using type = PipeSplitDma<BM, BN, 3, 4>; };  // internal: split-fp16 on fp32 A (the fp32 mode's sibling kernel, gemm_f16s_kernel)
+template <int BM, int BN> struct PipeSel<BM, BN, 18> { using type = PipeSplitDma<BM, BN, 3, 4>; };  // ... C written as GEMM pair words
+template <int BM, int BN> struct PipeSel<BM, BN, 19> { using type = PipeSplitDma<BM, BN, 3, 5>; };  // ... A read as GEMM pair words
+template <int BM, int BN> struct PipeSel<BM, BN, 20> { using type = PipeSplitDma<BM, BN, 3, 5>; };  // ... both
+template <int BM, int BN> struct PipeSel<BM, BN, 21> { using type = PipeSplitDma<BM, BN, 3, 4>; };  // ... C written as ATTENTION pair words (the K | V projection)
+template <int BM, int BN> struct PipeSel<BM, BN, 22> { using type = PipeSplitDma<BM, BN, 3, 5>; };  // ... and A read as GEMM pair words
 
 }  // namespace vlsat

@@ -47,7 +47,8 @@ namespace vlsat {
 double gemm_flops(const GemmArgs& a) { return 2.0 * a.M * (double)a.N * a.K; }
 
 // resident 256-thread blocks the persistent grid may use (2 per CU): a constant of the device, cached per device id
-static int slots() {
+static int slots() { return gemm_slots(); }
+int gemm_slots() {
     static int cache[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -78,6 +79,24 @@ constexpr TiledKernel kF16sKernels[][kGemmTileCount + 1] = {VLSAT_GEMM_F16S_TILE
 #undef VLSAT_F16S_KERNELS
 static_assert(sizeof kF16sKernels / sizeof kF16sKernels[0] == kGemmF16sTiledCount, "one row of kernels per row of the siblings' list");
 
+// ... and their forms on GEMM pair words (PREC 18 / 19 / 20: gemm_f16s_pair_prec), single launches only
+#define VLSAT_F16S_PAIR_KERNELS(ADD, PREC)                                                                                            \
+    {gemm_f16s_kernel<128, 128, ADD, PREC, 1>, gemm_f16s_kernel<128, 64, ADD, PREC, 1>, gemm_f16s_kernel<64, 128, ADD, PREC, 1>,       \
+     gemm_f16s_kernel<64, 64, ADD, PREC, 1>, gemm_f16s_kernel<64, 64, ADD, PREC, 2>},
+// (PREC 21 / 22, attention pair words: the row without additive operands only -- gemm_f16s_pair_built)
+template <int ADD, int PREC, int BM, int BN, int KSL> constexpr TiledKernel f16s_attn_kernel() {
+    if constexpr (gemm_f16s_pair_built(ADD, PREC)) return gemm_f16s_kernel<BM, BN, ADD, PREC, KSL>; else return nullptr;
+}
+#define VLSAT_F16S_ATTN_KERNELS(ADD, PREC)                                                                                            \
+    {f16s_attn_kernel<ADD, PREC, 128, 128, 1>(), f16s_attn_kernel<ADD, PREC, 128, 64, 1>(), f16s_attn_kernel<ADD, PREC, 64, 128, 1>(), \
+     f16s_attn_kernel<ADD, PREC, 64, 64, 1>(), f16s_attn_kernel<ADD, PREC, 64, 64, 2>()},
+#define VLSAT_F16S_PAIR_ROW(ADD) {VLSAT_F16S_PAIR_KERNELS(ADD, 18) VLSAT_F16S_PAIR_KERNELS(ADD, 19) VLSAT_F16S_PAIR_KERNELS(ADD, 20) \
+                                  VLSAT_F16S_ATTN_KERNELS(ADD, 21) VLSAT_F16S_ATTN_KERNELS(ADD, 22)},
+constexpr TiledKernel kF16sPairKernels[][5][kGemmTileCount] = {VLSAT_GEMM_F16S_TILED_VARIANTS(VLSAT_F16S_PAIR_ROW)};
+#undef VLSAT_F16S_PAIR_ROW
+#undef VLSAT_F16S_PAIR_KERNELS
+static_assert(sizeof kF16sPairKernels / sizeof kF16sPairKernels[0] == kGemmF16sTiledCount, "one row of kernels per row of the siblings' list");
+
 // the persistent kernel on the plan's tiles; b: the second problem of a pair (grid.y = 2), which launch_gemm_pair has planned
 // (GemmArgs::f16s 2 | 3: the split-fp16 sibling of an exact-fp32 row takes the launch as planned -- gemm_f16s_tiled_pick; a pair when both
 //  problems ask for it)
@@ -86,7 +105,12 @@ static int launch_tiled(const GemmArgs& a, const GemmPlan& p, hipStream_t s, con
     const int tile = b ? kGemmTileCount : gemm_tile_index(p.bm, p.bn, p.ksl);
     int fs = gemm_f16s_tiled_pick(a, p.variant).index;
     if (b && gemm_f16s_tiled_pick(*b, p.variant).index != fs) fs = -1;
-    const TiledKernel k = fs >= 0 ? kF16sKernels[fs][tile] : kTiledKernels[p.variant][tile];
+    // pair words: only the siblings read and write them -- anything else is an error, never another kernel on the wrong format
+    const bool pairs = a.a_pair || a.c_pair || (b && (b->a_pair || b->c_pair));
+    if (pairs && (fs < 0 || b)) return fail(-1, "gemm: pair words (a_pair / c_pair) on a launch the split-fp16 persistent kernel does not take");
+    const TiledKernel k = pairs ? kF16sPairKernels[fs][gemm_f16s_pair_prec(a.a_pair, a.c_pair) - 18][tile]
+                          : fs >= 0 ? kF16sKernels[fs][tile] : kTiledKernels[p.variant][tile];
+    if (!k) return fail(-1, "gemm: this pair-word form of the split-fp16 persistent kernel is not built");
     hipLaunchKernelGGL(k, dim3(p.grid, b ? 2 : 1), dim3(256), 0, s, a, b ? *b : a, p.n_tiles, (a.N + p.bn - 1) / p.bn);
     if (a.launches) ++*a.launches;         // a logical GEMM is a main launch plus (usually) a small-tile tail launch
     VLSAT_LAUNCH_CHECK((b ? "gemm_f32 (pair)" : "gemm_f32"));
@@ -95,6 +119,8 @@ static int launch_tiled(const GemmArgs& a, const GemmPlan& p, hipStream_t s, con
 
 // the launch of a plan on rows [0, m.M) (m.M == p.rows)
 static int launch_plan(const GemmArgs& m, const GemmPlan& p, hipStream_t s) {
+    if ((m.a_pair || m.c_pair) && p.family != GemmPlan::P8 && p.family != GemmPlan::TILED)
+        return fail(-1, "gemm: pair words (a_pair / c_pair) on a launch planned onto a kernel without the form");
     if (p.family == GemmPlan::SPLITK) return launch_gemm_splitk(m, p, s);
     if (p.family == GemmPlan::P8) return launch_gemm_p8(m, p, s);
     return p.family == GemmPlan::RING ? launch_gemm_ring(m, p, s) : launch_tiled(m, p, s);
@@ -121,6 +147,7 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
 
 // two problems, one launch (one-scene plans, round 6): which pairs, and as what, is gemm_pair_plan
 int launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t s) {
+    if (a.a_pair || a.c_pair || b.a_pair || b.c_pair) return fail(-1, "gemm: pair words on a pair of problems");
     const GemmPlan p = gemm_pair_plan(a, b, slots(), g_clock_probe != nullptr);
     if (p.variant < 0) return 1;
     return p.family == GemmPlan::SPLITK ? launch_gemm_splitk(a, p, s, &b) : launch_tiled(a, p, s, &b);

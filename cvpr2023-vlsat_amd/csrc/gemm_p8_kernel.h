@@ -31,20 +31,27 @@
 //   * three v_mfma_f32_32x32x16_f16 per product into one fp32 accumulator, small terms first: (Wh 2^-11).Al, Wl.Ah, Wh.Ah.
 //   * additive accumulator inits enter times 2^k; the epilogue multiplies by 2^-k before bias and activation.  Powers of two: exact,
 //     so the operation order of the exact-fp32 path is otherwise kept.
+//   * pair words (CF = PF of VLSAT_GEMM_P8S_PAIR_VARIANTS; GemmArgs::a_pair / c_pair, gemm_f16s_planes.h): bit 2 -- A holds Ah << 16 | Al, stored
+//     by the kernel that wrote the tensor, and the fresh phases separate the halves with byte permutes (f16s_unpack8: one VALU operation per
+//     word instead of 3.5; a pending ReLU is a signed max on the word) -- bit 0: the epilogue stores such words (f16s_pack2, after 2^-k, bias
+//     and activation); bit 1: the epilogue stores ATTENTION pair words (f16s_attn_pack2: the key | value projection, whose reader is the
+//     split-fp16 edge attention).  The MFMA operands are bit for bit those of the fp32 form.
 // Domain: |A| <= 65504 (beyond: the operand saturates, results stay finite); weights below 2^-16 of their tensor's maximum lose low bits.
 template <int MODE, int ADD, bool RELU, int CF, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void VLSAT_P8_NAME(GemmArgs p, int n_tiles, int nbn) {
     constexpr bool FS = VLSAT_P8_FS;
     constexpr bool F32 = MODE == 1, X3 = MODE == 2, H16 = MODE == 3, WORDS = F32 || X3;      // WORDS: 4-byte A elements, K-tiles of 32; H16: MODE 0 on fp16 (GemmArgs::half_f16)
-    static_assert(MODE == 3 ? (CF == 0 || CF == 3) : MODE == 0 ? (CF == 0 || CF == 2 || CF == 3) : F32 ? CF == 0 : (CF == 0 || CF == 1), "output format of the mode");
-    static_assert(!FS || (X3 && CF == 0 && ABL == 0), "the split-fp16 form is MODE 2 on fp32 tensors");
+    static_assert(MODE == 3 ? (CF == 0 || CF == 3) : MODE == 0 ? (CF == 0 || CF == 2 || CF == 3) : F32 ? CF == 0 : (CF == 0 || CF == 1 || (FS && (CF == 2 || CF == 4 || CF == 5 || CF == 6))), "output format of the mode");
+    static_assert(!FS || (X3 && ABL == 0), "the split-fp16 form is MODE 2 on fp32 tensors or pair words");
+    constexpr bool AP = FS && (CF & 4) != 0, CP = FS && (CF & 1) != 0;      // split-fp16 form: A read / C written as GEMM pair words
+    constexpr bool CPA = FS && (CF & 2) != 0;                                // ... C written as ATTENTION pair words (the K | V projection)
     __shared__ __attribute__((aligned(16))) char smem[10 * P8_HALF];
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     constexpr bool SPREAD = ADD == 0;             // epilogue strips 2 / 3 inside the next tile's first K-tile
     // (ABL bits 8, 9, gathered-row launches: 256 = the init loads in a row-contiguous lane pattern, 512 = no init loads)
-    constexpr bool HALF = CF >= 2;                // two bytes per element of C
+    constexpr bool HALF = !FS && (CF == 2 || CF == 3);                // two bytes per element of C
     constexpr int E = HALF ? 4 : 8;            // buffer stores per epilogue strip and lane
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -222,7 +229,15 @@ __global__ __launch_bounds__(512, 2) void VLSAT_P8_NAME(GemmArgs p, int n_tiles,
             // words of a k-step are the two chunks 2 ks, 2 ks + 1; phases 2 and 4 find them split).  No barrier between the split and the
             // MFMAs: the compiler spreads the VALU work of the later fragments under the first MFMAs.
             typedef float f32x8 __attribute__((ext_vector_type(8)));
-            if (FRESH) {
+            if constexpr (FRESH && AP) {          // pair words: the producer made the halves, two byte permutes per register pair separate them
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) {
+                        const f32x4 x0 = __builtin_bit_cast(f32x4, af[mt][2 * ks]), x1 = __builtin_bit_cast(f32x4, af[mt][2 * ks + 1]);
+                        f16s_unpack8<RELU>(x0, x1, af[mt][2 * ks], af[mt][2 * ks + 1]);
+                    }
+            } else if constexpr (FRESH) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -403,7 +418,24 @@ __global__ __launch_bounds__(512, 2) void VLSAT_P8_NAME(GemmArgs p, int n_tiles,
                             }
                         }
                         r = __builtin_bit_cast(u32x4, x);
-                        if (CF == 1) {         // split pairs (common.h pack_split), two elements at a time
+                        if constexpr (CPA) {   // attention pair words: this block's columns are K (below N / 2) or V (times 2^3)
+                            const float vs = 2 * n0 >= p.N ? 8.f : 1.f;
+#pragma unroll
+                            for (int c = 0; c < 4; c += 2) {
+                                unsigned w0, w1;
+                                f16s_attn_pack2(x[c], x[c + 1], vs, w0, w1);
+                                r[c] = w0;
+                                r[c + 1] = w1;
+                            }
+                        } else if constexpr (CP) { // GEMM pair words of the split-fp16 operand (gemm_f16s_planes.h), two elements at a time
+#pragma unroll
+                            for (int c = 0; c < 4; c += 2) {
+                                unsigned w0, w1;
+                                f16s_pack2(x[c], x[c + 1], w0, w1);
+                                r[c] = w0;
+                                r[c + 1] = w1;
+                            }
+                        } else if constexpr (CF == 1) {  // split pairs (common.h pack_split), two elements at a time
 #pragma unroll
                             for (int c = 0; c < 4; c += 2) {
                                 const f32x2 v2 = {x[c], x[c + 1]};

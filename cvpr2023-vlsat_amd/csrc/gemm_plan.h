@@ -65,7 +65,16 @@ struct GemmArgs {
     const uint16_t* Wh16 = nullptr;
     const uint16_t* Wl16 = nullptr;
     int w_exp = 0;
+    // fp32 mode, "edge_pairs": A is read / C is written as GEMM PAIR WORDS (gemm_f16s_planes.h: Ah << 16 | Al of the split-fp16 operand, one
+    // word per element, same pitch).  Only on the split-fp16 siblings (f16s == 2: every part of the launch on one; gemm_pairs_pick says
+    // whether a plan's part has the form) -- which launches get them is decided once per forward (edge_pairs.h).
+    // c_pair 2: C as ATTENTION pair words -- columns [0, N / 2) in the K format, [N / 2, N) in the V format (times 2^3) of the split-fp16 edge
+    // attention (the key | value projection; N % 512 == 0, no additive operands)
+    // (two 16-bit fields in what was the struct's tail padding: the kernel-argument layout, and with it the code of every kernel that existed
+    //  before them, is unchanged)
+    int16_t a_pair = 0, c_pair = 0;
 };
+static_assert(sizeof(GemmArgs) % 8 == 0 && offsetof(GemmArgs, c_pair) + 2 == sizeof(GemmArgs), "a_pair / c_pair fill the tail padding behind w_exp");
 // The first launch of a GEMM as plan_gemm chooses it: kernel family, the row of the family's list, geometry, and the rows [0, rows) it
 // covers -- the rows after them are planned again as a problem of their own (the tail).
 struct GemmPlan {
@@ -181,11 +190,30 @@ inline GemmPick gemm_p8_pick(const GemmArgs& a) {
 // Split-fp16 siblings of the exact-fp32 rows (MODE 1): X(ADD, RELU) = gemm_p8s_kernel<2, ADD, RELU, 0> -- the (additive operands,
 // ReLU-on-A) combinations the fp32 forward launches.  A sibling takes the launch of its MODE 1 row as planned: same tiles, grid and rows.
 #define VLSAT_GEMM_P8S_VARIANTS(X) X(0, false) X(0, true) X(1, false) X(6, false) X(6, true)
+// ... and their forms on GEMM pair words (GemmArgs::a_pair / c_pair): X(ADD, RELU, PF) = gemm_p8s_kernel<2, ADD, RELU, PF>, PF bit 0: C is
+// written as pair words, bit 1: C is written as ATTENTION pair words (c_pair 2), bit 2: A is read as pair words (PF 0 is the sibling
+// itself).  By line: nn_edge.0 (gathered rows; C = Hbig), the launches without additive operands (nn_edge.2, proj_edge, relation
+// encoder conv3, relation head), the key | value projection of the edge attention and its out-projection (A = Oe, + residual)
+#define VLSAT_GEMM_P8S_PAIR_VARIANTS(X)                                  \
+    X(6, false, 1) X(6, false, 5) X(6, true, 1) X(6, true, 5)            \
+    X(0, false, 1) X(0, false, 4) X(0, false, 5) X(0, true, 1) X(0, true, 4) X(0, true, 5)            \
+    X(0, false, 2) X(0, false, 6) X(1, false, 4)
 struct GemmP8sVariant { int add; bool relu; };
 #define VLSAT_ROW(A, R) {A, R},
 constexpr GemmP8sVariant kGemmP8sVariants[] = {VLSAT_GEMM_P8S_VARIANTS(VLSAT_ROW)};
 #undef VLSAT_ROW
 constexpr int kGemmP8sCount = (int)(sizeof kGemmP8sVariants / sizeof kGemmP8sVariants[0]);
+struct GemmP8sPairVariant { int add; bool relu; int pf; };
+#define VLSAT_ROW(A, R, P) {A, R, P},
+constexpr GemmP8sPairVariant kGemmP8sPairVariants[] = {VLSAT_GEMM_P8S_PAIR_VARIANTS(VLSAT_ROW)};
+#undef VLSAT_ROW
+constexpr int kGemmP8sPairCount = (int)(sizeof kGemmP8sPairVariants / sizeof kGemmP8sPairVariants[0]);
+constexpr int gemm_pair_form(int a_pair, int c_pair) { return (a_pair ? 4 : 0) | (c_pair == 2 ? 2 : c_pair ? 1 : 0); }
+constexpr int gemm_p8s_pair_find(int add, bool relu, int pf) {
+    for (int i = 0; i < kGemmP8sPairCount; ++i)
+        if (kGemmP8sPairVariants[i].add == add && kGemmP8sPairVariants[i].relu == relu && kGemmP8sPairVariants[i].pf == pf) return i;
+    return -1;
+}
 constexpr int gemm_p8s_find(int add, bool relu) {
     for (int i = 0; i < kGemmP8sCount; ++i)
         if (kGemmP8sVariants[i].add == add && kGemmP8sVariants[i].relu == relu) return i;
@@ -201,6 +229,12 @@ inline int gemm_p8s_pick(const GemmArgs& a, int variant) {
     if (!gemm_f16s_p8(a) || variant < 0 || variant >= kGemmP8Count) return -1;
     const GemmP8Variant& v = kGemmP8Variants[variant];
     return v.mode == 1 && v.abl == 0 ? gemm_p8s_find(v.add, v.relu) : -1;
+}
+// ... and for a launch on pair words (a_pair | c_pair): the row of the pair list that runs it, or -1 -- then NOTHING runs it (an error)
+inline int gemm_p8s_pair_pick(const GemmArgs& a, int variant) {
+    if (gemm_p8s_pick(a, variant) < 0) return -1;
+    const GemmP8Variant& v = kGemmP8Variants[variant];
+    return gemm_p8s_pair_find(v.add, v.relu, gemm_pair_form(a.a_pair, a.c_pair));
 }
 // n_tiles tiles of the problem on a grid of `grid` blocks: the kernel keeps one column tile per block (bias registers)
 inline bool gemm_p8_geometry_ok(int M, int N, long n_tiles, long grid) {
@@ -266,6 +300,11 @@ inline GemmPick gemm_tiled_pick(const GemmArgs& a, bool relu_a, bool twin = fals
 // kGemmTiles and as a twin.  One pipe for both ReLU-on-A settings (its clamp does the ReLU).  A sibling takes the launch as planned: same
 // tile, grid and rows.
 #define VLSAT_GEMM_F16S_TILED_VARIANTS(X) X(0) X(1) X(6)
+// ... on GEMM pair words (GemmArgs::a_pair / c_pair): PREC 18 (C written as pairs), 19 (A read as pairs), 20 (both) of the same rows, on every
+// tile (no twin form: a pair of problems never carries pair words); PREC 21 / 22 (C as ATTENTION pair words, c_pair 2; 22: A read as
+// pairs) of the row without additive operands only (the key | value projection)
+constexpr int gemm_f16s_pair_prec(int a_pair, int c_pair) { return c_pair == 2 ? 21 + (a_pair ? 1 : 0) : 17 + (c_pair ? 1 : 0) + (a_pair ? 2 : 0); }
+constexpr bool gemm_f16s_pair_built(int add, int prec) { return prec >= 18 && prec <= 22 && (prec <= 20 || add == 0); }
 #define VLSAT_ROW(A) A,
 constexpr int kGemmF16sTiledAdds[] = {VLSAT_GEMM_F16S_TILED_VARIANTS(VLSAT_ROW)};
 #undef VLSAT_ROW
@@ -319,6 +358,9 @@ inline const char* gemm_invalid(const GemmArgs& a) {
     if (a.f16s && (a.prec != 0 || !a.Wh16 || !a.Wl16 || (a.ldw & 7) || ((reinterpret_cast<uintptr_t>(a.Wh16) | reinterpret_cast<uintptr_t>(a.Wl16)) & 15) ||
                    a.w_exp < -100 || a.w_exp > 100))
         return "gemm: f16s is the exact-fp32 precision with two 16-byte aligned fp16 weight planes, ldw % 8 == 0 and |w_exp| <= 100";
+    if ((a.a_pair || a.c_pair) && (a.f16s != 2 || a.rowscale || a.act == ACT_SIGMOID || a.N % 64))
+        return "gemm: pair words are read and written by the split-fp16 siblings only (f16s 2), no row scale, no sigmoid, N % 64 == 0";
+    if (a.c_pair == 2 && (a.N % 512 || a.resid || a.g0 || a.g1 || a.act != ACT_NONE)) return "gemm: attention pair words are the output of a plain Linear with N % 512 == 0";
     if (a.g_f16 && (a.resid || !(a.g0 || a.g1) || a.N % 256 || ((a.ldg0 | a.ldg1) & 1) || ((reinterpret_cast<uintptr_t>(a.g0) | reinterpret_cast<uintptr_t>(a.g1)) & 7)))
         return "gemm: g_f16 needs gathered rows, no residual, N % 256 == 0 and 8-byte aligned tables";
     return nullptr;
@@ -474,7 +516,7 @@ inline bool twin_shapes(const GemmArgs& a, const GemmArgs& b) {
            a.ldg0 == b.ldg0 && a.ldg1 == b.ldg1 && a.act == b.act && a.prec == b.prec && a.a_split == b.a_split && a.r_split == b.r_split &&
            a.c_split == b.c_split && a.c_scale == b.c_scale && a.resid_scale == b.resid_scale && !a.bias == !b.bias && !a.resid == !b.resid &&
            !a.g0 == !b.g0 && !a.g1 == !b.g1 && !a.rowscale == !b.rowscale && a.no_dma == b.no_dma && a.no_ring == b.no_ring &&
-           a.no_p8 == b.no_p8 && a.k_rot == b.k_rot && a.c_f16_cols == b.c_f16_cols && a.g_f16 == b.g_f16 && a.half_f16 == b.half_f16 && !a.force_tile && !b.force_tile && !a.ablate && !b.ablate && a.prefetch == b.prefetch;
+           a.no_p8 == b.no_p8 && !a.a_pair && !a.c_pair && !b.a_pair && !b.c_pair && a.k_rot == b.k_rot && a.c_f16_cols == b.c_f16_cols && a.g_f16 == b.g_f16 && a.half_f16 == b.half_f16 && !a.force_tile && !b.force_tile && !a.ablate && !b.ablate && a.prefetch == b.prefetch;
 }
 inline bool same_plan(const GemmPlan& p, const GemmPlan& q) {
     return p.family == q.family && p.rows == q.rows && p.bm == q.bm && p.bn == q.bn && p.ksl == q.ksl && p.slot_mult == q.slot_mult &&

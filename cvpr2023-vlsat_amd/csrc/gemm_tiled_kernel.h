@@ -4,6 +4,9 @@
 // PREC 17 (FS): fp32 tensors in and out like PREC 4, the products as three fp16 MFMAs each on the planes Wh16 / Wl16 of the weight
 // (PipeSplitDma AFMT 4, gemm_core.h); the accumulator holds the result times 2^w_exp: additive inits enter times 2^w_exp, the epilogue
 // multiplies by 2^-w_exp before row scale, bias and activation (powers of two: exact, so the operation order of the exact kernel is kept).
+// PREC 21 / 22: C written as ATTENTION pair words (the key | value projection of the edge attention; 22: A read as GEMM pair words).
+// PREC 18 / 19 / 20: PREC 17 with C written / A read / both as GEMM pair words (gemm_f16s_planes.h; GemmArgs::c_pair / a_pair) -- the halves
+// of the split-fp16 operand, made once by the producer's epilogue instead of by every reader.
 // ADD (compile time, so the 64 accumulator-init loads per lane are branch-free and batched):
 //   bit 0 = residual, bit 1 = gathered rows g0, bit 2 = gathered rows g1.
 // PREC: 0 = exact fp32 (PipeF32), 1 / 3 = bf16 / split-bf16 operands (PipeBF16, gemm_core.h), 4 .. 17 the LDS-direct pipes (PipeSel).
@@ -14,7 +17,8 @@ template <int BM, int BN, int ADD, int PREC, int KSL, bool TWIN = false>
 __global__ __launch_bounds__(256, 2) void VLSAT_TILED_NAME(GemmArgs pa, GemmArgs pb, int n_tiles, int nbn) {
     const GemmArgs& p = (TWIN && blockIdx.y != 0) ? pb : pa;
     constexpr int TM = BM / 64, TN = BN / 64;
-    constexpr bool FS = PREC == 17;              // split-fp16 sibling: acc = result 2^w_exp
+    constexpr bool FS = PREC >= 17 && PREC <= 22;      // split-fp16 sibling: acc = result 2^w_exp
+    constexpr int CP = PREC == 18 || PREC == 20 ? 1 : PREC >= 21 ? 2 : 0;      // ... that writes C as GEMM (1) / attention (2) pair words (19, 20, 22: reads A as GEMM pair words, PipeSel)
     constexpr bool PLAIN = PREC == 0 || PREC == 4 || FS;      // fp32 tensors, c_scale 1: the format dispatch of tile_init / tile_epilogue folds away
     using Pipe = typename PipeSel<BM, BN, PREC>::type;
     constexpr int SLICE = Pipe::STAGE_BYTES;
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256, 2) void VLSAT_TILED_NAME(GemmArgs pa, GemmArgs
             }
             if (last) {
                 if constexpr (FS) scale_acc<TM, TN>(acc, f16s_pow2(-p.w_exp));
-                tile_epilogue<TM, TN, PLAIN>(p, m0, n0, BM, BN, wm, wn, lane, acc);
+                tile_epilogue<TM, TN, PLAIN, CP>(p, m0, n0, BM, BN, wm, wn, lane, acc);
                 zero_acc<TM, TN>(acc);
             }
             buf ^= 1;

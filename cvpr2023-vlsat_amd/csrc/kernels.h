@@ -22,6 +22,7 @@ int launch_gemm_ring(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 int launch_gemm_p8(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
 double gemm_flops(const GemmArgs& a);
 void gemm_set_clock_probe(long long* buf);
+int gemm_slots();                                // resident 256-thread blocks the persistent grid may use (2 per CU): what plan_gemm plans with
 
 // ---- PointNet object encoder (fused conv1..conv3 + ReLU + max over points) ----
 int launch_pointnet(const float* pts, int n_obj, int n_points, int cin, const float* w1, const float* b1,
@@ -68,7 +69,7 @@ int launch_flash_attn_bf16(const float* Q, int ldq, const float* K, const float*
 // what a call gets: flash_f16x3_pick of flash_pick.h; what is not in that list is an error.
 int launch_flash_attn_f16x3(const float* Q, int ldq, const float* K, const float* V, int ldkv, float* O, int ldo,
                             const int4* tiles, int n_tiles, float scale_log2e, int use_tr, hipStream_t s,
-                            const FlashSplit* split = nullptr, int head_dim = 64);
+                            const FlashSplit* split = nullptr, int head_dim = 64, int io = 0);      // io 4 | 5: pair words (flash_f16x3_pair_pick)
 
 // ---- node attention with distance bias (per scene, per head) ----
 // scene_ptr: device [n_scenes+1] node offsets; bias_ptr: device [n_scenes] offsets into bias
