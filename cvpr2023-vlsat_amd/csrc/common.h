@@ -91,4 +91,9 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+
+// Probability of a single-label model's log-probability (its relation head ends in log_softmax).  The ONE statement of it: the
+// element-wise kernel behind launch_exp / vlsat_k_exp (scene_graph.hip) and the triplet-rank kernel that exponentiates on load
+// (eval_ranks.hip) both call it, so a score formed in registers equals the one read back from an exp'd tensor bit for bit.
+__device__ __forceinline__ float log_prob_exp(float x) { return expf(x); }
 #endif

@@ -473,7 +473,7 @@ int vlsat_eval_ranks(const float* obj_logits, const float* obj_probs, const floa
         return fail(VLSAT_EINVAL, "eval_ranks: null edge argument");
     return launch_eval_ranks(obj_logits, obj_probs, rel_probs, gt_class, gt_rel, edges, n_nodes, n_edges, n_obj_class,
                              n_rel_class, topk_obj, topk_rel, topk_triplet, threshold, obj_rank, rel_rank, tri_rank, cnt, scratch,
-                             static_cast<hipStream_t>(stream));
+                             static_cast<hipStream_t>(stream), false);
 }
 
 int64_t vlsat_eval_ranks_scratch_floats(int32_t n_nodes, int32_t n_obj_class, int32_t topk_triplet) {
@@ -532,7 +532,9 @@ int vlsat_eval_triplet_split(const int32_t* tri_rank_3d, const int32_t* tri_rank
 // instead of six plus a dozen tensor allocations.  gt_rel: the multi-hot [E, R] int64 target; edges_e2: [E, 2] int64 (from, to) as
 // the loader yields it, in the plan's edge order; counts: device uint64 [1 + R + 2 (11 + 6 R)], zeroed once by the caller.
 // Top-k bounds and threshold are process_val's constants (topk 11 / 6 / 101, 0.5: reference :463-472).
-// MODEL.multi_rel_outputs only (the single-label variant ranks exp(log-softmax) in a second pass: use the separate entry points).
+// Single-label handles (MODEL.multi_rel_outputs = false) take the same call: gt_rel is the one-hot row of the label with column 0
+// ("none") cleared, the predicate ranks use the log-probabilities as they are and the triplet ranks their exp, taken inside the
+// triplet kernel (launch_eval_ranks, rel_is_log) -- the counts of vlsat_eval_ranks on rel and on vlsat_k_exp(rel), in one pass.
 // split_table / split_counts (vlsat_process_val_counts_split): the zero-shot split of the triplet ranks is counted as well.
 // obj_2d_feats NULL: the 3D-only step -- vlsat_forward without its 2D outputs, one softmax, one ranking pass, the one-branch counts and
 // split; the 2D blocks of counts / split_counts are not touched and the plan's scratch is the same (its 2D halves stay unused).
@@ -541,7 +543,6 @@ static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_poi
                               uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts, void* stream) {
     if (!h || !p || !gt_class || !counts) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: null argument");
     if (p->h != h) return fail(VLSAT_EINVAL, "plan belongs to a different handle");
-    if (!h->d.multi_rel_outputs) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: built for MODEL.multi_rel_outputs (use vlsat_forward + vlsat_eval_ranks + vlsat_eval_counts)");
     const int N = (int)p->N, E = (int)p->E, C = h->d.n_obj_class, R = h->d.n_rel_class;
     if (E > 0 && (!gt_rel || !edges_e2)) return fail(VLSAT_EINVAL, "vlsat_process_val_counts: null edge argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -549,13 +550,16 @@ static int process_val_counts(vlsat_handle h, vlsat_plan p, const float* obj_poi
     // obj_2d_feats NULL: the 3D-only step -- the 3D-only forward, one softmax, one ranking pass, the one-branch counts (and split); the 2D
     // halves of the scratch are not touched, the 2D blocks of counts / split_counts neither
     const bool do2d = obj_2d_feats != nullptr;
+    // single-label model: the relation outputs are log-probabilities -- the predicate ranks take them as they are, the triplet kernel
+    // exponentiates on load; still one ranking pass per branch, the same scratch, no [E, R] temporary
+    const bool rel_is_log = !h->d.multi_rel_outputs;
     RUN(vlsat_forward(h, p, obj_points, obj_2d_feats, descriptor, v.obj3, do2d ? v.obj2 : nullptr, v.rel3, do2d ? v.rel2 : nullptr, stream));
     for (int br = 0; br < (do2d ? 2 : 1); ++br) {
         const float* lg = br ? v.obj2 : v.obj3;
         float* pr = br ? v.prob2 : v.prob3;
         RUN(launch_softmax_rows(lg, C, N, C, pr, 0, s));
         RUN(launch_eval_ranks(lg, pr, br ? v.rel2 : v.rel3, gt_class, gt_rel, edges_e2, N, E, C, R, 11, 6, 101, 0.5f, br ? v.or2 : v.or3,
-                              br ? v.rr2 : v.rr3, br ? v.tr2 : v.tr3, br ? v.cn2 : v.cn3, v.sorted, s));
+                              br ? v.rr2 : v.rr3, br ? v.tr2 : v.tr3, br ? v.cn2 : v.cn3, v.sorted, s, rel_is_log));
     }
     RUN(launch_eval_counts(v.or3, do2d ? v.or2 : nullptr, v.rr3, do2d ? v.rr2 : nullptr, v.tr3, do2d ? v.tr2 : nullptr, v.cn3, gt_class, gt_rel,
                            edges_e2, N, E, R, n_scenes, reinterpret_cast<unsigned long long*>(counts), s));

@@ -136,6 +136,10 @@ __global__ __launch_bounds__(256) void sort_probs_kernel(const float* __restrict
 }
 
 // 32 lanes per edge (lane = relation class, R <= 32), 8 edges per block
+// REL_LOG: `rel` holds the log-probabilities of a single-label model (MODEL.multi_rel_outputs = false); each lane turns its own
+// score into a probability once, on load (log_prob_exp: the function launch_exp applies), and every product below is then the one
+// the kernel forms on an exp'd copy of `rel` -- the same ranks without the [E, R] temporary and without a second ranking pass.
+template <bool REL_LOG>
 __global__ __launch_bounds__(256) void tri_rank_kernel(const float* __restrict__ probs, const float* __restrict__ sorted,
                                                        const float* __restrict__ rel, const int64_t* __restrict__ gt_cls,
                                                        const int64_t* __restrict__ gt_rel, const int64_t* __restrict__ edges, int E, int C,
@@ -153,7 +157,8 @@ __global__ __launch_bounds__(256) void tri_rank_kernel(const float* __restrict__
     }
     __syncthreads();
     if (e >= E) return;
-    const float r = k < R ? rel[(size_t)e * R + k] : 0.f;
+    float r = k < R ? rel[(size_t)e * R + k] : 0.f;
+    if (REL_LOG && k < R) r = log_prob_exp(r);
     const bool is_gt = k < R && gt_rel[(size_t)e * R + k] == 1;
     const unsigned half = (unsigned)(__ballot(is_gt) >> (tid & 32));          // this edge's 32 lanes of the wave's 64-bit mask
     const float gs = __fmul_rn(probs[(size_t)a * C + gt_cls[a]], probs[(size_t)b * C + gt_cls[b]]);
@@ -515,7 +520,7 @@ int launch_softmax_rows(const float* x, int ld, int rows, int cols, float* out, 
 int launch_eval_ranks(const float* obj_logits, const float* obj_probs, const float* rel, const int64_t* gt_cls,
                       const int64_t* gt_rel, const int64_t* edges, int N, int E, int C, int R, int topk_obj,
                       int topk_rel, int topk_tri, float thr, int32_t* obj_rank, int32_t* rel_rank, int32_t* tri_rank,
-                      int32_t* cnt, float* sorted_probs, hipStream_t s) {
+                      int32_t* cnt, float* sorted_probs, hipStream_t s, bool rel_is_log) {
     if (C > 1024 || R > 32) return fail(-1, "eval_ranks: at most 1024 object and 32 relation classes");
     if (topk_tri < 1) return fail(-1, "eval_ranks: topk_triplet must be positive");
     if (N > 0) {
@@ -532,7 +537,9 @@ int launch_eval_ranks(const float* obj_logits, const float* obj_probs, const flo
         hipLaunchKernelGGL(sort_probs_kernel, dim3((N + 3) / 4), dim3(256), (size_t)4 * C * sizeof(float), s, obj_probs, N, C, K, sorted_probs,
                            (int32_t*)nullptr);
         VLSAT_LAUNCH_CHECK("sort_probs");
-        hipLaunchKernelGGL(tri_rank_kernel, dim3((E + 7) / 8), dim3(256), (size_t)16 * K * sizeof(float) + 256 * sizeof(int), s, obj_probs, sorted_probs, rel, gt_cls,
+        // rel_is_log: the predicate ranks above took the raw log-probabilities (evaluate_topk_predicate ranks them as they are,
+        // the 0.5 threshold of an edge without gt relation included); the triplet scores use their exp (eva_utils_acc.py:146-147)
+        hipLaunchKernelGGL(rel_is_log ? tri_rank_kernel<true> : tri_rank_kernel<false>, dim3((E + 7) / 8), dim3(256), (size_t)16 * K * sizeof(float) + 256 * sizeof(int), s, obj_probs, sorted_probs, rel, gt_cls,
                            gt_rel, edges, E, C, R, K, topk_tri, thr, tri_rank);
         VLSAT_LAUNCH_CHECK("tri_rank");
     }

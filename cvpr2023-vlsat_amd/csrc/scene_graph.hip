@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void sg_scene_ptr_kernel(const int64_t* __rest
 
 __global__ __launch_bounds__(256) void sg_exp_kernel(const float* x, float* out, size_t n) {      // (out may be x)
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = expf(x[i]);
+    if (i < n) out[i] = log_prob_exp(x[i]);
 }
 
 // one wave per edge, 4 edges per block; L = slots per edge (1 <= L <= 100; rels mode: L <= R)

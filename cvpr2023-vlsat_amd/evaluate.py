@@ -383,6 +383,11 @@ def _split_merged(pairs, b):
         yield tuple(out)
 
 
+def _model_n_rel(model) -> int:
+    """relation classes of the model's heads (the layout of the additive vectors); a model without a config: the reference's 26"""
+    return int(getattr(getattr(model, "config", None), "num_rel_class", N_REL))
+
+
 @torch.no_grad()
 def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, merge: int = 1, recall_k: bool = False,
                           zero_shot=None, use_2d: bool = True):
@@ -395,13 +400,16 @@ def _validation_pipelined(model, batches: Iterable[dict], device, workers: int, 
     ``merge`` > 1: every worker takes that many consecutive batches at a time and collates them on the device into one call
     (``merge_batches``): the forward then runs at its batched rate.  Counts are additive, so the summary is the same up to
     near-ties (a batched forward differs from a one-scene forward in the last bits: a rank may move by one).
+    Single-label models (``multi_rel_outputs=False``) ride the same path: one library call per batch, the vectors laid out for the
+    model's own ``num_rel_class``.
     ``use_2d=False``: every batch takes the 3D-only step (``obj_2d_feats`` is not read); the 2D entries of the vectors stay zero.
     Returns the counts vector; with ``recall_k`` or ``zero_shot`` (the device uint8 table) the tuple (counts, recall vector or
     None, split vector or None)."""
     from . import metrics as M
     dev = torch.device(device)
-    counts = [torch.zeros(len(fields()), dtype=torch.int64, device=dev) for _ in range(workers)]
-    recall = [torch.zeros(len(recall_fields()), dtype=torch.float64, device=dev) if recall_k else None for _ in range(workers)]
+    n_rel = _model_n_rel(model)
+    counts = [torch.zeros(len(fields(n_rel)), dtype=torch.int64, device=dev) for _ in range(workers)]
+    recall = [torch.zeros(len(recall_fields(n_rel)), dtype=torch.float64, device=dev) if recall_k else None for _ in range(workers)]
     split = [torch.zeros(len(split_fields()), dtype=torch.int64, device=dev) if zero_shot is not None else None for _ in range(workers)]
 
     def groups(it, n):                          # (the pool takes an item under its lock: a whole group is read there)
@@ -666,14 +674,16 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
     vector concatenated onto the others, still one all-reduce.  None: the result and the work are unchanged.
     use_2d = False: the model as deployed -- every batch takes the 3D-only forward and one ranking pass, ``obj_2d_feats`` is not
     read (a batch may lack the key).  The vectors keep their layout and length (the 2D entries stay zero: the same one all-reduce)
-    and the result holds ``scenes`` and the 3D branch's keys only, with the values of the two-branch run."""
+    and the result holds ``scenes`` and the 3D branch's keys only, with the values of the two-branch run.
+    Single-label models (``multi_rel_outputs=False``, ``gt_rel_cls`` the [E] label vector) take every path above, the pipelined one
+    included: one library call per batch, like multi-label models.  The vectors are laid out for the model's ``num_rel_class``."""
     from . import metrics as M
+    n_rel = _model_n_rel(model)
     if zero_shot is not None:
         if workers > 0:
             zero_shot = torch.as_tensor(zero_shot, dtype=torch.uint8).to(device).contiguous()
         else:                                   # (host accumulation: read the table once, not per batch)
             zero_shot = zero_shot.cpu().numpy() if isinstance(zero_shot, torch.Tensor) else np.asarray(zero_shot)
-        n_rel = int(getattr(getattr(model, "config", None), "num_rel_class", N_REL))
     if workers > 0:
         if device is None:
             raise ValueError("validation(workers > 0) needs the device")
@@ -681,11 +691,11 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
         if recall_k or zero_shot is not None:
             vec = np.concatenate([v for v in vec if v is not None])
             return _summaries(vdist.allreduce_metrics(torch.from_numpy(vec).to(device)).cpu().numpy(), recall_k, zero_shot is not None,
-                              use_2d)
+                              use_2d, n_rel)
         t = vdist.allreduce_metrics(torch.from_numpy(vec).to(device))
-        return summarize(t.cpu().numpy(), use_2d=use_2d)
-    vec = np.zeros(len(fields()), dtype=np.float64)
-    rvec = np.zeros(len(recall_fields()), dtype=np.float64) if recall_k else None
+        return summarize(t.cpu().numpy(), n_rel, use_2d=use_2d)
+    vec = np.zeros(len(fields(n_rel)), dtype=np.float64)
+    rvec = np.zeros(len(recall_fields(n_rel)), dtype=np.float64) if recall_k else None
     svec = np.zeros(len(split_fields()), dtype=np.float64) if zero_shot is not None else None
     for b in batches:
         # process_val, with the forward's outputs kept for the recall counts
@@ -695,7 +705,7 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
         ranks = dict(top_k_obj=out[0], top_k_obj_2d=out[1], top_k_rel=out[2], top_k_rel_2d=out[3],
                      top_k_triplet=out[4], top_k_triplet_2d=out[5])
         n_scenes = int(b["batch_ids"].max().item()) + 1 if b["batch_ids"].numel() else 0
-        accumulate(vec, ranks, out[6], n_scenes)
+        accumulate(vec, ranks, out[6], n_scenes, n_rel)
         if recall_k:
             multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
             bid = b["batch_ids"].view(-1)
@@ -709,16 +719,16 @@ def validation(model, batches: Iterable[dict], device=None, workers: int = 0, me
         t = t.to(device)
     t = vdist.allreduce_metrics(t)
     if recall_k or svec is not None:
-        return _summaries(t.cpu().numpy(), recall_k, svec is not None, use_2d)
-    return summarize(t.cpu().numpy(), use_2d=use_2d)
+        return _summaries(t.cpu().numpy(), recall_k, svec is not None, use_2d, n_rel)
+    return summarize(t.cpu().numpy(), n_rel, use_2d=use_2d)
 
 
-def _summaries(v: np.ndarray, recall_k: bool = True, split: bool = False, use_2d: bool = True) -> Dict[str, float]:
-    n = len(fields())
-    out = summarize(v[:n], use_2d=use_2d)
+def _summaries(v: np.ndarray, recall_k: bool = True, split: bool = False, use_2d: bool = True, n_rel: int = N_REL) -> Dict[str, float]:
+    n = len(fields(n_rel))
+    out = summarize(v[:n], n_rel, use_2d=use_2d)
     if recall_k:
-        m = n + len(recall_fields())
-        out.update(recall_summarize(v[n:m], use_2d=use_2d))
+        m = n + len(recall_fields(n_rel))
+        out.update(recall_summarize(v[n:m], n_rel, use_2d=use_2d))
         n = m
     if split:
         out.update(split_summarize(v[n:n + len(split_fields())], use_2d))

@@ -158,17 +158,23 @@ def process_val_counts(model, counts: torch.Tensor, obj_points, obj_2d_feats, gt
     ``split_table`` / ``split_counts``: the device uint8 zero-shot table (``zeroshot.zero_shot_table``) and the device int64 [12]
     vector of ``evaluate.split_fields()`` that additionally accumulates the zero-shot split of the triplet ranks.
     ``obj_2d_feats=None``: the 3D branch alone, on both routes -- the one call runs its 3D-only step, the separate calls are
-    ``forward_3d`` + one ``rank_tables`` + one ``recallk_counts``; the ``_2d`` entries of every vector are not touched."""
+    ``forward_3d`` + one ``rank_tables`` + one ``recallk_counts``; the ``_2d`` entries of every vector are not touched.
+    Single-label models (``multi_rel_outputs=False``, ``gt_rel_cls`` the [E] label vector) take the one call like multi-label ones;
+    the separate calls serve ``recall=`` and plans that had to permute the edges, for both settings."""
     if (split_table is None) != (split_counts is None):
         raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
     multi = bool(getattr(getattr(model, "config", None), "multi_rel_outputs", True))
     edges = edge_indices.to(torch.int64).contiguous()
-    if multi and recall is None and hasattr(model, "process_val_counts"):           # one library call: forward + ranking + counts in the plan's scratch
+    # one library call: forward + ranking + counts in the plan's scratch; a single-label model rides it too (its triplet kernel takes
+    # exp of the log-probabilities on load), with the one-hot target, column 0 cleared, that multihot_targets makes of its labels
+    if recall is None and hasattr(model, "process_val_counts"):
         r = model.config.num_rel_class
-        split = {} if split_table is None else {"split_table": split_table, "split_counts": split_counts}
+        extra = {} if split_table is None else {"split_table": split_table, "split_counts": split_counts}
+        if not multi:                               # (the method keeps its earlier refusal of such a model for callers that do not say so)
+            extra["single_label"] = True
         if model.process_val_counts(counts, obj_points, obj_2d_feats, gt_cls.to(torch.int64).contiguous().view(-1), descriptor,
                                     multihot_targets(gt_rel_cls, r).to(torch.int64).contiguous(), edges, batch_ids, n_scenes, fc_sizes,
-                                    **split):
+                                    **extra):
             return counts
     # with the fully-connected hint the plan never reads the edge list: the [2,E] view is enough (no transpose kernel)
     ei_t = edges.t() if fc_sizes is not None else edges.t().contiguous()

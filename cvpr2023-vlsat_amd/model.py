@@ -483,7 +483,8 @@ class VLSATModel:
 
     @torch.no_grad()
     def process_val_counts(self, counts, obj_points, obj_2d_feats, gt_cls, descriptor, gt_rel_multihot, edges_e2, batch_ids=None,
-                           n_scenes: int = 1, fc_sizes: Optional[Sequence[int]] = None, split_table=None, split_counts=None) -> bool:
+                           n_scenes: int = 1, fc_sizes: Optional[Sequence[int]] = None, split_table=None, split_counts=None,
+                           single_label: bool = False) -> bool:
         """``vlsat_process_val_counts``: forward + ranking of both branches + the additive counts of ``evaluate.fields()`` for one
         batch in ONE library call, intermediates in the plan's scratch (nothing allocated, nothing read back).  ``edges_e2`` is the
         loader's int64 [E,2] list, ``gt_rel_multihot`` int64 [E,R], ``gt_cls`` int64 [N], ``counts`` the device int64 vector.
@@ -491,11 +492,23 @@ class VLSATModel:
         also counts the zero-shot split of the triplet ranks (``vlsat_process_val_counts_split``; layout: evaluate.split_fields).
         ``obj_2d_feats=None``: the library's 3D-only step (3D-only forward, one ranking pass, one-branch counts and split) -- the
         ``_2d`` entries of ``counts`` / ``split_counts`` are not touched, the plan and its workspace are the same.
+        A single-label model (``multi_rel_outputs=False``) rides the same path when the caller says ``single_label=True``:
+        ``gt_rel_multihot`` is then the one-hot row of each label with column 0 cleared (``metrics.multihot_targets``), and the
+        library ranks the predicates on the log-probabilities and the triplets on their exp, in one ranking pass per branch.
+        Without the flag the method answers such a model as it always has -- ``VlsatError`` naming ``multi_rel_outputs``, nothing
+        enqueued -- so a caller written against that refusal (one that catches it to take the separate calls, say) meets what it
+        expects; ``metrics.process_val_counts`` and the validation loop pass the flag.  The flag means nothing for a multi-label model.
         Returns False (nothing enqueued) when the plan had to permute the edges -- the caller then takes the separate calls."""
         if (split_table is None) != (split_counts is None):
             raise ValueError("process_val_counts: give both split_table and split_counts, or neither")
+        if not self.config.multi_rel_outputs and not single_label:
+            raise L.VlsatError("process_val_counts: this model has MODEL.multi_rel_outputs = false; pass single_label=True with the one-hot "
+                               "target of metrics.multihot_targets (column 0 cleared), or take vlsat_forward + vlsat_eval_ranks + vlsat_eval_counts")
+        r = self.config.num_rel_class
+        if counts.dtype != torch.int64 or counts.numel() != 1 + r + 2 * (11 + 6 * r) or not counts.is_contiguous():      # (the library writes that many)
+            raise L.VlsatError(f"process_val_counts: counts must be a contiguous int64 vector of 1 + R + 2 (11 + 6 R) entries, R = {r}")
         if split_table is not None:
-            c, r = self.config.num_obj_class, self.config.num_rel_class
+            c = self.config.num_obj_class
             if (split_table.dtype != torch.uint8 or split_table.numel() != c * c * r or not split_table.is_contiguous()
                     or split_counts.dtype != torch.int64 or split_counts.numel() != 12 or not split_counts.is_contiguous()
                     or split_table.device != counts.device or split_counts.device != counts.device):

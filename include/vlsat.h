@@ -518,7 +518,13 @@ int vlsat_k_softmax_rows(const float* x, int32_t ld, int32_t rows, int32_t cols,
  * appends them (first cnt[e] slots, rest 0).  Flattening the used slots in edge order gives exactly
  * the reference's result arrays.  Triplet ranks are counted along a staircase over each node's sorted class probabilities
  * (csrc/eval_ranks.hip): `scratch` holds vlsat_eval_ranks_scratch_floats(n_nodes, n_obj_class, topk_triplet) floats of device
- * memory the call may overwrite (the topk largest probabilities per node; required when n_edges > 0). */
+ * memory the call may overwrite (the topk largest probabilities per node; required when n_edges > 0).
+ * Precondition: tri_rank is valid only for NON-NEGATIVE rel_probs (and obj_probs) -- the staircase relies on fl(fl(s * o) * r) being
+ * monotone in s and o, which a negative r reverses; obj_rank, rel_rank and cnt hold for any finite values.  A single-label model
+ * (MODEL.multi_rel_outputs = false: rel_probs are log-probabilities, all <= 0) therefore calls twice: with the raw values for
+ * rel_rank -- the reference ranks them as they are, the `threshold` compare of an edge without gt relation included -- and with
+ * their exp (vlsat_k_exp) for tri_rank; the tri_rank of the first call and the rel_rank of the second are to be discarded.
+ * vlsat_process_val_counts does both in one pass. */
 int vlsat_eval_ranks(const float* obj_logits, const float* obj_probs, const float* rel_probs,
                      const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges,
                      int32_t n_nodes, int32_t n_edges, int32_t n_obj_class, int32_t n_rel_class,
@@ -597,10 +603,15 @@ int64_t vlsat_eval_recallk_scratch_bytes(int64_t n_nodes, int64_t n_edges, int32
  * Mmgnet.process_val (reference src/model/SGFN_MMG/model.py:458-480) computes per scene, reduced to what MMGNet.validation keeps of
  * it (src/model/model.py:201-242).  Top-k bounds 11 / 6 / 101 and threshold 0.5 are process_val's.  gt_rel is the multi-hot
  * [E, R] int64 target, edges_e2 the [E, 2] int64 (from, to) list in the plan's edge order, counts as for vlsat_eval_counts.
- * MODEL.multi_rel_outputs only.  All device pointers; asynchronous; one library call per scene on the host side.
+ * All device pointers; asynchronous; one library call per scene on the host side.
+ * Single-label handles (MODEL.multi_rel_outputs = false) take the same call: gt_rel is then the one-hot row of the edge's label
+ * with column 0 ("none") cleared (get_gt, eva_utils_acc.py:19-22), the predicate ranks are taken on the log-probabilities as they
+ * are and the triplet ranks on their exp (eva_utils_acc.py:146-147), which the triplet kernel applies on load with the function of
+ * vlsat_k_exp: the counts are those of vlsat_eval_ranks on the outputs and on vlsat_k_exp of them, in ONE ranking pass per branch,
+ * without an [E, R] temporary and in the same scratch.
  * 3D-only: obj_2d_feats NULL runs vlsat_forward without its 2D outputs, ONE softmax, ONE ranking pass and the one-branch counts,
  * all on `stream`, intermediates in the same scratch (the plan's workspace_bytes does not change); the 2D block of counts is not
- * touched.  Single-label models stay refused here either way. */
+ * touched.  Both settings of MODEL.multi_rel_outputs take either form. */
 int vlsat_process_val_counts(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                              const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
                              int32_t n_scenes, uint64_t* counts, void* stream);
@@ -609,7 +620,7 @@ int vlsat_process_val_counts(vlsat_handle h, vlsat_plan plan, const float* obj_p
  * uint8 [C * C * R] zero-shot table of the model's n_obj_class C and n_rel_class R (layout: vlsat_eval_triplet_split),
  * split_counts the device uint64 [12] it accumulates into.  A one-scene-per-call loop with the zero-shot split on stays one
  * library call per scene.  counts and every other argument as for vlsat_process_val_counts; with obj_2d_feats NULL the split is
- * the one-branch one as well (split_counts[6..11] are not touched). */
+ * the one-branch one as well (split_counts[6..11] are not touched).  Single-label handles as for vlsat_process_val_counts. */
 int vlsat_process_val_counts_split(vlsat_handle h, vlsat_plan plan, const float* obj_points, const float* obj_2d_feats,
                                    const float* descriptor, const int64_t* gt_class, const int64_t* gt_rel, const int64_t* edges_e2,
                                    int32_t n_scenes, uint64_t* counts, const uint8_t* split_table, uint64_t* split_counts,
