@@ -10,7 +10,12 @@
 // tensor E3 (relation encoder conv3 / nn_edge.2 -> nn_edge.0, proj_edge, key | value projection, relation head); K | V of the edge
 // attention (key | value projection -> split-fp16 attention kernel, as ATTENTION pair words) and, with them, its output Oe (attention
 // kernel in one key part -> out-projection, as GEMM pair words; split-key partials and the merge kernel keep fp32).  Q stays fp32 (the
-// attention splits it once per block), E2 is read and written by the LayerNorm, KP by the gate: fp32.
+// attention splits it once per block) and KP is read by the gate: fp32.
+// The 2D chain tensor E2 holds two kinds of content in a layer.  What the LayerNorm of the edge attention writes (and, before the first
+// layer, conv3 of rel_encoder_2d) is read only as a GEMM A operand -- nn_edge.0 and proj_edge of gcn_2ds, after the last layer the first
+// Linear of the 2D relation head -- and travels as GEMM pair words (`e2`; the LayerNorm kernel packs with output format 6).  What
+// nn_edge.2 of gcn_2ds writes into the same buffer is also the fp32 residual of the out-projection (a pair word holds about 22 bits):
+// it stays fp32, and the query projection splits it on the fly.
 #pragma once
 #include "flash_pick.h"
 #include "gemm_plan.h"
@@ -22,6 +27,7 @@ struct EdgePairsIn {
     int D = 512;                 // edge feature width (nn_edge.0: D -> 2D -> D)
     int G = 512;                 // resident 256-thread blocks at two per CU (gemm_slots)
     int option = 1;              // debug option "edge_pairs": 0 = everything stays fp32 (the forward of the releases before the pair words)
+    int option_e2 = 1;           // debug option "edge_pairs_e2": 0 = E2 stays fp32 (the forward of the release before E2 paired)
     bool fp32_mode = true;       // precision mode 0 (prec == prec_edge == 0)
     bool gemm_exact = false, gemm_small_exact = false;     // debug options: exact kernels for the 8-phase / persistent launches
     bool no_dma = false, no_p8 = false, splitk = true;     // debug options "gemm_dma" 0, "gemm_p8" 0, "gemm_splitk"
@@ -39,10 +45,11 @@ struct EdgePairsIn {
 struct EdgePairs {
     bool hbig[2] = {false, false}, r1[2] = {false, false}, e3 = false;     // [branch]: 0 = 3D, 1 = 2D
     bool kv = false, oe = false;                                            // K | V (attention pair words), Oe (GEMM pair words)
+    bool e2 = false;                                                        // E2 as the LayerNorm / conv3 of rel_encoder_2d write it (nn_edge.2's E2 stays fp32)
     const char *why_hbig[2] = {nullptr, nullptr}, *why_r1[2] = {nullptr, nullptr}, *why_e3 = nullptr;      // why not (null: it pairs)
-    const char *why_kv = nullptr, *why_oe = nullptr;
+    const char *why_kv = nullptr, *why_oe = nullptr, *why_e2 = nullptr;
     int flash_io() const { return kv ? (oe ? 5 : 4) : 0; }                  // what the attention launch is told (flash_f16x3_pair_pick)
-    bool any() const { return hbig[0] || hbig[1] || r1[0] || r1[1] || e3 || kv || oe; }
+    bool any() const { return hbig[0] || hbig[1] || r1[0] || r1[1] || e3 || kv || oe || e2; }
 };
 
 // an edge-row Linear of the forward as the engine launches it in the fp32 mode, on placeholder operands (the planner looks at shapes,
@@ -98,7 +105,7 @@ inline EdgePairs edge_pairs_plan(const EdgePairsIn& in) {
     else if (in.E <= 0) all = "no edges";
     else if (in.paired) all = "paired schedule: the twin stages are launches of two problems";
     if (all) {
-        r.why_hbig[0] = r.why_hbig[1] = r.why_r1[0] = r.why_r1[1] = r.why_e3 = r.why_kv = r.why_oe = all;
+        r.why_hbig[0] = r.why_hbig[1] = r.why_r1[0] = r.why_r1[1] = r.why_e3 = r.why_kv = r.why_oe = r.why_e2 = all;
         return r;
     }
     const int D = in.D, G = in.G;
@@ -119,7 +126,9 @@ inline EdgePairs edge_pairs_plan(const EdgePairsIn& in) {
     r.r1[0] = !r1;
     // (the 2D head: its first Linear reads E2, an fp32 tensor, so it still splits its A operand AND packs its output -- measured per launch
     //  at the bench batch, the packing costs that launch what the second Linear then saves: 160.7 + 56.3 -> 167.9 + 49.4 us,
-    //  profiles/edge_pairs_ab.txt -- taken out; the 3D head reads E3 as pairs and gains in both launches)
+    //  profiles/edge_pairs_ab.txt -- taken out; the 3D head reads E3 as pairs and gains in both launches.  That was measured while E2 was
+    //  fp32 for every reader; with E2 paired (below) the first Linear no longer splits its A operand, and R1 of the 2D head has not been
+    //  measured again: 7 us, left as it is)
     r.r1[1] = false;
     if (!r1) r.why_r1[1] = in.do2d ? "measured: packing in the first Linear (A = E2, fp32) costs what the second saves" : "the 2D branch does not run";
     // E3: written by conv3 of rel_encoder_3d (128 -> D) and by nn_edge.2 of gcn_3ds; read by nn_edge.0, proj_edge, the key | value projection
@@ -154,6 +163,20 @@ inline EdgePairs edge_pairs_plan(const EdgePairsIn& in) {
                         edge_pairs_launch(edge_pairs_probe(in, 512, D, 0, false, ACT_RELU), G, 1, r.r1[0]));
     r.why_e3 = e3;
     r.e3 = !e3;
+    // E2 of the LayerNorm and of conv3 of rel_encoder_2d (128 -> D, C pairs): read by nn_edge.0 (no pending ReLU: the LayerNorm applies
+    // it) and proj_edge of gcn_2ds and by the first Linear of the 2D relation head (whose output R1 stays fp32, above)
+    const char* e2 = nullptr;
+    if (!in.option_e2) e2 = "edge_pairs_e2 is 0";
+    else if (!in.do2d) e2 = "the 2D branch does not run";
+    else if (in.debug_stop >= 0) e2 = "a debug stop: the caller may read E2";
+    else if (in.train) e2 = "training outputs: the first Linear of triplet_projector_2d reads E2 as fp32";
+    else if (in.feature_transform) e2 = "feature_transform: E2 is copied out of the encoder's fp32 rows";
+    if (!e2) e2 = edge_pairs_launch(edge_pairs_probe(in, D, 128, 0, false, ACT_RELU), G, 0, 1);                           // conv3
+    if (!e2) e2 = edge_pairs_launch(edge_pairs_probe(in, 2 * D, D, 6, false, ACT_RELU), G, 1, r.hbig[1]);                 // nn_edge.0
+    if (!e2 && in.use_gcn_edge) e2 = edge_pairs_launch(edge_pairs_probe(in, D, D, 0, false, ACT_NONE), G, 1, 0);          // proj_edge
+    if (!e2) e2 = edge_pairs_launch(edge_pairs_probe(in, 512, D, 0, false, ACT_RELU), G, 1, r.r1[1]);                     // relation head
+    r.why_e2 = e2;
+    r.e2 = !e2;
     return r;
 }
 

@@ -152,13 +152,14 @@ struct vlsat_ctx {
     int flash_qg = 0;                        // 64 queries per wave in the half-row bf16 edge attention (debug option "flash_qg" 1 | 2; FlashSplit::qg)
     int flash_bq_big = 1;                    // 256-query tiles for plans whose scenes all have >= 4096 edges (debug option "flash_bq_big" 0: always 128)
     int flash_dma = 1;                       // half-row bf16 edge attention: K / V by LDS-direct loads, one tile ahead (0: register-staged, round 3; 3 | 4: rings of three / four tile buffers)
-    int gate_fuse_agg = 1;                   // gate at the default head geometry, GCN_AGGR = max: aggregation fused into the gate kernel: 0 never, 1 the bf16 modes, 2 fp32 as well ("gate_fuse_agg")
+    int gate_fuse_agg = 1;                   // gate at the default head geometry, GCN_AGGR = max: aggregation fused into the gate kernel: 0 never, 1 the bf16 modes and, on plans of more than 16384 edges, fp32 (measured: profiles/e2_pairs_ab.txt), 2 fp32 on every plan ("gate_fuse_agg")
     int flash_ablate = 0;                    // timing experiments on the bf16 edge attention (FlashSplit::ablate; results are garbage)
     int flash_pv_terms = 3;                  // split-bf16 edge attention: MFMAs per P.V product (3, or 2 = probabilities single-rounded)
     int flash_exact = -1;                    // fp32 mode, head dim 64: -1 / 0 the split-fp16 edge attention (three f16 MFMAs per product), 1 the exact fp32-MFMA kernel (debug option "flash_exact")
     int gemm_small_exact = -1;               // fp32 mode: -1 / 0 the persistent GEMM kernel's launches (tails, small launches, node rows) on its split-fp16 siblings (GemmArgs::f16s 2 | 3), 1 exact, node rows exact on every kernel (debug option "gemm_small_exact")
     int pointnet_exact = -1;                // fp32 mode: -1 / 0 the object encoder's conv2 / conv3 on the split-fp16 kernel (pointnet_bf16_kernel<CIN, 5>), 1 the exact fp32-MFMA kernel (debug option "pointnet_exact")
     int edge_pairs = 1;                      // fp32 mode: edge tensors between split-fp16 GEMMs as pair words where every launch that touches them has the form (edge_pairs.h; debug option "edge_pairs", 0: all fp32)
+    int edge_pairs_e2 = 1;                   // ... E2 as the LayerNorm / conv3 of rel_encoder_2d write it among them (debug option "edge_pairs_e2", 0: E2 stays fp32)
     vlsat::EdgePairs pairs{};                // ... the answer for the forward being enqueued (forward_body sets it before the first launch)
     int gemm_exact = -1;                    // fp32 mode: -1 / 0 the large edge-row launches on the split-fp16 8-phase kernel (GemmArgs::f16s), 1 the exact fp32-MFMA kernels (debug option "gemm_exact")
     int ln_resid = 1;                        // split-pair mode: post-attention residual added in the LayerNorm kernel

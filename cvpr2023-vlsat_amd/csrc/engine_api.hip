@@ -40,7 +40,7 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 // settings).  The RELEASE library knows the ones a deployment or a test has a use for:
 //   "dual_stream" 0|1|2 a second (and third) stream for the 2D chains: 1 small plans only, 2 every plan (plans created afterwards)
 //   "sched"       -1|0|1  two-stream plans: dependency-exact three-lane schedule (1), the fork / join schedule of round 4 (0), or by
-//                       mode (-1, default: exact in the bf16 modes, fork / join in exact fp32)
+//                       plan size (-1, default: exact on plans of more than 16384 edges in every precision mode, fork / join below)
 //   "flash_split" 0|1   split-key edge attention for plans that cannot fill the chip (plans created afterwards)
 //   "prof_dual"   0|1   per-class profiling keeps the multi-stream execution (1, default) or serialises on the launch stream
 //   "pair_twins" 0|1 / "pair_max_edges" n   paired schedule of one-scene plans (engine_forward.hip): twin stages as launches of two problems
@@ -66,8 +66,12 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //   "edge_pairs" 0|1     fp32 mode: Hbig, R1 and the 3D chain tensor E3 travel between the split-fp16 GEMMs as pair words (the halves of the
 //                       split operand, made once by the writer) wherever every launch that touches them has the form (1, default;
 //                       edge_pairs.h), or stay fp32 (0: the forward of the releases before the pair words); same outputs bit for bit
+//   "edge_pairs_e2" 0|1  fp32 mode, with "edge_pairs" 1: the 2D chain tensor E2 as the LayerNorm of the edge attention and conv3 of
+//                       rel_encoder_2d write it (read only by nn_edge.0 / proj_edge of gcn_2ds and the 2D relation head) as pair words too
+//                       (1, default), or fp32 (0: the forward of the release before); what nn_edge.2 writes into E2 is fp32 either way
 //   "flash_bq_big" 0|1   half-row edge attention on plans whose scenes all have >= 4096 edges: 256 queries per block (1, default) or 128
-//   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes (default) / fp32 too
+//   "gate_fuse_agg" 0|1|2  max aggregation inside the gate kernel: never / bf16 modes, and fp32 on plans of more than 16384 edges (default) /
+//                       fp32 on every plan
 //   "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2   gate kernel variants the tests compare bit for bit
 // An EXPERIMENTS build (build.py --experiments, -DVLSAT_EXPERIMENTS) also accepts the lab switches -- "gate_grid" n, "gate_heads_bf16",
 // "flash_heads_bf16", "node_attn_split" n, "half_fmt", "flash_dma" 0|1|3|4, "flash_ablate" bits (GARBAGE results: timing only) -- and
@@ -98,6 +102,7 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "flash_pv_terms") h->flash_pv_terms = value == 2 ? 2 : 3;
     else if (k == "flash_exact") h->flash_exact = value < 0 ? -1 : value != 0;
     else if (k == "edge_pairs") h->edge_pairs = value != 0;
+    else if (k == "edge_pairs_e2") h->edge_pairs_e2 = value != 0;
     else if (k == "gemm_exact") h->gemm_exact = value < 0 ? -1 : value != 0;
     else if (k == "pointnet_exact") h->pointnet_exact = value < 0 ? -1 : value != 0;
     else if (k == "gemm_small_exact") h->gemm_small_exact = value < 0 ? -1 : value != 0;

@@ -26,7 +26,8 @@ namespace {
 // traffic (single-rounding modes, whose kernels never read a low part).
 // The fp32 mode (code 0 here) has a producer-side format of its own, the GEMM pair words of its split-fp16 kernels
 // (gemm_f16s_planes.h): which tensors carry them is vlsat_ctx::pairs, the answer of edge_pairs_plan (edge_pairs.h) for the forward
-// being enqueued -- Hbig, R1 and E3 where every launch that touches them has the form, GemmArgs::a_pair / c_pair on those launches.
+// being enqueued -- Hbig, R1, E3 and the LayerNorm's E2 where every launch that touches them has the form, GemmArgs::a_pair / c_pair on
+// those launches.
 // Everything else the fp32 kernels read and write is plain fp32.
 static int split_fmt(const vlsat_ctx* h) {
     // (head geometries other than 8 x 64: the chain tensors keep the format; Q / K|V / O of the edge attention and the gate's
@@ -47,11 +48,14 @@ static int gate_launch(vlsat_ctx* h, const GateChoice& gc, const GateArgs& g, hi
     return launch_gate(gc.kernel, g, h->H, h->D / h->H, h->A / h->H, h->prec_edge == 3 ? 3 : 1, (S == 2 && h->half_f16) ? 3 : S, s, twin);
 }
 // whether the max aggregation runs inside the gate kernel: GCN_AGGR = max on a kernel that implements it, no debug tap
-// (fp32: measured neutral -- 2196-2201 vs 2195 scenes/s -- and it moves waiting time into the GEMM class of the two-stream
-//  profile, so the exact-fp32 mode keeps the separate aggregate launch unless "gate_fuse_agg" is 2)
+// (fp32: neutral when the step was 29 ms -- 2196-2201 vs 2195 scenes/s -- and +0.6 % later, so the mode kept the separate aggregate
+//  launch; re-measured at 14.2 ms per step, five interleaved runs each at the bench batch: 14.100-14.138 ms fused against 14.223-14.239,
+//  faster in every pair, median 0.106 ms against a spread of 0.016 -- profiles/e2_pairs_ab.txt.  Since then the fp32 gate fuses it on
+//  plans that fill the chip, the size from which the schedule below is the dependency-exact one; smaller plans -- one scene per call,
+//  the paired schedule -- were not part of that measurement and keep the separate launch unless "gate_fuse_agg" is 2)
 static bool gate_fuses_agg(const vlsat_ctx* h, const GateChoice& gc, const GateArgs& g) {
-    return gc.fuse_agg && (h->gate_fuse_agg == 2 || (h->gate_fuse_agg == 1 && gc.bits16())) && h->d.gcn_aggr == 0 && !g.prob && h->debug_stop < 0 &&
-           g.row_map && g.n_edges > 0;
+    return gc.fuse_agg && (h->gate_fuse_agg == 2 || (h->gate_fuse_agg == 1 && (gc.bits16() || g.n_edges > 16384))) && h->d.gcn_aggr == 0 && !g.prob &&
+           h->debug_stop < 0 && g.row_map && g.n_edges > 0;
 }
 
 // ---- profiling helpers ----
@@ -283,7 +287,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
         RUN(gemm_n(h, s, a, nb));
     }
     for (int i = 0; i < nb; ++i) a[i] = nn_edge0_args(h, p, side[i].w->we1, side[i].e, side[i].e_relu_pending, *side[i].sc, gather_f16_on(h),
-                                                   side[i].br == 0 && P.e3, P.hbig[side[i].br]);
+                                                   side[i].br == 0 ? P.e3 : P.e2, P.hbig[side[i].br]);
     RUN(gemm_n(h, s, a, nb));
     if (h->d.use_gcn_edge) {              // proj_edge feeds only the gate MLP (reference network_MMG.py:98-102)
         for (int i = 0; i < nb; ++i) {
@@ -292,7 +296,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
             a[i].relu_a = b.e_relu_pending;
             a[i].a_split = S;
             a[i].c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
-            a[i].a_pair = b.br == 0 && P.e3;
+            a[i].a_pair = b.br == 0 ? P.e3 : P.e2;
         }
         RUN(gemm_n(h, s, a, nb));
     }
@@ -342,7 +346,7 @@ int rel_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const RelSide* side, 
         a[i] = G(b.e, D, b.w->w1, D, b.sc->R1, 512, E, 512, b.w->b1, ACT_RELU);
         a[i].relu_a = b.relu_a;
         a[i].a_split = S; a[i].c_split = S;
-        a[i].a_pair = b.br == 0 && h->pairs.e3; a[i].c_pair = h->pairs.r1[b.br];
+        a[i].a_pair = b.br == 0 ? h->pairs.e3 : h->pairs.e2; a[i].c_pair = h->pairs.r1[b.br];
     }
     RUN(gemm_n(h, s, a, nb));
     for (int i = 0; i < nb; ++i) {
@@ -393,7 +397,7 @@ int rel_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, int br0, int nb, c
     for (int i = 0, br = br0; i < nb; ++i, ++br) {
         a[i] = G(sc[br]->H2, 128, rel_enc_w(h, br).w3, 128, br ? p->E2 : p->E3, D, E, D, rel_enc_w(h, br).b3, ACT_RELU);
         a[i].a_split = S; a[i].c_split = S;
-        a[i].c_pair = br == 0 && h->pairs.e3;
+        a[i].c_pair = br == 0 ? h->pairs.e3 : h->pairs.e2;
     }
     return gemm_n(h, s, a, nb);
 }
@@ -484,7 +488,8 @@ int edge_attn_out(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, 
     RUN(gemm(h, s, o, f.PA));
     Scope sc(h, s, PC_LAYERNORM, 0);
     const int SL = (S == 2 && h->half_f16) ? 4 : S;          // (mode 5: the half rows the LayerNorm reads and writes hold fp16)
-    return launch_layernorm_to(pre_ln, D, p->E2, D, E, D, w.lng, w.lnb, relu, SL, s, f.ln_resid ? p->E2 : nullptr, D, SL, f.o16 ? 1 : 0);
+    // (fp32 mode, h->pairs.e2: the LayerNorm's E2 has only GEMM A operands as readers -- it leaves as GEMM pair words, format 6)
+    return launch_layernorm_to(pre_ln, D, p->E2, D, E, D, w.lng, w.lnb, relu, h->pairs.e2 ? 6 : SL, s, f.ln_resid ? p->E2 : nullptr, D, SL, f.o16 ? 1 : 0);
 }
 
 int stn_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const StnW& w, const float* h1, int ldh, size_t R, int P,
@@ -602,13 +607,16 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     // under the node attentions of layer l + 1.  The stages are the same bodies with nb = 2 (see gemm_n): bit-identical outputs.
     const bool pair = dual && h->pair_twins && p->E > 0 && p->E <= h->pair_max_edges && !h->d.feature_transform && gate_of(h).twin &&
                       !p->prob && h->sched != 1;
-    // (default: exact for the bf16 modes on plans that fill the chip by themselves.  One-scene plans keep two streams: with K replicas
+    // (default: exact on plans that fill the chip by themselves, in every precision mode.  The fp32 mode kept fork / join while its big
+    //  kernels sat on the fp32 matrix pipe -- exact measured -0.8 % at 29 ms per step; with the mode on split-fp16 MFMAs it is the bf16x3
+    //  case: 14.057-14.117 ms exact against 14.223-14.239 fork / join, five interleaved runs each, faster in every pair, median 0.144 ms
+    //  against a spread of 0.016 -- profiles/e2_pairs_ab.txt.  One-scene plans keep two streams: with K replicas
     //  in flight on K host threads the third stream of every replica competes for the few hardware queues -- 551 vs 926-953 scenes/s at
     //  four in flight in bf16_mixed, profiles/r05_probes/val_loop_bf16_mixed_three_lanes.txt)
-    const bool exact = dual && !pair && (h->sched < 0 ? (h->prec_edge != 0 && p->E > 16384) : h->sched != 0);
+    const bool exact = dual && !pair && (h->sched < 0 ? p->E > 16384 : h->sched != 0);
     {   // fp32 mode: which edge tensors travel as GEMM pair words in this forward -- one answer, read by every stage below
         EdgePairsIn in;
-        in.E = p->E; in.D = D; in.G = gemm_slots(); in.option = h->edge_pairs;
+        in.E = p->E; in.D = D; in.G = gemm_slots(); in.option = h->edge_pairs; in.option_e2 = h->edge_pairs_e2;
         in.fp32_mode = h->prec == 0 && h->prec_edge == 0 && h->prec_node == 0;
         in.gemm_exact = h->gemm_exact == 1; in.gemm_small_exact = h->gemm_small_exact == 1;
         in.no_dma = h->gemm_no_dma != 0; in.no_p8 = h->gemm_no_p8 != 0; in.splitk = h->gemm_splitk != 0;

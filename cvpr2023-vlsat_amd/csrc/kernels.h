@@ -95,8 +95,8 @@ int launch_desc_tail(const float* desc, int n_nodes, float* x, int ldx, int col0
 // in-place LayerNorm over rows of `dim` (dim == 512), optional ReLU
 int launch_layernorm(float* x, int ld, int rows, int dim, const float* gamma, const float* beta, int relu,
                      hipStream_t s);
-// out of place; out_split = 1 writes the split-pair format of the bf16 modes (common.h pack_split), 2 / 4 bf16 / fp16 half rows, 0 fp32;
-// any other value is refused, as is an x_f16 outside {0, 1}
+// out of place; out_split = 1 writes the split-pair format of the bf16 modes (common.h pack_split), 2 / 4 bf16 / fp16 half rows, 0 fp32,
+// 6 the GEMM pair words of the fp32 mode (gemm_f16s_planes.h f16s_pair_pack, packed by f16s_pack2 like a GEMM epilogue); any other value is refused, as is an x_f16 outside {0, 1}
 int launch_layernorm_to(const float* x, int ld, float* y, int ldy, int rows, int dim, const float* gamma, const float* beta,
                         int relu, int out_split, hipStream_t s, const float* resid = nullptr, int ldr = 0, int r_split = 0, int x_f16 = 0);
 // (x_f16: the rows of x are fp16 half rows -- what the out-projection of the single-rounded edge attention writes, GemmArgs::c_f16_cols == N)

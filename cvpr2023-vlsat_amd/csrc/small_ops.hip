@@ -1,5 +1,6 @@
 // Small fused VALU kernels of the path (all HBM/latency-bound glue around the MFMA kernels).
 #include "common.h"
+#include "gemm_core.h"
 #include "gemm_f16s_planes.h"
 #include "kernels.h"
 
@@ -143,8 +144,18 @@ __global__ __launch_bounds__(256) void layernorm512_kernel(const float* __restri
         if (relu) { a[c] = fmaxf(a[c], 0.f); b[c] = fmaxf(b[c], 0.f); }
         if (out_split == 1) { a[c] = pack_split(a[c]); b[c] = pack_split(b[c]); }     // bf16 modes: the consumers are GEMM A operands
     }
+    if (out_split == 6) {                                  // fp32 mode: GEMM pair words (the readers are split-fp16 A operands; the epilogues' own packing code)
+#pragma unroll
+        for (int c = 0; c < 4; c += 2) {
+            unsigned w0, w1;
+            f16s_pack2(a[c], a[c + 1], w0, w1);
+            a[c] = __uint_as_float(w0); a[c + 1] = __uint_as_float(w1);
+            f16s_pack2(b[c], b[c + 1], w0, w1);
+            b[c] = __uint_as_float(w0); b[c + 1] = __uint_as_float(w1);
+        }
+    }
     float* q = y + (size_t)row * ldy;
-    if (out_split == 4) {                                  // half rows of fp16 (clamped: the consumers are fp16 MFMA operands)
+    if (out_split == 4) {                                 // half rows of fp16 (clamped: the consumers are fp16 MFMA operands)
         typedef _Float16 f16x4_o __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int c = 0; c < 4; ++c) { a[c] = __builtin_amdgcn_fmed3f(a[c], -65504.f, 65504.f); b[c] = __builtin_amdgcn_fmed3f(b[c], -65504.f, 65504.f); }
@@ -172,8 +183,8 @@ int launch_layernorm_to(const float* x, int ld, float* y, int ldy, int rows, int
     if (rows <= 0) return 0;
     if (dim != 512 || (ld & 3) || (ldy & 3) || (resid && ((ldr & 3) || (r_split > 2 && r_split != 4))))
         return fail(-1, "layernorm: dim must be 512, ld a multiple of 4, residual fp32, split pairs or half rows");
-    if (out_split != 0 && out_split != 1 && out_split != 2 && out_split != 4)
-        return fail(-1, "layernorm: out_split must be 0 (fp32), 1 (split pairs), 2 (bf16 half rows) or 4 (fp16 half rows)");
+    if (out_split != 0 && out_split != 1 && out_split != 2 && out_split != 4 && out_split != 6)
+        return fail(-1, "layernorm: out_split must be 0 (fp32), 1 (split pairs), 2 (bf16 half rows), 4 (fp16 half rows) or 6 (GEMM pair words)");
     if (x_f16 != 0 && x_f16 != 1) return fail(-1, "layernorm: x_f16 must be 0 or 1");
     hipLaunchKernelGGL(layernorm512_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ld, y, ldy, rows, gamma, beta, relu, out_split,
                        resid, ldr, r_split, x_f16);

@@ -308,7 +308,8 @@ int vlsat_k_pointnet_ex(const float* pts, int32_t n_obj, int32_t n_points, int32
  * ldy, ldr in floats, multiples of 4; y may be x or resid).  x_f16 = 1: the rows of x are fp16 half rows (fp16 values at
  * byte 2 * column).  resid may be NULL; resid_fmt: 0 fp32, 1 split-pair words, 2 bf16 half rows, 4 fp16 half rows.
  * out_fmt: 0 fp32, 1 split-pair words, 2 bf16 half rows, 4 fp16 half rows clamped to +-65504 (a half row fills the first
- * 1024 bytes of the row of y).  Any other out_fmt or x_f16 is refused.  Asynchronous. */
+ * 1024 bytes of the row of y), 6 GEMM pair words of the fp32 mode (Ah << 16 | Al, Ah = f16(yc), Al = f16((yc - Ah) 2^11), yc = y
+ * clamped to +-65504: csrc/gemm_f16s_planes.h; one word per element).  Any other out_fmt or x_f16 is refused.  Asynchronous. */
 int vlsat_k_layernorm_to(const float* x, int32_t ld, float* y, int32_t ldy, int32_t rows, int32_t dim,
                          const float* gamma, const float* beta, int32_t relu, int32_t out_fmt,
                          const float* resid, int32_t ldr, int32_t resid_fmt, int32_t x_f16, void* stream);
@@ -770,8 +771,8 @@ int vlsat_debug_gemm_clock_probe(int64_t* buf);
  *   "dual_stream" 0|1|2   extra streams for the 2D chains (1: launch-bound plans only, 2 = default: every plan; such a plan owns a second
  *                         scratch set, +11.3 KB per edge, and falls back to one stream past 48 GiB of workspace) -- plans created afterwards;
  *   "sched" -1|0|1        schedule of a multi-stream plan: 1 = dependency-exact, three lanes (3D chain / 2D edge chain / 2D node chain)
- *                         coupled by one event per data-flow edge; 0 = fork / join, lanes meet twice per layer; -1 (default) = exact in
- *                         the bf16 modes on plans of more than 16 384 edges, fork / join otherwise.  Bit-identical results;
+ *                         coupled by one event per data-flow edge; 0 = fork / join, lanes meet twice per layer; -1 (default) = exact on
+ *                         plans of more than 16 384 edges (every precision mode), fork / join otherwise.  Bit-identical results;
  *   "flash_split" 0|1     split-key edge attention for plans that cannot fill the chip (plans created afterwards);
  *   "prof_dual" 0|1       per-class profiling keeps the multi-stream execution (1, default) or serialises on the launch stream;
  *   "pair_twins" 0|1, "pair_max_edges" n   plans of at most n edges (default 4096: one scene per call) run the 3D / 2D twin stages --
@@ -806,7 +807,10 @@ int vlsat_debug_gemm_clock_probe(int64_t* buf);
  *                         fragment; 2 = group 0's P.V product in front of group 1's softmax).  Bit-identical to 0; 4-7 % slower per step
  *                         at BASELINE configs[2] and configs[4] (profiles/r06_probes/ab_flash_qg.txt): default 0;
  *   "flash_pv_terms" 3|2  split-bf16 edge attention: MFMAs per P.V product;  "gate_fuse_agg" 0|1|2: max aggregation inside the gate
- *                         kernel (never / bf16 modes / fp32 too);  "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2: gate kernel variants.
+ *                         kernel (never / default: bf16 modes, and fp32 on plans of more than 16 384 edges / fp32 on every plan);
+ *                         "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2: gate kernel variants;
+ *   "edge_pairs", "edge_pairs_e2" 0|1   fp32 mode: edge tensors between the split-fp16 kernels as pair words (csrc/edge_pairs.h; default 1),
+ *                         the second one for the 2D chain tensor E2 as the LayerNorm and rel_encoder_2d write it.  Bit-identical results.
  * Lab switches ("gate_grid", "gate_heads_bf16", "flash_heads_bf16", "node_attn_split", "half_fmt", "flash_dma", "flash_ablate" -- the
  * last one produces GARBAGE results for timing) exist in the experiments build only (`build.py --experiments`, -DVLSAT_EXPERIMENTS ->
  * tools/bin/libvlsat_hip_exp.so); the release library answers them with VLSAT_EINVAL. */
