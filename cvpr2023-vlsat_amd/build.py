@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libvlsat_hip.so")
-SOURCES = ["engine_weights.hip", "engine_plan.hip", "engine_forward.hip", "engine_api.hip", "gemm_f32.hip", "gemm_bf16_ring.hip", "gemm_bf16_p8.hip", "gemm_splitk.hip", "flash_attn_f32.hip", "flash_attn_bf16.hip", "pointnet.hip", "pointnet_bf16.hip", "edge_gate.hip", "edge_gate_bf16.hip", "edge_gate_heads.hip", "edge_gate_bf16_heads.hip", "small_ops.hip", "stn.hip", "eval_ranks.hip", "eval_recall.hip", "scene_graph.hip", "graph_decode.hip", "prep.hip", "proximity.hip", "label_transfer.hip", "segment_merge.hip", "scene_split.hip", "calibration.hip", "mesh_segment.hip", "cloud.hip", "voxel.hip", "objects.hip", "convex.hip", "comm.hip"]
+SOURCES = ["engine_weights.hip", "engine_plan.hip", "engine_forward.hip", "engine_api.hip", "gemm_f32.hip", "gemm_bf16_ring.hip", "gemm_bf16_p8.hip", "gemm_splitk.hip", "flash_attn_f32.hip", "flash_attn_bf16.hip", "pointnet.hip", "pointnet_bf16.hip", "edge_gate.hip", "edge_gate_f16s.hip", "edge_gate_bf16.hip", "edge_gate_heads.hip", "edge_gate_bf16_heads.hip", "small_ops.hip", "stn.hip", "eval_ranks.hip", "eval_recall.hip", "scene_graph.hip", "graph_decode.hip", "prep.hip", "proximity.hip", "label_transfer.hip", "segment_merge.hip", "scene_split.hip", "calibration.hip", "mesh_segment.hip", "cloud.hip", "voxel.hip", "objects.hip", "convex.hip", "comm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # appended after FLAGS (the last -ffp-contract wins): proximity.hip's pair distance, label_transfer.hip's point distance,
 # segment_merge.hip's pooled sum, scene_split.hip's fp64 seed distance and pooled sum, mesh_segment.hip's edge weight cloud.hip's point distance and fp64 covariance and Jacobi steps, voxel.hip's cell coordinate, mean and normal length, objects.hip's fp64 plane and fp32 score and convex.hip's convexity value must round every product and sum on their own so that numpy reproduces them bit for bit, and with -ffp-contract=fast the backend fuses

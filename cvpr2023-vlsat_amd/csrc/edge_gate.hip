@@ -3,7 +3,8 @@
 //     HBM (float4 per lane) / the hidden registers, v_mfma_f32_32x32x2_f32.  One wave = 32 rows per step (192 MFMAs); a block of
 //     4 waves;
 //   * the VALU kernel for any head geometry;
-//   * launch_gate: the argument checks and the dispatch to the five kernels' launchers.
+//   * launch_gate: the argument checks and the dispatch to the five kernels' launchers (GATE_F32 with GateArgs::f16s: its split-fp16
+//     sibling, edge_gate_f16s.hip).
 #include <cstdlib>
 #include "gate_core.h"
 #include "gate_agg.h"
@@ -177,7 +178,7 @@ int launch_gate(GateKernel kernel, const GateArgs& a, int n_heads, int dk, int d
     if (twin && !can.twin) return fail(-1, "edge_gate: this kernel does not implement a twin launch");
     if (!a.row_map && !can.row_map0) return fail(-1, "edge_gate: this kernel has the 32-edges-per-wave row map only");
     if (twin && (twin->n_edges != a.n_edges || !twin->agg != !a.agg || twin->row_map != a.row_map || twin->use_edge != a.use_edge ||
-                 !twin->prob != !a.prob || twin->grid_cap != a.grid_cap || twin->src != a.src || twin->dst != a.dst))
+                 !twin->prob != !a.prob || twin->grid_cap != a.grid_cap || twin->f16s != a.f16s || twin->src != a.src || twin->dst != a.dst))
         return fail(-1, "edge_gate: a twin launch needs two problems on the same edge list with the same options");
     if (a.agg && (!a.row_map || a.prob || (a.ld_agg & 3))) return fail(-1, "edge_gate: the fused aggregation needs the 32-edges-per-wave row map and no prob tap");
     if (kernel != GATE_VALU && ((a.ld_node & 3) || (a.gq_off & 3) || (a.v_off & 3)))       // (float4 accesses; the VALU kernel reads scalars)
@@ -191,7 +192,8 @@ int launch_gate(GateKernel kernel, const GateArgs& a, int n_heads, int dk, int d
         case GATE_VALU: return launch_gate_valu(a, n_heads, dk, dox, s);
         case GATE_F32: case GATE_16:
             if (!shipped) return fail(-1, "edge_gate: the shipped kernels are built for 8 heads x (64, 32) only");
-            return kernel == GATE_F32 ? launch_gate_f32(a, s, twin) : launch_gate_16(a, terms, kproj_split, s, twin);
+            if (kernel == GATE_F32) return a.f16s ? launch_gate_f16s(a, s, twin) : launch_gate_f32(a, s, twin);
+            return launch_gate_16(a, terms, kproj_split, s, twin);
         case GATE_F32_HEADS: case GATE_16_HEADS:
             if (!gate_heads_built(n_heads, dk, dox) || (kernel == GATE_16_HEADS && terms == 3 && dk == 128))
                 return fail(-1, "edge_gate: head geometry / terms not built on the MFMA template");

@@ -161,6 +161,7 @@ struct vlsat_ctx {
     int edge_pairs = 1;                      // fp32 mode: edge tensors between split-fp16 GEMMs as pair words where every launch that touches them has the form (edge_pairs.h; debug option "edge_pairs", 0: all fp32)
     int edge_pairs_e2 = 1;                   // ... E2 as the LayerNorm / conv3 of rel_encoder_2d write it among them (debug option "edge_pairs_e2", 0: E2 stays fp32)
     vlsat::EdgePairs pairs{};                // ... the answer for the forward being enqueued (forward_body sets it before the first launch)
+    int gate_exact = -1;                    // fp32 mode, shipped head geometry: -1 / 0 the edge gate on the split-fp16 kernel (GateArgs::f16s; edge_gate_f16s.hip), 1 the exact fp32-MFMA kernel (debug option "gate_exact")
     int gemm_exact = -1;                    // fp32 mode: -1 / 0 the large edge-row launches on the split-fp16 8-phase kernel (GemmArgs::f16s), 1 the exact fp32-MFMA kernels (debug option "gemm_exact")
     int ln_resid = 1;                        // split-pair mode: post-attention residual added in the LayerNorm kernel
     int half_fmt = 1;                        // single-rounding modes: those tensors as plain bf16 (half rows) instead of split pairs

@@ -61,8 +61,10 @@ int vlsat_set_edge_attention_scope(vlsat_handle h, int32_t scope) {
 //                       per product (-1 default, 0; gemm_f16s_kernel) or exact, and node rows exact on every kernel (1); independent of "gemm_exact"
 //   "pointnet_exact" -1|0|1  fp32 mode: conv2 / conv3 of the object encoder as three fp16 MFMAs per product (-1 default, 0;
 //                       pointnet_bf16_kernel<CIN, 5>) or the exact fp32-MFMA kernel (1)
-//                       ("flash_exact", "gemm_exact", "gemm_small_exact" and "pointnet_exact" all 1: the forward of the releases before the
-//                       split-fp16 kernels, bit for bit)
+//   "gate_exact" -1|0|1    fp32 mode, shipped head geometry: the edge gate's products as three fp16 MFMAs each (-1 default, 0;
+//                       edge_gate_f16s_kernel) or the exact fp32-MFMA kernel (1: the forward of the release before, bit for bit)
+//                       ("flash_exact", "gemm_exact", "gemm_small_exact", "pointnet_exact" and "gate_exact" all 1: the forward of the
+//                       releases before the split-fp16 kernels, bit for bit)
 //   "edge_pairs" 0|1     fp32 mode: Hbig, R1 and the 3D chain tensor E3 travel between the split-fp16 GEMMs as pair words (the halves of the
 //                       split operand, made once by the writer) wherever every launch that touches them has the form (1, default;
 //                       edge_pairs.h), or stay fp32 (0: the forward of the releases before the pair words); same outputs bit for bit
@@ -106,6 +108,7 @@ int vlsat_debug_option(vlsat_handle h, const char* name, int32_t value) {
     else if (k == "gemm_exact") h->gemm_exact = value < 0 ? -1 : value != 0;
     else if (k == "pointnet_exact") h->pointnet_exact = value < 0 ? -1 : value != 0;
     else if (k == "gemm_small_exact") h->gemm_small_exact = value < 0 ? -1 : value != 0;
+    else if (k == "gate_exact") h->gate_exact = value < 0 ? -1 : value != 0;
     else if (k == "flash_bf16") h->flash_bf16 = value != 0;
     else if (k == "pointnet_bf16") h->pointnet_bf16 = value != 0;
     else if (k == "gate_bf16") h->gate_bf16 = value != 0;
@@ -789,9 +792,13 @@ int vlsat_k_edge_gate(const float* kproj, const float* node, int32_t ld_node, in
     GateArgs g{};
     g.kproj = kproj; g.node = node; g.ld_node = ld_node; g.gq_off = gq_off; g.v_off = v_off; g.src = src; g.dst = dst;
     g.w0k = w0k; g.w3 = w3; g.b3 = b3; g.gated = gated; g.prob = prob; g.n_edges = n_edges; g.use_edge = use_edge != 0;
-    if (variant < 0 || variant > 4) return fail(VLSAT_EINVAL, "edge_gate: variant 0..4");
-    // 0: what the fp32 forward launches for this geometry; 1: the VALU kernel; 2: the fp32 template; 3 | 4: the split-bf16 | single-rounded
-    // bf16 kernel of this geometry
+    if (variant < 0 || variant > 5) return fail(VLSAT_EINVAL, "edge_gate: variant 0..5");
+    // 0: the exact fp32 kernel of this geometry; 1: the VALU kernel; 2: the fp32 template; 3 | 4: the split-bf16 | single-rounded
+    // bf16 kernel of this geometry; 5: the split-fp16 kernel of the fp32 mode (shipped geometry only)
+    if (variant == 5) {
+        if (n_heads != 8 || dk != 64 || dox != 32) return fail(VLSAT_EINVAL, "edge_gate: the split-fp16 kernel is built for 8 heads x (64, 32) only");
+        g.f16s = 1;
+    }
     const int terms = variant == 3 ? 3 : variant == 4 ? 1 : 0;
     const GateChoice gc = variant == 1 ? gate_choice(GATE_VALU) : gate_select(n_heads, dk, dox, terms, true, variant == 2 ? 2 : 1, true);
     if (variant == 2 && gc.kernel != GATE_F32_HEADS) return fail(VLSAT_EINVAL, "edge_gate: head geometry not built on the MFMA template");

@@ -313,6 +313,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
         g[i].src = p->d_src; g[i].dst = p->d_dst; g[i].w0k = b.w->w0k; g[i].w3 = b.w->w3; g[i].b3 = b.w->b3; g[i].gated = b.sc->G;
         g[i].prob = nb == 1 ? p->prob : nullptr;     // (the probability tap: single launches only)
         g[i].n_edges = E; g[i].use_edge = h->d.use_gcn_edge; g[i].grid_cap = h->gate_grid; g[i].row_map = gc.row_map0 ? h->gate_row_map : 1;
+        g[i].f16s = gc.kernel == GATE_F32 && h->prec_edge == 0 && h->gate_exact != 1;      // fp32 mode: three fp16 MFMAs per product ("gate_exact" 1: the exact kernel)
     }
     // fused: no [E, A] tensor of gated messages, no aggregate launch; the start values go in first
     const bool fused_agg = gate_fuses_agg(h, gc, g[0]);

@@ -1,6 +1,7 @@
 // Shared code of the edge-gate kernels of MultiHeadedEdgeAttention.forward (reference network_MMG.py:96-104).  This header is the
 // one place that describes the gate's algebra and lane model; the kernels say only what differs between them:
 //   edge_gate.hip             fp32 MFMA at the shipped 8 x (64, 64, 32), the VALU kernel for any geometry, and launch_gate
+//   edge_gate_f16s.hip        the fp32 mode's split-fp16 sibling of the fp32 MFMA kernel (GateArgs::f16s): three fp16 MFMAs per product
 //   edge_gate_bf16.hip        bf16 / fp16 MFMA at the shipped geometry
 //   edge_gate_heads.hip       fp32 MFMA template for the other head geometries
 //   edge_gate_bf16_heads.hip  bf16 / fp16 MFMA template for the other head geometries
@@ -40,6 +41,7 @@ namespace vlsat {
 // ---- launchers of the five kernels: called by launch_gate (edge_gate.hip) only, which has checked the arguments ----
 int launch_gate_valu(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s);
 int launch_gate_f32(const GateArgs& a, hipStream_t s, const GateArgs* twin);
+int launch_gate_f16s(const GateArgs& a, hipStream_t s, const GateArgs* twin);      // GATE_F32 with GateArgs::f16s (edge_gate_f16s.hip)
 int launch_gate_f32_heads(const GateArgs& a, int n_heads, int dk, int dox, hipStream_t s);
 int launch_gate_16(const GateArgs& a, int terms, int kproj_split, hipStream_t s, const GateArgs* twin);
 int launch_gate_16_heads(const GateArgs& a, int n_heads, int dk, int dox, int terms, int kproj_split, hipStream_t s);

@@ -134,6 +134,7 @@ struct GateArgs {
     float* agg = nullptr;
     int ld_agg = 0;
     int row_map = 1;         // rows of a wave: 1 = 32 edges of one head, 0 = 4 edges x 8 heads (vlsat_debug_option "gate_row_map")
+    int f16s = 0;            // GATE_F32 only (fp32 mode): 1 = every product as three fp16 MFMAs, fp32 tensors in and out (edge_gate_f16s.hip; as GemmArgs::f16s)
 };
 // The five gate kernels, and the ONE place that says which of them runs and what it can do besides the plain gate.
 enum GateKernel {

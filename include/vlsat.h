@@ -260,8 +260,10 @@ int vlsat_k_layernorm(float* x, int32_t ld, int32_t rows, int32_t dim, const flo
  * w0k [2dk, dk] = nn.0.weight[:, dk:2dk], w3 [dox, 2dk] = nn.3.weight, b3 [dox].  Outputs: gated [E, H*dox] head-major
  * (column h*dox + m; the reference's is m*H + h) and, if not NULL, prob [E, dox, H] in the REFERENCE layout.
  * use_edge = 0: MODEL.USE_GCN_EDGE false (hidden = relu(Gq), kproj / w0k unread).  ld_node, gq_off, v_off % 4 == 0.
- * variant: 0 = the kernel the fp32 forward picks for the geometry, 1 = VALU kernel (any geometry), 2 = fp32 MFMA template
- * (NUM_HEADS in {4,8,16} x DIM_ATTEN in {128,256,512}), 3 / 4 = bf16 matrix cores, split-bf16 / single-rounded (kproj fp32).
+ * variant: 0 = the exact fp32 kernel of the geometry, 1 = VALU kernel (any geometry), 2 = fp32 MFMA template
+ * (NUM_HEADS in {4,8,16} x DIM_ATTEN in {128,256,512}), 3 / 4 = bf16 matrix cores, split-bf16 / single-rounded (kproj fp32),
+ * 5 = the split-fp16 kernel the fp32 forward runs at 8 heads x (64, 32): three fp16 MFMAs per product, fp32 tensors in and out,
+ * raw fp32 weights (the kernel makes its planes itself); any other geometry is VLSAT_EINVAL.
  * All device pointers; asynchronous. */
 int vlsat_k_edge_gate(const float* kproj, const float* node, int32_t ld_node, int32_t gq_off, int32_t v_off,
                       const int32_t* src, const int32_t* dst, const float* w0k, const float* w3, const float* b3,
@@ -808,7 +810,8 @@ int vlsat_debug_gemm_clock_probe(int64_t* buf);
  *                         at BASELINE configs[2] and configs[4] (profiles/r06_probes/ab_flash_qg.txt): default 0;
  *   "flash_pv_terms" 3|2  split-bf16 edge attention: MFMAs per P.V product;  "gate_fuse_agg" 0|1|2: max aggregation inside the gate
  *                         kernel (never / default: bf16 modes, and fp32 on plans of more than 16 384 edges / fp32 on every plan);
- *                         "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2: gate kernel variants;
+ *                         "gate_row_map" 0|1, "gate_heads_mfma" 0|1|2: gate kernel variants; "gate_exact" -1|0|1: fp32 mode, the edge
+ *                         gate of 8 heads x (64, 32) as three fp16 MFMAs per product (-1, 0) or on the exact fp32-MFMA kernel (1);
  *   "edge_pairs", "edge_pairs_e2" 0|1   fp32 mode: edge tensors between the split-fp16 kernels as pair words (csrc/edge_pairs.h; default 1),
  *                         the second one for the 2D chain tensor E2 as the LayerNorm and rel_encoder_2d write it.  Bit-identical results.
  * Lab switches ("gate_grid", "gate_heads_bf16", "flash_heads_bf16", "node_attn_split", "half_fmt", "flash_dma", "flash_ablate" -- the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Largest |A| the split-fp16 kernels of the fp32 mode see, from the CPU oracle (no GPU): the inputs of PointNet's conv2 / conv3 (H1, H2),
-of the Linears on node rows and of the Linears on edge rows -- on the bench weights and on the x 3 / x 4 stress weights, three scenes of
+of the Linears on node rows, of the Linears on edge rows and of the two layers of the edge gate (its kproj rows KP and its hidden vector) -- on the bench weights and on the x 3 / x 4 stress weights, three scenes of
 40 objects x 256 points.  The operand domain is +-65504 (beyond it the operand saturates).
 
     python tools/f16s_domain.py
@@ -39,11 +39,31 @@ def main():
                 seen[cls] = (v, name)
             return inner(x, wt, name)
 
+        inner_gate = O.edge_atten
+
+        def edge_atten(x, e, ei, wt, prefix, n_heads, taps=None):
+            # the operands of the gate's two layers (edge_gate_f16s.hip): KP = proj_edge(e), hidden = relu(nn.0([q | k]) + b0)
+            p = prefix + ".edgeatten."
+            xi, _ = O.gen_index(x, ei, "target_to_source")
+            E = e.shape[0]
+            q = inner(xi, wt, p + "proj_query.0")
+            k = inner(e, wt, p + "proj_edge.0")
+            q, k = q.view(E, q.shape[1] // n_heads, n_heads), k.view(E, k.shape[1] // n_heads, n_heads)
+            w0, b0 = wt[p + "nn.0.weight"][:, :, 0], wt[p + "nn.0.bias"]
+            z = torch.cat([q, k], 1) if w0.shape[1] == q.shape[1] + k.shape[1] else q
+            hid = torch.relu(torch.einsum("oc,ech->eoh", w0, z) + b0[None, :, None])
+            for cls, v in (("gate KP", float(k.abs().max())), ("gate hidden", float(hid.max()))):
+                if v > seen.get(cls, (0.0, ""))[0]:
+                    seen[cls] = (v, prefix)
+            return inner_gate(x, e, ei, wt, prefix, n_heads, taps)
+
         O.lin = lin
+        O.edge_atten = edge_atten
         try:
             O.forward(O.to_torch(w, torch.float32), cfg, b["obj_points"], b["obj_2d_feats"], b["edge_indices"], b["descriptor"], b["batch_ids"])
         finally:
             O.lin = inner
+            O.edge_atten = inner_gate
         print(label + ": " + "; ".join(f"{c} {v:.4g} ({n})" for c, (v, n) in sorted(seen.items())))
 
 

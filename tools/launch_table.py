@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-launch table of the matrix kernels of one forward from two SERIAL kernel traces (`rocprofv3 --kernel-trace --stats -d DIR -o NAME --
+"""Per-launch table of the matrix kernels (GEMMs, attention, LayerNorm, edge gate and its aggregation launches) of one forward from two SERIAL kernel traces (`rocprofv3 --kernel-trace --stats -d DIR -o NAME --
 python bench.py ... --no-profile --debug-option dual_stream=0`, one per build; rocpd databases), side by side: the launches of a
 forward in stream order, each averaged over the traced forwards after the first two.  Both builds launch the same sequence, so row i
 is the same stage in both (profiles/edge_pairs_ab.txt).
@@ -18,8 +18,8 @@ def launches(db):
         if "pointnet" in name:
             cur = []
             fw.append(cur)
-        if cur is not None and ("gemm_" in name or "flash_" in name or "layernorm" in name):
-            m = re.search(r"(gemm_\w+|flash_\w+|layernorm\w*)(<[^>]*>)?", name)
+        if cur is not None and ("gemm_" in name or "flash_" in name or "layernorm" in name or "edge_gate" in name or "agg" in name):
+            m = re.search(r"(gemm_\w+|flash_\w+|layernorm\w*|edge_gate\w*|agg\w*)(<[^>]*>)?", name)
             cur.append(((m.group(1) + (m.group(2) or "")) if m else name[:60], blocks, dur))
     fw = [f for f in fw if len(f) == len(fw[-1])][2:]           # drop the warm-up forwards
     out = []
@@ -33,8 +33,8 @@ print(f"forwards averaged: {na} / {nb}; launches per forward: {len(a)} / {len(b)
 assert len(a) == len(b)
 ta = tb = 0.0
 for i, (x, y) in enumerate(zip(a, b)):
-    big = "p8s" in x[0] or "flash" in x[0] or x[2] > 15
+    big = "p8s" in x[0] or "flash" in x[0] or "gate" in x[0] or "agg" in x[0] or x[2] > 15
     if big:
         print(f"{i:4d}  {x[0]:50s} {x[1]:5d} {x[2]:8.1f}   {y[0]:50s} {y[2]:8.1f}  {y[2] - x[2]:+7.1f}")
     ta += x[2]; tb += y[2]
-print(f"sum of all gemm / flash / layernorm launches per forward: {ta / 1e3:.3f} ms -> {tb / 1e3:.3f} ms")
+print(f"sum of all gemm / flash / layernorm / gate / aggregation launches per forward: {ta / 1e3:.3f} ms -> {tb / 1e3:.3f} ms")
