@@ -3,6 +3,8 @@
 //   plan_graph.h        graph plan, the host-only part: graph analysis, attention tile tables, the list of the arena's buffers
 //   engine_plan.hip     graph plan, the HIP objects: arena pool, pinned staging, asynchronous index upload
 //   engine_forward.hip  the forward orchestration (vlsat_forward / vlsat_forward_train) and per-class profiling
+//   edge_stages.h       every edge-row Linear of the forward as the GemmArgs of its launch (host-only: the forward launches them,
+//   edge_pairs.h        the fp32 mode's pair-word plan asks the GEMM planner about the same ones)
 //   engine_api.hip      kernel-level C entry points and debug hooks
 // The public surface is include/vlsat.h.
 #pragma once
@@ -252,6 +254,9 @@ inline int npc_of(const vlsat_ctx* h) { return 6 * h->D + h->A; }
 // never in the exact-fp32 mode and never when the node rows run in fp32
 inline bool gather_f16_on(const vlsat_ctx* h) { return h->prec_edge != 0 && h->prec_node != 0 && (h->gather_f16 >= 0 ? h->gather_f16 != 0 : h->prec_edge == 1); }
 inline bool default_heads(const vlsat_ctx* h) { return h->H == 8 && h->A == 256; }
+// The fp32 precision mode.  vlsat_set_gemm_precision is the only writer of prec / prec_edge / prec_node / prec_attn: mode 0 sets all four
+// to 0 and no other mode sets any of them to 0, so this is also "prec_edge == 0", "prec_node == 0" and "prec_attn == 0"
+inline bool fp32_mode(const vlsat_ctx* h) { return h->prec == 0; }
 
 #define RUN(expr)                  \
     do {                           \

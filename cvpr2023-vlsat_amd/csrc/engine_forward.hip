@@ -126,14 +126,10 @@ static int gemm_resolve(vlsat_ctx* h, int ws_lane, GemmArgs& a, int prec_overrid
         a.Whi = it->second.first;
         a.Wlo = it->second.second;
     }
-    // fp32 mode: every launch may run on the split-fp16 siblings of the exact kernels (GemmArgs::f16s) -- the full rounds of an 8-phase launch
-    // (launch_gemm_p8) unless "gemm_exact" asks for the exact kernel, the persistent kernel's launches (tails, small launches, node rows;
-    // gemm_f16s_tiled_pick) unless "gemm_small_exact" does.  With "gemm_small_exact" 1 node-row launches are exact whatever they run on
-    // (the releases before the persistent kernel's siblings).  Split-K launches are always exact.
-    if (prec == 0 && h->prec_edge == 0) {
-        const bool node = a.M == h->cur_N && !edge_fmt;
-        const bool small = h->gemm_small_exact != 1, big = h->gemm_exact != 1 && !(node && !small);
-        const int f16s = small ? (big ? 2 : 3) : (big ? 1 : 0);
+    // fp32 mode: every launch may run on the split-fp16 siblings of the exact kernels (GemmArgs::f16s; which, by the debug options and the
+    // row class: gemm_f16s_code of gemm_plan.h).  Split-K launches are always exact.
+    if (fp32_mode(h)) {
+        const int f16s = gemm_f16s_code(h->gemm_exact == 1, h->gemm_small_exact == 1, a.M == h->cur_N && !edge_fmt);
         if (f16s) {
             auto f = h->f16s.find(a.W);
             if (f == h->f16s.end()) return fail(VLSAT_ESTATE, "gemm: weight has no split-fp16 planes");
@@ -258,26 +254,14 @@ GemmArgs node_project_args(const vlsat_ctx* h, const vlsat_plan_s* p, const GcnW
 int gcn_node_project(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnW& w, const float* x, const Scratch& sc) {
     return gemm(h, s, node_project_args(h, p, w, x, sc));
 }
-// nn_edge.0 on the edge part `we` of its weight: Hbig = relu(e . we^T + P_i[src] + P_j[dst]); the node columns (with the bias) were made
-// on N rows by the node-side projection.  g_f16: they are fp16 half rows (never for triplet_projector_2d's first Linear, the other caller)
-// e_pair / hbig_pair (fp32 mode): e is read / Hbig is written as GEMM pair words (vlsat_ctx::pairs)
-GemmArgs nn_edge0_args(const vlsat_ctx* h, const vlsat_plan_s* p, const float* we, const float* e, int relu_a, const Scratch& sc, bool g_f16,
-                       bool e_pair, bool hbig_pair) {
-    const int D = h->D, NPC = npc_of(h), S = split_fmt(h);
-    GemmArgs e1 = G(e, D, we, D, sc.Hbig, 2 * D, (int)p->E, 2 * D, nullptr, ACT_RELU);
-    e1.relu_a = relu_a;
-    e1.a_split = S; e1.c_split = S;
-    e1.a_pair = e_pair; e1.c_pair = hbig_pair;
-    e1.g0 = sc.NP; e1.gi0 = p->d_src; e1.ldg0 = NPC;
-    e1.g_f16 = g_f16;
-    e1.g1 = sc.NP + (g_f16 ? D : 2 * D); e1.gi1 = p->d_dst; e1.ldg1 = NPC;       // (fp16 half rows: P_j starts at byte 2 * 2D of the row)
-    return e1;
-}
+// The edge-row Linears are the stages of edge_stages.h: a site below fills the operands and launches what the builder returns.
+// SA: the format of Q / K|V / O, for the edge attention's projections (EdgeAttnFmt)
+EdgeDims edge_dims(const vlsat_ctx* h, const vlsat_plan_s* p, int SA = 0) { return {(int)p->E, h->D, npc_of(h), h->d.n_rel_class, split_fmt(h), SA}; }
 
 // node_done: sc.NP has already been filled by gcn_node_project (on another lane; the caller has ordered this lane behind it)
 int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side, int nb, int out_relu, bool node_done = false) {
     const int N = (int)p->N, E = (int)p->E, D = h->D, A = h->A, LDX = ldx_of(h), NPC = npc_of(h);
-    const int S = split_fmt(h);
+    const EdgeDims d = edge_dims(h, p);
     const GateChoice gc = gate_of(h);
     const EdgePairs& P = h->pairs;
     GemmArgs a[2];
@@ -286,26 +270,19 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
         for (int i = 0; i < nb; ++i) a[i] = node_project_args(h, p, *side[i].w, side[i].x, *side[i].sc);
         RUN(gemm_n(h, s, a, nb));
     }
-    for (int i = 0; i < nb; ++i) a[i] = nn_edge0_args(h, p, side[i].w->we1, side[i].e, side[i].e_relu_pending, *side[i].sc, gather_f16_on(h),
-                                                   side[i].br == 0 ? P.e3 : P.e2, P.hbig[side[i].br]);
+    for (int i = 0; i < nb; ++i) {
+        const GcnSide& b = side[i];
+        a[i] = stage_nn_edge0(d, {b.e, b.w->we1, nullptr, b.sc->Hbig, nullptr, b.sc->NP, p->d_src, p->d_dst}, P, b.br, b.e_relu_pending, gather_f16_on(h));
+    }
     RUN(gemm_n(h, s, a, nb));
     if (h->d.use_gcn_edge) {              // proj_edge feeds only the gate MLP (reference network_MMG.py:98-102)
         for (int i = 0; i < nb; ++i) {
             const GcnSide& b = side[i];
-            a[i] = G(b.e, D, b.w->wpe, D, b.sc->KP, D, E, D, b.w->bpe);
-            a[i].relu_a = b.e_relu_pending;
-            a[i].a_split = S;
-            a[i].c_split = gc.bits16() ? S : 0;      // (the fp32 gate kernels read plain fp32)
-            a[i].a_pair = b.br == 0 ? P.e3 : P.e2;
+            a[i] = stage_proj_edge(d, {b.e, b.w->wpe, b.w->bpe, b.sc->KP}, P, b.br, b.e_relu_pending, gc.bits16());
         }
         RUN(gemm_n(h, s, a, nb));
     }
-    for (int i = 0; i < nb; ++i) {
-        const GcnSide& b = side[i];
-        a[i] = G(b.sc->Hbig, 2 * D, b.w->we2, 2 * D, b.e, D, E, D, b.w->be2);       // e <- nn_edge output (pre-activation)
-        a[i].a_split = S; a[i].c_split = S;
-        a[i].a_pair = P.hbig[b.br]; a[i].c_pair = b.br == 0 && P.e3;
-    }
+    for (int i = 0; i < nb; ++i) a[i] = stage_nn_edge2(d, {side[i].sc->Hbig, side[i].w->we2, side[i].w->be2, side[i].e}, P, side[i].br);
     RUN(gemm_n(h, s, a, nb));
     for (int i = 0; i < nb; ++i) {
         const GcnSide& b = side[i];
@@ -313,7 +290,7 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
         g[i].src = p->d_src; g[i].dst = p->d_dst; g[i].w0k = b.w->w0k; g[i].w3 = b.w->w3; g[i].b3 = b.w->b3; g[i].gated = b.sc->G;
         g[i].prob = nb == 1 ? p->prob : nullptr;     // (the probability tap: single launches only)
         g[i].n_edges = E; g[i].use_edge = h->d.use_gcn_edge; g[i].grid_cap = h->gate_grid; g[i].row_map = gc.row_map0 ? h->gate_row_map : 1;
-        g[i].f16s = gc.kernel == GATE_F32 && h->prec_edge == 0 && h->gate_exact != 1;      // fp32 mode: three fp16 MFMAs per product ("gate_exact" 1: the exact kernel)
+        g[i].f16s = gc.kernel == GATE_F32 && fp32_mode(h) && h->gate_exact != 1;      // fp32 mode: three fp16 MFMAs per product ("gate_exact" 1: the exact kernel)
     }
     // fused: no [E, A] tensor of gated messages, no aggregate launch; the start values go in first
     const bool fused_agg = gate_fuses_agg(h, gc, g[0]);
@@ -339,30 +316,16 @@ int gcn_block(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const GcnSide* side,
 }
 
 int rel_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const RelSide* side, int nb) {
-    const int E = (int)p->E, D = h->D, R = h->d.n_rel_class;
-    const int S = split_fmt(h);
+    const int E = (int)p->E, R = h->d.n_rel_class;
+    const EdgeDims d = edge_dims(h, p);
+    const EdgePairs& P = h->pairs;
     GemmArgs a[2];
-    for (int i = 0; i < nb; ++i) {
-        const RelSide& b = side[i];
-        a[i] = G(b.e, D, b.w->w1, D, b.sc->R1, 512, E, 512, b.w->b1, ACT_RELU);
-        a[i].relu_a = b.relu_a;
-        a[i].a_split = S; a[i].c_split = S;
-        a[i].a_pair = b.br == 0 ? h->pairs.e3 : h->pairs.e2; a[i].c_pair = h->pairs.r1[b.br];
-    }
+    for (int i = 0; i < nb; ++i) a[i] = stage_rel_head1(d, {side[i].e, side[i].w->w1, side[i].w->b1, side[i].sc->R1}, P, side[i].br, side[i].relu_a);
     RUN(gemm_n(h, s, a, nb));
-    for (int i = 0; i < nb; ++i) {
-        const RelSide& b = side[i];
-        a[i] = G(b.sc->R1, 512, b.w->w2, 512, b.sc->R2, 256, E, 256, b.w->b2, ACT_RELU);
-        a[i].a_split = S; a[i].c_split = S;
-        a[i].a_pair = h->pairs.r1[b.br];
-    }
+    for (int i = 0; i < nb; ++i) a[i] = stage_rel_head2(d, {side[i].sc->R1, side[i].w->w2, side[i].w->b2, side[i].sc->R2}, P, side[i].br);
     RUN(gemm_n(h, s, a, nb));
     // multi_rel_outputs: sigmoid (PointNetRelClsMulti) or log_softmax over the R classes (PointNetRelCls)
-    for (int i = 0; i < nb; ++i) {
-        const RelSide& b = side[i];
-        a[i] = G(b.sc->R2, 256, b.w->w3, 256, b.out, R, E, R, b.w->b3, h->d.multi_rel_outputs ? ACT_SIGMOID : ACT_NONE);
-        a[i].a_split = S;
-    }
+    for (int i = 0; i < nb; ++i) a[i] = stage_rel_head3(d, {side[i].sc->R2, side[i].w->w3, side[i].w->b3, side[i].out}, h->d.multi_rel_outputs != 0);
     RUN(gemm_n(h, s, a, nb));
     if (!h->d.multi_rel_outputs) {
         Scope scope(h, s, PC_MISC, 0);
@@ -388,18 +351,11 @@ int obj_head(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const ObjSide* side, 
 
 // conv2 / conv3 of the relation encoders br0 .. br0 + nb - 1 on the edge embedding H1 [E, 64 | 64] -> E3 / E2
 int rel_encoder(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, int br0, int nb, const Scratch* const* sc) {
-    const int E = (int)p->E, D = h->D, S = split_fmt(h);
+    const EdgeDims d = edge_dims(h, p);
     GemmArgs a[2];
-    for (int i = 0, br = br0; i < nb; ++i, ++br) {
-        a[i] = G(p->H1 + 64 * br, 128, rel_enc_w(h, br).w2, 64, sc[br]->H2, 128, E, 128, rel_enc_w(h, br).b2, ACT_RELU);
-        a[i].c_split = S;
-    }
+    for (int i = 0, br = br0; i < nb; ++i, ++br) a[i] = stage_conv2(d, {p->H1 + 64 * br, rel_enc_w(h, br).w2, rel_enc_w(h, br).b2, sc[br]->H2});
     RUN(gemm_n(h, s, a, nb));
-    for (int i = 0, br = br0; i < nb; ++i, ++br) {
-        a[i] = G(sc[br]->H2, 128, rel_enc_w(h, br).w3, 128, br ? p->E2 : p->E3, D, E, D, rel_enc_w(h, br).b3, ACT_RELU);
-        a[i].a_split = S; a[i].c_split = S;
-        a[i].c_pair = br == 0 ? h->pairs.e3 : h->pairs.e2;
-    }
+    for (int i = 0, br = br0; i < nb; ++i, ++br) a[i] = stage_conv3(d, {sc[br]->H2, rel_enc_w(h, br).w3, rel_enc_w(h, br).b3, br ? p->E2 : p->E3}, h->pairs, br);
     return gemm_n(h, s, a, nb);
 }
 
@@ -427,7 +383,7 @@ EdgeAttnFmt edge_attn_fmt(const vlsat_ctx* h) {
     //  which puts the attention on its LDS-direct kernel and the out-projection on the 8-phase one)
     f.SA = f.fa16 ? ((PA == 1 && S == 1 && h->half_fmt && dh == 64) ? 2 : S) : 0;
     // fp32 mode: the split-fp16 attention kernel where its list has one (head dim 64); every other case keeps the exact fp32 kernel
-    f.x3 = h->prec == 0 && PA == 0 && h->flash_exact != 1 && flash_f16x3_supports(dh, h->flash_tr ? 1 : 0);
+    f.x3 = fp32_mode(h) && h->flash_exact != 1 && flash_f16x3_supports(dh, h->flash_tr ? 1 : 0);
     // Split-pair mode: the residual is added by the LayerNorm kernel (as an accumulator init it made the out-projection 60 % slower
     // there -- 397 vs 243 us at the bench size -- against +1 KB per row in the LayerNorm).  Half rows: the same (the 8-phase GEMM has no
     // fast accumulator-init path).
@@ -439,18 +395,10 @@ EdgeAttnFmt edge_attn_fmt(const vlsat_ctx* h) {
     return f;
 }
 int edge_attn_q(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f) {
-    const int E = (int)p->E, D = h->D;
-    GemmArgs gq = G(p->E2, D, w.wq, D, p->Qe, D, E, D, w.bq);
-    gq.a_split = f.S; gq.c_split = f.SA;
-    if (f.SA) gq.c_scale = f.qscale;                                 // the split-format attention takes Q pre-scaled
-    return gemm(h, s, gq, f.PA);
+    return gemm(h, s, stage_attn_q(edge_dims(h, p, f.SA), {p->E2, w.wq, w.bq, p->Qe}, h->pairs, f.qscale), f.PA);
 }
 int edge_attn_kv(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f, float* kve) {
-    const int E = (int)p->E, D = h->D;
-    GemmArgs gkv = G(p->E3, D, w.wkv, D, kve, 2 * D, E, 2 * D, w.bkv);
-    gkv.a_split = f.S; gkv.c_split = f.SA;
-    gkv.a_pair = h->pairs.e3; gkv.c_pair = h->pairs.kv ? 2 : 0;      // (fp32 mode: K | V as attention pair words for the split-fp16 kernel)
-    return gemm(h, s, gkv, f.PA);
+    return gemm(h, s, stage_attn_kv(edge_dims(h, p, f.SA), {p->E3, w.wkv, w.bkv, kve}, h->pairs), f.PA);
 }
 int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAttnFmt& f, const float* kve) {
     const int E = (int)p->E, D = h->D, dh = f.dh, SA = f.SA;
@@ -481,12 +429,7 @@ int edge_attn_attend(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const EdgeAtt
 int edge_attn_out(vlsat_ctx* h, vlsat_plan_s* p, hipStream_t s, const AttnW& w, const EdgeAttnFmt& f, int relu) {
     const int E = (int)p->E, D = h->D, S = f.S;
     float* pre_ln = S ? p->Qe : p->E2;
-    GemmArgs o = G(p->Oe, D, w.wo, D, pre_ln, D, E, D, w.bo);
-    if (!f.ln_resid) { o.resid = p->E2; o.ldr = D; o.r_split = S; }
-    o.a_split = f.SA;
-    o.a_pair = h->pairs.oe;
-    if (f.o16) o.c_f16_cols = D;
-    RUN(gemm(h, s, o, f.PA));
+    RUN(gemm(h, s, stage_attn_out(edge_dims(h, p, f.SA), {p->Oe, w.wo, w.bo, pre_ln, p->E2}, h->pairs, f.ln_resid, f.o16), f.PA));
     Scope sc(h, s, PC_LAYERNORM, 0);
     const int SL = (S == 2 && h->half_f16) ? 4 : S;          // (mode 5: the half rows the LayerNorm reads and writes hold fp16)
     // (fp32 mode, h->pairs.e2: the LayerNorm's E2 has only GEMM A operands as readers -- it leaves as GEMM pair words, format 6)
@@ -617,8 +560,8 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
     const bool exact = dual && !pair && (h->sched < 0 ? p->E > 16384 : h->sched != 0);
     {   // fp32 mode: which edge tensors travel as GEMM pair words in this forward -- one answer, read by every stage below
         EdgePairsIn in;
-        in.E = p->E; in.D = D; in.G = gemm_slots(); in.option = h->edge_pairs; in.option_e2 = h->edge_pairs_e2;
-        in.fp32_mode = h->prec == 0 && h->prec_edge == 0 && h->prec_node == 0;
+        in.E = p->E; in.D = D; in.A = h->A; in.G = gemm_slots(); in.option = h->edge_pairs; in.option_e2 = h->edge_pairs_e2;
+        in.fp32_mode = fp32_mode(h);
         in.gemm_exact = h->gemm_exact == 1; in.gemm_small_exact = h->gemm_small_exact == 1;
         in.no_dma = h->gemm_no_dma != 0; in.no_p8 = h->gemm_no_p8 != 0; in.splitk = h->gemm_splitk != 0;
         in.p8_part_min = h->gemm_p8_part_min; in.sk_max_tiles = h->gemm_splitk_max_tiles;
@@ -691,7 +634,7 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
             }
             RUN(launch_pointnet_bf16(pts, N, p->P, h->d.dim_point, h->pn_w1, h->pn_b1, w2h, w2->second.second, h->pn_b2,
                                      w3h, w3->second.second, h->pn_b3, h->C_pt, terms, p->F, s));
-        } else if (h->prec == 0 && h->pointnet_exact != 1) {     // fp32 mode: conv2 / conv3 as three fp16 MFMAs per product, on the planes
+        } else if (fp32_mode(h) && h->pointnet_exact != 1) {     // fp32 mode: conv2 / conv3 as three fp16 MFMAs per product, on the planes
             auto w2 = h->f16s.find(h->pn_w2), w3 = h->f16s.find(h->pn_w3);      // split_all_weights made ("pointnet_exact" 1: the exact kernel)
             if (w2 == h->f16s.end() || w3 == h->f16s.end()) return fail(VLSAT_ESTATE, "pointnet: weights have no split-fp16 planes");
             RUN(launch_pointnet_bf16(pts, N, p->P, h->d.dim_point, h->pn_w1, h->pn_b1, w2->second.hi, w2->second.lo, h->pn_b2,
@@ -841,11 +784,8 @@ static int forward_body(vlsat_handle h, vlsat_plan p, const float* pts, const fl
         // its first Linear on N rows, gathered into the edge GEMM's accumulators like nn_edge.0 (fp32 tables, no ReLU pending)
         if (!h->trip.wnode) return fail(VLSAT_ESTATE, "forward(istrain=True): triplet_projector_2d weights were not loaded");
         RUN(gemm(h, s, G(p->X2, LDX, h->trip.wnode, D, sc2.NP, npc_of(h), N, 4 * D, h->trip.bnode)));
-        RUN(gemm(h, s, nn_edge0_args(h, p, h->trip.we, p->E2, 0, sc2, false, false, h->pairs.hbig[1])));
-        GemmArgs e2 = G(sc2.Hbig, 2 * D, h->trip.w2, 2 * D, tr->edge_dis, D, E, D, h->trip.b2);
-        e2.a_split = split_fmt(h);
-        e2.a_pair = h->pairs.hbig[1];
-        RUN(gemm(h, s, e2));
+        RUN(gemm(h, s, stage_triplet0(edge_dims(h, p), {p->E2, h->trip.we, nullptr, sc2.Hbig, nullptr, sc2.NP, p->d_src, p->d_dst}, h->pairs)));
+        RUN(gemm(h, s, stage_triplet2(edge_dims(h, p), {sc2.Hbig, h->trip.w2, h->trip.b2, tr->edge_dis}, h->pairs)));
     }
     // a-15 relation heads, a-16 object heads
     const RelSide rs[2] = {{&h->rel3, p->E3, e3_pending_relu, rel3d, &sc3, 0}, {&h->rel2, p->E2, 0, rel2d, &sc2, 1}};

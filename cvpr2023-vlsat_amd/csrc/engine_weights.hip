@@ -480,6 +480,7 @@ int vlsat_set_gemm_precision(vlsat_handle h, int32_t mode) {
     if (mode < 0 || mode > 5) return fail(VLSAT_EINVAL, "gemm precision must be 0 (fp32), 1 (bf16), 2 (mixed), 3 (bf16x3), 4 (bf16x3 with a single-rounded edge attention) or 5 (mixed on fp16)");
     // mode 5: mode 2 with fp16 half rows and v_mfma_f32_32x32x16_f16 on the edge-row kernels (GEMM, attention, gate): the same rate, 2^-12 instead of
     // 2^-9 per stored value and operand
+    // (the only writer of prec / prec_edge / prec_node / prec_attn: mode 0 leaves all four 0, every other mode none -- fp32_mode of engine.h)
     ++h->config_epoch;
     h->prec = mode;
     h->half_f16 = mode == 5;

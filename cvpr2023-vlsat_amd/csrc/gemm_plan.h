@@ -221,6 +221,14 @@ constexpr int gemm_p8s_find(int add, bool relu) {
 }
 // GemmArgs::f16s: which exact-fp32 launches of a problem run on their split-fp16 sibling -- 1 the 8-phase launches, 2 those and the
 // persistent kernel's, 3 the persistent kernel's only (the split-K launches always stay exact)
+// The code of a launch of the fp32 mode, the one place that states it (gemm_resolve of engine_forward.hip and edge_pairs_plan ask): the
+// full rounds of an 8-phase launch run on the sibling unless "gemm_exact" asks for the exact kernel, the persistent kernel's launches
+// (tails, small launches, node rows) unless "gemm_small_exact" does -- and with "gemm_small_exact" node-row launches are exact whatever
+// they run on (the releases before the persistent kernel's siblings)
+inline int gemm_f16s_code(bool gemm_exact, bool gemm_small_exact, bool node_rows) {
+    const bool small = !gemm_small_exact, big = !gemm_exact && !(node_rows && !small);
+    return small ? (big ? 2 : 3) : (big ? 1 : 0);
+}
 inline bool gemm_f16s_p8(const GemmArgs& a) { return a.f16s == 1 || a.f16s == 2; }
 inline bool gemm_f16s_tiled(const GemmArgs& a) { return a.f16s == 2 || a.f16s == 3; }
 // The sibling that runs row `variant` of the 8-phase list for a launch with GemmArgs::f16s 1 or 2, or -1: the row itself runs.  The one

@@ -17,12 +17,12 @@
 
 using namespace vlsat;
 
-// the parts of one launch, in this program's own words: plan, take the rows the plan covers, plan the rest
-static std::string parts(const EdgePairsIn& in, int N, int K, int add, int act, int a_pair, int c_pair) {
-    GemmArgs a = edge_pairs_probe(in, N, K, add, false, act);
+// the parts of one launch (a stage of csrc/edge_stages.h, as the forward launches it), in this program's own words: plan, take the rows
+// the plan covers, plan the rest
+static std::string parts(const EdgePairsIn& in, const GemmArgs& stage) {
+    GemmArgs a = edge_pairs_resolve(in, stage);
     if (a.M <= 0) return "none";
     if (a.f16s != 2) return "exact-";
-    a.a_pair = (int16_t)a_pair; a.c_pair = (int16_t)c_pair;
     if (gemm_invalid(a)) return "invalid-";
     std::string out;
     for (int guard = 0; guard < 64 && a.M > 0; ++guard) {
@@ -41,11 +41,15 @@ static std::string parts(const EdgePairsIn& in, int N, int K, int add, int act, 
 
 static void plan_line(const char* name, const EdgePairsIn& in) {
     const EdgePairs r = edge_pairs_plan(in);
-    const int D = in.D;
+    // the launches of the 2D branch that touch that E2, with E2 as pair words and Hbig / R1 as the plan decided them
+    const EdgeDims d = edge_pairs_dims(in);
+    const EdgeOps o = edge_ops_placeholder();
+    EdgePairs q = r;
+    q.e2 = true;
     std::printf("%s -> E2 %s | Hbig2 %d | conv3 %s | nn_edge.0 %s | proj_edge %s | head %s\n", name,
                 r.e2 ? "pairs" : (std::string("fp32 (") + (r.why_e2 ? r.why_e2 : "?") + ")").c_str(), r.hbig[1] ? 1 : 0,
-                parts(in, D, 128, 0, ACT_RELU, 0, 1).c_str(), parts(in, 2 * D, D, 6, ACT_RELU, 1, r.hbig[1] ? 1 : 0).c_str(),
-                in.use_gcn_edge ? parts(in, D, D, 0, ACT_NONE, 1, 0).c_str() : "none", parts(in, 512, D, 0, ACT_RELU, 1, r.r1[1] ? 1 : 0).c_str());
+                parts(in, stage_conv3(d, o, q, 1)).c_str(), parts(in, stage_nn_edge0(d, o, q, 1, 0, false)).c_str(),
+                in.use_gcn_edge ? parts(in, stage_proj_edge(d, o, q, 1, 0, false)).c_str() : "none", parts(in, stage_rel_head1(d, o, q, 1, 0)).c_str());
 }
 
 int main(int argc, char** argv) {
